@@ -11,9 +11,17 @@ are already resident in HBM: per rank, F frames of 2160x3840 uint8 Y ->
 K1 embed (stego + Sc) -> K2+K4 extract (scrambled-watermark estimate), after
 the watermark's singular values were broadcast from rank 0 (RCCL; the one
 exchange step of the path).  Weak scaling: every rank processes F frames.
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra
-objects: ``roofline`` (embed kernel, algorithmic bytes / HIP-event time) and
-``cpu_baseline`` (the NumPy oracle timed on this box's host cores, N=1 only).
+Prints ONE JSON line on rank 0 (the contract line) with a ``roofline`` object
+(embed kernel, algorithmic bytes / HIP-event time of the timed steps, HBM
+traffic replayed from profiles/).
+
+A plain run sets up, warms up, times --steps steps and prints that line; with
+--dump-outputs DIR it first writes the last timed step's stego, sigma_c and
+scrambled-watermark estimate (rank 0) as DIR/<name>.npy.  Everything else moves
+behind --full (N=1 only): ``cpu_baseline`` / ``parity`` (the NumPy oracle on
+the host cores), the process-pool and reference-semantics CPU baselines, the
+``fullframe``, ``full_extract`` and ``end_to_end`` sections, and the child
+rocprofv3 counter passes that measure the roofline's traffic in the run.
 """
 from __future__ import annotations
 
@@ -33,6 +41,23 @@ PKG = "digital-watermarking-for-image-video-using-dct-svd-singular-value-decompo
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 VALU_PEAK_LANE_OPS = 73e12     # measured v_pk_fma_f32 lane-op/s ceiling on this part (tools/ubench_valu)
+DUMP_MAX_ELEMS = 4 << 20       # --dump-outputs: float32 elements per array (three arrays: 48 MiB in all)
+DUMP_SEED = 20250
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the device arrays a caller of the timed path receives, as DIR/<name>.npy in float32.  An array of
+    at most DUMP_MAX_ELEMS elements is written whole in its own shape; a larger one as the 1-D sample of DUMP_MAX_ELEMS
+    elements at sorted flat indices drawn without replacement by a generator seeded with DUMP_SEED - the same
+    positions whenever the shape is the same, so that two builds' files compare element for element."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def parse():
@@ -46,22 +71,31 @@ def parse():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--alpha", type=float, default=0.15)
-    ap.add_argument("--cpu-frames", type=int, default=3, help="frames in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: CPU baselines and parity, the full-frame section, "
+                         "full extract, end-to-end and the live rocprofv3 counter passes (tile mode); the CPU sample and the "
+                         "16-plane figure (--mode fullframe).  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy in float32: "
+                         "whole arrays up to %d elements, a fixed seeded sample of that many beyond" % DUMP_MAX_ELEMS)
+    ap.add_argument("--cpu-frames", type=int, default=3, help="with --full: frames in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--mode", choices=("tile", "fullframe"), default="tile",
                     help="tile: the 8x8 hot path (contract default); fullframe: the reference's own "
                          "semantics (one dense SVD per plane), secondary workload")
     ap.add_argument("--ff-frames", type=int, default=64,
                     help="full-frame section: planes per rank per step (round 3: 16).  The two-level block Jacobi with its split-f16 "
                          "products keeps gaining up to ~64 planes per call: 180 / 201 / 214 / 232 / 242 frames/s at 16 / 24 / 32 / 48 / 64 "
-                         "(the flat tournament: 138-142 throughout); the 16-plane figure is still reported as value_at_16_planes")
+                         "(the flat tournament: 138-142 throughout); with --full the 16-plane figure is reported as value_at_16_planes")
     ap.add_argument("--ff-height", type=int, default=1080)
     ap.add_argument("--ff-width", type=int, default=1920)
-    ap.add_argument("--no-fullframe", action="store_true", help="skip the full-frame section of the default line")
+    ap.add_argument("--no-fullframe", action="store_true", help="with --full: skip the full-frame section")
     ap.add_argument("--quick", action="store_true",
-                    help="the contract line only: skip the end-to-end, pool / reference-semantics CPU and full-frame sections")
+                    help="with --full: skip the end-to-end, pool / reference-semantics CPU and full-frame sections and the live "
+                         "counter passes (without --full these never run)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not run the rocprofv3 --pmc child passes that measure roofline.traffic / roofline.valu in this run "
-                         "(the committed profile is replayed instead, and labelled so)")
+                    help="with --full: do not run the rocprofv3 --pmc child passes that measure roofline.traffic / roofline.valu "
+                         "in this run (the committed profile is replayed instead, and labelled so, as without --full)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1 only: initialise the process group (RCCL, world size 1) and issue the per-step broadcast of the "
@@ -358,10 +392,11 @@ def full_extract_section(torch, api, ctx, dev, frames, Sw, Ux, Vxt, stego, sigma
 MFMA_F32_PEAK_TFLOPS = 157.3   # dense f32 MFMA peak (MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 runs at the vector rate)
 
 
-def fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup, cpu_sample=True):
+def fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup, cpu_sample=True, at16=True, dump=None):
     """Reference semantics (tile=None): one dense SVD per plane (single:172-177, 205-218) on BASELINE config 2's
     shape, F planes per rank per step, device-resident through the wm_ref_*_dev entry points.  Returns the
-    object that goes into the bench line (rank 0) - its own frames/s, MFMA roofline and CPU baseline."""
+    object that goes into the bench line (rank 0) - its own frames/s, MFMA roofline and CPU baseline (cpu_sample)
+    and the 16-plane figure (at16).  dump: directory for the last timed step's outputs (rank 0)."""
     H = a.ff_height; W = a.ff_width; F = a.ff_frames
     L = min(H, W); K = max(8, int(0.6 * L)); alpha = a.alpha
     g = torch.Generator(device=dev); g.manual_seed(4242 + rank)
@@ -404,6 +439,8 @@ def fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup,
         sweeps = step()
     barrier()
     dt = time.perf_counter() - t0
+    if dump and rank == 0:
+        dump_outputs(dump, {"stego": stego, "sigma_c": sc, "wm_scrambled": wm_out})
     # embed alone, for the roofline of the block-Jacobi step kernels
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
@@ -434,7 +471,7 @@ def fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup,
     achieved_alg = alg_flops / t_embed / 1e12
     # the same workload at round 3's batch (16 planes per step: the flat tournament), for continuity
     v16 = None
-    if F != 16 and world == 1 and not os.environ.get("WM_BENCH_NO_V16"):
+    if at16 and F != 16 and world == 1 and not os.environ.get("WM_BENCH_NO_V16"):
         f16, s16, c16, w16 = frames[:16].contiguous(), stego[:16].contiguous(), sc[:16].contiguous(), wm_out[:16].contiguous()
         def step16():
             ctx.ref_embed_planes_u8_dev(f16.data_ptr(), Sw.data_ptr(), s16.data_ptr(), c16.data_ptr(), None, 16, H, W, W, H * W, 0, alpha, K)
@@ -506,8 +543,9 @@ def main_fullframe(a):
             dist.init_process_group(a.backend)
     api = importlib.import_module(PKG + ".hostapi")
     ctx = api.Context(local_rank, stream=torch.cuda.current_stream(dev).cuda_stream)
-    steps = max(1, min(a.steps, 5)); warmup = max(1, min(a.warmup, 1))
-    r = fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup, cpu_sample=(world == 1 and a.cpu_frames > 0))
+    steps, warmup = a.steps, a.warmup
+    r = fullframe_section(a, torch, dist, api, dev, rank, world, ctx, steps, warmup,
+                          cpu_sample=(a.full and world == 1 and a.cpu_frames > 0), at16=a.full, dump=a.dump_outputs)
     if rank == 0:
         out = {"metric": r["metric"], "value": r["value"], "unit": "frames/s", "n_gpus": world, "steps": steps,
                "warmup": warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak",
@@ -627,7 +665,7 @@ def live_pmc_fullframe(a, timeout_s=240):
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [rocprof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", os.path.join(tmp, counter), "--",
-                   sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "fullframe", "--steps", "1", "--cpu-frames", "0",
+                   sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "fullframe", "--steps", "1", "--warmup", "1", "--cpu-frames", "0",
                    "--ff-frames", str(a.ff_frames), "--ff-height", str(a.ff_height), "--ff-width", str(a.ff_width), "--alpha", str(a.alpha)]
             p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
@@ -807,6 +845,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ctx.check_status()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"stego": stego, "sigma_c": sigma_c, "wm_scrambled": wm_out})
     bcast_ms = None
     if forced:                                       # the collective on its own: 10 synchronous broadcasts of Sw, then the scalar gather
         torch.cuda.synchronize(dev)
@@ -844,7 +884,7 @@ def main():
             except Exception:
                 traffic = None
         live = None
-        if world == 1 and not a.quick and not a.no_live_pmc:
+        if world == 1 and a.full and not a.quick and not a.no_live_pmc:
             t_l = time.perf_counter()
             live = live_pmc_section(a, F, H, W)
             if live is not None:
@@ -871,7 +911,7 @@ def main():
                          "note": "path is FP32-VALU-bound (~6.5e3 VALU instructions per 64-tile wave against 192 B "
                                  "per tile, VALU busy 0.99): the HBM fraction cannot approach 1, see DESIGN.md 3.3"},
         }
-        if world == 1 and a.cpu_frames > 0:
+        if world == 1 and a.full and a.cpu_frames > 0:
             n = min(a.cpu_frames, F)
             cb, par = cpu_baseline(frames[:n].cpu().numpy(), wys_np, alpha,
                                    stego[:n].cpu().numpy(),
@@ -883,7 +923,7 @@ def main():
                 out["cpu_baseline_pool"] = cpu_baseline_pool(frames[:16].cpu().numpy(), alpha)
                 out["cpu_baseline_reference_semantics"] = cpu_reference_semantics(frames[0].cpu().numpy(), wys_np, alpha)
         skip = set(os.environ.get("WM_BENCH_SKIP", "").split(","))         # development: leave sections out
-        if world == 1 and not a.no_fullframe and not a.quick and (H, W) == (2160, 3840) and "fullframe" not in skip:
+        if world == 1 and a.full and not a.no_fullframe and not a.quick and (H, W) == (2160, 3840) and "fullframe" not in skip:
             # after the timed tile-mode region (value / ms_per_step above are untouched): the reference's own
             # full-frame semantics on BASELINE config 2's shape, with its own roofline and CPU baseline
             out["fullframe"] = fullframe_section(a, torch, dist, api, dev, rank, world, ctx, 2, 1,
@@ -896,7 +936,7 @@ def main():
                     rf["traffic"] = live_ff["traffic"]
                     rf["traffic_detail"] = {k: v for k, v in live_ff.items() if k != "traffic"}
                     rf["traffic_over_plane_bytes"] = live_ff["traffic"] / (a.ff_frames * 4.0 * a.ff_height * a.ff_width)
-        if world == 1 and not a.quick:
+        if world == 1 and a.full and not a.quick:
             hg = importlib.import_module(PKG + ".hostglue")
             idx = hg.permutation_index(H, W, hg.derive_key("bench", bytes(8)))       # single:62-69, host (NumPy PCG64)
             if "full_extract" not in skip:

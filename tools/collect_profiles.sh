@@ -14,5 +14,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_AC
   --output-format csv -d "$OUT/sq" -- $CMD > "$OUT/sq.json" 2> "$OUT/sq.err" || exit 1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- $CMD > "$OUT/fetch.json" 2> "$OUT/fetch.err" || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- $CMD > "$OUT/write.json" 2> "$OUT/write.err" || exit 1
-python bench.py --steps 20 --warmup 3 > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err" || exit 1
+python bench.py --steps 20 --warmup 3 --full > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err" || exit 1
 cat "$OUT/bench_unprofiled.json"
