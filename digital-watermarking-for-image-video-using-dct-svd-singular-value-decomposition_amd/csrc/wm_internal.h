@@ -68,6 +68,18 @@ struct wm_ctx {
   hipStream_t aux_stream[MAX_AUX] = {};
   hipEvent_t ev_fork[MAX_AUX] = {}, ev_join[MAX_AUX] = {};
   hipEvent_t ev[wmi::N_EVENTS] = {};
+  // extract post-processing chain (wm_enhance.hip)
+  void* enh_ws = nullptr;         // grow-only intermediates of wm_enhance_extract_u8_dev / wm_nlmeans / wm_clahe
+  size_t enh_ws_bytes = 0;
+  void* enh_tab = nullptr;        // device tables: ENH_SLOTS NL-means weight prefixes, then the Lab tables
+  static constexpr int ENH_SLOTS = 4;
+  static constexpr int ENH_LUT = 2048;   // == wme::NLM_MAX_LUT
+  uint64_t enh_key[ENH_SLOTS] = {};      // (h bits, channels) + 1 of the prefix a slot holds, 0 = empty
+  int enh_n[ENH_SLOTS] = {};
+  int enh_next = 0;
+  int enh_lab_ready = 0;
+  int enh_host[ENH_SLOTS][ENH_LUT] = {}; // host source of each slot's upload (kept until the slot is reused)
+  uint16_t enh_lab_host[3072] = {};     // host source of the Lab cube-root table upload
 };
 
 namespace wmi {

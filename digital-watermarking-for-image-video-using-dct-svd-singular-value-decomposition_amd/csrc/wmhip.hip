@@ -1003,6 +1003,8 @@ int wm_destroy(wm_ctx* ctx) {
   }
   if (ctx->hier_ws) (void)hipFree(ctx->hier_ws);
   for (int i = 0; i < 2; ++i) if (ctx->dct_mat[i]) (void)hipFree(ctx->dct_mat[i]);
+  if (ctx->enh_ws) (void)hipFree(ctx->enh_ws);
+  if (ctx->enh_tab) (void)hipFree(ctx->enh_tab);
   if (ctx->owns_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return WM_OK;

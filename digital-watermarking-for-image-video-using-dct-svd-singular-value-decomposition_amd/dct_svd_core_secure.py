@@ -265,9 +265,11 @@ def _detect_plane_resized(ctx, plane_u8, Sc, Sw, alpha) -> float:
 
 
 def extract_arrays(stego: np.ndarray, meta, password: str, normalize: bool = True,
-                   device: int = 0) -> np.ndarray:
-    """Watermark estimate (uint8 [H,W] gray / [H,W,3] colour) before the
-    reference's cosmetic denoise/enhance step (single:223-227,275-277)."""
+                   device: int = 0, *, enhance=False) -> np.ndarray:
+    """Watermark estimate (uint8 [H,W] gray / [H,W,3] colour).  ``enhance``: False (default) returns it before the
+    reference's denoise/enhance step (single:223-227,275-277); True applies the unsharp half on the host; "reference"
+    runs the reference's whole chain (NL-means, CLAHE, unsharp) on the device."""
+    hg.check_enhance(enhance)
     _check_password(password, "extract")
     if not password:
         raise ValueError("Vui lòng nhập mật khẩu để giải trích.")          # single:193-194
@@ -302,7 +304,9 @@ def extract_arrays(stego: np.ndarray, meta, password: str, normalize: bool = Tru
         raise
     if not check.result():
         raise ValueError("Sai mật khẩu hoặc meta không khớp.")             # single:208-209,246-247
-    return out
+    if enhance is False:
+        return out
+    return hg.apply_enhance(_ctx(device) if isinstance(enhance, str) else None, out, enhance)   # single:223-227,275-277
 
 
 def _extract_checked(stego, meta, mode, alpha, kfrac, k_floor, H, W, key, normalize, device):
@@ -417,19 +421,18 @@ def embed(cover_path: str, wm_source: str, out_path: str, meta_path: str,
 
 
 def extract(stego_path: str, meta_path: str, out_path: str, password: str,
-            normalize: bool = True, *, enhance: bool = False, device: int = 0) -> str:
-    """single:192-282.  ``enhance=True`` applies the unsharp half of the
-    reference's cosmetic post-processing (CLAHE / NL-means are OpenCV-only and
-    wrapped in try/except there); default writes the extracted plane as is."""
+            normalize: bool = True, *, enhance=False, device: int = 0) -> str:
+    """single:192-282.  ``enhance="reference"`` writes what the reference writes: the estimate after its
+    post-processing chain (NL-means, CLAHE, unsharp; single:223-227,275-277), on the device.  ``enhance=True`` applies
+    the unsharp half only, on the host; the default writes the extracted plane as is."""
+    hg.check_enhance(enhance)
     _check_password(password, "extract")
     if not password:
         raise ValueError("Vui lòng nhập mật khẩu để giải trích.")
     img = _Later(lambda: hg.read_image_bgr(stego_path))                    # single:201, decoded while the meta is read
     data = hg.load_npz(meta_path)                                          # single:195 (all members, inflated concurrently); its errors come first, as in the reference
     st = img.result()
-    wm = extract_arrays(st, data, password, normalize, device)
-    if enhance:
-        wm = hg.unsharp(wm, 0.25 if wm.ndim == 2 else 0.15)               # single:95,109
+    wm = extract_arrays(st, data, password, normalize, device, enhance=enhance)   # single:223-227,275-277 per enhance
     if not out_path.lower().endswith(".png"):
         out_path = os.path.splitext(out_path)[0] + "_wm.png"               # single:225-226,278-279
     if not hg.write_png(out_path, wm, 1):

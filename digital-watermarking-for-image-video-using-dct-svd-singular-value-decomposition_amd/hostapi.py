@@ -111,6 +111,13 @@ SIGNATURES = {
     "wm_psnr_u8": [_vp, _vp, _vp, _sz, C.POINTER(C.c_double)],
     "wm_ssim": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_double)],
     "wm_normalize_u8": [_vp, _vp, _sz, _i, _vp],
+    "wm_nlmeans_u8_dev": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i],
+    "wm_clahe_u8_dev": [_vp, _vp, _vp, _i, _i, _f, _i, _i],
+    "wm_unsharp_u8_dev": [_vp, _vp, _vp, _i, _i, _i, _f],
+    "wm_bgr_to_lab_u8_dev": [_vp, _vp, _vp, _sz],
+    "wm_lab_to_bgr_u8_dev": [_vp, _vp, _vp, _sz],
+    "wm_enhance_extract_u8_dev": [_vp, _vp, _vp, _i, _i, _i],
+    "wm_enhance_extract_u8": [_vp, _vp, _vp, _i, _i, _i],
 }
 
 
@@ -197,6 +204,8 @@ class Context:
         if getattr(self, "_h", None):
             for ent in self.__dict__.pop("_idx_cache", []):
                 self._drop_index(ent)
+            for d in self.__dict__.pop("_enh_bufs", (0, 0, 0))[1:]:
+                self.lib.wm_free(self._h, _vp(d))
             self.lib.wm_destroy(self._h)
             self._h = None
 
@@ -845,4 +854,70 @@ class Context:
         x = np.ascontiguousarray(x, dtype=np.float32)
         out = np.empty(x.shape, np.uint8)
         self._call("wm_normalize_u8", _vp(x.ctypes.data), x.size, 1 if normalize else 0, _vp(out.ctypes.data))
+        return out
+
+    # ---- extract post-processing (NL-means, CLAHE, unsharp, Lab; include/wmhip.h) ----------------------------------
+    def _enh_pair(self, nbytes: int):
+        """two grow-only device buffers of at least nbytes for the host-array wrappers below (freed by close())"""
+        have, a, b = self.__dict__.get("_enh_bufs", (0, 0, 0))
+        if have < nbytes:
+            for d in (a, b):
+                if d:
+                    self.free(d)
+            self.__dict__["_enh_bufs"] = (0, 0, 0)
+            a, b = self.malloc(nbytes), self.malloc(nbytes)
+            self.__dict__["_enh_bufs"] = (nbytes, a, b)
+        return a, b
+
+    @staticmethod
+    def _u8_image(img: np.ndarray, channels) -> np.ndarray:
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError("image must be uint8")
+        ch = 1 if img.ndim == 2 else (img.shape[2] if img.ndim == 3 else 0)
+        if ch not in channels:
+            raise ValueError(f"image must be [H, W] or [H, W, C] with C in {channels}")
+        return img
+
+    def _enh_run(self, img: np.ndarray, fn, *args) -> np.ndarray:
+        a, b = self._enh_pair(max(img.nbytes, 1))
+        self.h2d(a, img)
+        self._call(fn, _vp(a), _vp(b), *args)
+        out = np.empty_like(img)
+        self.d2h(out, b)
+        self.sync()
+        return out
+
+    def nlmeans_u8(self, img: np.ndarray, h: float, template_ws: int = 7, search_ws: int = 21) -> np.ndarray:
+        """cv2.fastNlMeansDenoising(img, None, h, template_ws, search_ws): uint8 [H, W] or [H, W, 2] (interleaved)."""
+        img = self._u8_image(img, (1, 2))
+        ch = 1 if img.ndim == 2 else 2
+        return self._enh_run(img, "wm_nlmeans_u8_dev", img.shape[0], img.shape[1], ch, float(h), int(template_ws),
+                             int(search_ws))
+
+    def clahe_u8(self, img: np.ndarray, clip_limit: float = 2.0, tiles=(8, 8)) -> np.ndarray:
+        """cv2.createCLAHE(clip_limit, tiles).apply(img): uint8 [H, W]; tiles = (tiles_x, tiles_y)."""
+        img = self._u8_image(img, (1,))
+        return self._enh_run(img, "wm_clahe_u8_dev", img.shape[0], img.shape[1], float(clip_limit), int(tiles[0]),
+                             int(tiles[1]))
+
+    def unsharp_u8(self, img: np.ndarray, amount: float) -> np.ndarray:
+        """addWeighted(img, 1 + amount, GaussianBlur(img, (0, 0), 1.0), -amount, 0): uint8 [H, W] or [H, W, 3]."""
+        img = self._u8_image(img, (1, 3))
+        ch = 1 if img.ndim == 2 else 3
+        return self._enh_run(img, "wm_unsharp_u8_dev", img.shape[0], img.shape[1], ch, float(amount))
+
+    def lab_u8(self, img: np.ndarray, inverse: bool = False) -> np.ndarray:
+        """COLOR_LBGR2Lab (inverse: COLOR_Lab2LBGR), 8-bit: uint8 [..., 3]."""
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8 or img.shape[-1] != 3:
+            raise ValueError("image must be uint8 [..., 3]")
+        return self._enh_run(img, "wm_lab_to_bgr_u8_dev" if inverse else "wm_bgr_to_lab_u8_dev", img.size // 3)
+
+    def enhance_extract_u8(self, img: np.ndarray) -> np.ndarray:
+        """The reference's extract post-processing: gray [H, W] single:223-227, BGR [H, W, 3] single:275-277."""
+        img = self._u8_image(img, (1, 3))
+        out = np.empty_like(img)
+        ch = 1 if img.ndim == 2 else 3
+        self._call("wm_enhance_extract_u8", _vp(img.ctypes.data), _vp(out.ctypes.data), img.shape[0], img.shape[1], ch)
         return out

@@ -487,3 +487,24 @@ def unsharp(img_u8: np.ndarray, amount: float) -> np.ndarray:
     sig = (1.0, 1.0) if f.ndim == 2 else (1.0, 1.0, 0.0)
     blur = scipy.ndimage.gaussian_filter(f, sigma=sig, mode="mirror", truncate=4.0)
     return np.clip(np.floor((1.0 + amount) * f - amount * blur + 0.5), 0, 255).astype(np.uint8)
+
+
+ENHANCE_MODES = (False, True, "reference")
+
+
+def check_enhance(enhance) -> None:
+    """extract's ``enhance``: False (the estimate as is), True (unsharp only, on the host) or "reference" (the
+    reference's whole post-processing chain - NL-means, CLAHE, unsharp - on the device).  Raised before any device work."""
+    if isinstance(enhance, (bool, np.bool_)) or (isinstance(enhance, str) and enhance == "reference"):
+        return
+    raise ValueError(f"enhance must be False, True or 'reference', got {enhance!r}")
+
+
+def apply_enhance(ctx, img_u8: np.ndarray, enhance) -> np.ndarray:
+    """single:223-227 (gray) / 275-277 (colour) after the estimate; ctx is a hostapi.Context (only for "reference")."""
+    check_enhance(enhance)
+    if isinstance(enhance, str):
+        return ctx.enhance_extract_u8(img_u8)
+    if enhance:
+        return unsharp(img_u8, 0.25 if img_u8.ndim == 2 else 0.15)        # single:95,109
+    return img_u8

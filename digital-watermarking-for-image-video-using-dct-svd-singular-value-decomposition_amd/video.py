@@ -252,8 +252,10 @@ def _marked_luma(stego_video_path: str, data) -> np.ndarray:
 
 
 def extract_watermark_video(stego_video_path: str, metadata_path: str, output_image_path: str,
-                            password: str, normalize: bool = True, *, batch: int = 32, device: int = 0) -> str:
-    """Averaged multi-frame extraction -> watermark image (PNG)."""
+                            password: str, normalize: bool = True, *, batch: int = 32, device: int = 0,
+                            enhance=False) -> str:
+    """Averaged multi-frame extraction -> watermark image (PNG).  ``enhance`` as in dct_svd_core_secure.extract."""
+    hg.check_enhance(enhance)
     if not password:
         raise ValueError("Vui lòng nhập mật khẩu để giải trích.")
     data = _load_video_meta(metadata_path)
@@ -270,6 +272,7 @@ def extract_watermark_video(stego_video_path: str, metadata_path: str, output_im
         K = _k_of(tile, float(data["kfrac"]), int(data["k_floor"]), H, W)
         wy_s = extract_frames_mean(ctx, ys, data["Sc"], data["Uw"], data["Vwt"], float(data["alpha"]), K, batch, tile)
         img = ctx.unpermute_normalize_u8(wy_s, hg.permutation_index(H, W, key), normalize)   # single:74-80, 221-222 on the device
+        img = hg.apply_enhance(ctx, img, enhance)                                           # single:223-227
     finally:
         ctx.close()
     if not output_image_path.lower().endswith(".png"):
@@ -431,8 +434,10 @@ def _marked_bgr(ctx: hostapi.Context, stego_video_path: str, data) -> np.ndarray
 
 
 def extract_watermark_video_color(stego_video_path: str, metadata_path: str, output_image_path: str, password: str,
-                                  normalize: bool = True, *, batch: int = 8, device: int = 0) -> str:
-    """Averaged multi-frame extraction per channel -> colour watermark image (PNG)."""
+                                  normalize: bool = True, *, batch: int = 8, device: int = 0, enhance=False) -> str:
+    """Averaged multi-frame extraction per channel -> colour watermark image (PNG).  ``enhance`` as in
+    dct_svd_core_secure.extract."""
+    hg.check_enhance(enhance)
     if not password:
         raise ValueError("Vui lòng nhập mật khẩu để giải trích.")
     data = _load_video_meta_color(metadata_path)
@@ -453,7 +458,7 @@ def extract_watermark_video_color(stego_video_path: str, metadata_path: str, out
             w_s = extract_frames_mean(ctx, np.ascontiguousarray(planes[:, ch]), data["S" + n], data["UW" + n], data["VW" + n + "t"],
                                       float(data["alpha"]), K, batch, tile)
             chans.append(ctx.unpermute_normalize_u8(w_s, idx, normalize))                    # single:265-271 per channel
-        img = np.stack(chans, axis=-1)
+        img = hg.apply_enhance(ctx, np.stack(chans, axis=-1), enhance)                     # single:275-277
     finally:
         ctx.close()
     if not output_image_path.lower().endswith(".png"):

@@ -352,6 +352,26 @@ int wm_psnr_u8(wm_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, double
 int wm_ssim(wm_ctx* ctx, const void* img1, const void* img2, int H, int W, int kind, double* ssim_out);
 int wm_normalize_u8(wm_ctx* ctx, const float* x, size_t n, int do_norm, uint8_t* out);
 
+/* ---- extract post-processing (single:223-227 gray, 275-277 colour, 88-110) ----------------------------
+ * The reference writes, as the _wm.png, the estimate after cv2.fastNlMeansDenoising(wy, None, 7, 7, 21) + CLAHE(2.0,
+ * 8x8) + unsharp (gray) or cv2.fastNlMeansDenoisingColored(out, None, 3, 3, 7, 21) + CLAHE on Y of YCrCb + unsharp
+ * (colour).  OpenCV 4.x's 8-bit algorithms, restated in tests/enhance_oracle.py.  Images are
+ * dense, row-major, interleaved uint8.  Unsupported sizes / parameters return WM_ERR_BADARG.
+ *   wm_nlmeans_u8_dev   channels 1 or 2 (interleaved); template_ws 7 with search_ws 21 only; not in place
+ *   wm_clahe_u8_dev     tiles_x, tiles_y 1..16; may run in place
+ *   wm_unsharp_u8_dev   GaussianBlur(sigma 1) + addWeighted(e, 1 + amount, blur, -amount, 0); channels 1 or 3; not in place
+ *   wm_*_lab_*          COLOR_LBGR2Lab / COLOR_Lab2LBGR (linear RGB, D65), n_px interleaved pixels
+ *   wm_enhance_extract  the whole chain: channels 1 (gray) or 3 (BGR); src may equal dst
+ * The _dev forms keep their intermediates in the context's grow-only workspace (nothing allocated once warm). */
+int wm_nlmeans_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, int W, int channels,
+                      float h, int template_ws, int search_ws);
+int wm_clahe_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, int W, float clip_limit, int tiles_x, int tiles_y);
+int wm_unsharp_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, int W, int channels, float amount);
+int wm_bgr_to_lab_u8_dev(wm_ctx* ctx, const uint8_t* bgr, uint8_t* lab, size_t n_px);
+int wm_lab_to_bgr_u8_dev(wm_ctx* ctx, const uint8_t* lab, uint8_t* bgr, size_t n_px);
+int wm_enhance_extract_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, int W, int channels);
+int wm_enhance_extract_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, int W, int channels);
+
 #ifdef __cplusplus
 }
 #endif
