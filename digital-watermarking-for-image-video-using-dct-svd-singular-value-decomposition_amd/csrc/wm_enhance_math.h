@@ -83,10 +83,13 @@ WME_HD void clahe_padded(int H, int W, int tiles_x, int tiles_y, int& Hp, int& W
   Hp = H + tiles_y - H % tiles_y;
   Wp = W + tiles_x - W % tiles_x;
 }
+// clip_limit * total / 256, at least 1; saturates at INT_MAX instead of an undefined cast: a count
+// at or above the tile's pixel count clips nothing, so a huge clip equals clip <= 0
 WME_HD int clahe_clip_count(double clip_limit, int tile_total) {
   if (!(clip_limit > 0.0)) return 0;
-  const int c = (int)(clip_limit * tile_total / CLAHE_BINS);
-  return c > 1 ? c : 1;
+  const double c = clip_limit * tile_total / CLAHE_BINS;
+  if (c >= 2147483647.0) return 2147483647;
+  return c > 1.0 ? (int)c : 1;
 }
 // clip at `clip`, spread the excess: excess / 256 to every bin, then one more to bins 0, step, 2 step, ... for the
 // residual (step = max(256 / residual, 1)).  clip == 0: no clipping.

@@ -107,9 +107,14 @@ def clahe_padded(H: int, W: int, tiles_x: int = 8, tiles_y: int = 8):
 
 
 def clahe_clip_count(clip_limit: float, tile_total: int) -> int:
+    """clip_limit * total / 256 (in double), at least 1, saturated at INT_MAX: a count at or above the tile's pixel
+    count clips nothing, so a huge clip equals clip <= 0 (OpenCV's int cast is undefined there)."""
     if not clip_limit > 0:
         return 0
-    return max(int(clip_limit * tile_total / 256), 1)
+    c = float(clip_limit) * tile_total / 256
+    if c >= 2 ** 31 - 1:
+        return 2 ** 31 - 1
+    return max(int(c), 1)
 
 
 def clahe_clip_hist(hist: np.ndarray, clip: int) -> np.ndarray:
@@ -142,7 +147,7 @@ def clahe_luts(img: np.ndarray, clip_limit: float = 2.0, tiles_x: int = 8, tiles
     src = pad101(img, 0, Hp - H, 0, Wp - W)
     th, tw = Hp // tiles_y, Wp // tiles_x
     total = th * tw
-    clip = clahe_clip_count(clip_limit, total)
+    clip = clahe_clip_count(float(F32(clip_limit)), total)      # the C ABI takes clip_limit as a float
     scale = F32(255.0 / total)
     luts = np.empty((tiles_y, tiles_x, 256), np.uint8)
     for ty in range(tiles_y):
@@ -301,3 +306,17 @@ def enhance_color(bgr: np.ndarray) -> np.ndarray:
 
 def enhance(img: np.ndarray) -> np.ndarray:
     return enhance_gray(img) if img.ndim == 2 else enhance_color(img)
+
+
+def nlm_boundary_h(channels: int, cap: int = 2048) -> float:
+    """The largest float32 h whose weight table's non-zero prefix fits cap - 1 entries (plus its 0): the kernels keep
+    cap = 2048 entries in LDS and refuse any h above this one.  Bisection over float32 bit patterns (the prefix grows
+    with h)."""
+    def fits(bits):
+        return len(nlm_weights(float(np.uint32(bits).view(F32)), channels)) - 1 <= cap - 1
+    lo, hi = int(F32(1.0).view(np.uint32)), int(F32(1000.0).view(np.uint32))
+    assert fits(lo) and not fits(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return float(np.uint32(lo).view(F32))

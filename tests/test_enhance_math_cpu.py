@@ -96,3 +96,40 @@ def test_lab_both_ways(eh):
     back = np.empty_like(every)
     eh.eh_lab_to_bgr(every, back, len(every))
     assert np.array_equal(back, eo.lab_to_bgr(every))
+
+
+@pytest.mark.parametrize("shape,tiles", [((17, 33), (1, 1)), ((64, 64), (8, 8)), ((131, 77), (3, 5))])
+def test_clahe_huge_clip_clips_nothing(eh, shape, tiles):
+    """clip * total / 256 past INT_MAX saturates (a plain int cast is undefined there and gave a count of 1 on x86:
+    maximal equalisation); a count at or above the tile's pixel count clips nothing, so the result is clip 0's."""
+    rng = np.random.default_rng(8)
+    Hp, Wp = eo.clahe_padded(*shape, *tiles)
+    total = (Hp // tiles[1]) * (Wp // tiles[0])
+    for name, img in _images(rng, *shape).items():
+        luts = np.empty(tiles[::-1] + (256,), np.uint8)
+        out0 = np.empty_like(img)
+        assert eh.eh_clahe(img, out0, *shape, 0.0, *tiles, luts) == 0
+        for clip in (1e9, 1e30):
+            if clip * total / 256 < 2 ** 31:
+                continue                                           # only the shapes where the count overflows
+            out = np.empty_like(img)
+            assert eh.eh_clahe(img, out, *shape, clip, *tiles, luts) == 2 ** 31 - 1
+            assert np.array_equal(luts, eo.clahe_luts(img, clip, *tiles)), (name, clip)
+            assert np.array_equal(out, eo.clahe(img, clip, *tiles)), (name, clip)
+            assert np.array_equal(out, out0), (name, clip)
+        assert np.array_equal(out0, eo.clahe(img, 0.0, *tiles)), name
+
+
+@pytest.mark.parametrize("ch", [1, 2])
+def test_weight_table_at_the_lds_boundary(eh, ch):
+    """The longest table the kernels keep (2047 non-zero entries + the 0): at the largest h that fits, the header's
+    table is the oracle's; one float32 step up it is refused."""
+    h = eo.nlm_boundary_h(ch)
+    ref = eo.nlm_weights(h, ch)
+    assert len(ref) - 1 == 2047
+    w = np.zeros(2048, np.int32)
+    n = eh.eh_nlm_weights(h, ch, w, 2048)
+    assert n == len(ref) - 1 and np.array_equal(w[:n + 1], ref)
+    up = float(np.nextafter(np.float32(h), np.float32(np.inf)))
+    assert len(eo.nlm_weights(up, ch)) - 1 > 2047
+    assert eh.eh_nlm_weights(up, ch, w, 2048) == -1

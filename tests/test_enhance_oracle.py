@@ -122,3 +122,22 @@ def test_dropin_rejects_an_unknown_enhance_mode_without_a_device(tmp_path):
         video.extract_watermark_video("none.y4m", "none.npz", "o.png", "pw", enhance=2)
     with pytest.raises(ValueError, match="enhance"):
         video.extract_watermark_video_color("none.y4m", "none.npz", "o.png", "pw", enhance="x")
+
+
+def test_clahe_clip_count_saturates():
+    big = 2 ** 31 - 1
+    assert eo.clahe_clip_count(2.0, 64) == 1 and eo.clahe_clip_count(2.0, 8100) == 63
+    assert eo.clahe_clip_count(0.0, 561) == 0 and eo.clahe_clip_count(-1.0, 561) == 0
+    assert eo.clahe_clip_count(float(big - 1), 256) == big - 1          # the largest count that is not saturated
+    for clip, total in ((1e9, 561), (1e9, 550), (1e30, 1), (float(big), 256), (float("inf"), 64)):
+        assert eo.clahe_clip_count(clip, total) == big, (clip, total)
+    # a count >= the tile's pixel count leaves the histogram alone, so a huge clip equals no clipping at all
+    hist = np.zeros(256, np.int64); hist[7] = 561
+    assert np.array_equal(eo.clahe_clip_hist(hist, big), hist)
+    rng = np.random.default_rng(4)
+    img = rng.integers(0, 64, (17, 33), dtype=np.uint8)
+    for tiles in ((1, 1), (3, 5)):
+        none = eo.clahe(img, 0.0, *tiles)
+        assert np.array_equal(eo.clahe(img, 1e9, *tiles), none)
+        assert np.array_equal(eo.clahe(img, 1e30, *tiles), none)
+        assert not np.array_equal(eo.clahe(img, 0.01, *tiles), none)      # clip count 1: maximal equalisation differs
