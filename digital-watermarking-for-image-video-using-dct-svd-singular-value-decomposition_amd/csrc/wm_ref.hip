@@ -875,6 +875,50 @@ __global__ void k_rf_scale_cols_b(const float* __restrict__ src, const size_t s_
     dst[(size_t)r * cols + k] = src[(size_t)r * cols + k] * d[k];
 }
 
+// The guard of the split-f16 reconstruct: the largest squared row norm of U[:n,:n] (leading dimension lu) into mx[0] and the
+// largest squared column norm of V[:n,:n] (leading dimension lv) into mx[1], as float bits (non-negative floats and NaN order
+// like their bits; the caller zeroes mx).  Blocks below nbu take four rows of U, a wave each; the others 16 columns of V in 16
+// row phases.  Fixed summation order: the same factors give the same bits.
+__global__ __launch_bounds__(256) void k_rf_corner_norms(const float* __restrict__ U, const int lu, const float* __restrict__ V,
+                                                          const int lv, const int n, const int nbu, unsigned* __restrict__ mx) {
+  __shared__ float part[16][17];
+  __shared__ unsigned colmax[16];
+  const int t = threadIdx.x;
+  if ((int)blockIdx.x < nbu) {
+    const int r = 4 * blockIdx.x + (t >> 6);
+    float s = 0.0f;
+    if (r < n)
+      for (int k = t & 63; k < n; k += 64) { const float u = U[(size_t)r * lu + k]; s = fmaf(u, u, s); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((t & 63) == 0 && r < n) atomicMax(&mx[0], __float_as_uint(s));
+    return;
+  }
+  const int c = 16 * ((int)blockIdx.x - nbu) + (t & 15), ph = t >> 4;
+  float s0 = 0.0f, s1 = 0.0f;
+  if (c < n) {
+    int k = ph;
+    for (; k + 16 < n; k += 32) {
+      const float a = V[(size_t)k * lv + c], b = V[(size_t)(k + 16) * lv + c];
+      s0 = fmaf(a, a, s0); s1 = fmaf(b, b, s1);
+    }
+    if (k < n) { const float a = V[(size_t)k * lv + c]; s0 = fmaf(a, a, s0); }
+  }
+  part[ph][t & 15] = s0 + s1;
+  __syncthreads();
+  if (t < 16) {
+    float s = 0.0f;
+    for (int i = 0; i < 16; ++i) s += part[i][t];
+    colmax[t] = __float_as_uint(s);
+  }
+  __syncthreads();
+  if (t == 0) {
+    unsigned m = 0;
+    for (int i = 0; i < 16; ++i) m = colmax[i] > m ? colmax[i] : m;
+    atomicMax(&mx[1], m);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1270,7 +1314,8 @@ int fetch_norms_t(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const float* A0
   if (final_f16() && hgemm_ok(A0, p.M, w.aug, p.ld)) {
     // A0 holds uint8 samples (every caller decomposes uint8 planes): exact in f16; B's rows are bounded by 255 sqrt(L)
     hipLaunchKernelGGL((k_hgemm<true, true, false>), dim3((p.Lp + 127) / 128, (p.L + 127) / 128, p.B), dim3(256), 0, ctx->stream, p.L, p.Lp, p.M,
-                       A0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0, T, p.Lp, (size_t)p.L * p.Lp, (const float*)nullptr, (size_t)0, 1.0f);
+                       A0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0, T, p.Lp, (size_t)p.L * p.Lp, (const float*)nullptr, (size_t)0, 1.0f,
+                       1.0f, (const float*)nullptr);
   } else
   WM_TRY(sgemm_b(ctx, false, true, p.L, p.Lp, p.M, 1.0f, A0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0.0f, T, p.Lp,
                  (size_t)p.L * p.Lp, p.B));
@@ -1566,7 +1611,8 @@ int ref_embed_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t*
   // Yw += T (diag(e) B):   [L x Lp] times [Lp x M], all planes in one launch
   if (f16_prod)
     hipLaunchKernelGGL((k_hgemm<false, false, true>), dim3((p.M + 127) / 128, (p.L + 127) / 128, p.B), dim3(256), 0, ctx->stream, p.L, p.M, p.Lp,
-                       d_t, p.Lp, (size_t)p.L * p.Lp, w.aug, p.ld, p.aug_ps, 1, d_yw, p.M, yw_ps, w.dvec + (size_t)p.B * p.Lp, (size_t)p.Lp, 1.0f);
+                       d_t, p.Lp, (size_t)p.L * p.Lp, w.aug, p.ld, p.aug_ps, 1, d_yw, p.M, yw_ps, w.dvec + (size_t)p.B * p.Lp, (size_t)p.Lp, 1.0f,
+                       1.0f, (const float*)nullptr);
   else
   WM_TRY(sgemm_b(ctx, false, false, p.L, p.M, p.Lp, 1.0f, d_t, p.Lp, (size_t)p.L * p.Lp, w.aug, p.ld, p.aug_ps, 1.0f,
                  d_yw, p.M, yw_ps, p.B));
@@ -1589,27 +1635,56 @@ int ref_reconstruct_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const st
   float *dH, *dW;
   WM_TRY(get_dct_pair(ctx, H, W, &dH, &dW));
   if (final_f16() && L % 4 == 0 && W % 4 == 0 && H % 4 == 0 && hgemm_ok(d_uw, L, d_vwt, W) && hgemm_ok(d_mid, W, d_out, W)) {
-    // Split-f16 products (k_hgemm): Uw, Vwt and the DCT bases are orthonormal; the estimates are scaled by a power of two so
-    // that |X| <= max |sw_hat| * scale stays below 3e4, and the last product multiplies it out again (exact both ways).
-    float mx = 0.0f;
-    for (float v : sh) mx = fmaxf(mx, fabsf(v));
-    int e = 0;
-    if (mx > 0.0f && std::isfinite(mx)) { (void)frexpf(mx / 3.0e4f, &e); if (e < 0) e = 0; }
-    const float scale = ldexpf(1.0f, -e);
-    std::vector<float> shs(sh);
-    for (float& v : shs) v *= scale;
-    WM_HIP(hipMemcpyAsync(w.dvec, shs.data(), shs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemsetAsync(d_out, 0, (size_t)p.B * H * W * 4, ctx->stream));                                   // single:215
-    const float* dHt = dH + (size_t)H * H;
-    hipLaunchKernelGGL((k_hgemm<false, false, true>), dim3((Lx + 127) / 128, (Lx + 127) / 128, p.B), dim3(256), 0, ctx->stream, Lx, Lx, Lx,
-                       d_uw, L, (size_t)0, d_vwt, W, (size_t)0, 0, d_out, W, (size_t)H * W, w.dvec, (size_t)p.Lp, 1.0f);          // single:214, 216-217
-    hipLaunchKernelGGL((k_hgemm<false, false, false>), dim3((W + 127) / 128, (H + 127) / 128, p.B), dim3(256), 0, ctx->stream, H, W, H,
-                       dHt, H, (size_t)0, d_out, W, (size_t)H * W, 0, d_mid, W, (size_t)H * W, (const float*)nullptr, (size_t)0, 1.0f);   // idct2: D_H^T X
-    hipLaunchKernelGGL((k_hgemm<false, false, false>), dim3((W + 127) / 128, (H + 127) / 128, p.B), dim3(256), 0, ctx->stream, H, W, W,
-                       d_mid, W, (size_t)H * W, dW, W, (size_t)0, 0, d_out, W, (size_t)H * W, (const float*)nullptr, (size_t)0, 1.0f / scale);   //        ... D_W   single:218
-    WM_HIP(hipGetLastError());
-    WM_HIP(hipStreamSynchronize(ctx->stream));       // (shs is a local)
-    return WM_OK;
+    // Split-f16 products (k_hgemm), only for factors whose corners have rows of Uw / columns of Vwt of norm mu / mv <= 1 + 2^-10
+    // (corners of orthonormal factors always do); k_sgemm for any other factors.  Every f16 operand is then brought into
+    // [~1, 3e4) by powers of two (exact both ways): per plane, sw_hat by 2^-e so that max |sw_hat| mu lies in [1.5e4, 3e4)
+    // (this bounds |Uw diag(sh)| and |X|); a Vwt with mv < 1/2 by 2^sv up to [1/2, 1); D_H^T X, whose entries are bounded by
+    // the column norms of X, up to sqrt(Lx) |X| for factors that are not orthonormal, by 2^-m < 1 / sqrt(Lx).  The last
+    // product multiplies 2^(e + m - sv) out again, per plane.
+    float* d_az = w.dvec + (size_t)p.B * p.Lp;                 // after the estimates: per-plane alphas, then the guard's bits
+    unsigned* d_mx = reinterpret_cast<unsigned*>(d_az + p.B);
+    WM_HIP(hipMemsetAsync(d_mx, 0, 2 * sizeof(unsigned), ctx->stream));
+    const int nbu = (Lx + 3) / 4;
+    hipLaunchKernelGGL(k_rf_corner_norms, dim3(nbu + (Lx + 15) / 16), dim3(256), 0, ctx->stream, d_uw, L, d_vwt, W, Lx, nbu, d_mx);
+    unsigned mxb[2] = {0u, 0u};
+    WM_HIP(hipMemcpyAsync(mxb, d_mx, sizeof(mxb), hipMemcpyDeviceToHost, ctx->stream));
+    WM_HIP(hipStreamSynchronize(ctx->stream));
+    const double mu = sqrt((double)__builtin_bit_cast(float, mxb[0])), mv = sqrt((double)__builtin_bit_cast(float, mxb[1]));
+    const double lim = 1.0 + 1.0 / 1024.0;
+    bool ok = mu > 0.0 && mv > 0.0 && mu <= lim && mv <= lim;          // (false for NaN)
+    int ev = 0, m = 0;
+    if (ok) { (void)frexp(mv, &ev); (void)frexp(sqrt((double)Lx), &m); }
+    const int sv = ev < 0 ? -ev : 0;
+    std::vector<float> dv((size_t)p.B * p.Lp + p.B, 0.0f);           // sw_hat 2^-e [B][Lp] | 2^(e + m - sv) [B]
+    for (int z = 0; z < p.B && ok; ++z) {
+      const float* shz = &sh[(size_t)z * p.Lp];
+      float mx = 0.0f;
+      for (int i = 0; i < Lx; ++i) mx = fmaxf(mx, fabsf(shz[i]));
+      const double bound = (double)mx * mu;
+      int e = 0;
+      if (bound > 0.0) (void)frexp(bound / 3.0e4, &e);
+      // every scale a normal float (estimates within ~2^+-100 of 3e4 / mu; k_sgemm beyond)
+      if (!std::isfinite(bound) || sv > 100 || e < -100 || e > 100) { ok = false; break; }
+      for (int i = 0; i < p.Lp; ++i) dv[(size_t)z * p.Lp + i] = ldexpf(shz[i], -e);
+      dv[(size_t)p.B * p.Lp + z] = ldexpf(1.0f, e + m - sv);
+    }
+    if (ok) {
+      WM_HIP(hipMemcpyAsync(w.dvec, dv.data(), dv.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+      WM_HIP(hipMemsetAsync(d_out, 0, (size_t)p.B * H * W * 4, ctx->stream));                                   // single:215
+      const float* dHt = dH + (size_t)H * H;
+      hipLaunchKernelGGL((k_hgemm<false, false, true>), dim3((Lx + 127) / 128, (Lx + 127) / 128, p.B), dim3(256), 0, ctx->stream, Lx, Lx, Lx,
+                         d_uw, L, (size_t)0, d_vwt, W, (size_t)0, 0, d_out, W, (size_t)H * W, w.dvec, (size_t)p.Lp, 1.0f,
+                         ldexpf(1.0f, sv), (const float*)nullptr);                                                 // single:214, 216-217
+      hipLaunchKernelGGL((k_hgemm<false, false, false>), dim3((W + 127) / 128, (H + 127) / 128, p.B), dim3(256), 0, ctx->stream, H, W, H,
+                         dHt, H, (size_t)0, d_out, W, (size_t)H * W, 0, d_mid, W, (size_t)H * W, (const float*)nullptr, (size_t)0,
+                         ldexpf(1.0f, -m), 1.0f, (const float*)nullptr);                                           // idct2: D_H^T X
+      hipLaunchKernelGGL((k_hgemm<false, false, false>), dim3((W + 127) / 128, (H + 127) / 128, p.B), dim3(256), 0, ctx->stream, H, W, W,
+                         d_mid, W, (size_t)H * W, dW, W, (size_t)0, 0, d_out, W, (size_t)H * W, (const float*)nullptr, (size_t)0, 1.0f,
+                         1.0f, d_az);                                                                              //        ... D_W   single:218
+      WM_HIP(hipGetLastError());
+      WM_HIP(hipStreamSynchronize(ctx->stream));       // (dv is a local)
+      return WM_OK;
+    }
   }
   WM_HIP(hipMemcpyAsync(w.dvec, sh.data(), sh.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   // Uw[:Lx,:Lx] * sh (column scaling) per plane: the first Lx rows of Uw (leading dimension L)

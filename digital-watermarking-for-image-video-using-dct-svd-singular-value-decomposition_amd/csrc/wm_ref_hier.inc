@@ -414,19 +414,22 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
 //   Yw += (T diag(ca)) (diag(cb) B)   (the embed's U diag(alpha Sw) V^T, ref_embed_core): the caller has scaled B's rows to
 //                unit norm, ca[k] = alpha sw / (sigma |b|) is applied to A's columns while they are staged (SCALE_A), so both
 //                operands are far inside f16's range whatever the plane's scale;
-//   the extract's  Uw diag(sw_hat) Vwt  and its inverse DCT  D_H^T X D_W  (ref_reconstruct_core): orthonormal factors, sw_hat
-//                scaled by a power of two so that X stays below 3e4, undone by the last product's alpha.
+//   the extract's  Uw diag(sw_hat) Vwt  and its inverse DCT  D_H^T X D_W  (ref_reconstruct_core): factors whose corner rows /
+//                columns have norms <= 1 + 2^-10, every operand brought into [~1, 3e4) by powers of two (per plane for sw_hat,
+//                bscale for a small Vwt, alpha for D_H^T X), undone by the last product's per-plane alphaZ.
 // 128 x 128 tile of C per 256-thread workgroup (a 64 x 64 quarter per wave), K in chunks of 32 through one LDS image per operand
 // ([row][k], pitch 40 halfs: 16-byte operand reads conflict-free); a [K][N] operand is transposed on the way in as 4 x 4
 // register pieces (lane (kg, ng): 8-byte writes that cover the 64 banks once per pass, like k_happly_h's staging).
 // Against k_sgemm (f32 MFMA, 64 x 64 tiles, scalar loads: 54 - 74 TF on these shapes) the matrix-pipe time is 5.3 x / 8 x shorter.
-// Preconditions (hgemm_ok): row strides multiples of 4 floats, 16-byte aligned bases.
+// Preconditions (hgemm_ok): row strides multiples of 4 floats, 16-byte aligned bases.  B is multiplied by bscale while it is
+// staged; alphaZ (optional, [grid.z]) multiplies alpha per plane.  Both are meant to be powers of two (exact).
 // ---------------------------------------------------------------------------
 template <bool TB, bool A_EXACT, bool SCALE_A>
 __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const int K, const float* __restrict__ A, const int lda, const size_t sA,
                                               const float* __restrict__ B, const int ldb, const size_t sB, const int accumulate,
                                               float* __restrict__ C, const int ldc, const size_t sC,
-                                              const float* __restrict__ scaleA, const size_t sS, const float alpha) {
+                                              const float* __restrict__ scaleA, const size_t sS, const float alpha,
+                                              const float bscale, const float* __restrict__ alphaZ) {
   constexpr int TM = 128, KC = 32;
   __shared__ __attribute__((aligned(16))) _Float16 Ah[TM][HG_HP];
   __shared__ __attribute__((aligned(16))) _Float16 Al[A_EXACT ? 1 : TM][HG_HP];
@@ -465,6 +468,8 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
 #pragma unroll
       for (int r = 0; r < 4; ++r) rb[r] = load4(B, ldb, k0 + 4 * kg + r, K, bn + 4 * ng, N);
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { rb[i].x *= bscale; rb[i].y *= bscale; rb[i].z *= bscale; rb[i].w *= bscale; }
   };
   auto stash = [&]() {
 #pragma unroll
@@ -525,6 +530,7 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
         }
     }
   }
+  const float az = alphaZ ? alpha * alphaZ[blockIdx.z] : alpha;
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -536,7 +542,7 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
         const int gm = bm + 64 * wi + 32 * x + 8 * (v / 4) + 4 * h + (v % 4);
         if (gm < M) {
           float* c = C + (size_t)gm * ldc + gn;
-          *c = accumulate ? *c + alpha * acc[x][y][v] : alpha * acc[x][y][v];
+          *c = accumulate ? *c + az * acc[x][y][v] : az * acc[x][y][v];
         }
       }
     }

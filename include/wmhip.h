@@ -241,7 +241,9 @@ int wm_ref_extract_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, c
  * the meta's own when the stego handed to extract is not the size the meta was written for
  * (resized / cropped stego) - the drop-in then takes sigma of the stego with wm_ref_sigma_u8,
  * forms Sw_hat on the host (single:211-213) and calls this.
- *   Uw [H][min(H,W)], sw_hat [L], Vwt [min(H,W)][W], out [H][W] float32, all host memory. */
+ *   Uw [H][min(H,W)], sw_hat [L], Vwt [min(H,W)][W], out [H][W] float32, all host memory.
+ * Any finite factors and estimates are accepted; they need not be orthonormal.  Factors whose [:L,:L] corners have a row of
+ * Uw or a column of Vwt longer than 1 + 2^-10 take the f32 products instead of the split-f16 ones. */
 int wm_ref_reconstruct_f32(wm_ctx* ctx, const float* Uw, const float* sw_hat, const float* Vwt, float* out,
                            int H, int W, int L);
 
