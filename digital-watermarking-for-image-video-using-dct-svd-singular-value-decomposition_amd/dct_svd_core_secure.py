@@ -14,8 +14,9 @@ defaults where the reference has a behaviour:
            own full-frame extract.  ``tile=None``: the reference's own
            full-frame semantics (one DCT + one dense SVD per plane) on the
            GPU; stego + meta written this way are what the reference's
-           extract/detect expect (same keys, shapes, HMAC coverage).  Neither
-           mode has a CPU fallback.
+           extract/detect expect (same keys, dtypes, shapes, HMAC coverage):
+           tests/test_gpu_reference_files.py puts them through the reference
+           program itself.  Neither mode has a CPU fallback.
   k_floor  the literal 8 of ``K = max(8, int(kfrac*L))`` (single:174); at
            tile=8 the formula is 8 for every kfrac, so a mid-band sweep sets
            k_floor < 8.
@@ -402,7 +403,8 @@ def embed(cover_path: str, wm_source: str, out_path: str, meta_path: str,
           kfrac: float = K_FRAC_DEFAULT, *, tile: Optional[int] = TILE, k_floor: int = 8,
           nonce: Optional[bytes] = None, device: int = 0, compress_meta: bool = True):
     """single:112-190.  Returns (out_path, meta_path, psnr, ssim).  ``compress_meta=False`` writes the .npz
-    uncompressed (np.load - and the reference's extract / detect - read either form): the tile-mode factors are
+    uncompressed (np.load - and the reference's extract / detect - read either form; tests/test_gpu_reference_files.py runs
+    the reference program on both): the tile-mode factors are
     float noise to zlib, and compressing the 70 MB of a 4K cover costs ten times the rest of the call."""
     _check_password(password, "embed")
     if not password:

@@ -29,13 +29,18 @@ Two modes, one code path:
   compute).  Border rows/columns that do not fill a tile are passed through
   unchanged by embed and read as zero by extract.
 
-PARITY UNPINNED
----------------
+WHAT PINS THIS FILE
+-------------------
 The reference ships no tests, golden vectors, sample images or known-answer
-values, and cannot run here (``import cv2`` -> ModuleNotFoundError; its
-vendored venv is win_amd64 with the binaries missing).  Nothing outside this
-file therefore pins its outputs: the golden fixtures under ``tests/golden``
-are ORACLE-generated, not reference-generated.  What *is* pinned
+values, and OpenCV is not installed here.  But the reference *program* runs:
+``oracle/ref_build.py`` byte-compiles it into ``oracle/_ref/`` and
+``tests/ref_program.py`` executes it over a stand-in ``cv2`` made of the
+restatements below.  ``tests/test_reference_program.py`` holds this file to
+it bit for bit (stego, every meta member, the enhanced watermark, PSNR, SSIM,
+detect) and to the reference-written fixtures under
+``tests/golden/reference``: the program logic and the file formats are
+pinned, OpenCV's own arithmetic is not.  The fixtures
+directly under ``tests/golden`` are ORACLE-generated.  Also pinned
 independently: the DCT against the closed-form basis ``D X D^T``, the SVD by
 reconstruction/orthogonality, the key/permutation/HMAC glue against
 hashlib/NumPy known answers (tests/test_oracle.py).

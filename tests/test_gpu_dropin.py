@@ -173,8 +173,9 @@ def test_config5_8k_embed_extract_detect_kfloor_sweep(gpu_ctx):
 @pytest.mark.parametrize("path", GOLDEN_REF, ids=[os.path.basename(p)[:-4] for p in GOLDEN_REF])
 def test_fullframe_golden_fixture_through_the_dropin(core, path):
     """tile=None: the reference's own semantics.  Files written this way carry exactly
-    the reference's meta keys, so the reference's extract/detect (here: the oracle's
-    restatement of them) read them, and vice versa."""
+    the reference's meta keys, so the reference's extract/detect read them, and vice versa:
+    here through the oracle's restatement of them, which tests/test_reference_program.py holds to
+    the reference program bit for bit; through the program itself in tests/test_gpu_reference_files.py."""
     g = np.load(path, allow_pickle=False)
     nonce = bytes(g["meta_nonce"].tolist())
     color = bool(g["color"])

@@ -1,5 +1,6 @@
-"""CPU tests of the oracle itself (no GPU).  The reference holds no golden
-vectors, so what can be pinned independently is pinned here: the DCT against
+"""CPU tests of the oracle itself (no GPU).  The oracle against the reference program
+and reference-written files is tests/test_reference_program.py; what can be pinned
+independently of both is pinned here: the DCT against
 its closed form, the SVD by reconstruction, the key / permutation / HMAC glue
 against hashlib / RFC 4231 known answers, and the committed (oracle-generated)
 fixtures as a drift check."""
