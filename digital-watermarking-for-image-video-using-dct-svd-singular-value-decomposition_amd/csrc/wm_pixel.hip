@@ -229,7 +229,8 @@ __global__ __launch_bounds__(256) void k_sum_u64(const unsigned long long* __res
 
 // ---- SSIM (single:44-57) ---------------------------------------------------------------
 // mean of  (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2))  with the 11 x 11, sigma 1.5 Gaussian moments.
-// s1 and s2 only enter as their SUM, so FOUR blurred fields suffice instead of the reference's five: x, y, x^2 + y^2, xy.
+// s1 and s2 only enter as their SUM, so FOUR blurred fields suffice instead of the reference's five: x, y, x^2 + y^2, xy
+// (of x - c and y - c, c one constant per wave: see the row loop).
 //
 // Form (72 -> 37 us per 4K plane over round 3): one wave per strip of 64 columns, one image COLUMN per
 // lane, the wave walks down SS_R output rows.  Per input row: the row's (x, y, x^2 + y^2, xy) of the wave's 74 columns go to
@@ -325,6 +326,14 @@ __global__ __launch_bounds__(64 * SS_WPB) __attribute__((amdgpu_waves_per_eu(WM_
   // with its SGPR tap, as much as a packed one that does two (tools/ubench_ssim_fma.hip, profiles/r03y_ubench_ssim_fma.log)
   typedef float f2 __attribute__((ext_vector_type(2)));
   f2 ringA[11], ringB[11];
+  // Both images are shifted by one wave-uniform constant c (the first pixel this wave loaded, rounded to an integer so
+  // that uint8 input shifts exactly) before the four fields are formed.  The variance terms do not change under a common
+  // shift; the means get c back below.  On flat bright content (white backgrounds) E[x^2 + y^2] - mu1^2 - mu2^2 was a
+  // difference of two numbers near 1.3e5, whose float32 rounding - and the float32 taps' sum, 1 only to 1e-7, which scales
+  // E[x^2] and mu^2 differently - is 1e-2 against C2 = 58.5: white against 254 came out 1.3e-4 low.
+  const float c_first = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(am[0])));
+  const float c = fabsf(c_first) < 1e30f ? rintf(c_first) : 0.0f;      // not for a NaN / Inf first pixel
+  const f2 c2 = {c, c};
   float acc = 0.0f;
 #ifdef WM_SSIM_STAMPS
   unsigned long long st_e = 0, st_d = 0, t_mid = 0;
@@ -366,9 +375,9 @@ __global__ __launch_bounds__(64 * SS_WPB) __attribute__((amdgpu_waves_per_eu(WM_
       SSIM_FETCH((s + PF) % 11, ir + PF);                  // rows past n_in: clamped, never used
       float4* rb = rowbuf[ir & 1];                         // 11 is odd: the parity of s alone flips with base
       {
-        const float a = am[s], b = bm[s], c = ah[s], d = bh[s];
+        const float a = am[s] - c, b = bm[s] - c, g = ah[s] - c, d = bh[s] - c;
         rb[lane] = make_float4(a, b, fmaf(a, a, b * b), a * b);
-        rb[SS_W + lane] = make_float4(c, d, fmaf(c, c, d * d), c * d);
+        rb[SS_W + lane] = make_float4(g, d, fmaf(g, g, d * d), g * d);
       }
 #if defined(WM_SSIM_SYNC)
       __syncthreads();
@@ -401,10 +410,11 @@ __global__ __launch_bounds__(64 * SS_WPB) __attribute__((amdgpu_waves_per_eu(WM_
           mA = __builtin_elementwise_fma(w2, ringA[r], mA);
           mB = __builtin_elementwise_fma(w2, ringB[r], mB);
         }
-        const float m1 = mA.x, m2 = mA.y, e = mB.x, q = mB.y;
-        const float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
-        const float num = (2.0f * m12 + C1) * (2.0f * (q - m12) + C2);
-        const float den = (m11 + m22 + C1) * ((e - m11 - m22) + C2) + 1e-12f;
+        const float e = mB.x, q = mB.y;
+        const f2 sq = mA * mA;                             // shifted means: the variance terms
+        const f2 M = mA + c2, SQ = M * M;                  // the means themselves: the luminance term
+        const float num = (2.0f * (M.x * M.y) + C1) * (2.0f * (q - mA.x * mA.y) + C2);
+        const float den = (SQ.x + SQ.y + C1) * ((e - sq.x - sq.y) + C2) + 1e-12f;
         const int oy = y0 + ir - 2 * SH;
         const float v = num * __builtin_amdgcn_rcpf(den);
         acc += (col_ok && oy < H) ? v : 0.0f;
