@@ -855,6 +855,16 @@ __global__ __launch_bounds__(256) void k_rf_gather_rows_t(const float* __restric
   }
 }
 
+// rows of a dense [n][ncols] matrix into chosen slots of a gathered factor:  dst[pos[k] * ld_slot + j * ld_elem] = src[k][j]
+// (ld_elem = 1: the slot is a row of Vt;  ld_slot = 1: the slot is a column of U)
+__global__ void k_rf_put_rows(const float* __restrict__ src, const int ncols, const int* __restrict__ pos,
+                              float* __restrict__ dst, const size_t ld_slot, const size_t ld_elem) {
+  const int k = blockIdx.y;
+  float* d = dst + (size_t)pos[k] * ld_slot;
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ncols; j += gridDim.x * blockDim.x)
+    d[(size_t)j * ld_elem] = src[(size_t)k * ncols + j];
+}
+
 // deterministic pseudo-random pattern in (-1, 1): the start vectors of the null-space completion
 // (rank-deficient planes); element (r, c) of the matrix with seed `seed`
 __global__ void k_rf_pattern(float* __restrict__ dst, const int cols, const unsigned seed) {
@@ -1538,6 +1548,67 @@ int ref_complete_plane(wm_ctx* ctx, const RefPlan& p, const RefWs& w, int z, con
   return WM_OK;
 }
 
+// Null-space completion of one factor of ONE rank-deficient plane z of the watermark-side SVD.  The rows of [B | Qt] whose B
+// part is below the Jacobi's numerical-null floor are rounding residue - they take no part in its convergence test, so
+// nothing makes them orthogonal - and b_i / |b_i| of such a row is not a singular vector.  Their Qt parts were measured
+// non-orthogonal too on planes whose DCT has exactly vanishing rows (an unscrambled logo of two bars: |U^T U - I| = 1.0 on
+// the null columns, the valid ones exact).  LAPACK returns an orthonormal completion there; here the slots of those rows
+// in BOTH gathered factors get one, side 0 of ref_complete_plane: deterministic start vectors, projected twice off the
+// valid rows, orthogonalised by the block Jacobi, normalised.
+//   side 0: the long-side factor (B part, vectors of length M);  side 1: the short-side factor (first L columns of the Qt part)
+//   valid [Lp]: 1 for rows that are singular directions;  n2 [Lp]: squared norms of that part of the rows;
+//   slots [n]: where the n completed vectors go;  dst + slot * ld_slot + j * ld_elem: element j of that slot's vector
+int ref_complete_factor(wm_ctx* ctx, const RefPlan& p0, const RefWs& w, int z, int side, const std::vector<unsigned char>& valid,
+                        const double* b2, const std::vector<int>& slots, float* dst, size_t ld_slot, size_t ld_elem) {
+  const int n = (int)slots.size();
+  if (n == 0) return WM_OK;
+  const float* Bz = w.aug + (size_t)z * p0.aug_ps + (side == 0 ? 0 : p0.M);
+  struct { int M, Lp, ld; } p = {side == 0 ? p0.M : p0.L, p0.Lp, p0.ld};       // vector length, rows, leading dimension
+  const RefPlan pv = make_plan(n, p.M);
+  RefWs wv;
+  // tmp1: Z [n][M] | C [n][Lp] | coefficients [Lp]
+  WM_TRY(plan_workspace(ctx, pv, wv, (size_t)n * (p.M + p.Lp) + p.Lp + 64, 16, 1));
+  float* Z = wv.tmp1; float* C = Z + (size_t)n * p.M; float* coef = C + (size_t)n * p.Lp;
+  std::vector<float> gv(p.Lp);
+  for (int i = 0; i < p.Lp; ++i) gv[i] = (valid[i] && b2[i] > 0.0) ? (float)(1.0 / b2[i]) : 0.0f;
+  hipLaunchKernelGGL(k_rf_pattern, dim3(8, n), dim3(256), 0, ctx->stream, Z, p.M, side == 0 ? 0x1234567u : 0x7654321u);
+  WM_HIP(hipMemcpyAsync(coef, gv.data(), (size_t)p.Lp * 4, hipMemcpyHostToDevice, ctx->stream));
+  // Two rounds of (project, orthonormalise).  The complement of the valid short-side vectors has exactly n dimensions, so the
+  // n projected start vectors are a SQUARE random matrix there, condition ~n..n^2: the Jacobi works on float32 Gram entries
+  // and leaves its small rows eps * cond^2 off (measured 3.3e-4 on a 56x40 plane of rank 3), and normalising a small row
+  // amplifies what the projection left of the valid vectors.  The second round starts from rows that are orthonormal to
+  // that error, condition 1, and ends at rounding level.
+  for (int round = 0; round < 2; ++round) {
+  for (int pass = 0; pass < 2; ++pass) {            // project twice: classical Gram-Schmidt loses digits once
+    WM_TRY(sgemm(ctx, false, true, n, p.Lp, p.M, 1.0f, Z, p.M, Bz, p.ld, 0.0f, C, p.Lp));                         // Z B^T
+    hipLaunchKernelGGL(k_rf_scale_cols_b, dim3(8, n, 1), dim3(256), 0, ctx->stream, C, (size_t)0, C, (size_t)0, p.Lp, coef, (size_t)0);
+    WM_TRY(sgemm(ctx, false, false, n, p.M, p.Lp, -1.0f, C, p.Lp, Bz, p.ld, 1.0f, Z, p.M));                       // Z -= C B
+  }
+  WM_HIP(hipStreamSynchronize(ctx->stream));        // gv is a local
+  hipLaunchKernelGGL((k_rf_load<float>), dim3(8, pv.Lp, 1), dim3(256), 0, ctx->stream, Z, (size_t)p.M, (size_t)0, 0,
+                     wv.aug, pv.aug_ps, pv.ld, pv.L, pv.Lp, pv.M);
+  int sweeps = 0;
+  WM_TRY(jacobi_rows(ctx, pv, wv, JR_ORTH, &sweeps));
+  if (sweeps < 0) return set_err(WM_ERR_NOCONV, "null-space completion did not converge");
+  std::vector<double> norms2, dummy;
+  WM_TRY(fetch_norms(ctx, pv, wv, false, norms2, dummy));
+  std::vector<int> ord(pv.Lp);
+  std::iota(ord.begin(), ord.end(), 0);
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return norms2[a] > norms2[b]; });
+  std::vector<float> sc(n);
+  for (int k = 0; k < n; ++k) sc[k] = norms2[ord[k]] > 0.0 ? (float)(1.0 / sqrt(norms2[ord[k]])) : 0.0f;
+  WM_HIP(hipMemcpyAsync(wv.order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  WM_HIP(hipMemcpyAsync(wv.scale, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_rf_gather_rows, dim3(8, n), dim3(256), 0, ctx->stream, wv.aug, pv.ld, p.M, wv.order, wv.scale, Z, p.M);
+  WM_HIP(hipStreamSynchronize(ctx->stream));        // ord / sc are locals; wv.order is free again
+  }
+  WM_HIP(hipMemcpyAsync(wv.order, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_rf_put_rows, dim3(8, n), dim3(256), 0, ctx->stream, Z, p.M, wv.order, dst, ld_slot, ld_elem);
+  WM_HIP(hipGetLastError());
+  WM_HIP(hipStreamSynchronize(ctx->stream));        // slots is the caller's
+  return WM_OK;
+}
+
 // embed of p.B planes on the device.  d_in / d_out: uint8 planes (same strides; may alias);
 // d_ywout: optional dense float [B][H][W]; sigma_w: HOST [B or 1][L]; sigma_c: HOST [B][L] out.
 // d_yw [B][L][M] and d_t [B][L][Lp] are workspace.
@@ -1931,6 +2002,8 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
   WM_HIP(hipStreamSynchronize(ctx->stream));
   std::vector<float> sq((size_t)B * lp64, 0.0f), sb((size_t)B * lp64, 0.0f), sig;
   std::vector<int> order, ord_all((size_t)B * lp64, 0);
+  struct NullRows { int z; std::vector<unsigned char> valid; std::vector<int> slots; };
+  std::vector<NullRows> todo;                           // rank-deficient planes: slots of the long-side factor to complete
   for (int z = 0; z < B; ++z) {
     const double* b2z = &b2[(size_t)z * p.Lp]; const double* q2z = &q2[(size_t)z * p.Lp]; const double* t2 = &t2all[(size_t)z * p.Lp];
     std::vector<double> q2s(q2z, q2z + p.Lp);           // q2 itself still normalises the columns of the short-side factor
@@ -1952,12 +2025,21 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
     sort_sigma(p, b2z, q2s.data(), order, sig);
     memcpy(S + (size_t)z * p.L, sig.data(), (size_t)p.L * 4);
     // short-side factor: columns q_i/|q_i|   (rows of Qt), long-side factor: rows b_i/|b_i|
+    // A row of B at or below the Jacobi's numerical-null floor (NULL_ROW_RATIO |A|_F; rotations preserve the Frobenius norm)
+    // is rounding residue of a rank-deficient plane, not a singular direction: its slot is completed below.
+    double f2 = 0.0;
+    for (int i = 0; i < p.Lp; ++i) f2 += b2z[i];
+    const double floor2 = NULL_ROW_RATIO * NULL_ROW_RATIO * f2;
+    NullRows nr; nr.z = z; nr.valid.assign(p.Lp, 0);
+    for (int i = 0; i < p.Lp; ++i) nr.valid[i] = b2z[i] > floor2 ? 1 : 0;
     for (int k = 0; k < p.L; ++k) {
       const int i = order[k];
       ord_all[(size_t)z * lp64 + k] = i;
       sq[(size_t)z * lp64 + k] = q2z[i] > 0 ? (float)(1.0 / sqrt(q2z[i])) : 0.0f;
       sb[(size_t)z * lp64 + k] = b2z[i] > 0 ? (float)(1.0 / sqrt(b2z[i])) : 0.0f;
+      if (!nr.valid[i]) nr.slots.push_back(k);
     }
+    if (!nr.slots.empty()) todo.push_back(std::move(nr));
   }
   WM_HIP(hipMemcpyAsync(d_ord, ord_all.data(), ord_all.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   WM_HIP(hipMemcpyAsync(d_sq, sq.data(), sq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1978,6 +2060,17 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
     hipLaunchKernelGGL(k_rf_gather_rows_b, dim3(8, p.L, B), dim3(256), 0, ctx->stream, w.aug + p.M, p.aug_ps, p.ld, p.L, d_ord, d_sq, lp, d_vt, fl, W);
   }
   WM_HIP(hipGetLastError());
+  for (const NullRows& nr : todo) {                     // full-rank planes: nothing to do, the factors are the gathered rows
+    float* fu = d_u + (size_t)nr.z * fl; float* fv = d_vt + (size_t)nr.z * fl;
+    const double* nb = &b2[(size_t)nr.z * p.Lp]; const double* nq = &q2[(size_t)nr.z * p.Lp];
+    if (!p.transpose) {
+      WM_TRY(ref_complete_factor(ctx, p, w, nr.z, 0, nr.valid, nb, nr.slots, fv, (size_t)W, 1));            // rows of Vt
+      WM_TRY(ref_complete_factor(ctx, p, w, nr.z, 1, nr.valid, nq, nr.slots, fu, 1, (size_t)p.L));          // columns of U
+    } else {
+      WM_TRY(ref_complete_factor(ctx, p, w, nr.z, 0, nr.valid, nb, nr.slots, fu, 1, (size_t)p.L));          // columns of U
+      WM_TRY(ref_complete_factor(ctx, p, w, nr.z, 1, nr.valid, nq, nr.slots, fv, (size_t)W, 1));            // rows of Vt
+    }
+  }
   for (int z = 0; z < B; ++z) {
     WM_HIP(hipMemcpyAsync(U + (size_t)z * H * p.L, d_u + (size_t)z * fl, (size_t)H * p.L * 4, hipMemcpyDeviceToHost, ctx->stream));
     WM_HIP(hipMemcpyAsync(Vt + (size_t)z * p.L * W, d_vt + (size_t)z * fl, (size_t)p.L * W * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -217,7 +217,10 @@ int wm_ref_embed_planes_u8_when(wm_ctx* ctx, const uint8_t* host, const float* s
 
 /* Replaces  Wm = dct2(wy_s); Uw, Sw, Vwt = np.linalg.svd(Wm, full_matrices=False)
  * (single:173, 131-134) when apply_dct != 0 (plain thin SVD of the plane otherwise).
- *   U [H][L], S [L], Vt [L][W]. */
+ *   U [H][L], S [L], Vt [L][W].
+ * A rank-deficient plane (a blank, sparse or constant logo plane) returns U and Vt with L orthonormal columns / rows all the
+ * same: the singular vectors of its null singular values (S at rounding level, 0 for a zero plane) are a deterministic
+ * orthonormal completion, as arbitrary as LAPACK's. */
 int wm_ref_svd_f32(wm_ctx* ctx, const float* plane, float* U, float* S, float* Vt, int H, int W,
                    int row_stride, int apply_dct);
 
