@@ -64,6 +64,7 @@ struct wm_ctx {
   double ref_last_flops = 0.0;    // matrix-core flops its Gram / rotation products issued (nominal: skipped pairs counted)
   int ref_last_hier = 0;          // 1: it ran the two-level scheme
   float ref_skip_thr = 0.0f;      // residual cosine the last full-frame Jacobi may have left between two rows
+  bool hier_attr_set = false;     // the two-level rotation kernels' dynamic-LDS limits are raised on this context's device
   static constexpr int MAX_AUX = 7;   // extra queues of the batched full-frame Jacobi (created on first use)
   hipStream_t aux_stream[MAX_AUX] = {};
   hipEvent_t ev_fork[MAX_AUX] = {}, ev_join[MAX_AUX] = {};
@@ -94,6 +95,23 @@ inline int use_ctx(const wm_ctx* ctx) {
 }
 // grow-only device buffer (synchronises the stream before freeing the old one)
 int grow(wm_ctx* ctx, void** buf, size_t* have, size_t bytes, const char* what);
+// arrays carved out of such a buffer, each on a 256-byte line.  base == nullptr is the sizing pass: the same takes return
+// nullptr and pad256(off) is what the buffer must hold
+struct Carve {
+  char* base; size_t off;
+  template <typename T> T* take(size_t n) {
+    off = (off + 255) & ~(size_t)255;
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += n * sizeof(T);
+    return p;
+  }
+};
+inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+// elements from the first sample of the first plane to the last sample of the last one
+inline size_t plane_span(int n_planes, int H, int row_stride, size_t plane_stride, int W) {
+  if (n_planes == 0 || H == 0) return 0;
+  return (size_t)(n_planes - 1) * plane_stride + (size_t)(H - 1) * row_stride + (size_t)W;
+}
 // wm_ref.hip: releases the host part of a two-level tournament table (wm_ctx::hier_host)
 void hier_host_free(void* tab);
 // wm_route.hip: routed unscramble + normalise; mm_ext != NULL: n_part_ext {min, max} pairs per plane already on the device

@@ -939,6 +939,38 @@ struct RefPlan {
   bool transpose;        // A = plane^T (portrait planes: the short side must index rows)
 };
 
+// Every WM_RF_* environment knob, with its default and its range.  The values are read where they were always read - at
+// the start of the call that uses them: tests switch WM_RF_HIER*, WM_RF_QUEUES, WM_RF_HGRAM3 and WM_RF_FINAL_F16 between
+// calls on one context - except the three marked "process", which keep what the first call saw.
+struct RefKnobs {
+  int apply_tiles, full_sweeps, queues, hier, hier_f16, hier_sb, hgram3, hdbg;
+  float conv_sigma;
+  bool drift_cal, debug_drift, final_f16;
+};
+
+RefKnobs ref_knobs() {
+  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  auto flag = [](const char* name) { const char* e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; };     // -1: unset
+  static const int full_sweeps = num("WM_RF_FULL_SWEEPS", FULL_INNER_SWEEPS);                        // process
+  static const float conv_sigma = getenv("WM_RF_CONV_SIGMA") ? (float)atof(getenv("WM_RF_CONV_SIGMA")) : CONV_COS_SIGMA;   // process
+  static const bool drift_cal = flag("WM_RF_DRIFT_CAL") != 0;                                        // process; 0: rows below the switch stay uncalibrated
+  RefKnobs k;
+  k.full_sweeps = full_sweeps; k.conv_sigma = conv_sigma; k.drift_cal = drift_cal;
+  k.apply_tiles = num("WM_RF_APPLY_TILES", 1);                  // 1..8: 32-column blocks per wave of k_rf_apply (tuning)
+  if (k.apply_tiles < 1 || k.apply_tiles > 8) k.apply_tiles = 1;
+  k.debug_drift = getenv("WM_RF_DEBUG_DRIFT") != nullptr;       // set: print each plane's drift factors
+  // plane groups (HIP queues) 1..1 + MAX_AUX, WM_RF_ONE_QUEUE=1 is the old spelling of 1; 0: by batch size
+  k.queues = flag("WM_RF_ONE_QUEUE") == 1 ? 1 : std::min(std::max(num("WM_RF_QUEUES", 0), 0), 1 + wm_ctx::MAX_AUX);
+  k.hier = flag("WM_RF_HIER");                                  // 0 / 1: the flat tournament / the two-level scheme; unset: by batch size
+  k.hier_f16 = num("WM_RF_HIER_F16", HIER_F16_DEFAULT);         // bit 0: Gram tiles, bit 1: rotation products from split-f16 operands
+  k.hier_sb = num("WM_RF_HIER_SB", 6);                          // 2, 4 or 6 blocks per super-block
+  if (k.hier_sb != 2 && k.hier_sb != 4 && k.hier_sb != 6) k.hier_sb = 6;
+  k.hgram3 = flag("WM_RF_HGRAM3");                              // 0 / 1: never / always k_hgram_h3 where it applies; unset: where it fills the chip
+  k.hdbg = num("WM_RF_HDBG", 0);                                // debug bits handed to k_hgram and (from bit 4) k_happly
+  k.final_f16 = flag("WM_RF_FINAL_F16") != 0;                   // 0 keeps the finalisation's large products in f32
+  return k;
+}
+
 RefPlan make_plan(int H, int W, int B = 1) {
   RefPlan p;
   p.H = H; p.W = W; p.B = B;
@@ -954,8 +986,7 @@ RefPlan make_plan(int H, int W, int B = 1) {
   // (round 2 gave a workgroup two 32-column blocks per wave from 96 (pair, plane) items per step on; with the batch split
   // into two or three plane groups a launch rarely gets there, and one block per wave measures the same or better at every
   // batch size: 8 planes 106.8 / 106.4, 16 planes 139.3 / 137.2, 24 planes 140.4 / 139.4 frames/s - profiles/r03z_fullframe_queues.log)
-  p.apply_tiles = 1;
-  if (const char* e = getenv("WM_RF_APPLY_TILES")) { const int v = atoi(e); if (v >= 1 && v <= 8) p.apply_tiles = v; }   // tuning knob
+  p.apply_tiles = ref_knobs().apply_tiles;
   p.nch = (p.M + GRAM_CC - 1) / GRAM_CC;    // Gram stays in many small units: a float4 / double-buffered / 512-column variant measured slower (36-40 vs 31 us)
   return p;
 }
@@ -963,9 +994,8 @@ RefPlan make_plan(int H, int W, int B = 1) {
 struct RefWs {           // carved out of a grow-only context buffer; every per-plane array is [B][...]
   float* aug; float* partials; float* R; const int2* pairs; unsigned* maxcos; float* floor2; int* skip; double* b2; double* q2;
   float* dvec; int* order; float* scale; float* tmp1; float* tmp2;
+  float* a0; float* t;   // plan_decompose_ws: tmp2 split into A0 (the embed's Yw) [B][L][M] | T = A0 B^T [B][L][Lp]
 };
-
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The round-robin tournament of a plan depends on its block count only: built once per context and
 // block count (a handful of sizes per process), kept on the device, handed out without a copy or a sync.
@@ -1009,22 +1039,31 @@ int get_pairs(wm_ctx* ctx, const RefPlan& p, const int2** out) {
 // which = 0: the context's main full-frame workspace; 1: the second one (null-space completion, so that the
 // first call's arrays stay where they are)
 int plan_workspace(wm_ctx* ctx, const RefPlan& p, RefWs& w, size_t extra_f32_a, size_t extra_f32_b, int which = 0) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += a256(bytes); return o; };
   const size_t B = (size_t)p.B;
-  const size_t o_aug = take(B * p.aug_ps * 4), o_par = take(B * p.npairs * p.nch * GRAM_PART * 4),
-               o_R = take(B * p.npairs * RP * RP * 4),
-               o_mc = take(B * 4 + 256), o_fl = take(B * 4 + 256), o_skip = take(B * p.npairs * 4 + (size_t)(2 + wm_ctx::MAX_AUX) * 256), o_b2 = take(B * p.Lp * 8), o_q2 = take(B * p.Lp * 8),
-               o_d = take(2 * B * p.Lp * 4), o_ord = take((size_t)p.Lp * 4), o_sc = take((size_t)p.Lp * 4),
-               o_t1 = take(extra_f32_a * 4), o_t2 = take(extra_f32_b * 4);
-  if (which == 0) WM_TRY(grow(ctx, &ctx->ref_ws, &ctx->ref_ws_bytes, off, "full-frame workspace"));
-  else WM_TRY(grow(ctx, &ctx->ref_ws2, &ctx->ref_ws2_bytes, off, "full-frame completion workspace"));
-  char* b = (char*)(which == 0 ? ctx->ref_ws : ctx->ref_ws2);
-  w.aug = (float*)(b + o_aug); w.partials = (float*)(b + o_par); w.R = (float*)(b + o_R);
-  w.maxcos = (unsigned*)(b + o_mc); w.floor2 = (float*)(b + o_fl); w.skip = (int*)(b + o_skip); w.b2 = (double*)(b + o_b2);
-  w.q2 = (double*)(b + o_q2); w.dvec = (float*)(b + o_d); w.order = (int*)(b + o_ord);
-  w.scale = (float*)(b + o_sc); w.tmp1 = (float*)(b + o_t1); w.tmp2 = (float*)(b + o_t2);
+  auto carve = [&](Carve cv) {
+    w.aug = cv.take<float>(B * p.aug_ps); w.partials = cv.take<float>(B * p.npairs * p.nch * GRAM_PART);
+    w.R = cv.take<float>(B * p.npairs * RP * RP);
+    w.maxcos = cv.take<unsigned>(B + 64); w.floor2 = cv.take<float>(B + 64);
+    w.skip = cv.take<int>(B * p.npairs + (size_t)(2 + wm_ctx::MAX_AUX) * 64); w.b2 = cv.take<double>(B * p.Lp); w.q2 = cv.take<double>(B * p.Lp);
+    w.dvec = cv.take<float>(2 * B * p.Lp); w.order = cv.take<int>((size_t)p.Lp); w.scale = cv.take<float>((size_t)p.Lp);
+    w.tmp1 = cv.take<float>(extra_f32_a); w.tmp2 = cv.take<float>(extra_f32_b);
+    return pad256(cv.off);
+  };
+  const size_t bytes = carve(Carve{nullptr, 0});
+  if (which == 0) WM_TRY(grow(ctx, &ctx->ref_ws, &ctx->ref_ws_bytes, bytes, "full-frame workspace"));
+  else WM_TRY(grow(ctx, &ctx->ref_ws2, &ctx->ref_ws2_bytes, bytes, "full-frame completion workspace"));
+  carve(Carve{(char*)(which == 0 ? ctx->ref_ws : ctx->ref_ws2), 0});
+  w.a0 = w.t = nullptr;
   WM_TRY(get_pairs(ctx, p, &w.pairs));
+  return WM_OK;
+}
+
+// the main workspace of a call that decomposes uint8 planes: tmp2 holds A0 [B][L][M] | T [B][L][Lp] (and min_f32_b floats
+// at least, for what the call keeps there afterwards), handed out as w.a0 and w.t
+int plan_decompose_ws(wm_ctx* ctx, const RefPlan& p, RefWs& w, size_t extra_f32_a, size_t min_f32_b = 0) {
+  const size_t n_a0 = (size_t)p.B * p.L * p.M;
+  WM_TRY(plan_workspace(ctx, p, w, extra_f32_a, std::max(n_a0 + (size_t)p.B * p.L * p.Lp, min_f32_b)));
+  w.a0 = w.tmp2; w.t = w.tmp2 + n_a0;
   return WM_OK;
 }
 
@@ -1077,69 +1116,45 @@ int get_dct_pair(wm_ctx* ctx, int H, int W, float** dH, float** dW) {
 
 #include "wm_ref_hier.inc"
 
-// block one-sided Jacobi on the B Aug matrices (already loaded); every launch covers
-// a group of planes (grid.z), sweeps continue until every plane's Gram matrices are
-// diagonal to CONV_COS.  sweeps_out: sweeps used (negative: bound hit).
-//
-// A step is gram -> inner -> apply, and k_rf_inner is one latency-bound workgroup per
-// block pair (~35 us with most of the chip idle).  With two or more planes the batch is
-// split into two groups on two HIP streams, the second started one gram later, so one
-// group's inner solve runs under the other group's gram/apply tiles.
-// what the rotated rows are needed for: their norms only (extract / detect), their directions too (embed:
-// u_i, v_i enter the stego), or the accumulated left factor as well (watermark-side SVD, [A | I])
-// JR_ORTH: orthogonalise the rows only (null-space completion): no left factor, the tight stopping cosine
-enum JacobiUse { JR_SIGMA, JR_EMBED, JR_SVD, JR_ORTH };
+// (NULL_ROW_RATIO * |A|_F)^2 of one plane from the squared norms of its Lp rows: the numerical-null floor.  Rotations
+// preserve the Frobenius norm, so the rotated rows give the same floor as the loaded input.
+double null_floor2(const double* row2, const int Lp) {
+  double f2 = 0.0;
+  for (int i = 0; i < Lp; ++i) f2 += row2[i];
+  return NULL_ROW_RATIO * NULL_ROW_RATIO * f2;
+}
 
-int jacobi_rows(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiUse use, int* sweeps_out) {
-  const bool with_q = use == JR_SVD, sigma_only = use == JR_SIGMA;
-  const int ncols = with_q ? p.M + p.Lp : p.M;
-  int sweep = 0;
-  bool done = false;
-  std::vector<unsigned> bits(p.B);
-  static const int full_sweeps = getenv("WM_RF_FULL_SWEEPS") ? atoi(getenv("WM_RF_FULL_SWEEPS")) : FULL_INNER_SWEEPS;
-  // number of plane groups (HIP queues): WM_RF_QUEUES=n (1..4), WM_RF_ONE_QUEUE=1 is the old spelling of n = 1
-  // default: two groups, three from 12 planes on (16 planes: 131 -> 137 frames/s on two boxes, 24: 138 -> 139; 8 planes: 107 / 106)
-  const int env_queues = [] {          // (read on every call)
-    if (getenv("WM_RF_ONE_QUEUE") && atoi(getenv("WM_RF_ONE_QUEUE"))) return 1;
-    const int n = getenv("WM_RF_QUEUES") ? atoi(getenv("WM_RF_QUEUES")) : 0;
-    return n < 1 ? 0 : (n > 1 + wm_ctx::MAX_AUX ? 1 + wm_ctx::MAX_AUX : n);
-  }();
-  const int max_queues = env_queues ? env_queues : std::min(1 + wm_ctx::MAX_AUX, p.B >= 12 ? DEFAULT_QUEUES + 1 : DEFAULT_QUEUES);
-  static const float conv_sigma = getenv("WM_RF_CONV_SIGMA") ? (float)atof(getenv("WM_RF_CONV_SIGMA")) : CONV_COS_SIGMA;
-  // The accumulated factor of JR_SVD needs every rotation; the other two uses stop earlier: a residual
-  // cosine c moves the stego by c * s_max / s_i of a (sub-LSB) term and the singular values by the
-  // bounds documented at fetch_norms_t, the same for embed and extract so that it cancels in S_cw - Sc.
-  const float conv_cos = (with_q || use == JR_ORTH) ? CONV_COS : conv_sigma;
-  const float skip_thr = SKIP_FRACTION * conv_cos;
-  (void)sigma_only;
-  ctx->ref_skip_thr = skip_thr;
-  const int NQ = std::min(max_queues, p.B);               // group g owns planes [zb[g], zb[g + 1])
-  int zb[2 + wm_ctx::MAX_AUX];
-  for (int g = 0; g <= NQ; ++g) zb[g] = (int)((long long)g * p.B / NQ);
-  for (int g = 1; g < NQ; ++g)
-    if (!ctx->aux_stream[g - 1]) {
-      WM_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[g - 1], hipStreamNonBlocking));
-      WM_HIP(hipEventCreateWithFlags(&ctx->ev_fork[g - 1], hipEventDisableTiming));
-      WM_HIP(hipEventCreateWithFlags(&ctx->ev_join[g - 1], hipEventDisableTiming));
-    }
-  // numerical-null floor per plane: (NULL_ROW_RATIO * |A|_F)^2 from the row norms of the loaded input
-  {
-    hipLaunchKernelGGL(k_rf_rownorms, dim3(p.Lp, p.B), dim3(256), 0, ctx->stream, w.aug, p.aug_ps, p.ld, p.M, 0, w.b2, w.q2);
-    std::vector<double> r2((size_t)p.B * p.Lp);
-    WM_HIP(hipMemcpyAsync(r2.data(), w.b2, r2.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    WM_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<float> fl(p.B);
-    for (int z = 0; z < p.B; ++z) {
-      double f2 = 0.0;
-      for (int i = 0; i < p.Lp; ++i) f2 += r2[(size_t)z * p.Lp + i];
-      fl[z] = (float)(NULL_ROW_RATIO * NULL_ROW_RATIO * f2);
-    }
-    WM_HIP(hipMemcpyAsync(w.floor2, fl.data(), fl.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipStreamSynchronize(ctx->stream));       // fl is a local
-  }
+// numerical-null floor per plane into w.floor2, from the row norms of the loaded input
+int load_null_floors(wm_ctx* ctx, const RefPlan& p, const RefWs& w) {
+  hipLaunchKernelGGL(k_rf_rownorms, dim3(p.Lp, p.B), dim3(256), 0, ctx->stream, w.aug, p.aug_ps, p.ld, p.M, 0, w.b2, w.q2);
+  std::vector<double> r2((size_t)p.B * p.Lp);
+  WM_HIP(hipMemcpyAsync(r2.data(), w.b2, r2.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WM_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<float> fl(p.B);
+  for (int z = 0; z < p.B; ++z) fl[z] = (float)null_floor2(&r2[(size_t)z * p.Lp], p.Lp);
+  WM_HIP(hipMemcpyAsync(w.floor2, fl.data(), fl.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  WM_HIP(hipStreamSynchronize(ctx->stream));       // fl is a local
+  return WM_OK;
+}
+
+struct JacobiRun {                       // what one jacobi_rows call fixes for all its sweeps
+  RefKnobs k;
+  int ncols;                             // columns the rotations are applied to: A, and the accumulated factor of JR_SVD
+  float skip_thr;
+  int NQ, zb[2 + wm_ctx::MAX_AUX];       // plane groups: group g owns planes [zb[g], zb[g + 1]) and runs on queue g
+  bool gram_f16, apply_f16;              // two-level scheme: which of its products take split-f16 operands
+  const HierTab* ht; HierWs hw;          // ... its tables and workspace
+  hipStream_t q(const wm_ctx* ctx, int g) const { return g == 0 ? ctx->stream : ctx->aux_stream[g - 1]; }
+};
+
+// one sweep of the flat tournament.  A step is gram -> inner -> apply, and k_rf_inner is one latency-bound workgroup per
+// block pair (~35 us with most of the chip idle): group g starts one gram after group g - 1, so that the groups' inner
+// solves fall under each other's gram / apply tiles instead of all at the same time
+int flat_sweep(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiRun& r, int sweep) {
   const size_t par_ps = (size_t)p.npairs * p.nch * GRAM_PART, r_ps = (size_t)p.npairs * RP * RP;
-  auto step = [&](hipStream_t st, int g, int s, int part) {
-    const int z0 = zb[g], nz = zb[g + 1] - zb[g];
+  auto step = [&](int g, int s, int part) {       // part: 1 = gram, 2 = inner + apply
+    const hipStream_t st = r.q(ctx, g);
+    const int z0 = r.zb[g], nz = r.zb[g + 1] - r.zb[g];
     const int2* pr = w.pairs + (size_t)s * p.npairs;
     float* aug = w.aug + (size_t)z0 * p.aug_ps;
     float* par = w.partials + (size_t)z0 * par_ps;
@@ -1148,118 +1163,147 @@ int jacobi_rows(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiUse u
       hipLaunchKernelGGL(k_rf_gram, dim3(p.npairs, p.nch, nz), dim3(256), 0, st, aug, p.aug_ps, p.ld, p.M, pr, par);
     if (part & 2) {
       hipLaunchKernelGGL(k_rf_inner, dim3(p.npairs, 1, nz), dim3(INNER_NT), 0, st, par, p.nch, R, w.maxcos + z0,
-                         w.floor2 + z0, (s == 0 || sweep < full_sweeps) ? 0 : 1, hier_flag_base(w.skip, (size_t)p.npairs, z0, g),
-                         skip_thr, (const int*)nullptr, (float*)nullptr, (int*)nullptr, 0, (float*)nullptr, (int*)nullptr, 0);
-      const int n_blk = (ncols + 31) / 32, per_wg = 4 * p.apply_tiles;     // 32-column blocks, 4 waves per workgroup
+                         w.floor2 + z0, (s == 0 || sweep < r.k.full_sweeps) ? 0 : 1, hier_flag_base(w.skip, (size_t)p.npairs, z0, g),
+                         r.skip_thr, (const int*)nullptr, (float*)nullptr, (int*)nullptr, 0, (float*)nullptr, (int*)nullptr, 0);
+      const int n_blk = (r.ncols + 31) / 32, per_wg = 4 * p.apply_tiles;     // 32-column blocks, 4 waves per workgroup
       hipLaunchKernelGGL(k_rf_apply, dim3(p.npairs, (n_blk + per_wg - 1) / per_wg, nz), dim3(256), 0, st,
-                         aug, p.aug_ps, p.ld, ncols, p.apply_tiles, pr, R, hier_flag_base(w.skip, (size_t)p.npairs, z0, g));
+                         aug, p.aug_ps, p.ld, r.ncols, p.apply_tiles, pr, R, hier_flag_base(w.skip, (size_t)p.npairs, z0, g));
     }
   };
-  // Two-level scheme (wm_ref_hier.inc): the same rotations with the rows streamed 3 times per SUPER-step.
-  // WM_RF_HIER=0 / 1 forces the flat tournament / the two-level scheme (read per call, so that a test can hold the two against each other);
-  // WM_RF_HIER_SB = blocks per super-block (2, 4 or 6).
-  // Default (measured on 1080p planes, profiles/r04_hier_crossover.log): with the split-f16 kernels - uint8 planes, i.e. every
+  for (int g = 0; g < r.NQ; ++g) {
+    if (g > 0) WM_HIP(hipStreamWaitEvent(r.q(ctx, g), ctx->ev_fork[g - 1], 0));
+    step(g, 0, 1);
+    if (g + 1 < r.NQ) WM_HIP(hipEventRecord(ctx->ev_fork[g], r.q(ctx, g)));
+  }
+  for (int g = 0; g < r.NQ; ++g) step(g, 0, 2);
+  for (int s = 1; s < p.nsteps; ++s)
+    for (int g = 0; g < r.NQ; ++g) step(g, s, 3);
+  return WM_OK;
+}
+
+// one sweep of the two-level scheme (wm_ref_hier.inc): the same rotations with the rows streamed 3 times per SUPER-step
+int hier_sweep(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiRun& r) {
+  const HierTab* ht = r.ht;
+  const HierWs& hw = r.hw;
+  for (int g = 1; g < r.NQ; ++g) {               // the other queues start behind the sweep's memset
+    if (g == 1) WM_HIP(hipEventRecord(ctx->ev_fork[0], ctx->stream));
+    WM_HIP(hipStreamWaitEvent(r.q(ctx, g), ctx->ev_fork[0], 0));
+  }
+  for (int s1 = 0; s1 < ht->nsteps1; ++s1)
+    for (int g = 0; g < r.NQ; ++g) {               // super-step s1 of plane group g
+      const hipStream_t st = r.q(ctx, g);
+      const int z0 = r.zb[g], nz = r.zb[g + 1] - r.zb[g], nsp = ht->nsp;
+      const HSuper* sup = ht->d_super + (size_t)s1 * nsp;
+      float* aug = w.aug + (size_t)z0 * p.aug_ps;
+      float* Gs = hw.Gs + (size_t)z0 * nsp * HN * HN;
+      float* R = hw.R + (size_t)z0 * nsp * HU * RP * RP;
+      float* par = hw.partials + (size_t)z0 * nsp * HG_TILES * hw.KS * HG_T * HG_T;
+      int* skip = hier_flag_base(hw.skip, (size_t)nsp * HU, z0, g);
+      int* anyrot = hier_flag_base(hw.anyrot, (size_t)nsp, z0, g);
+      // per-stage rotations (packed) and skip flags of this group's planes: [stage][plane][super-pair * HU + unit]
+      float* Rpk = hw.Rpk + (size_t)z0 * HT_MAX * nsp * HU * RP * RP;
+      int* skipT = hier_flag_base(hw.skipT, (size_t)HT_MAX * nsp * HU, z0, g);
+      const size_t rpk_stage = (size_t)nz * nsp * HU * RP * RP, skip_stage = (size_t)nz * nsp * HU;
+      const int n32 = ht->nmax * RB, npmax = (n32 + HG_T - 1) / HG_T;
+      const int nchunk = (p.M + HG_KC - 1) / HG_KC;
+      // (one workgroup per (super-pair, plane, split) instead of three: only where that still fills the chip - from 11 planes per launch on;
+      //  16 planes on three queues: 209 against 213 frames/s with it, 64 planes: 308 against 297)
+      const bool h3 = r.k.hgram3 >= 0 ? r.k.hgram3 != 0 : nsp * hw.KS * nz >= 256;
+      const bool use_h3 = r.gram_f16 && npmax == 3 && h3;     // (its column splits weigh more: every split writes the whole upper triangle - 2.0 against 0.25: +2 % at 64 and 128 planes)
+      const int KS = hier_ks(nsp, nz, use_h3 ? 1 : npmax, nchunk, hw.KS, use_h3 ? 2.0 : 0.25), cps = (nchunk + KS - 1) / KS;
+      const int ngrp = nsp * KS * nz;               // (super-pair, split, plane) groups of npmax workgroups, dealt over the XCDs
+      // Gram tiles on the f16 matrix pipe with split operands (k_hgram_h; WM_RF_HIER_F16=0: the f32 form)
+      if (use_h3)                                     // three panels: the rows fetched once per chunk (k_hgram_h3)
+        hipLaunchKernelGGL(k_hgram_h3, dim3(((ngrp + 7) / 8) * 8), dim3(H3_NT), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
+                           par, KS, cps, nz);
+      else if (r.gram_f16)
+        hipLaunchKernelGGL(k_hgram_h, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
+                           par, KS, cps, npmax, nz);
+      else
+        hipLaunchKernelGGL(k_hgram, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
+                           par, KS, cps, npmax, nz, r.k.hdbg);
+      hipLaunchKernelGGL(k_hreduce, dim3(HSB * (HSB + 1) / 2, nsp, nz), dim3(256), 0, st, par, sup, nsp, KS, Gs, anyrot);
+      constexpr int NG = HU * (HU - 1) / 2;
+      const int T = ht->T[s1];
+      const int* un0 = ht->d_units + (size_t)ht->stage_off[s1] * nsp * HU;
+      for (int t = 0; t < T; ++t) {
+        const int* un = un0 + (size_t)t * nsp * HU;
+        hipLaunchKernelGGL(k_rf_inner, dim3(nsp * HU, 1, nz), dim3(INNER_NT), 0, st, (const float*)nullptr, 0, R, w.maxcos + z0,
+                           w.floor2 + z0, (s1 == 0 && t == 0) ? 0 : 1, skip, r.skip_thr, un, Gs, anyrot, nsp, Rpk + t * rpk_stage,
+                           skipT + t * skip_stage, r.apply_f16 ? 1 : 0);
+        if (t + 1 < T)                               // nothing reads G_s after the last stage
+          hipLaunchKernelGGL(k_hupdate, dim3(NG, nsp, nz), dim3(256), 0, st, un, sup, nsp, R, skip, Gs);
+      }
+      const int ntask = nsp * nz * ((r.ncols + 63) / 64);
+      if (r.apply_f16)
+        hipLaunchKernelGGL((k_happly_h<64>), dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)2 * 64 * HA_CP * 2, st, aug, p.aug_ps, p.ld,
+                           r.ncols, sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, r.k.hdbg >> 4);
+      else
+        hipLaunchKernelGGL(k_happly, dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)n32 * 65 * 4, st, aug, p.aug_ps, p.ld, r.ncols,
+                           sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, r.k.hdbg >> 4);
+    }
+  return WM_OK;
+}
+
+// block one-sided Jacobi on the B Aug matrices (already loaded); every launch covers
+// a group of planes (grid.z), sweeps continue until every plane's Gram matrices are
+// diagonal to CONV_COS.  sweeps_out: sweeps used (negative: bound hit).
+// what the rotated rows are needed for: their norms only (extract / detect), their directions too (embed:
+// u_i, v_i enter the stego), or the accumulated left factor as well (watermark-side SVD, [A | I])
+// JR_ORTH: orthogonalise the rows only (null-space completion): no left factor, the tight stopping cosine
+enum JacobiUse { JR_SIGMA, JR_EMBED, JR_SVD, JR_ORTH };
+
+int jacobi_rows(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiUse use, int* sweeps_out) {
+  const bool with_q = use == JR_SVD;
+  JacobiRun r{};
+  r.k = ref_knobs();
+  r.ncols = with_q ? p.M + p.Lp : p.M;
+  // plane groups (HIP queues), by default two, three from 12 planes on (16 planes: 131 -> 137 frames/s on two boxes, 24: 138 -> 139; 8 planes: 107 / 106)
+  const int max_queues = r.k.queues ? r.k.queues : std::min(1 + wm_ctx::MAX_AUX, p.B >= 12 ? DEFAULT_QUEUES + 1 : DEFAULT_QUEUES);
+  // The accumulated factor of JR_SVD needs every rotation; the other two uses stop earlier: a residual
+  // cosine c moves the stego by c * s_max / s_i of a (sub-LSB) term and the singular values by the
+  // bounds documented at fetch_norms_t, the same for embed and extract so that it cancels in S_cw - Sc.
+  const float conv_cos = (with_q || use == JR_ORTH) ? CONV_COS : r.k.conv_sigma;
+  r.skip_thr = SKIP_FRACTION * conv_cos;
+  ctx->ref_skip_thr = r.skip_thr;
+  r.NQ = std::min(max_queues, p.B);
+  for (int g = 0; g <= r.NQ; ++g) r.zb[g] = (int)((long long)g * p.B / r.NQ);
+  for (int g = 1; g < r.NQ; ++g)
+    if (!ctx->aux_stream[g - 1]) {
+      WM_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[g - 1], hipStreamNonBlocking));
+      WM_HIP(hipEventCreateWithFlags(&ctx->ev_fork[g - 1], hipEventDisableTiming));
+      WM_HIP(hipEventCreateWithFlags(&ctx->ev_join[g - 1], hipEventDisableTiming));
+    }
+  WM_TRY(load_null_floors(ctx, p, w));
+  // Flat or two-level by default (measured on 1080p planes, profiles/r04_hier_crossover.log): with the split-f16 kernels - uint8 planes, i.e. every
   // embed / sigma / extract / detect call - the two-level scheme wins from 4 planes per call on (2: 44 / 44, 4: 72 / 79, 8: 104 / 128,
   // 16: 138 / 180, 64: 140 / 242 frames/s flat / two-level) and is used from HIER_MIN_PLANES_F16 = 3; with the f32 kernels (float
   // inputs: the watermark-side SVD, the completion) only from HIER_MIN_PLANES = 20 (2 planes: 20.9 / 26.5 ms - a small batch is
   // latency-bound and the flat step's chain gram - inner - apply is the shorter one).
-  const int f16_env = getenv("WM_RF_HIER_F16") ? atoi(getenv("WM_RF_HIER_F16")) : HIER_F16_DEFAULT;     // bit 0: Gram, bit 1: rotation products
-  const bool f16_ok = use == JR_SIGMA || use == JR_EMBED;     // rows of uint8 planes: |entries| <= 255 sqrt(L) < 65 504 under orthogonal rotations
-  const bool gram_f16 = (f16_env & 1) && f16_ok, apply_f16 = (f16_env & 2) && f16_ok;
-  const bool hier = getenv("WM_RF_HIER") ? atoi(getenv("WM_RF_HIER")) != 0
-                                         : p.B >= ((gram_f16 && apply_f16) ? HIER_MIN_PLANES_F16 : HIER_MIN_PLANES);
-  const HierTab* ht = nullptr;
-  HierWs hw{};
-  const int hdbg = getenv("WM_RF_HDBG") ? atoi(getenv("WM_RF_HDBG")) : 0;
-  // Gram tiles on the f16 matrix pipe with split operands (k_hgram_h; WM_RF_HIER_F16=0: the f32 form).  Row entries are bounded
-  // by 255 sqrt(L): beyond L = 65 536 (never a plane) f16 would overflow, and float inputs (the watermark-side SVD of a DCT
-  // plane, the completion's random vectors) have no such bound - those uses keep the f32 kernel.
+  // Row entries of uint8 planes are bounded by 255 sqrt(L) < 65 504 under orthogonal rotations: beyond L = 65 536 (never a plane)
+  // f16 would overflow, and float inputs (the watermark-side SVD of a DCT plane, the completion's random vectors) have no such
+  // bound - those uses keep the f32 kernels.
+  const bool f16_ok = use == JR_SIGMA || use == JR_EMBED;
+  r.gram_f16 = (r.k.hier_f16 & 1) && f16_ok; r.apply_f16 = (r.k.hier_f16 & 2) && f16_ok;
+  const bool hier = r.k.hier >= 0 ? r.k.hier != 0 : p.B >= ((r.gram_f16 && r.apply_f16) ? HIER_MIN_PLANES_F16 : HIER_MIN_PLANES);
   if (hier) {
-    int sb = 6;
-    if (const char* e = getenv("WM_RF_HIER_SB")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 6) sb = v; }
-    WM_TRY(get_hier(ctx, p.nbk, sb, &ht));
-    WM_TRY(plan_hier_ws(ctx, p, *ht, (p.B + NQ - 1) / NQ, hw));
-    static bool attr_set = false;
-    if (!attr_set) {
+    WM_TRY(get_hier(ctx, p.nbk, r.k.hier_sb, &r.ht));
+    WM_TRY(plan_hier_ws(ctx, p, *r.ht, r.hw));
+    if (!ctx->hier_attr_set) {                     // per context: the limit belongs to the device the context made current
       WM_HIP(hipFuncSetAttribute((const void*)k_happly, hipFuncAttributeMaxDynamicSharedMemorySize, HN * 65 * 4));
       WM_HIP(hipFuncSetAttribute((const void*)k_happly_h<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * HA_CP * 2));
-      attr_set = true;
+      ctx->hier_attr_set = true;
     }
   }
-  auto hstep = [&](hipStream_t st, int g, int s1) {
-    const int z0 = zb[g], nz = zb[g + 1] - zb[g], nsp = ht->nsp;
-    const HSuper* sup = ht->d_super + (size_t)s1 * nsp;
-    float* aug = w.aug + (size_t)z0 * p.aug_ps;
-    float* Gs = hw.Gs + (size_t)z0 * nsp * HN * HN;
-    float* R = hw.R + (size_t)z0 * nsp * HU * RP * RP;
-    float* par = hw.partials + (size_t)z0 * nsp * HG_TILES * hw.KS * HG_T * HG_T;
-    int* skip = hier_flag_base(hw.skip, (size_t)nsp * HU, z0, g);
-    int* anyrot = hier_flag_base(hw.anyrot, (size_t)nsp, z0, g);
-    // per-stage rotations (packed) and skip flags of this group's planes: [stage][plane][super-pair * HU + unit]
-    float* Rpk = hw.Rpk + (size_t)z0 * HT_MAX * nsp * HU * RP * RP;
-    int* skipT = hier_flag_base(hw.skipT, (size_t)HT_MAX * nsp * HU, z0, g);
-    const size_t rpk_stage = (size_t)nz * nsp * HU * RP * RP, skip_stage = (size_t)nz * nsp * HU;
-    const int n32 = ht->nmax * RB, npmax = (n32 + HG_T - 1) / HG_T;
-    const int nchunk = (p.M + HG_KC - 1) / HG_KC;
-    // (one workgroup per (super-pair, plane, split) instead of three: only where that still fills the chip - from 11 planes per launch on;
-    //  16 planes on three queues: 209 against 213 frames/s with it, 64 planes: 308 against 297)
-    const bool h3 = getenv("WM_RF_HGRAM3") ? atoi(getenv("WM_RF_HGRAM3")) != 0 : nsp * hw.KS * nz >= 256;
-    const bool use_h3 = gram_f16 && npmax == 3 && h3;     // (its column splits weigh more: every split writes the whole upper triangle - 2.0 against 0.25: +2 % at 64 and 128 planes)
-    const int KS = hier_ks(nsp, nz, use_h3 ? 1 : npmax, nchunk, hw.KS, use_h3 ? 2.0 : 0.25), cps = (nchunk + KS - 1) / KS;
-    const int ngrp = nsp * KS * nz;               // (super-pair, split, plane) groups of npmax workgroups, dealt over the XCDs
-    if (gram_f16 && npmax == 3 && h3)               // three panels: the rows fetched once per chunk (k_hgram_h3)
-      hipLaunchKernelGGL(k_hgram_h3, dim3(((ngrp + 7) / 8) * 8), dim3(H3_NT), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
-                         par, KS, cps, nz);
-    else if (gram_f16)
-      hipLaunchKernelGGL(k_hgram_h, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
-                         par, KS, cps, npmax, nz);
-    else
-      hipLaunchKernelGGL(k_hgram, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
-                         par, KS, cps, npmax, nz, hdbg);
-    hipLaunchKernelGGL(k_hreduce, dim3(HSB * (HSB + 1) / 2, nsp, nz), dim3(256), 0, st, par, sup, nsp, KS, Gs, anyrot);
-    constexpr int NG = HU * (HU - 1) / 2;
-    const int T = ht->T[s1];
-    const int* un0 = ht->d_units + (size_t)ht->stage_off[s1] * nsp * HU;
-    for (int t = 0; t < T; ++t) {
-      const int* un = un0 + (size_t)t * nsp * HU;
-      hipLaunchKernelGGL(k_rf_inner, dim3(nsp * HU, 1, nz), dim3(INNER_NT), 0, st, (const float*)nullptr, 0, R, w.maxcos + z0,
-                         w.floor2 + z0, (s1 == 0 && t == 0) ? 0 : 1, skip, skip_thr, un, Gs, anyrot, nsp, Rpk + t * rpk_stage,
-                         skipT + t * skip_stage, apply_f16 ? 1 : 0);
-      if (t + 1 < T)                               // nothing reads G_s after the last stage
-        hipLaunchKernelGGL(k_hupdate, dim3(NG, nsp, nz), dim3(256), 0, st, un, sup, nsp, R, skip, Gs);
-    }
-    const int ntask = nsp * nz * ((ncols + 63) / 64);
-    if (apply_f16)
-      hipLaunchKernelGGL((k_happly_h<64>), dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)2 * 64 * HA_CP * 2, st, aug, p.aug_ps, p.ld,
-                         ncols, sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, hdbg >> 4);
-    else
-      hipLaunchKernelGGL(k_happly, dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)n32 * 65 * 4, st, aug, p.aug_ps, p.ld, ncols,
-                         sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, hdbg >> 4);
-  };
+  int sweep = 0;
+  bool done = false;
+  std::vector<unsigned> bits(p.B);
   while (!done && sweep < MAX_SWEEPS) {
     WM_HIP(hipMemsetAsync(w.maxcos, 0, (size_t)p.B * sizeof(unsigned), ctx->stream));
-    // group g starts one gram after group g - 1, so that the groups' latency-bound inner solves
-    // fall under each other's gram / apply tiles instead of all at the same time
-    auto q = [&](int g) { return g == 0 ? ctx->stream : ctx->aux_stream[g - 1]; };
-    if (hier) {
-      for (int g = 1; g < NQ; ++g) {               // the other queues start behind the memset
-        if (g == 1) WM_HIP(hipEventRecord(ctx->ev_fork[0], ctx->stream));
-        WM_HIP(hipStreamWaitEvent(q(g), ctx->ev_fork[0], 0));
-      }
-      for (int s1 = 0; s1 < ht->nsteps1; ++s1)
-        for (int g = 0; g < NQ; ++g) hstep(q(g), g, s1);
-    } else {
-    for (int g = 0; g < NQ; ++g) {
-      if (g > 0) WM_HIP(hipStreamWaitEvent(q(g), ctx->ev_fork[g - 1], 0));
-      step(q(g), g, 0, 1);
-      if (g + 1 < NQ) WM_HIP(hipEventRecord(ctx->ev_fork[g], q(g)));
-    }
-    for (int g = 0; g < NQ; ++g) step(q(g), g, 0, 2);
-    for (int s = 1; s < p.nsteps; ++s)
-      for (int g = 0; g < NQ; ++g) step(q(g), g, s, 3);
-    }
-    for (int g = 1; g < NQ; ++g) {
-      WM_HIP(hipEventRecord(ctx->ev_join[g - 1], q(g)));
+    if (hier) WM_TRY(hier_sweep(ctx, p, w, r));
+    else WM_TRY(flat_sweep(ctx, p, w, r, sweep));
+    for (int g = 1; g < r.NQ; ++g) {
+      WM_HIP(hipEventRecord(ctx->ev_join[g - 1], r.q(ctx, g)));
       WM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[g - 1], 0));
     }
     WM_HIP(hipGetLastError());
@@ -1274,12 +1318,12 @@ int jacobi_rows(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiUse u
   {   // nominal matrix-core flops of one sweep (every pair counted as rotated), for bench.py's roofline
     double f = 0.0;
     if (hier) {
-      for (int s1 = 0; s1 < ht->nsteps1; ++s1) {
+      for (int s1 = 0; s1 < r.ht->nsteps1; ++s1) {
         // the host copy of the tables holds the stage counts; the super-pairs' sizes follow from the block counts
-        f += ht->flops_step[s1] * ((double)p.M) + ht->flops_apply_step[s1] * (double)ncols + ht->flops_stage_step[s1];
+        f += r.ht->flops_step[s1] * ((double)p.M) + r.ht->flops_apply_step[s1] * (double)r.ncols + r.ht->flops_stage_step[s1];
       }
     } else {
-      f = (double)p.nsteps * p.npairs * (2.0 * 3 * RB * RB * p.M + 2.0 * RP * RP * ncols);
+      f = (double)p.nsteps * p.npairs * (2.0 * 3 * RB * RB * p.M + 2.0 * RP * RP * r.ncols);
     }
     ctx->ref_last_flops = f * sweep * p.B;
     ctx->ref_last_hier = hier ? 1 : 0;
@@ -1301,102 +1345,101 @@ int fetch_norms(wm_ctx* ctx, const RefPlan& p, const RefWs& w, bool with_q, std:
   return WM_OK;
 }
 
-// Q-free finalisation after jacobi_rows(with_q = false).  The rotated rows are b_i = s_i v_i^T
+static bool final_f16() { return ref_knobs().final_f16; }      // (read on every call, like WM_RF_HIER: tests switch it)
+
+// The spectrum rule of one plane: which estimate of s_i each of the Lp rotated rows gets.
+//   b2 = |b_i|^2;  q2 in: |q_i|^2 of the accumulated factor's row ([A | I] formulation; all 1 where there is none, and every
+//   term below then reduces exactly: b2 / 1, sqrt(t2 * 1), 1 * gcal);  t2 = |T[:, i]|^2 = |A0 b_i^T|^2.
+//   q2 out: the factor that makes sqrt(b2 / q2) the singular value.
+// |T[:, i]| = |b_i| s_i must agree with |b_i|^2 / |q_i| up to the rotations' scale drift (a few 1e-4).
+// A row that fails this is rounding residue of a rank-deficient plane - its direction is noise,
+// A0 b_i^T measures nothing - and keeps its own (tiny) norm as singular value; reliable (optional) marks the rows that pass.
+// zero_residue: a row below the numerical-null floor (the one the convergence test uses) whose A0 b_i^T is RESIDUE_RHO times
+// larger than a singular direction of that norm could give is rounding residue: its singular value is 0 (b2 = 0), as the
+// float32 cast of LAPACK's 1e-13-sized values would be.  A genuinely small value (clean synthetic images)
+// has rho near 1 - off by c^2 (s_max / s_i)^2 / 2 at worst - and keeps its norm.
+void spectrum_rule(const int Lp, double* b2, double* q2, const double* t2, const double skip_thr, const bool zero_residue,
+                   const bool drift_cal, const int debug_plane, unsigned char* reliable) {
+  const double floor2 = null_floor2(b2, Lp);
+  double smax2 = 0.0;
+  for (int i = 0; i < Lp; ++i) if (q2[i] > 0.0) smax2 = std::max(smax2, b2[i] / q2[i]);
+  // |A0 b_i^T| / |b_i| against |b_i| / |q_i|: 1 up to the scale drift unless b_i is residue
+  auto rho_of = [&](int i) { return (b2[i] > 0.0 && q2[i] > 0.0 && t2[i] > 0.0) ? sqrt(t2[i] * q2[i]) / b2[i] : 1e300; };
+  // Which estimate: with a residual cosine c between rows i and j, |A0 b_i^T| / |b_i| is off by
+  // c^2 (s_j / s_i)^2 / 2 relative, |b_i| by c^2 plus the scale drift (1e-4 relative, i.e. nothing in
+  // absolute terms for a small value).  The Jacobi leaves c <= skip_thr, so the first estimate is
+  // used down to s_i = T_SWITCH * c * s_max (error <= 1.25e-5) and the plain norm below.
+  const double ratio = T_SWITCH * skip_thr;
+  // Scale drift of the rotated rows, measured: every row goes through the same ~3e4..3e5 rotations, each of which
+  // shrinks it by the few 1e-8 that v_rsq_f32 leaves cos^2 + sin^2 below 1, so |b_i|^2 / s_i^2 is nearly the SAME
+  // factor g < 1 for all rows of a plane (1 - g = 6e-4 at 1080p, 1.6e-3 at 8K).  Where both estimates exist (the
+  // rows above the switch) g_i = |b_i|^4 / (|q_i|^2 |T[:, i]|^2) is known; its median calibrates the rows below the
+  // switch, whose |b_i| / |q_i| is the only estimate: s_i = |b_i| / (|q_i| sqrt(g)).  Without it the largest error of a whole
+  // spectrum sat right below the switch (3.3e-6 s_1 at 4K, 7.8e-6 at 8K - tests/test_gpu_fullframe_large.py).
+  std::vector<double> g;
+  std::vector<unsigned char> above(Lp, 0);
+  for (int i = 0; i < Lp; ++i) {
+    const bool consistent = fabs(rho_of(i) - 1.0) < DRIFT_TOL;
+    if (reliable) reliable[i] = consistent ? 1 : 0;
+    if (consistent && b2[i] / q2[i] >= ratio * ratio * smax2) { above[i] = 1; g.push_back(b2[i] * b2[i] / (q2[i] * t2[i])); }
+  }
+  double gcal = 1.0;
+  if (g.size() >= 8) {
+    std::sort(g.begin(), g.end());
+    if (drift_cal) gcal = g[g.size() / 2];
+    if (debug_plane >= 0)
+      fprintf(stderr, "[wm_ref] plane %d: drift factor g over %zu rows: p05 %.3e  median %.3e  p95 %.3e  (1 - g)\n", debug_plane,
+              g.size(), 1.0 - g[g.size() / 20], 1.0 - g[g.size() / 2], 1.0 - g[g.size() - 1 - g.size() / 20]);
+  }
+  for (int i = 0; i < Lp; ++i) {
+    if (above[i]) {
+      q2[i] = b2[i] * b2[i] / t2[i];                                    // sigma = |T[:, i]| / |b_i|
+    } else if (zero_residue && rho_of(i) > RESIDUE_RHO && b2[i] < floor2) {
+      b2[i] = 0.0; q2[i] = 1.0;                                         // residue below the floor: sigma = 0
+    } else {
+      q2[i] = q2[i] * gcal;                                             // sigma = |b_i| / (|q_i| sqrt(g)): the norm, drift calibrated
+    }
+  }
+}
+
+struct RefSpectrum {                     // host-side result of one batched Jacobi + T = A0 B^T pass
+  std::vector<double> b2, q2, t2;        // [B][Lp] |b_i|^2, the factor that turns it into sigma_i^2, |T[:, i]|^2
+  std::vector<unsigned char> reliable;   // [B][Lp] u_i = T[:, i] / (|b_i| s_i) is a usable left vector
+};
+
+// Q-free finalisation after jacobi_rows(JR_SIGMA / JR_EMBED).  The rotated rows are b_i = s_i v_i^T
 // up to the scale drift of ~3e4 float32 rotations per row (v_rsq_f32 rounds cos^2 + sin^2 a few
 // 1e-8 below 1, every time); the DIRECTION v_i is good to the convergence threshold.  So the
 // singular value is measured on the untouched input instead:  T = A0 B^T  (T[:, i] = A0 b_i^T =
 // |b_i| s_i u_i), s_i = |T[:, i]| / |b_i| - the drift cancels, and T doubles as the left factor
-// of the embed (u_i = T[:, i] / (|b_i| s_i)).  b2 = |b_i|^2, and q2 is returned as
-// b2^2 / |T[:, i]|^2 so that sqrt(b2 / q2) is s_i like in the [A | I] formulation.
-//   A0: dense [B][L][M] copy of the input rows;  T: dense [B][L][Lp] (left on the device).
+// of the embed (u_i = T[:, i] / (|b_i| s_i)).  sp.b2 = |b_i|^2, and sp.q2 is returned as
+// b2^2 / |T[:, i]|^2 so that sqrt(b2 / q2) is s_i like in the [A | I] formulation (spectrum_rule).
+//   w.a0: dense [B][L][M] copy of the input rows;  w.t: T, dense [B][L][Lp] (left on the device).
 // The finalisation's large products from split-f16 operands (k_hgemm, wm_ref_hier.inc) unless WM_RF_FINAL_F16=0 or the shapes
 // do not allow 16-byte loads; the f32 k_sgemm otherwise.
-static bool final_f16() {            // (read on every call, like WM_RF_HIER: tests switch it)
-  const char* e = getenv("WM_RF_FINAL_F16");
-  return !(e && atoi(e) == 0);
-}
-
-int fetch_norms_t(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const float* A0, float* T, std::vector<double>& b2,
-                  std::vector<double>& q2, std::vector<unsigned char>* reliable = nullptr,
-                  std::vector<double>* t2_raw = nullptr) {
+int fetch_norms_t(wm_ctx* ctx, const RefPlan& p, const RefWs& w, RefSpectrum& sp) {
   // all planes' products in one launch (grid.z = plane)
   hipLaunchKernelGGL(k_rf_rownorms, dim3(p.Lp, p.B), dim3(256), 0, ctx->stream, w.aug, p.aug_ps, p.ld, p.M, 0, w.b2, w.q2);
-  if (final_f16() && hgemm_ok(A0, p.M, w.aug, p.ld)) {
+  if (final_f16() && hgemm_ok(w.a0, p.M, w.aug, p.ld)) {
     // A0 holds uint8 samples (every caller decomposes uint8 planes): exact in f16; B's rows are bounded by 255 sqrt(L)
     hipLaunchKernelGGL((k_hgemm<true, true, false>), dim3((p.Lp + 127) / 128, (p.L + 127) / 128, p.B), dim3(256), 0, ctx->stream, p.L, p.Lp, p.M,
-                       A0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0, T, p.Lp, (size_t)p.L * p.Lp, (const float*)nullptr, (size_t)0, 1.0f,
+                       w.a0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0, w.t, p.Lp, (size_t)p.L * p.Lp, (const float*)nullptr, (size_t)0, 1.0f,
                        1.0f, (const float*)nullptr);
   } else
-  WM_TRY(sgemm_b(ctx, false, true, p.L, p.Lp, p.M, 1.0f, A0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0.0f, T, p.Lp,
+  WM_TRY(sgemm_b(ctx, false, true, p.L, p.Lp, p.M, 1.0f, w.a0, p.M, (size_t)p.L * p.M, w.aug, p.ld, p.aug_ps, 0.0f, w.t, p.Lp,
                  (size_t)p.L * p.Lp, p.B));
-  hipLaunchKernelGGL(k_rf_colnorms, dim3((p.Lp + 63) / 64, p.B), dim3(256), 0, ctx->stream, T, (size_t)p.L * p.Lp, p.L, p.Lp, w.q2);
+  hipLaunchKernelGGL(k_rf_colnorms, dim3((p.Lp + 63) / 64, p.B), dim3(256), 0, ctx->stream, w.t, (size_t)p.L * p.Lp, p.L, p.Lp, w.q2);
   WM_HIP(hipGetLastError());
-  b2.resize((size_t)p.B * p.Lp); q2.resize((size_t)p.B * p.Lp);
-  WM_HIP(hipMemcpyAsync(b2.data(), w.b2, b2.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  WM_HIP(hipMemcpyAsync(q2.data(), w.q2, q2.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  const size_t n = (size_t)p.B * p.Lp;
+  sp.b2.resize(n); sp.t2.resize(n);
+  WM_HIP(hipMemcpyAsync(sp.b2.data(), w.b2, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WM_HIP(hipMemcpyAsync(sp.t2.data(), w.q2, n * 8, hipMemcpyDeviceToHost, ctx->stream));
   WM_HIP(hipStreamSynchronize(ctx->stream));
-  if (t2_raw) *t2_raw = q2;                            // |T[:, i]|^2 as measured, before q2 becomes the sigma factor
-  // |T[:, i]| = |b_i| s_i must agree with |b_i|^2 up to the rotations' scale drift (a few 1e-4).
-  // A row that fails this is rounding residue of a rank-deficient plane - its direction is noise,
-  // A0 b_i^T measures nothing - and keeps its own (tiny) norm as singular value.
-  if (reliable) reliable->assign(b2.size(), 0);
-  // a row below the numerical-null floor (the one the convergence test uses: NULL_ROW_RATIO |A|_F;
-  // rotations preserve the Frobenius norm) whose A0 b_i^T is RESIDUE_RHO times larger than a singular
-  // direction of that norm could give is rounding residue: its singular value is 0, as the float32
-  // cast of LAPACK's 1e-13-sized values would be.  A genuinely small value (clean synthetic images)
-  // has rho near 1 - off by c^2 (s_max / s_i)^2 / 2 at worst - and keeps its norm.
-  std::vector<double> floor2(p.B, 0.0), bmax(p.B, 0.0);
+  sp.q2.assign(n, 1.0); sp.reliable.assign(n, 0);
+  const RefKnobs k = ref_knobs();
   for (int z = 0; z < p.B; ++z) {
-    double f2 = 0.0;
-    for (int i = 0; i < p.Lp; ++i) { f2 += b2[(size_t)z * p.Lp + i]; bmax[z] = std::max(bmax[z], b2[(size_t)z * p.Lp + i]); }
-    floor2[z] = NULL_ROW_RATIO * NULL_ROW_RATIO * f2;
-  }
-  // Scale drift of the rotated rows, measured: every row goes through the same ~3e4..3e5 rotations, each of which
-  // shrinks it by the few 1e-8 that v_rsq_f32 leaves cos^2 + sin^2 below 1, so |b_i|^2 / s_i^2 is nearly the SAME
-  // factor g < 1 for all rows of a plane (1 - g = 6e-4 at 1080p, 1.6e-3 at 8K).  Where both estimates exist (the
-  // rows above the switch below) g_i = |b_i|^4 / |T[:, i]|^2 is known; its median calibrates the rows below the
-  // switch, whose |b_i| is the only estimate: s_i = |b_i| / sqrt(g).  Without it the largest error of a whole
-  // spectrum sat right below the switch (3.3e-6 s_1 at 4K, 7.8e-6 at 8K - tests/test_gpu_fullframe_large.py).
-  static const bool drift_cal = !(getenv("WM_RF_DRIFT_CAL") && atoi(getenv("WM_RF_DRIFT_CAL")) == 0);
-  std::vector<double> gcal(p.B, 1.0);
-  {
-    const double ratio0 = T_SWITCH * (double)ctx->ref_skip_thr;
-    std::vector<double> g;
-    for (int z = 0; z < p.B; ++z) {
-      g.clear();
-      for (int i = 0; i < p.Lp; ++i) {
-        const size_t k = (size_t)z * p.Lp + i;
-        if (!(q2[k] > 0.0 && b2[k] > 0.0) || b2[k] < ratio0 * ratio0 * bmax[z]) continue;
-        const double gi = b2[k] * b2[k] / q2[k];
-        if (fabs(sqrt(q2[k]) / b2[k] - 1.0) < DRIFT_TOL) g.push_back(gi);
-      }
-      if (g.size() >= 8) {
-        std::sort(g.begin(), g.end());
-        if (drift_cal) gcal[z] = g[g.size() / 2];
-        if (getenv("WM_RF_DEBUG_DRIFT"))
-          fprintf(stderr, "[wm_ref] plane %d: drift factor g over %zu rows: p05 %.3e  median %.3e  p95 %.3e  (1 - g)\n", z,
-                  g.size(), 1.0 - g[g.size() / 20], 1.0 - g[g.size() / 2], 1.0 - g[g.size() - 1 - g.size() / 20]);
-      }
-    }
-  }
-  for (size_t i = 0; i < b2.size(); ++i) {
-    const double t2 = q2[i];
-    // |A0 b_i^T| / |b_i| agrees with |b_i| up to the rotations' scale drift unless b_i is residue
-    const double rho = (t2 > 0.0 && b2[i] > 0.0) ? sqrt(t2) / b2[i] : 1e300;
-    const bool consistent = fabs(rho - 1.0) < DRIFT_TOL;
-    if (reliable && consistent) (*reliable)[i] = 1;
-    // Which estimate: with a residual cosine c between rows i and j, |A0 b_i^T| / |b_i| is off by
-    // c^2 (s_j / s_i)^2 / 2 relative, |b_i| by c^2 plus the scale drift (1e-4 relative, i.e. nothing in
-    // absolute terms for a small value).  The Jacobi leaves c <= ref_skip_thr, so the first estimate is
-    // used down to s_i = T_SWITCH * c * s_max (error <= 1.25e-5) and the plain norm below.
-    const double ratio = T_SWITCH * (double)ctx->ref_skip_thr;
-    if (consistent && b2[i] >= ratio * ratio * bmax[i / p.Lp]) {
-      q2[i] = b2[i] * b2[i] / t2;                                       // sigma = |T[:, i]| / |b_i|
-    } else if (rho > RESIDUE_RHO && b2[i] < floor2[i / p.Lp]) {
-      b2[i] = 0.0; q2[i] = 1.0;                                         // residue below the floor: sigma = 0
-    } else {
-      q2[i] = gcal[i / p.Lp];                                           // sigma = |b_i| / sqrt(g): the norm, drift calibrated
-    }
+    const size_t o = (size_t)z * p.Lp;
+    spectrum_rule(p.Lp, &sp.b2[o], &sp.q2[o], &sp.t2[o], (double)ctx->ref_skip_thr, true, k.drift_cal, k.debug_drift ? z : -1, &sp.reliable[o]);
   }
   return WM_OK;
 }
@@ -1431,39 +1474,30 @@ int check_ref_args(wm_ctx* ctx, const void* plane, int n_planes, int H, int W, i
   return WM_OK;
 }
 
-inline size_t span_of(int n_planes, int H, int W, int row_stride, size_t plane_stride) {
-  return (size_t)(n_planes - 1) * plane_stride + (size_t)(H - 1) * row_stride + (size_t)W;
-}
-
 
 // ---------------------------------------------------------------------------
 // cores: every plane-sized array is DEVICE memory; the small per-plane vectors (singular values, the
 // embed coefficients) cross to the host once per call, where they are sorted / classified
 // ---------------------------------------------------------------------------
-struct RefSpectrum {                     // host-side result of one batched Jacobi + T = A0 B^T pass
-  std::vector<double> b2, q2, t2;        // [B][Lp] |b_i|^2, the factor that turns it into sigma_i^2, |T[:, i]|^2
-  std::vector<unsigned char> reliable;   // [B][Lp] u_i = T[:, i] / (|b_i| s_i) is a usable left vector
-};
-
-// planes (uint8, device) -> rotated rows B in w.aug, A0 copy in d_a0 [B][L][M], T = A0 B^T in d_t [B][L][Lp],
+// planes (uint8, device) -> rotated rows B in w.aug, A0 copy in w.a0 [B][L][M], T = A0 B^T in w.t [B][L][Lp],
 // spectrum on the host
 int ref_decompose(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t* d_planes, size_t row_stride,
-                  size_t plane_stride, float* d_a0, float* d_t, JacobiUse use, RefSpectrum& sp) {
+                  size_t plane_stride, JacobiUse use, RefSpectrum& sp) {
   hipLaunchKernelGGL((k_rf_load<uint8_t>), dim3(8, p.Lp, p.B), dim3(256), 0, ctx->stream, d_planes, row_stride,
                      plane_stride, p.transpose ? 1 : 0, w.aug, p.aug_ps, p.ld, p.L, p.Lp, p.M);
-  WM_TRY(copy_a_part(ctx, p, w, d_a0));
+  WM_TRY(copy_a_part(ctx, p, w, w.a0));
   int sweeps = 0;
   WM_TRY(jacobi_rows(ctx, p, w, use, &sweeps));
   if (sweeps < 0) return set_err(WM_ERR_NOCONV, "SVD did not converge");
-  WM_TRY(fetch_norms_t(ctx, p, w, d_a0, d_t, sp.b2, sp.q2, &sp.reliable, &sp.t2));
+  WM_TRY(fetch_norms_t(ctx, p, w, sp));
   return WM_OK;
 }
 
 // singular values of n planes on the device -> host sig [B][L]
 int ref_sigma_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t* d_planes, size_t row_stride,
-                   size_t plane_stride, float* d_a0, float* d_t, float* sig_host) {
+                   size_t plane_stride, float* sig_host) {
   RefSpectrum sp;
-  WM_TRY(ref_decompose(ctx, p, w, d_planes, row_stride, plane_stride, d_a0, d_t, JR_SIGMA, sp));
+  WM_TRY(ref_decompose(ctx, p, w, d_planes, row_stride, plane_stride, JR_SIGMA, sp));
   std::vector<int> order; std::vector<float> sig;
   for (int z = 0; z < p.B; ++z) {
     sort_sigma(p, &sp.b2[(size_t)z * p.Lp], &sp.q2[(size_t)z * p.Lp], order, sig);
@@ -1472,11 +1506,54 @@ int ref_sigma_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t*
   return WM_OK;
 }
 
+// The core of every null-space completion: the n vectors Z [n][len] (device) become an orthonormal set orthogonal to the
+// valid vectors of a basis - `rounds` times: projected off the basis (twice), orthogonalised by the block Jacobi (the row
+// span is preserved), the n largest rows gathered back into Z, normalised.
+//   basis, ldb: Lp vectors of length len - rows of basis (by_rows: the rotated rows B, the Qt part) or its columns (T);
+//   coef [Lp] HOST: 1 / |vector i|^2 of the valid ones, 0 for the others;
+//   wv: a workspace planned for make_plan(n, len) or a longer vector length with the same n (its arrays are then large
+//   enough), with C [n][Lp] and d_coef [Lp] in its tmp1.  The caller plans it: a second set of vectors may live there too.
+int ref_complete_vectors(wm_ctx* ctx, const RefWs& wv, float* Z, const int n, const int len, const float* basis, const int ldb,
+                         const int Lp, const bool by_rows, const std::vector<float>& coef, float* C, float* d_coef, const int rounds) {
+  const RefPlan pp = make_plan(n, len);
+  RefWs ww = wv;
+  WM_TRY(get_pairs(ctx, pp, &ww.pairs));
+  WM_HIP(hipMemcpyAsync(d_coef, coef.data(), (size_t)Lp * 4, hipMemcpyHostToDevice, ctx->stream));
+  for (int round = 0; round < rounds; ++round) {
+    for (int pass = 0; pass < 2; ++pass) {          // project twice: classical Gram-Schmidt loses digits once
+      if (by_rows) WM_TRY(sgemm(ctx, false, true, n, Lp, len, 1.0f, Z, len, basis, ldb, 0.0f, C, Lp));            // Z B^T
+      else WM_TRY(sgemm(ctx, false, false, n, Lp, len, 1.0f, Z, len, basis, ldb, 0.0f, C, Lp));                   // Z T
+      hipLaunchKernelGGL(k_rf_scale_cols_b, dim3(8, n, 1), dim3(256), 0, ctx->stream, C, (size_t)0, C, (size_t)0, Lp, d_coef, (size_t)0);
+      if (by_rows) WM_TRY(sgemm(ctx, false, false, n, len, Lp, -1.0f, C, Lp, basis, ldb, 1.0f, Z, len));          // Z -= C B
+      else WM_TRY(sgemm(ctx, false, true, n, len, Lp, -1.0f, C, Lp, basis, ldb, 1.0f, Z, len));                   // Z -= C T^T
+    }
+    WM_HIP(hipStreamSynchronize(ctx->stream));      // coef is the caller's, d_coef may be reused
+    hipLaunchKernelGGL((k_rf_load<float>), dim3(8, pp.Lp, 1), dim3(256), 0, ctx->stream, Z, (size_t)len, (size_t)0, 0,
+                       ww.aug, pp.aug_ps, pp.ld, pp.L, pp.Lp, pp.M);
+    int sweeps = 0;
+    WM_TRY(jacobi_rows(ctx, pp, ww, JR_ORTH, &sweeps));
+    if (sweeps < 0) return set_err(WM_ERR_NOCONV, "null-space completion did not converge");
+    std::vector<double> norms2, dummy;
+    WM_TRY(fetch_norms(ctx, pp, ww, false, norms2, dummy));
+    std::vector<int> ord(pp.Lp);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return norms2[a] > norms2[b]; });
+    // gather the n largest rows back into Z, normalised
+    std::vector<float> sc(n);
+    for (int k = 0; k < n; ++k) sc[k] = norms2[ord[k]] > 0.0 ? (float)(1.0 / sqrt(norms2[ord[k]])) : 0.0f;
+    WM_HIP(hipMemcpyAsync(ww.order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    WM_HIP(hipMemcpyAsync(ww.scale, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_rf_gather_rows, dim3(8, n), dim3(256), 0, ctx->stream, ww.aug, pp.ld, len, ww.order, ww.scale, Z, len);
+    WM_HIP(hipStreamSynchronize(ctx->stream));      // ord / sc are locals; ww.order is free again
+  }
+  return WM_OK;
+}
+
 // Null-space completion of ONE rank-deficient plane z.  The reference injects alpha*Sw[k]
 // for EVERY k < K (single:174-176): where the plane has no k-th singular direction LAPACK supplies some
 // orthonormal completion of the null spaces.  Here: n deterministic pseudo-random vectors per side are
-// projected off the valid singular vectors (twice), orthogonalised by the same block Jacobi, normalised,
-// and  sum_k w_k u_k v_k^T  is added to Yw.  With every u and every v orthonormal,
+// projected off the valid singular vectors (twice), orthogonalised by the same block Jacobi, normalised
+// (ref_complete_vectors, one round), and  sum_k w_k u_k v_k^T  is added to Yw.  With every u and every v orthonormal,
 // svd(Yw) = {s_i + w_i} U {w_k}: the reference's invariant  S(Cw)[:K] = Sc[:K] + alpha Sw[:K].
 //   valid [Lp]: 1 for rows of B that are singular directions; wk [n]: the energies of the missing ranks;
 //   tnorm2 [Lp]: |T[:, i]|^2.  d_yw: this plane's Yw in A layout [L][M].
@@ -1486,12 +1563,11 @@ int ref_complete_plane(wm_ctx* ctx, const RefPlan& p, const RefWs& w, int z, con
   const int n = (int)wk.size();
   if (n == 0) return WM_OK;
   const float* Bz = w.aug + (size_t)z * p.aug_ps;
-  // side 0: right vectors (length M, against the rows of B); side 1: left vectors (length L, against the columns of T)
-  const RefPlan pv = make_plan(n, p.M), pu = make_plan(n, p.L);
   RefWs wv;
   // second workspace, planned for the larger of the two Jacobi runs (n x M; the n x L one has the same
   // block count and fewer columns and reuses its arrays).  tmp1: Zv [n][M] | Zu [n][L] | C [n][Lp] | coefficients [Lp]
-  WM_TRY(plan_workspace(ctx, pv, wv, (size_t)n * (p.M + p.L + p.Lp) + p.Lp + 64, 16, 1));
+  // Zv and Zu both live until the product below, so both sides share this one plan
+  WM_TRY(plan_workspace(ctx, make_plan(n, p.M), wv, (size_t)n * (p.M + p.L + p.Lp) + p.Lp + 64, 16, 1));
   float* Zv = wv.tmp1; float* Zu = Zv + (size_t)n * p.M; float* C = Zu + (size_t)n * p.L; float* coef = C + (size_t)n * p.Lp;
   std::vector<float> gv(p.Lp), gu(p.Lp);
   for (int i = 0; i < p.Lp; ++i) {
@@ -1500,46 +1576,9 @@ int ref_complete_plane(wm_ctx* ctx, const RefPlan& p, const RefWs& w, int z, con
   }
   hipLaunchKernelGGL(k_rf_pattern, dim3(8, n), dim3(256), 0, ctx->stream, Zv, p.M, 0x1234567u);
   hipLaunchKernelGGL(k_rf_pattern, dim3(8, n), dim3(256), 0, ctx->stream, Zu, p.L, 0x7654321u);
-  for (int side = 0; side < 2; ++side) {
-    float* Z = side == 0 ? Zv : Zu;
-    WM_HIP(hipMemcpyAsync(coef, (side == 0 ? gv : gu).data(), (size_t)p.Lp * 4, hipMemcpyHostToDevice, ctx->stream));
-    for (int pass = 0; pass < 2; ++pass) {          // project twice: classical Gram-Schmidt loses digits once
-      if (side == 0) WM_TRY(sgemm(ctx, false, true, n, p.Lp, p.M, 1.0f, Z, p.M, Bz, p.ld, 0.0f, C, p.Lp));       // Z B^T
-      else WM_TRY(sgemm(ctx, false, false, n, p.Lp, p.L, 1.0f, Z, p.L, d_t_z, p.Lp, 0.0f, C, p.Lp));              // Z T
-      hipLaunchKernelGGL(k_rf_scale_cols_b, dim3(8, n, 1), dim3(256), 0, ctx->stream, C, (size_t)0, C, (size_t)0, p.Lp, coef, (size_t)0);
-      if (side == 0) WM_TRY(sgemm(ctx, false, false, n, p.M, p.Lp, -1.0f, C, p.Lp, Bz, p.ld, 1.0f, Z, p.M));      // Z -= C B
-      else WM_TRY(sgemm(ctx, false, true, n, p.L, p.Lp, -1.0f, C, p.Lp, d_t_z, p.Lp, 1.0f, Z, p.L));              // Z -= C T^T
-    }
-    WM_HIP(hipStreamSynchronize(ctx->stream));      // gv / gu are locals reused by the next side
-  }
-  // orthogonalise the rows of each Z with the block Jacobi (row span is preserved), then  Yw += Zu^T diag(d) Zv
-  std::vector<double> nv, nu, dummy;
-  std::vector<int> ordv, ordu;
-  float* aug2 = wv.aug;
-  auto orth = [&](const RefPlan& pp, float* Z, int len, std::vector<double>& norms2, std::vector<int>& ord) -> int {
-    RefWs ww = wv;
-    WM_TRY(get_pairs(ctx, pp, &ww.pairs));
-    hipLaunchKernelGGL((k_rf_load<float>), dim3(8, pp.Lp, 1), dim3(256), 0, ctx->stream, Z, (size_t)len, (size_t)0, 0,
-                       aug2, pp.aug_ps, pp.ld, pp.L, pp.Lp, pp.M);
-    int sweeps = 0;
-    WM_TRY(jacobi_rows(ctx, pp, ww, JR_ORTH, &sweeps));
-    if (sweeps < 0) return set_err(WM_ERR_NOCONV, "null-space completion did not converge");
-    WM_TRY(fetch_norms(ctx, pp, ww, false, norms2, dummy));
-    ord.resize(pp.Lp);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return norms2[a] > norms2[b]; });
-    // gather the n largest rows back into Z, normalised
-    std::vector<float> sc(n);
-    for (int k = 0; k < n; ++k) sc[k] = norms2[ord[k]] > 0.0 ? (float)(1.0 / sqrt(norms2[ord[k]])) : 0.0f;
-    WM_HIP(hipMemcpyAsync(ww.order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(ww.scale, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_rf_gather_rows, dim3(8, n), dim3(256), 0, ctx->stream, aug2, pp.ld, len, ww.order, ww.scale, Z, len);
-    WM_HIP(hipStreamSynchronize(ctx->stream));       // ord / sc are locals
-    return WM_OK;
-  };
-  // the workspace arrays of wv were sized for pv = (n, M); pu = (n, L) has the same row count and fewer columns
-  WM_TRY(orth(pv, Zv, p.M, nv, ordv));
-  WM_TRY(orth(pu, Zu, p.L, nu, ordu));
+  // right vectors (length M, against the rows of B), then left vectors (length L, against the columns of T)
+  WM_TRY(ref_complete_vectors(ctx, wv, Zv, n, p.M, Bz, p.ld, p.Lp, true, gv, C, coef, 1));
+  WM_TRY(ref_complete_vectors(ctx, wv, Zu, n, p.L, d_t_z, p.Lp, p.Lp, false, gu, C, coef, 1));
   // Zu rows scaled by the energies, then Yw += Zu^T Zv   ([L x n] [n x M])
   WM_HIP(hipMemcpyAsync(coef, wk.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_rf_scale_rows, dim3(8, n, 1), dim3(256), 0, ctx->stream, Zu, (size_t)0, p.L, p.L, coef);
@@ -1554,56 +1593,31 @@ int ref_complete_plane(wm_ctx* ctx, const RefPlan& p, const RefWs& w, int z, con
 // non-orthogonal too on planes whose DCT has exactly vanishing rows (an unscrambled logo of two bars: |U^T U - I| = 1.0 on
 // the null columns, the valid ones exact).  LAPACK returns an orthonormal completion there; here the slots of those rows
 // in BOTH gathered factors get one, side 0 of ref_complete_plane: deterministic start vectors, projected twice off the
-// valid rows, orthogonalised by the block Jacobi, normalised.
+// valid rows, orthogonalised by the block Jacobi, normalised (ref_complete_vectors, two rounds).
 //   side 0: the long-side factor (B part, vectors of length M);  side 1: the short-side factor (first L columns of the Qt part)
 //   valid [Lp]: 1 for rows that are singular directions;  n2 [Lp]: squared norms of that part of the rows;
 //   slots [n]: where the n completed vectors go;  dst + slot * ld_slot + j * ld_elem: element j of that slot's vector
-int ref_complete_factor(wm_ctx* ctx, const RefPlan& p0, const RefWs& w, int z, int side, const std::vector<unsigned char>& valid,
-                        const double* b2, const std::vector<int>& slots, float* dst, size_t ld_slot, size_t ld_elem) {
+int ref_complete_factor(wm_ctx* ctx, const RefPlan& p, const RefWs& w, int z, int side, const std::vector<unsigned char>& valid,
+                        const double* n2, const std::vector<int>& slots, float* dst, size_t ld_slot, size_t ld_elem) {
   const int n = (int)slots.size();
   if (n == 0) return WM_OK;
-  const float* Bz = w.aug + (size_t)z * p0.aug_ps + (side == 0 ? 0 : p0.M);
-  struct { int M, Lp, ld; } p = {side == 0 ? p0.M : p0.L, p0.Lp, p0.ld};       // vector length, rows, leading dimension
-  const RefPlan pv = make_plan(n, p.M);
+  const float* Bz = w.aug + (size_t)z * p.aug_ps + (side == 0 ? 0 : p.M);
+  const int len = side == 0 ? p.M : p.L;
   RefWs wv;
-  // tmp1: Z [n][M] | C [n][Lp] | coefficients [Lp]
-  WM_TRY(plan_workspace(ctx, pv, wv, (size_t)n * (p.M + p.Lp) + p.Lp + 64, 16, 1));
-  float* Z = wv.tmp1; float* C = Z + (size_t)n * p.M; float* coef = C + (size_t)n * p.Lp;
+  // tmp1: Z [n][len] | C [n][Lp] | coefficients [Lp]
+  WM_TRY(plan_workspace(ctx, make_plan(n, len), wv, (size_t)n * (len + p.Lp) + p.Lp + 64, 16, 1));
+  float* Z = wv.tmp1; float* C = Z + (size_t)n * len; float* coef = C + (size_t)n * p.Lp;
   std::vector<float> gv(p.Lp);
-  for (int i = 0; i < p.Lp; ++i) gv[i] = (valid[i] && b2[i] > 0.0) ? (float)(1.0 / b2[i]) : 0.0f;
-  hipLaunchKernelGGL(k_rf_pattern, dim3(8, n), dim3(256), 0, ctx->stream, Z, p.M, side == 0 ? 0x1234567u : 0x7654321u);
-  WM_HIP(hipMemcpyAsync(coef, gv.data(), (size_t)p.Lp * 4, hipMemcpyHostToDevice, ctx->stream));
+  for (int i = 0; i < p.Lp; ++i) gv[i] = (valid[i] && n2[i] > 0.0) ? (float)(1.0 / n2[i]) : 0.0f;
+  hipLaunchKernelGGL(k_rf_pattern, dim3(8, n), dim3(256), 0, ctx->stream, Z, len, side == 0 ? 0x1234567u : 0x7654321u);
   // Two rounds of (project, orthonormalise).  The complement of the valid short-side vectors has exactly n dimensions, so the
   // n projected start vectors are a SQUARE random matrix there, condition ~n..n^2: the Jacobi works on float32 Gram entries
   // and leaves its small rows eps * cond^2 off (measured 3.3e-4 on a 56x40 plane of rank 3), and normalising a small row
   // amplifies what the projection left of the valid vectors.  The second round starts from rows that are orthonormal to
   // that error, condition 1, and ends at rounding level.
-  for (int round = 0; round < 2; ++round) {
-  for (int pass = 0; pass < 2; ++pass) {            // project twice: classical Gram-Schmidt loses digits once
-    WM_TRY(sgemm(ctx, false, true, n, p.Lp, p.M, 1.0f, Z, p.M, Bz, p.ld, 0.0f, C, p.Lp));                         // Z B^T
-    hipLaunchKernelGGL(k_rf_scale_cols_b, dim3(8, n, 1), dim3(256), 0, ctx->stream, C, (size_t)0, C, (size_t)0, p.Lp, coef, (size_t)0);
-    WM_TRY(sgemm(ctx, false, false, n, p.M, p.Lp, -1.0f, C, p.Lp, Bz, p.ld, 1.0f, Z, p.M));                       // Z -= C B
-  }
-  WM_HIP(hipStreamSynchronize(ctx->stream));        // gv is a local
-  hipLaunchKernelGGL((k_rf_load<float>), dim3(8, pv.Lp, 1), dim3(256), 0, ctx->stream, Z, (size_t)p.M, (size_t)0, 0,
-                     wv.aug, pv.aug_ps, pv.ld, pv.L, pv.Lp, pv.M);
-  int sweeps = 0;
-  WM_TRY(jacobi_rows(ctx, pv, wv, JR_ORTH, &sweeps));
-  if (sweeps < 0) return set_err(WM_ERR_NOCONV, "null-space completion did not converge");
-  std::vector<double> norms2, dummy;
-  WM_TRY(fetch_norms(ctx, pv, wv, false, norms2, dummy));
-  std::vector<int> ord(pv.Lp);
-  std::iota(ord.begin(), ord.end(), 0);
-  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return norms2[a] > norms2[b]; });
-  std::vector<float> sc(n);
-  for (int k = 0; k < n; ++k) sc[k] = norms2[ord[k]] > 0.0 ? (float)(1.0 / sqrt(norms2[ord[k]])) : 0.0f;
-  WM_HIP(hipMemcpyAsync(wv.order, ord.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_HIP(hipMemcpyAsync(wv.scale, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rf_gather_rows, dim3(8, n), dim3(256), 0, ctx->stream, wv.aug, pv.ld, p.M, wv.order, wv.scale, Z, p.M);
-  WM_HIP(hipStreamSynchronize(ctx->stream));        // ord / sc are locals; wv.order is free again
-  }
+  WM_TRY(ref_complete_vectors(ctx, wv, Z, n, len, Bz, p.ld, p.Lp, true, gv, C, coef, 2));
   WM_HIP(hipMemcpyAsync(wv.order, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_rf_put_rows, dim3(8, n), dim3(256), 0, ctx->stream, Z, p.M, wv.order, dst, ld_slot, ld_elem);
+  hipLaunchKernelGGL(k_rf_put_rows, dim3(8, n), dim3(256), 0, ctx->stream, Z, len, wv.order, dst, ld_slot, ld_elem);
   WM_HIP(hipGetLastError());
   WM_HIP(hipStreamSynchronize(ctx->stream));        // slots is the caller's
   return WM_OK;
@@ -1611,14 +1625,15 @@ int ref_complete_factor(wm_ctx* ctx, const RefPlan& p0, const RefWs& w, int z, i
 
 // embed of p.B planes on the device.  d_in / d_out: uint8 planes (same strides; may alias);
 // d_ywout: optional dense float [B][H][W]; sigma_w: HOST [B or 1][L]; sigma_c: HOST [B][L] out.
-// d_yw [B][L][M] and d_t [B][L][Lp] are workspace.
+// Yw [B][L][M] is built in w.a0, beside T in w.t.
 int ref_embed_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t* d_in, uint8_t* d_out, float* d_ywout,
-                   size_t row_stride, size_t plane_stride, float* d_yw, float* d_t, const float* sigma_w,
+                   size_t row_stride, size_t plane_stride, const float* sigma_w,
                    size_t sigma_w_plane_stride, float* sigma_c, float alpha, int K, const int* sigma_w_ready = nullptr) {
   const size_t yw_ps = (size_t)p.L * p.M;
+  float* const d_yw = w.a0; float* const d_t = w.t;
   RefSpectrum sp;
-  // Yw starts as A itself (exactly the pixels): ref_decompose leaves that copy in d_yw
-  WM_TRY(ref_decompose(ctx, p, w, d_in, row_stride, plane_stride, d_yw, d_t, JR_EMBED, sp));
+  // Yw starts as A itself (exactly the pixels): ref_decompose leaves that copy in w.a0
+  WM_TRY(ref_decompose(ctx, p, w, d_in, row_stride, plane_stride, JR_EMBED, sp));
   // sigma_w is first read here, after the host planes' decomposition (the long part of the call): a caller that is still
   // computing it - the watermark's own SVD on another context and thread, single:172-173's two independent statements -
   // says so with a flag: > 0 once sigma_w is written, < 0 if it never will be
@@ -1642,7 +1657,7 @@ int ref_embed_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t*
   }
   std::vector<float> d((size_t)p.B * p.Lp * (f16_prod ? 2 : 1), 0.0f);       // row scales of B [, then column scales of T]
   std::vector<int> order; std::vector<float> sig;
-  struct Todo { int z; std::vector<unsigned char> valid; std::vector<float> wk; std::vector<double> t2; };
+  struct Todo { int z; std::vector<unsigned char> valid; std::vector<float> wk; };
   std::vector<Todo> todo;
   for (int z = 0; z < p.B; ++z) {
     const double* pb = &sp.b2[(size_t)z * p.Lp]; const double* pq = &sp.q2[(size_t)z * p.Lp];
@@ -1651,7 +1666,6 @@ int ref_embed_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t*
     const float* sw = sigma_w + (size_t)z * sigma_w_plane_stride;
     const double s1 = sig.empty() ? 0.0 : (double)sig[0];
     Todo td; td.z = z; td.valid.assign(p.Lp, 0);
-    td.t2.assign(sp.t2.begin() + (size_t)z * p.Lp, sp.t2.begin() + (size_t)(z + 1) * p.Lp);
     for (int i = 0; i < p.Lp; ++i) {
       // a singular direction: consistent T column, above the null ratio (sigma_i^2 = b2 / q2)
       const double s2 = pb[i] / (pq[i] > 0 ? pq[i] : 1.0);
@@ -1675,7 +1689,7 @@ int ref_embed_core(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const uint8_t*
   if (!todo.empty()) {
     WM_HIP(hipStreamSynchronize(ctx->stream));
     for (const Todo& td : todo)
-      WM_TRY(ref_complete_plane(ctx, p, w, td.z, td.valid, &sp.b2[(size_t)td.z * p.Lp], td.t2.data(), td.wk,
+      WM_TRY(ref_complete_plane(ctx, p, w, td.z, td.valid, &sp.b2[(size_t)td.z * p.Lp], &sp.t2[(size_t)td.z * p.Lp], td.wk,
                                 d_t + (size_t)td.z * p.L * p.Lp, d_yw + (size_t)td.z * yw_ps));
   }
   hipLaunchKernelGGL(k_rf_scale_rows, dim3(8, p.Lp, p.B), dim3(256), 0, ctx->stream, w.aug, p.aug_ps, p.ld, p.M, w.dvec);
@@ -1820,10 +1834,9 @@ int wm_ref_sigma_planes_u8_dev(wm_ctx* ctx, const uint8_t* planes, float* sigma,
   if (!sigma) return set_err(WM_ERR_BADARG, "sigma is NULL");
   const RefPlan p = make_plan(H, W, n_planes);
   RefWs w;
-  WM_TRY(plan_workspace(ctx, p, w, 16, (size_t)n_planes * p.L * (p.M + p.Lp)));   // tmp2: A0 [B][L][M] | T [B][L][Lp]
+  WM_TRY(plan_decompose_ws(ctx, p, w, 16));
   std::vector<float> sig((size_t)n_planes * p.L);
-  WM_TRY(ref_sigma_core(ctx, p, w, planes, (size_t)row_stride, plane_stride, w.tmp2, w.tmp2 + (size_t)n_planes * p.L * p.M,
-                        sig.data()));
+  WM_TRY(ref_sigma_core(ctx, p, w, planes, (size_t)row_stride, plane_stride, sig.data()));
   WM_HIP(hipMemcpyAsync(sigma, sig.data(), sig.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   WM_HIP(hipStreamSynchronize(ctx->stream));
   return WM_OK;
@@ -1837,12 +1850,12 @@ int wm_ref_embed_planes_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* si
   const RefPlan p = make_plan(H, W, n_planes);
   if (K < 0 || K > p.L) return set_err(WM_ERR_BADARG, "K must be in 0..min(H,W)");
   RefWs w;
-  WM_TRY(plan_workspace(ctx, p, w, 16, (size_t)n_planes * p.L * (p.M + p.Lp)));   // tmp2: Yw [B][L][M] | T [B][L][Lp]
+  WM_TRY(plan_decompose_ws(ctx, p, w, 16));
   std::vector<float> sw, sc((size_t)n_planes * p.L);
   WM_TRY(fetch_f32(ctx, sigma_w, sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + p.L : (size_t)p.L, sw));
   // pixels the tiles do not cover do not exist in this mode: every pixel of stego is written by the quantiser
-  WM_TRY(ref_embed_core(ctx, p, w, host, stego, yw, (size_t)row_stride, plane_stride, w.tmp2,
-                        w.tmp2 + (size_t)n_planes * p.L * p.M, sw.data(), sigma_w_plane_stride, sc.data(), alpha, K));
+  WM_TRY(ref_embed_core(ctx, p, w, host, stego, yw, (size_t)row_stride, plane_stride, sw.data(), sigma_w_plane_stride, sc.data(),
+                        alpha, K));
   WM_HIP(hipMemcpyAsync(sigma_c, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   WM_HIP(hipStreamSynchronize(ctx->stream));
   return WM_OK;
@@ -1858,11 +1871,9 @@ int wm_ref_extract_planes_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float*
   if (K < 0 || K > L) return set_err(WM_ERR_BADARG, "K must be in 0..min(H,W)");
   RefWs w;
   // tmp1: Uw diag(sh) [B][L][L];  tmp2: A0 [B][L][M] | T [B][L][Lp], reused afterwards as the GEMM intermediate [B][H][W]
-  WM_TRY(plan_workspace(ctx, p, w, (size_t)n_planes * L * L + 16,
-                        std::max((size_t)n_planes * p.L * (p.M + p.Lp), (size_t)n_planes * H * W)));
+  WM_TRY(plan_decompose_ws(ctx, p, w, (size_t)n_planes * L * L + 16, (size_t)n_planes * H * W));
   std::vector<float> s_cw((size_t)n_planes * L), sc;
-  WM_TRY(ref_sigma_core(ctx, p, w, stego, (size_t)row_stride, plane_stride, w.tmp2, w.tmp2 + (size_t)n_planes * p.L * p.M,
-                        s_cw.data()));                                                                   // single:205
+  WM_TRY(ref_sigma_core(ctx, p, w, stego, (size_t)row_stride, plane_stride, s_cw.data()));                // single:205
   WM_TRY(fetch_f32(ctx, sigma_c, (size_t)n_planes * L, sc));
   return ref_extract_core(ctx, p, w, s_cw.data(), sc.data(), Uw, Vwt, w.tmp1, w.tmp2, out, alpha, K);
 }
@@ -1874,10 +1885,9 @@ int wm_ref_detect_planes_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* 
   if (!sigma_c || !sigma_w || !scores) return set_err(WM_ERR_BADARG, "NULL argument");
   const RefPlan p = make_plan(H, W, n_planes);
   RefWs w;
-  WM_TRY(plan_workspace(ctx, p, w, 16, (size_t)n_planes * p.L * (p.M + p.Lp)));
+  WM_TRY(plan_decompose_ws(ctx, p, w, 16));
   std::vector<float> s_cw((size_t)n_planes * p.L), sc, sw;
-  WM_TRY(ref_sigma_core(ctx, p, w, stego, (size_t)row_stride, plane_stride, w.tmp2, w.tmp2 + (size_t)n_planes * p.L * p.M,
-                        s_cw.data()));
+  WM_TRY(ref_sigma_core(ctx, p, w, stego, (size_t)row_stride, plane_stride, s_cw.data()));
   WM_TRY(fetch_f32(ctx, sigma_c, (size_t)n_planes * p.L, sc));
   WM_TRY(fetch_f32(ctx, sigma_w, (size_t)p.L, sw));
   std::vector<double> sco(n_planes);
@@ -1895,12 +1905,12 @@ int wm_ref_sigma_planes_u8(wm_ctx* ctx, const uint8_t* planes, float* sigma, int
   if (!sigma) return set_err(WM_ERR_BADARG, "sigma is NULL");
   const RefPlan p = make_plan(H, W, n_planes);
   RefWs w;
-  const size_t n_in = span_of(n_planes, H, W, row_stride, plane_stride);
-  // tmp1: uint8 input span; tmp2: A0 [B][L][M] | T [B][L][Lp]
-  WM_TRY(plan_workspace(ctx, p, w, (n_in + 3) / 4 + 4, (size_t)n_planes * p.L * (p.M + p.Lp)));
+  const size_t n_in = plane_span(n_planes, H, row_stride, plane_stride, W);
+  // tmp1: uint8 input span
+  WM_TRY(plan_decompose_ws(ctx, p, w, (n_in + 3) / 4 + 4));
   uint8_t* d_in = (uint8_t*)w.tmp1;
   WM_HIP(hipMemcpyAsync(d_in, planes, n_in, hipMemcpyHostToDevice, ctx->stream));
-  return ref_sigma_core(ctx, p, w, d_in, (size_t)row_stride, plane_stride, w.tmp2, w.tmp2 + (size_t)n_planes * p.L * p.M, sigma);
+  return ref_sigma_core(ctx, p, w, d_in, (size_t)row_stride, plane_stride, sigma);
 }
 
 int wm_ref_sigma_u8(wm_ctx* ctx, const uint8_t* plane, float* sigma, int H, int W, int row_stride) {
@@ -1915,12 +1925,11 @@ int wm_ref_embed_planes_u8_when(wm_ctx* ctx, const uint8_t* host, const float* s
   const RefPlan p = make_plan(H, W, n_planes);
   if (K < 0 || K > p.L) return set_err(WM_ERR_BADARG, "K must be in 0..min(H,W)");
   RefWs w;
-  const size_t n_in = span_of(n_planes, H, W, row_stride, plane_stride);
+  const size_t n_in = plane_span(n_planes, H, row_stride, plane_stride, W);
   const size_t n_in16 = (n_in + 15) & ~(size_t)15;
   const size_t yw_elems = yw ? (size_t)n_planes * H * W : 0;
-  // tmp1: uint8 input + output spans (+ dense float Yw for the caller);
-  // tmp2: Yw in A layout [B][L][M] (starts as A0, the pixels) | T [B][L][Lp]
-  WM_TRY(plan_workspace(ctx, p, w, (2 * n_in16) / 4 + 8 + yw_elems, (size_t)n_planes * p.L * (p.M + p.Lp)));
+  // tmp1: uint8 input + output spans (+ dense float Yw for the caller)
+  WM_TRY(plan_decompose_ws(ctx, p, w, (2 * n_in16) / 4 + 8 + yw_elems));
   uint8_t* d_in = (uint8_t*)w.tmp1;
   uint8_t* d_out = d_in + n_in16;
   float* d_ywout = yw ? (float*)(d_out + n_in16) : nullptr;
@@ -1928,8 +1937,8 @@ int wm_ref_embed_planes_u8_when(wm_ctx* ctx, const uint8_t* host, const float* s
   // bytes between rows / planes that belong to the caller's stego buffer are carried through
   if (stego != host) WM_HIP(hipMemcpyAsync(d_out, stego, n_in, hipMemcpyHostToDevice, ctx->stream));
   else WM_HIP(hipMemcpyAsync(d_out, d_in, n_in, hipMemcpyDeviceToDevice, ctx->stream));
-  WM_TRY(ref_embed_core(ctx, p, w, d_in, d_out, d_ywout, (size_t)row_stride, plane_stride, w.tmp2,
-                        w.tmp2 + (size_t)n_planes * p.L * p.M, sigma_w, sigma_w_plane_stride, sigma_c, alpha, K, sigma_w_ready));
+  WM_TRY(ref_embed_core(ctx, p, w, d_in, d_out, d_ywout, (size_t)row_stride, plane_stride, sigma_w, sigma_w_plane_stride, sigma_c,
+                        alpha, K, sigma_w_ready));
   WM_HIP(hipMemcpyAsync(stego, d_out, n_in, hipMemcpyDeviceToHost, ctx->stream));
   if (yw) WM_HIP(hipMemcpyAsync(yw, d_ywout, yw_elems * 4, hipMemcpyDeviceToHost, ctx->stream));
   WM_HIP(hipStreamSynchronize(ctx->stream));
@@ -1960,7 +1969,7 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
   const int B = n_planes;
   const RefPlan p = make_plan(H, W, B);
   RefWs w;
-  const size_t n_in = span_of(B, H, W, row_stride, plane_stride);
+  const size_t n_in = plane_span(B, H, row_stride, plane_stride, W);
   const size_t n_in_a = (n_in + 63) & ~(size_t)63, hw = (size_t)H * W, fl = (size_t)p.L * (p.M + p.L), lp64 = ((size_t)p.Lp + 63) & ~(size_t)63;
   // tmp1: input planes | DCT planes [B][H][W] | every plane's sorted factors in the caller's layout, U [H][L] | Vt [L][W] | per plane: order, 1 / |q_i|,
   // 1 / |b_i|;  tmp2: DCT intermediate [B][H][W], then T = A0 B^T [B][L][Lp]
@@ -1991,7 +2000,8 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
   // independently through ~1e5 MFMA row updates: measured 7e-5 relative low at 8K (3e-5 at 1080p), the same for
   // every value.  Like the sigma-only path (fetch_norms_t) the large values are therefore measured on the untouched
   // input, s_i = |A0 b_i^T| / |b_i| (error c^2 (s_max / s_i)^2 / 2 with the residual cosine c <= ref_skip_thr), and
-  // the ratio of the two estimates there (median) calibrates |b_i| / |q_i| for the values below the switch.
+  // the ratio of the two estimates there (median) calibrates |b_i| / |q_i| for the values below the switch (spectrum_rule;
+  // a row that is residue keeps its |b_i| / |q_i| here: its slot is completed below).
   float* d_T = w.tmp2;
   WM_TRY(sgemm_b(ctx, p.transpose, true, p.L, p.Lp, p.M, 1.0f, src, (int)src_stride, src_ps, w.aug, p.ld, p.aug_ps, 0.0f, d_T, p.Lp,
                  (size_t)p.L * p.Lp, B));
@@ -2005,31 +2015,15 @@ int wm_ref_svd_planes_f32(wm_ctx* ctx, const float* planes, float* U, float* S, 
   struct NullRows { int z; std::vector<unsigned char> valid; std::vector<int> slots; };
   std::vector<NullRows> todo;                           // rank-deficient planes: slots of the long-side factor to complete
   for (int z = 0; z < B; ++z) {
-    const double* b2z = &b2[(size_t)z * p.Lp]; const double* q2z = &q2[(size_t)z * p.Lp]; const double* t2 = &t2all[(size_t)z * p.Lp];
+    double* b2z = &b2[(size_t)z * p.Lp]; const double* q2z = &q2[(size_t)z * p.Lp];
     std::vector<double> q2s(q2z, q2z + p.Lp);           // q2 itself still normalises the columns of the short-side factor
-    double smax2 = 0.0;
-    for (int i = 0; i < p.Lp; ++i) if (q2z[i] > 0.0) smax2 = std::max(smax2, b2z[i] / q2z[i]);
-    const double ratio = T_SWITCH * (double)ctx->ref_skip_thr;
-    std::vector<double> g;
-    std::vector<unsigned char> above(p.Lp, 0);
-    for (int i = 0; i < p.Lp; ++i) {
-      if (!(b2z[i] > 0.0 && q2z[i] > 0.0 && t2[i] > 0.0)) continue;
-      const double s2 = b2z[i] / q2z[i];
-      const double rho = sqrt(t2[i] * q2z[i]) / b2z[i];            // |T[:, i]| against |b_i| * (|b_i| / |q_i|)
-      if (fabs(rho - 1.0) < DRIFT_TOL && s2 >= ratio * ratio * smax2) { above[i] = 1; g.push_back(b2z[i] * b2z[i] / (q2z[i] * t2[i])); }
-    }
-    double gcal = 1.0;
-    if (g.size() >= 8) { std::sort(g.begin(), g.end()); gcal = g[g.size() / 2]; }
-    for (int i = 0; i < p.Lp; ++i)
-      q2s[i] = above[i] ? b2z[i] * b2z[i] / t2[i] : q2z[i] * gcal;
+    spectrum_rule(p.Lp, b2z, q2s.data(), &t2all[(size_t)z * p.Lp], (double)ctx->ref_skip_thr, false, true, -1, nullptr);
     sort_sigma(p, b2z, q2s.data(), order, sig);
     memcpy(S + (size_t)z * p.L, sig.data(), (size_t)p.L * 4);
     // short-side factor: columns q_i/|q_i|   (rows of Qt), long-side factor: rows b_i/|b_i|
-    // A row of B at or below the Jacobi's numerical-null floor (NULL_ROW_RATIO |A|_F; rotations preserve the Frobenius norm)
-    // is rounding residue of a rank-deficient plane, not a singular direction: its slot is completed below.
-    double f2 = 0.0;
-    for (int i = 0; i < p.Lp; ++i) f2 += b2z[i];
-    const double floor2 = NULL_ROW_RATIO * NULL_ROW_RATIO * f2;
+    // A row of B at or below the Jacobi's numerical-null floor is rounding residue of a rank-deficient plane, not a singular
+    // direction: its slot is completed below.
+    const double floor2 = null_floor2(b2z, p.Lp);
     NullRows nr; nr.z = z; nr.valid.assign(p.Lp, 0);
     for (int i = 0; i < p.Lp; ++i) nr.valid[i] = b2z[i] > floor2 ? 1 : 0;
     for (int k = 0; k < p.L; ++k) {
@@ -2096,12 +2090,12 @@ int wm_ref_extract_planes_u8(wm_ctx* ctx, const uint8_t* stego, const float* sig
   const int L = p.L;
   if (K < 0 || K > L) return set_err(WM_ERR_BADARG, "K must be in 0..min(H,W)");
   RefWs w;
-  const size_t n_in = span_of(n_planes, H, W, row_stride, plane_stride);
+  const size_t n_in = plane_span(n_planes, H, row_stride, plane_stride, W);
   const size_t n_in4 = (n_in + 3) / 4 + 4;
   // tmp1: uint8 stego span | Uw[:L,:L] | Vwt [L][W] | Uw diag(sh) [B][L][L] | result [B][H][W]
   // tmp2: A0 [B][L][M] | T [B][L][Lp], reused afterwards as the GEMM intermediate [B][H][W]
-  WM_TRY(plan_workspace(ctx, p, w, n_in4 + (size_t)L * L + (size_t)L * W + (size_t)n_planes * L * L + (size_t)n_planes * H * W,
-                        std::max((size_t)n_planes * p.L * (p.M + p.Lp), (size_t)n_planes * H * W)));
+  WM_TRY(plan_decompose_ws(ctx, p, w, n_in4 + (size_t)L * L + (size_t)L * W + (size_t)n_planes * L * L + (size_t)n_planes * H * W,
+                           (size_t)n_planes * H * W));
   uint8_t* d_in = (uint8_t*)w.tmp1;
   float* d_u = w.tmp1 + n_in4; float* d_v = d_u + (size_t)L * L; float* d_us = d_v + (size_t)L * W;
   float* d_full = d_us + (size_t)n_planes * L * L;
@@ -2109,8 +2103,7 @@ int wm_ref_extract_planes_u8(wm_ctx* ctx, const uint8_t* stego, const float* sig
   WM_HIP(hipMemcpyAsync(d_u, Uw, (size_t)L * L * 4, hipMemcpyHostToDevice, ctx->stream));            // Uw[:L,:L] (H x L, rows < L)
   WM_HIP(hipMemcpyAsync(d_v, Vwt, (size_t)L * W * 4, hipMemcpyHostToDevice, ctx->stream));           // Vwt [L][W]; [:L,:L] = leading dimension W
   std::vector<float> s_cw((size_t)n_planes * L);
-  WM_TRY(ref_sigma_core(ctx, p, w, d_in, (size_t)row_stride, plane_stride, w.tmp2, w.tmp2 + (size_t)n_planes * p.L * p.M,
-                        s_cw.data()));                                                                   // single:205
+  WM_TRY(ref_sigma_core(ctx, p, w, d_in, (size_t)row_stride, plane_stride, s_cw.data()));                 // single:205
   WM_TRY(ref_extract_core(ctx, p, w, s_cw.data(), sigma_c, d_u, d_v, d_us, w.tmp2, d_full, alpha, K));
   WM_HIP(hipMemcpyAsync(out, d_full, (size_t)n_planes * H * W * 4, hipMemcpyDeviceToHost, ctx->stream));
   WM_HIP(hipStreamSynchronize(ctx->stream));

@@ -1138,7 +1138,7 @@ int get_hier(wm_ctx* ctx, const int nbk, const int sb, const HierTab** out) {
       for (int k = 0; k < ht->nsp; ++k)
         for (int u = 0; u < HU; ++u) units.push_back(tt < (int)st[k].size() ? st[k][tt][u] : -1);
   }
-  const size_t b_sup = (supers.size() * sizeof(HSuper) + 255) & ~(size_t)255, b_un = units.size() * sizeof(int);
+  const size_t b_sup = pad256(supers.size() * sizeof(HSuper)), b_un = units.size() * sizeof(int);
   void* dev = nullptr;
   if (hipMalloc(&dev, b_sup + std::max<size_t>(b_un, 4)) != hipSuccess) {
     (void)hipGetLastError();
@@ -1178,23 +1178,22 @@ inline int* hier_flag_base(int* arr, const size_t ints_per_plane, const int z0, 
 }
 struct HierWs { float* Rpk; int* skipT; float* Gs; float* R; float* partials; int* skip; int* anyrot; int KS; int cps; };
 
-int plan_hier_ws(wm_ctx* ctx, const RefPlan& p, const HierTab& ht, const int planes_per_launch, HierWs& hw) {
+int plan_hier_ws(wm_ctx* ctx, const RefPlan& p, const HierTab& ht, HierWs& hw) {
   // column splits of a Gram tile: enough workgroups to fill the chip, few enough that the partial sums stay a
   // fraction of the rows' own bytes
-  const int ntiles = ht.nmax * RB <= HG_T ? 1 : ht.nmax * RB <= 2 * HG_T ? 3 : HG_TILES;
   const int nchunk = (p.M + HG_KC - 1) / HG_KC;
   int KS = std::min(HG_KS_MAX, std::max(1, nchunk / 4));      // the most any launch may use (hier_ks picks per launch)
   hw.KS = KS; hw.cps = (nchunk + KS - 1) / KS;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += a256(bytes); return o; };
   const size_t B = (size_t)p.B, nsp = (size_t)ht.nsp;
-  constexpr size_t GSLACK = (size_t)(2 + wm_ctx::MAX_AUX) * 256;     // flag arrays: one spare line per plane group (hier_flag_base)
-  const size_t o_k = take(B * HT_MAX * nsp * HU * RP * RP * 4), o_kt = take(B * HT_MAX * nsp * HU * 4 + GSLACK);
-  const size_t o_g = take(B * nsp * HN * HN * 4), o_r = take(B * nsp * HU * RP * RP * 4),
-               o_p = take(B * nsp * HG_TILES * KS * HG_T * HG_T * 4), o_s = take(B * nsp * HU * 4 + GSLACK), o_a = take(B * nsp * 4 + GSLACK);
-  WM_TRY(grow(ctx, &ctx->hier_ws, &ctx->hier_ws_bytes, off, "full-frame two-level workspace"));
-  char* b = (char*)ctx->hier_ws;
-  hw.Rpk = (float*)(b + o_k); hw.skipT = (int*)(b + o_kt); hw.Gs = (float*)(b + o_g); hw.R = (float*)(b + o_r); hw.partials = (float*)(b + o_p);
-  hw.skip = (int*)(b + o_s); hw.anyrot = (int*)(b + o_a);
+  constexpr size_t GSLACK = (size_t)(2 + wm_ctx::MAX_AUX) * 64;      // flag arrays: one spare line per plane group (hier_flag_base)
+  auto carve = [&](Carve cv) {
+    hw.Rpk = cv.take<float>(B * HT_MAX * nsp * HU * RP * RP); hw.skipT = cv.take<int>(B * HT_MAX * nsp * HU + GSLACK);
+    hw.Gs = cv.take<float>(B * nsp * HN * HN); hw.R = cv.take<float>(B * nsp * HU * RP * RP);
+    hw.partials = cv.take<float>(B * nsp * HG_TILES * KS * HG_T * HG_T); hw.skip = cv.take<int>(B * nsp * HU + GSLACK);
+    hw.anyrot = cv.take<int>(B * nsp + GSLACK);
+    return pad256(cv.off);
+  };
+  WM_TRY(grow(ctx, &ctx->hier_ws, &ctx->hier_ws_bytes, carve(Carve{nullptr, 0}), "full-frame two-level workspace"));
+  carve(Carve{(char*)ctx->hier_ws, 0});
   return WM_OK;
 }

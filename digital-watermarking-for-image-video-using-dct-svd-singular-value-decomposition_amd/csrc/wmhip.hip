@@ -915,23 +915,6 @@ inline dim3 tile_grid(const Geom& g, int n_planes) {
 
 }  // namespace
 
-namespace {
-struct Carve {
-  char* base; size_t off;
-  template <typename T> T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline size_t plane_span(int n_planes, int H, int row_stride, size_t plane_stride, int W) {
-  if (n_planes == 0 || H == 0) return 0;
-  return (size_t)(n_planes - 1) * plane_stride + (size_t)(H - 1) * row_stride + (size_t)W;
-}
-}  // namespace
-
 // ===========================================================================
 // C ABI
 // ===========================================================================
