@@ -248,7 +248,6 @@ inline unsigned grid_for(size_t n, unsigned cap = 256 * 8) {
   const size_t g = (n + 255) / 256;
   return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- device tables -----------------------------------------------------------------------------------------------
 constexpr size_t TAB_LUT_BYTES = (size_t)wm_ctx::ENH_SLOTS * wm_ctx::ENH_LUT * sizeof(int);
@@ -421,12 +420,15 @@ int wm_enhance_extract_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int
   WM_TRY(check_plane(ctx, src, dst, H, W));
   if (channels != 1 && channels != 3) return set_err(WM_ERR_BADARG, "the chain takes 1 (gray) or 3 (BGR) channels");
   const size_t n = (size_t)H * W;
-  const size_t seg = up256(n) + up256(2 * n);      // an L plane + an ab pair, or one interleaved BGR / YCrCb image
-  WM_TRY(grow(ctx, &ctx->enh_ws, &ctx->enh_ws_bytes, CLAHE_LUT_BYTES + 3 * seg, "enhance workspace"));
-  uint8_t* luts = (uint8_t*)ctx->enh_ws;
-  uint8_t* A = luts + CLAHE_LUT_BYTES;
-  uint8_t* B = A + seg;
-  uint8_t* C = B + seg;
+  // three segments, each an L plane and the ab pair on the next 256-byte line behind it; from its first byte a segment
+  // also holds one interleaved BGR / YCrCb image (3 n bytes end no later than the ab pair does)
+  uint8_t *luts, *A, *AB, *B, *AB2, *C;
+  WM_TRY(staged(ctx, &ctx->enh_ws, &ctx->enh_ws_bytes, "enhance workspace", [&](Carve& cv) {
+    luts = cv.take<uint8_t>(CLAHE_LUT_BYTES);
+    A = cv.take<uint8_t>(n); AB = cv.take<uint8_t>(2 * n);
+    B = cv.take<uint8_t>(n); AB2 = cv.take<uint8_t>(2 * n);
+    C = cv.take<uint8_t>(3 * n);
+  }));
   if (channels == 1) {
     WM_TRY(nlmeans_launch(ctx, src, A, H, W, 1, 7.0f));
     WM_TRY(clahe_launch(ctx, A, B, H, W, 1, 2.0f, 8, 8, luts));
@@ -436,7 +438,7 @@ int wm_enhance_extract_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int
   LabFwd f;
   LabInv inv;
   WM_TRY(lab_table(ctx, &tab, &f, &inv));
-  uint8_t *L = A, *AB = A + up256(n), *L2 = B, *AB2 = B + up256(n);
+  uint8_t *L = A, *L2 = B;
   hipLaunchKernelGGL(k_lab_fwd, dim3(grid_for(n)), dim3(256), 0, ctx->stream, src, tab, f, L, 1, AB, 2, n);
   WM_HIP(hipGetLastError());
   WM_TRY(nlmeans_launch(ctx, L, L2, H, W, 1, 3.0f));
@@ -453,9 +455,10 @@ int wm_enhance_extract_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int H, 
   WM_TRY(check_plane(ctx, src, dst, H, W));
   if (channels != 1 && channels != 3) return set_err(WM_ERR_BADARG, "the chain takes 1 (gray) or 3 (BGR) channels");
   const size_t bytes = (size_t)H * W * channels;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes, 2 * up256(bytes) + 4096, "scratch"));
-  uint8_t* d_src = (uint8_t*)ctx->scratch;
-  uint8_t* d_dst = d_src + up256(bytes);
+  uint8_t *d_src, *d_dst;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_src = cv.take<uint8_t>(bytes); d_dst = cv.take<uint8_t>(bytes);
+  }));
   WM_HIP(hipMemcpyAsync(d_src, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_enhance_extract_u8_dev(ctx, d_src, d_dst, H, W, channels));
   WM_HIP(hipMemcpyAsync(dst, d_dst, bytes, hipMemcpyDeviceToHost, ctx->stream));

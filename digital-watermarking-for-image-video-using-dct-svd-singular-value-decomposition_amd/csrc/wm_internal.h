@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/wmhip.h"
 
 namespace wmi {
@@ -107,6 +109,23 @@ struct Carve {
   }
 };
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+// A layout stated once: `lay(Carve&)` sets the caller's pointers.  It runs on a null base for the size, the grow-only buffer
+// (*buf, *have) grows to it, and it runs again on the buffer.  Every byte a kernel touches must be part of a take.
+template <typename Lay>
+int staged(wm_ctx* ctx, void** buf, size_t* have, const char* what, Lay&& lay) {
+  Carve cv{nullptr, 0};
+  lay(cv);
+  WM_TRY(grow(ctx, buf, have, pad256(cv.off), what));
+  cv = Carve{(char*)*buf, 0};
+  lay(cv);
+  return WM_OK;
+}
+// runtime bools as template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <typename F> void with_bools(F&& f) { f(); }
+template <typename F, typename... Bs> void with_bools(F&& f, bool b, Bs... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 // elements from the first sample of the first plane to the last sample of the last one
 inline size_t plane_span(int n_planes, int H, int row_stride, size_t plane_stride, int W) {
   if (n_planes == 0 || H == 0) return 0;

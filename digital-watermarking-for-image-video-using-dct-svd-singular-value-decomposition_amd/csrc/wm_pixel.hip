@@ -665,22 +665,16 @@ int wm_unpermute_f32_dev(wm_ctx* ctx, const float* src, const int* idx, float* d
 }
 
 // ---- host-pointer conveniences ------------------------------------------------------
-static int stage(wm_ctx* ctx, size_t bytes, char** base) {
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes, bytes + 4096, "scratch"));
-  *base = (char*)ctx->scratch;
-  return WM_OK;
-}
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int wm_color_u8(wm_ctx* ctx, int op, const uint8_t* in3, const uint8_t* plane_in, uint8_t* out3, uint8_t* plane_out,
                 size_t n_px) {
   WM_TRY(wmi::use_ctx(ctx));
   if (op < 0 || op > 4) return set_err(WM_ERR_BADARG, "unknown colour op");
   if (n_px == 0) return WM_OK;
-  char* b;
-  WM_TRY(stage(ctx, 2 * up256(n_px * 3) + 2 * up256(n_px), &b));
-  uint8_t* d_in3 = (uint8_t*)b; uint8_t* d_out3 = d_in3 + up256(n_px * 3);
-  uint8_t* d_pin = d_out3 + up256(n_px * 3); uint8_t* d_pout = d_pin + up256(n_px);
+  uint8_t *d_in3, *d_out3, *d_pin, *d_pout;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_in3 = cv.take<uint8_t>(n_px * 3); d_out3 = cv.take<uint8_t>(n_px * 3);
+    d_pin = cv.take<uint8_t>(n_px); d_pout = cv.take<uint8_t>(n_px);
+  }));
   if (!in3) return set_err(WM_ERR_BADARG, "input is NULL");
   WM_HIP(hipMemcpyAsync(d_in3, in3, n_px * 3, hipMemcpyHostToDevice, ctx->stream));
   if (op == Y_INTO_YCC_TO_BGR) {
@@ -704,10 +698,10 @@ int wm_psnr_u8(wm_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, double
   WM_TRY(wmi::use_ctx(ctx));
   if (n == 0) { *psnr_out = 99.0; return WM_OK; }
   if (!a || !b) return set_err(WM_ERR_BADARG, "NULL argument");
-  char* base;
-  WM_TRY(stage(ctx, 2 * up256(n) + 256, &base));
-  uint8_t* da = (uint8_t*)base; uint8_t* db = da + up256(n);
-  unsigned long long* d_ssd = (unsigned long long*)(db + up256(n));
+  uint8_t *da, *db; unsigned long long* d_ssd;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    da = cv.take<uint8_t>(n); db = cv.take<uint8_t>(n); d_ssd = cv.take<unsigned long long>(1);
+  }));
   WM_HIP(hipMemcpyAsync(da, a, n, hipMemcpyHostToDevice, ctx->stream));
   WM_HIP(hipMemcpyAsync(db, b, n, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_sqdiff_u8_dev(ctx, da, db, n, d_ssd));
@@ -726,9 +720,10 @@ int wm_ssim(wm_ctx* ctx, const void* img1, const void* img2, int H, int W, int k
   if (H <= 0 || W <= 0) return set_err(WM_ERR_BADARG, "H and W must be positive");
   const size_t n = (size_t)H * W;
   const size_t b1 = n * ((kind & 1) ? 4 : 1), b2 = n * ((kind & 2) ? 4 : 1);
-  char* base;
-  WM_TRY(stage(ctx, up256(b1) + up256(b2) + 256, &base));
-  char* d1 = base; char* d2 = d1 + up256(b1); double* d_s = (double*)(d2 + up256(b2));
+  char *d1, *d2; double* d_s;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d1 = cv.take<char>(b1); d2 = cv.take<char>(b2); d_s = cv.take<double>(1);
+  }));
   WM_HIP(hipMemcpyAsync(d1, img1, b1, hipMemcpyHostToDevice, ctx->stream));
   WM_HIP(hipMemcpyAsync(d2, img2, b2, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_ssim_dev(ctx, d1, (size_t)W, d2, (size_t)W, H, W, kind, d_s));
@@ -743,9 +738,10 @@ int wm_normalize_u8(wm_ctx* ctx, const float* x, size_t n, int do_norm, uint8_t*
   WM_TRY(wmi::use_ctx(ctx));
   if (n == 0) return WM_OK;
   if (!x || !out) return set_err(WM_ERR_BADARG, "NULL argument");
-  char* base;
-  WM_TRY(stage(ctx, up256(n * 4) + up256(n), &base));
-  float* dx = (float*)base; uint8_t* dout = (uint8_t*)(base + up256(n * 4));
+  float* dx; uint8_t* dout;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    dx = cv.take<float>(n); dout = cv.take<uint8_t>(n);
+  }));
   WM_HIP(hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_normalize_u8_dev(ctx, dx, n, do_norm, dout));
   WM_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -1040,19 +1040,16 @@ int get_pairs(wm_ctx* ctx, const RefPlan& p, const int2** out) {
 // first call's arrays stay where they are)
 int plan_workspace(wm_ctx* ctx, const RefPlan& p, RefWs& w, size_t extra_f32_a, size_t extra_f32_b, int which = 0) {
   const size_t B = (size_t)p.B;
-  auto carve = [&](Carve cv) {
+  auto lay = [&](Carve& cv) {
     w.aug = cv.take<float>(B * p.aug_ps); w.partials = cv.take<float>(B * p.npairs * p.nch * GRAM_PART);
     w.R = cv.take<float>(B * p.npairs * RP * RP);
     w.maxcos = cv.take<unsigned>(B + 64); w.floor2 = cv.take<float>(B + 64);
     w.skip = cv.take<int>(B * p.npairs + (size_t)(2 + wm_ctx::MAX_AUX) * 64); w.b2 = cv.take<double>(B * p.Lp); w.q2 = cv.take<double>(B * p.Lp);
     w.dvec = cv.take<float>(2 * B * p.Lp); w.order = cv.take<int>((size_t)p.Lp); w.scale = cv.take<float>((size_t)p.Lp);
     w.tmp1 = cv.take<float>(extra_f32_a); w.tmp2 = cv.take<float>(extra_f32_b);
-    return pad256(cv.off);
   };
-  const size_t bytes = carve(Carve{nullptr, 0});
-  if (which == 0) WM_TRY(grow(ctx, &ctx->ref_ws, &ctx->ref_ws_bytes, bytes, "full-frame workspace"));
-  else WM_TRY(grow(ctx, &ctx->ref_ws2, &ctx->ref_ws2_bytes, bytes, "full-frame completion workspace"));
-  carve(Carve{(char*)(which == 0 ? ctx->ref_ws : ctx->ref_ws2), 0});
+  if (which == 0) WM_TRY(staged(ctx, &ctx->ref_ws, &ctx->ref_ws_bytes, "full-frame workspace", lay));
+  else WM_TRY(staged(ctx, &ctx->ref_ws2, &ctx->ref_ws2_bytes, "full-frame completion workspace", lay));
   w.a0 = w.t = nullptr;
   WM_TRY(get_pairs(ctx, p, &w.pairs));
   return WM_OK;

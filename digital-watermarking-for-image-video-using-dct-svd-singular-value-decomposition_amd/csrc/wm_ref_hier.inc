@@ -1186,14 +1186,10 @@ int plan_hier_ws(wm_ctx* ctx, const RefPlan& p, const HierTab& ht, HierWs& hw) {
   hw.KS = KS; hw.cps = (nchunk + KS - 1) / KS;
   const size_t B = (size_t)p.B, nsp = (size_t)ht.nsp;
   constexpr size_t GSLACK = (size_t)(2 + wm_ctx::MAX_AUX) * 64;      // flag arrays: one spare line per plane group (hier_flag_base)
-  auto carve = [&](Carve cv) {
+  return staged(ctx, &ctx->hier_ws, &ctx->hier_ws_bytes, "full-frame two-level workspace", [&](Carve& cv) {
     hw.Rpk = cv.take<float>(B * HT_MAX * nsp * HU * RP * RP); hw.skipT = cv.take<int>(B * HT_MAX * nsp * HU + GSLACK);
     hw.Gs = cv.take<float>(B * nsp * HN * HN); hw.R = cv.take<float>(B * nsp * HU * RP * RP);
     hw.partials = cv.take<float>(B * nsp * HG_TILES * KS * HG_T * HG_T); hw.skip = cv.take<int>(B * nsp * HU + GSLACK);
     hw.anyrot = cv.take<int>(B * nsp + GSLACK);
-    return pad256(cv.off);
-  };
-  WM_TRY(grow(ctx, &ctx->hier_ws, &ctx->hier_ws_bytes, carve(Carve{nullptr, 0}), "full-frame two-level workspace"));
-  carve(Carve{(char*)ctx->hier_ws, 0});
-  return WM_OK;
+  });
 }

@@ -240,8 +240,6 @@ __global__ void k_copy_tail(const uint8_t* __restrict__ src, uint8_t* __restrict
   if (i < n) dst[i] = src[i];
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 namespace wmi {
@@ -254,12 +252,13 @@ int route_unpermute_normalize(wm_ctx* ctx, const float* src, const wm_route* r, 
   if (r->device != ctx->device) return set_err(WM_ERR_BADARG, "the route lives on another device");
   if (n_planes == 0) return WM_OK;
   if (!src || !dst) return set_err(WM_ERR_BADARG, "NULL argument");
-  WM_TRY(grow(ctx, &ctx->route_tmp, &ctx->route_tmp_bytes, (size_t)n_planes * n + (size_t)n_planes * MM_BLOCKS * 8 + 256, "route staging"));
-  uint8_t* tmp = (uint8_t*)ctx->route_tmp;
+  uint8_t* tmp; unsigned* mm_own;
+  WM_TRY(staged(ctx, &ctx->route_tmp, &ctx->route_tmp_bytes, "route staging", [&](Carve& cv) {
+    tmp = cv.take<uint8_t>((size_t)n_planes * n); mm_own = cv.take<unsigned>((size_t)n_planes * MM_BLOCKS * 2);
+  }));
   const unsigned* mm = mm_ext;
   unsigned n_part = n_part_ext;
   if (do_norm && !mm_ext) {
-    unsigned* mm_own = (unsigned*)((char*)ctx->route_tmp + a256((size_t)n_planes * n));
     n_part = (unsigned)std::min<size_t>(MM_BLOCKS, (n / 4 + 256) / 256);
     hipLaunchKernelGGL(k_minmax_planes, dim3(n_part, n_planes), dim3(256), 0, ctx->stream, src, n, mm_own);
     mm = mm_own;
@@ -287,7 +286,7 @@ int wm_route_create_dev(wm_ctx* ctx, const int* idx, size_t n, wm_route** route_
   if (!r) return set_err(WM_ERR_NOMEM, "host allocation failed for %s", "route");
   r->n = n; r->log_s = ROUTE_LOG_S; r->S = S; r->nb = (int)nb; r->device = ctx->device;
   size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += a256(bytes); return o; };
+  auto take = [&](size_t bytes) { const size_t o = off; off += pad256(bytes); return o; };
   const size_t o_l1 = take(n * 2), o_bkt = take(nb * S * 2), o_l2 = take(n * 2), o_lrs = take(nb * (nb + 1) * 4),
                o_cs = take(nb * nb * 4), o_cnt = take(nb * nb * 4), o_bad = take(256), o_seen = take((n + 31) / 32 * 4);
   if (hipMalloc(&r->base, off) != hipSuccess) {
@@ -360,8 +359,8 @@ int wm_permute_u8_f32_routed_dev(wm_ctx* ctx, const uint8_t* src, const wm_route
   if (r->device != ctx->device) return set_err(WM_ERR_BADARG, "the route lives on another device");
   if (n_planes == 0) return WM_OK;
   if (!src || !dst) return set_err(WM_ERR_BADARG, "NULL argument");
-  WM_TRY(grow(ctx, &ctx->route_tmp, &ctx->route_tmp_bytes, (size_t)n_planes * n + 256, "route staging"));
-  uint8_t* tmp = (uint8_t*)ctx->route_tmp;
+  uint8_t* tmp;
+  WM_TRY(staged(ctx, &ctx->route_tmp, &ctx->route_tmp_bytes, "route staging", [&](Carve& cv) { tmp = cv.take<uint8_t>((size_t)n_planes * n); }));
   hipLaunchKernelGGL(k_route_ga, dim3(r->nb, n_planes), dim3(ROUTE_NT), (size_t)r->S, ctx->stream, src, n, r->log_s, r->l2, tmp);
   hipLaunchKernelGGL(k_route_gb, dim3(r->nb, n_planes), dim3(ROUTE_NT), (size_t)(2 * r->nb + 2) * 4 + r->S, ctx->stream, tmp, n,
                      r->log_s, r->nb, r->l1, r->bkt, r->lrs, r->cstart, dst);

@@ -1091,34 +1091,28 @@ int wm_embed_tiles_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w
     if (cap > 0x7fffffffull) return set_err(WM_ERR_BADARG, "more than 2^31 tiles in one call");
     // kind 3 keeps its tiles' B (256 bytes each): its sub-lists hold cap / 16 entries (>= 64), the rest takes the literal chain
     const size_t cap3 = std::max<size_t>(WAVE, cap / 16);
-    const size_t list_bytes = ((size_t)3 * FB_SUB * cap + (size_t)FB_SUB * cap3) * sizeof(uint32_t);
-    const size_t cnt_bytes = (size_t)FB_KINDS * FB_SUB * FB_PAD * sizeof(int);
-    const size_t b_off = (list_bytes + cnt_bytes + 255) & ~(size_t)255;
-    WM_TRY(grow(ctx, &ctx->fb_list, &ctx->fb_bytes, b_off + (size_t)FB_SUB * cap3 * 64 * sizeof(float), "fallback lists"));
-    uint32_t* fb = (uint32_t*)ctx->fb_list;
-    int* fb_cnt = (int*)((char*)ctx->fb_list + list_bytes);
-    float* fb_b = (float*)((char*)ctx->fb_list + b_off);
+    const size_t n_cnt = (size_t)FB_KINDS * FB_SUB * FB_PAD;
+    uint32_t* fb; int* fb_cnt; float* fb_b;
+    WM_TRY(staged(ctx, &ctx->fb_list, &ctx->fb_bytes, "fallback lists", [&](Carve& cv) {
+      fb = cv.take<uint32_t>((size_t)3 * FB_SUB * cap + (size_t)FB_SUB * cap3);
+      fb_cnt = cv.take<int>(n_cnt);
+      fb_b = cv.take<float>((size_t)FB_SUB * cap3 * 64);
+    }));
     const uint32_t fb_cap3 = (uint32_t)cap3;
-    WM_HIP(hipMemsetAsync(fb_cnt, 0, cnt_bytes, ctx->stream));
+    WM_HIP(hipMemsetAsync(fb_cnt, 0, n_cnt * sizeof(int), ctx->stream));
     const uint32_t fb_cap = (uint32_t)cap;
     const dim3 fgrid((unsigned)(n_waves < 2048 ? n_waves : 2048));
-#define WM_LAUNCH_EMBED(A, Y)                                                                      \
-  do {                                                                                             \
-    hipLaunchKernelGGL((k_embed_tiles<A, Y>), grid, block, 0, ctx->stream, host, sigma_w, stego,   \
-                       sigma_c, yw, g, n_groups, sigma_w_plane_stride, alpha, K,                   \
-                       ctx->d_status, fb, fb_cnt, fb_cap, fb_b, fb_cap3);                           \
-    hipLaunchKernelGGL((k_embed_fallback<A, Y>), fgrid, block, 0, ctx->stream, host, sigma_w,      \
-                       stego, sigma_c, yw, g, sigma_w_plane_stride, alpha, K, ctx->d_status, fb,   \
-                       fb_cnt, fb_cap, fb_b, fb_cap3);                                             \
-    hipLaunchKernelGGL((k_embed_one_small<A, Y>), fgrid, block, 0, ctx->stream, host, sigma_w,     \
-                       stego, sigma_c, yw, g, sigma_w_plane_stride, alpha, K, ctx->d_status, fb,   \
-                       fb_cnt, fb_cap, fb_b, fb_cap3);                                             \
-  } while (0)
-    if (al && yw) WM_LAUNCH_EMBED(true, true);
-    else if (al) WM_LAUNCH_EMBED(true, false);
-    else if (yw) WM_LAUNCH_EMBED(false, true);
-    else WM_LAUNCH_EMBED(false, false);
-#undef WM_LAUNCH_EMBED
+    with_bools([&](auto A, auto Y) {
+      hipLaunchKernelGGL((k_embed_tiles<A.value, Y.value>), grid, block, 0, ctx->stream, host, sigma_w, stego,
+                         sigma_c, yw, g, n_groups, sigma_w_plane_stride, alpha, K,
+                         ctx->d_status, fb, fb_cnt, fb_cap, fb_b, fb_cap3);
+      hipLaunchKernelGGL((k_embed_fallback<A.value, Y.value>), fgrid, block, 0, ctx->stream, host, sigma_w,
+                         stego, sigma_c, yw, g, sigma_w_plane_stride, alpha, K, ctx->d_status, fb,
+                         fb_cnt, fb_cap, fb_b, fb_cap3);
+      hipLaunchKernelGGL((k_embed_one_small<A.value, Y.value>), fgrid, block, 0, ctx->stream, host, sigma_w,
+                         stego, sigma_c, yw, g, sigma_w_plane_stride, alpha, K, ctx->d_status, fb,
+                         fb_cnt, fb_cap, fb_b, fb_cap3);
+    }, al, yw != nullptr);
     WM_HIP(hipGetLastError());
   }
   const int Hb = (H / 8) * 8, Wb = (W / 8) * 8;
@@ -1140,10 +1134,9 @@ int wm_sigma_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, float* sigma, int 
   if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
   if (!sigma || ((uintptr_t)sigma & 15u)) return set_err(WM_ERR_BADARG, "sigma is NULL or not 16-byte aligned");
   const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  if (u8_aligned(planes, planes, row_stride, plane_stride))
-    hipLaunchKernelGGL((k_sigma_tiles<true>), grid, block, 0, ctx->stream, planes, sigma, g, ctx->d_status);
-  else
-    hipLaunchKernelGGL((k_sigma_tiles<false>), grid, block, 0, ctx->stream, planes, sigma, g, ctx->d_status);
+  with_bools([&](auto A) {
+    hipLaunchKernelGGL((k_sigma_tiles<A.value>), grid, block, 0, ctx->stream, planes, sigma, g, ctx->d_status);
+  }, u8_aligned(planes, planes, row_stride, plane_stride));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1157,10 +1150,9 @@ int wm_svd_tiles_f32_dev(wm_ctx* ctx, const float* planes, float* U, float* S, f
   if (!U || !S || !Vt || (((uintptr_t)U | (uintptr_t)S | (uintptr_t)Vt) & 15u))
     return set_err(WM_ERR_BADARG, "U/S/Vt is NULL or not 16-byte aligned");
   const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  if (f32_vec_ok(planes, (size_t)row_stride, plane_stride))
-    hipLaunchKernelGGL((k_svd_tiles<true>), grid, block, 0, ctx->stream, planes, U, S, Vt, g, ctx->d_status);
-  else
-    hipLaunchKernelGGL((k_svd_tiles<false>), grid, block, 0, ctx->stream, planes, U, S, Vt, g, ctx->d_status);
+  with_bools([&](auto V) {
+    hipLaunchKernelGGL((k_svd_tiles<V.value>), grid, block, 0, ctx->stream, planes, U, S, Vt, g, ctx->d_status);
+  }, f32_vec_ok(planes, (size_t)row_stride, plane_stride));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1187,25 +1179,10 @@ static int extract_tiles_dev(wm_ctx* ctx, const uint8_t* stego, const float* sig
   if ((((size_t)g.n_tiles + WAVE - 1) / WAVE + N_XCD) * (size_t)n_planes > 0x7fffffffull)
     return set_err(WM_ERR_BADARG, "more than 2^31 tile groups in one call");
   const dim3 grid = tile_grid_planefast(g, n_planes), block(WAVE);
-#define WM_LAUNCH_EXTRACT(A, V, P)                                                                    \
-  do {                                                                                                \
-    if (mm) hipLaunchKernelGGL((k_extract_tiles<A, V, P, true>), grid, block, 0, ctx->stream, stego, sigma_c, Uw, Vwt, \
-                               out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm); \
-    else hipLaunchKernelGGL((k_extract_tiles<A, V, P, false>), grid, block, 0, ctx->stream, stego, sigma_c, Uw, Vwt, \
-                            out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm); \
-  } while (0)
-  if (px) {
-    if (al && vf) WM_LAUNCH_EXTRACT(true, true, true);
-    else if (al) WM_LAUNCH_EXTRACT(true, false, true);
-    else if (vf) WM_LAUNCH_EXTRACT(false, true, true);
-    else WM_LAUNCH_EXTRACT(false, false, true);
-  } else {
-    if (al && vf) WM_LAUNCH_EXTRACT(true, true, false);
-    else if (al) WM_LAUNCH_EXTRACT(true, false, false);
-    else if (vf) WM_LAUNCH_EXTRACT(false, true, false);
-    else WM_LAUNCH_EXTRACT(false, false, false);
-  }
-#undef WM_LAUNCH_EXTRACT
+  with_bools([&](auto P, auto A, auto V, auto M) {
+    hipLaunchKernelGGL((k_extract_tiles<A.value, V.value, P.value, M.value>), grid, block, 0, ctx->stream, stego, sigma_c, Uw, Vwt,
+                       out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm);
+  }, px, al, vf, mm != nullptr);
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1235,11 +1212,11 @@ int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float
   const size_t n = (size_t)H * W;
   const Geom g = make_geom(H, W, row_stride, plane_stride);
   const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE;
-  const size_t f_bytes = ((size_t)n_planes * n * sizeof(float) + 255) & ~(size_t)255;
-  WM_TRY(grow(ctx, &ctx->extract_f32, &ctx->extract_f32_bytes, f_bytes + (size_t)n_planes * (groups + 1) * 2 * sizeof(unsigned) + 256,
-              "extract staging"));
-  float* w = (float*)ctx->extract_f32;
-  unsigned* mm = (unsigned*)((char*)ctx->extract_f32 + f_bytes);
+  float* w; unsigned* mm;      // the estimate, then one {min, max} pair per plane and tile group (k_extract_tiles<MM> writes grp < groups only)
+  WM_TRY(staged(ctx, &ctx->extract_f32, &ctx->extract_f32_bytes, "extract staging", [&](Carve& cv) {
+    w = cv.take<float>((size_t)n_planes * n);
+    mm = cv.take<unsigned>((size_t)n_planes * groups * 2);
+  }));
   const bool use_mm = do_norm && g.n_tiles > 0;
   WM_TRY(extract_tiles_dev(ctx, stego, sigma_c, Uw, Vwt, w, n_planes, H, W, row_stride, plane_stride, uv_plane_stride, alpha, K,
                            px != 0, use_mm ? mm : nullptr));
@@ -1275,10 +1252,9 @@ int wm_reconstruct_tiles_dev(wm_ctx* ctx, const float* Uw, const float* sw_hat, 
   if (!Uw || !sw_hat || !Vwt || (((uintptr_t)Uw | (uintptr_t)sw_hat | (uintptr_t)Vwt) & 15u))
     return set_err(WM_ERR_BADARG, "Uw/sw_hat/Vwt is NULL or not 16-byte aligned");
   const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  if (f32_vec_ok(out, (size_t)W, g.HW))
-    hipLaunchKernelGGL((k_reconstruct_tiles<true>), grid, block, 0, ctx->stream, Uw, sw_hat, Vwt, out, g);
-  else
-    hipLaunchKernelGGL((k_reconstruct_tiles<false>), grid, block, 0, ctx->stream, Uw, sw_hat, Vwt, out, g);
+  with_bools([&](auto V) {
+    hipLaunchKernelGGL((k_reconstruct_tiles<V.value>), grid, block, 0, ctx->stream, Uw, sw_hat, Vwt, out, g);
+  }, f32_vec_ok(out, (size_t)W, g.HW));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1301,12 +1277,10 @@ int wm_detect_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma
                 (size_t)n_planes * n_waves * N_SUMS * sizeof(double), "detect partial sums"));
     const float inv_alpha = 1.0f / fmaxf(alpha, 1e-8f);
     const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-    if (u8_aligned(stego, stego, row_stride, plane_stride))
-      hipLaunchKernelGGL((k_detect_tiles<true>), grid, block, 0, ctx->stream, stego, sigma_c, sigma_w,
+    with_bools([&](auto A) {
+      hipLaunchKernelGGL((k_detect_tiles<A.value>), grid, block, 0, ctx->stream, stego, sigma_c, sigma_w,
                          (double*)ctx->partials, g, sigma_w_plane_stride, inv_alpha, ctx->d_status);
-    else
-      hipLaunchKernelGGL((k_detect_tiles<false>), grid, block, 0, ctx->stream, stego, sigma_c, sigma_w,
-                         (double*)ctx->partials, g, sigma_w_plane_stride, inv_alpha, ctx->d_status);
+    }, u8_aligned(stego, stego, row_stride, plane_stride));
     WM_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(k_detect_finalize, dim3((unsigned)n_planes), dim3(256), 0, ctx->stream,
@@ -1332,14 +1306,14 @@ int wm_embed_tiles_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, ui
   const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
   const size_t n_sc = (size_t)n_planes * nt * 8;
   const size_t n_yw = yw ? (size_t)n_planes * H * W : 0;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes,
-              2 * pad256(span) + pad256(n_sw * 4) + pad256(n_sc * 4) + pad256(n_yw * 4) + 2048, "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  uint8_t* d_host = cv.take<uint8_t>(span);
-  uint8_t* d_stego = cv.take<uint8_t>(span);
-  float* d_sw = cv.take<float>(n_sw);
-  float* d_sc = cv.take<float>(n_sc);
-  float* d_yw = yw ? cv.take<float>(n_yw) : nullptr;
+  uint8_t *d_host, *d_stego; float *d_sw, *d_sc, *d_yw;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_host = cv.take<uint8_t>(span);
+    d_stego = cv.take<uint8_t>(span);
+    d_sw = cv.take<float>(n_sw);
+    d_sc = cv.take<float>(n_sc);
+    d_yw = yw ? cv.take<float>(n_yw) : nullptr;
+  }));
   WM_HIP(hipMemcpyAsync(d_host, host, span, hipMemcpyHostToDevice, ctx->stream));
   // bytes between rows / planes that belong to the caller must survive the round trip
   if (stego != host) WM_HIP(hipMemcpyAsync(d_stego, stego, span, hipMemcpyHostToDevice, ctx->stream));
@@ -1361,10 +1335,11 @@ int wm_sigma_tiles_u8(wm_ctx* ctx, const uint8_t* planes, float* sigma, int n_pl
   if (!sigma) return set_err(WM_ERR_BADARG, "sigma is NULL");
   const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
   const size_t n_s = (size_t)n_planes * nt * 8;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes, pad256(span) + pad256(n_s * 4) + 1024, "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  uint8_t* d_p = cv.take<uint8_t>(span);
-  float* d_s = cv.take<float>(n_s);
+  uint8_t* d_p; float* d_s;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_s = cv.take<float>(n_s);
+  }));
   WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_sigma_tiles_u8_dev(ctx, d_p, d_s, n_planes, H, W, row_stride, plane_stride));
   WM_HIP(hipMemcpyAsync(sigma, d_s, n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1379,13 +1354,13 @@ int wm_svd_tiles_f32(wm_ctx* ctx, const float* planes, float* U, float* S, float
   if (!U || !S || !Vt) return set_err(WM_ERR_BADARG, "U/S/Vt is NULL");
   const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
   const size_t n_m = (size_t)n_planes * nt * 64, n_s = (size_t)n_planes * nt * 8;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes,
-              pad256(span * 4) + 2 * pad256(n_m * 4) + pad256(n_s * 4) + 2048, "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  float* d_p = cv.take<float>(span);
-  float* d_U = cv.take<float>(n_m);
-  float* d_V = cv.take<float>(n_m);
-  float* d_S = cv.take<float>(n_s);
+  float *d_p, *d_U, *d_V, *d_S;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<float>(span);
+    d_U = cv.take<float>(n_m);
+    d_V = cv.take<float>(n_m);
+    d_S = cv.take<float>(n_s);
+  }));
   WM_HIP(hipMemcpyAsync(d_p, planes, span * 4, hipMemcpyHostToDevice, ctx->stream));
   WM_TRY(wm_svd_tiles_f32_dev(ctx, d_p, d_U, d_S, d_V, n_planes, H, W, row_stride, plane_stride));
   WM_HIP(hipMemcpyAsync(U, d_U, n_m * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1406,15 +1381,15 @@ static int extract_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* si
   const size_t n_sc = (size_t)n_planes * nt * 8;
   const size_t n_uv = (uv_plane_stride ? (size_t)n_planes : (size_t)1) * nt * 64;
   const size_t hw = (size_t)H * W, n_out = (size_t)n_planes * hw;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes,
-              pad256(span) + pad256(n_sc * 4) + 2 * pad256(n_uv * 4) + pad256(n_out * 4) + pad256(hw * 4) + 2048, "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  uint8_t* d_p = cv.take<uint8_t>(span);
-  float* d_sc = cv.take<float>(n_sc);
-  float* d_U = cv.take<float>(n_uv);
-  float* d_V = cv.take<float>(n_uv);
-  float* d_o = cv.take<float>(n_out);
-  float* d_sum = cv.take<float>(hw);
+  uint8_t* d_p; float *d_sc, *d_U, *d_V, *d_o, *d_sum;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_sc = cv.take<float>(n_sc);
+    d_U = cv.take<float>(n_uv);
+    d_V = cv.take<float>(n_uv);
+    d_o = cv.take<float>(n_out);
+    d_sum = cv.take<float>(hw);
+  }));
   WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
   if (nt) {
     WM_HIP(hipMemcpyAsync(d_sc, sigma_c, n_sc * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1458,13 +1433,13 @@ int wm_reconstruct_tiles(wm_ctx* ctx, const float* Uw, const float* sw_hat, cons
   if (nt > 0 && (!Uw || !sw_hat || !Vwt)) return set_err(WM_ERR_BADARG, "Uw/sw_hat/Vwt is NULL");
   const size_t n_m = (size_t)n_planes * nt * 64, n_s = (size_t)n_planes * nt * 8;
   const size_t n_out = (size_t)n_planes * H * W;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes,
-              2 * pad256(n_m * 4) + pad256(n_s * 4) + pad256(n_out * 4) + 2048, "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  float* d_U = cv.take<float>(n_m);
-  float* d_V = cv.take<float>(n_m);
-  float* d_s = cv.take<float>(n_s);
-  float* d_o = cv.take<float>(n_out);
+  float *d_U, *d_V, *d_s, *d_o;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_U = cv.take<float>(n_m);
+    d_V = cv.take<float>(n_m);
+    d_s = cv.take<float>(n_s);
+    d_o = cv.take<float>(n_out);
+  }));
   if (nt) {
     WM_HIP(hipMemcpyAsync(d_U, Uw, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
     WM_HIP(hipMemcpyAsync(d_V, Vwt, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1487,14 +1462,13 @@ int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, 
   const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
   const size_t n_sc = (size_t)n_planes * nt * 8;
   const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
-  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes,
-              pad256(span) + pad256(n_sc * 4) + pad256(n_sw * 4) + pad256((size_t)n_planes * 8) + 2048,
-              "scratch"));
-  Carve cv{(char*)ctx->scratch, 0};
-  uint8_t* d_p = cv.take<uint8_t>(span ? span : 1);
-  float* d_sc = cv.take<float>(n_sc);
-  float* d_sw = cv.take<float>(n_sw);
-  double* d_scores = cv.take<double>((size_t)n_planes);
+  uint8_t* d_p; float *d_sc, *d_sw; double* d_scores;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span ? span : 1);
+    d_sc = cv.take<float>(n_sc);
+    d_sw = cv.take<float>(n_sw);
+    d_scores = cv.take<double>((size_t)n_planes);
+  }));
   if (span) WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
   if (nt) {
     WM_HIP(hipMemcpyAsync(d_sc, sigma_c, n_sc * 4, hipMemcpyHostToDevice, ctx->stream));
