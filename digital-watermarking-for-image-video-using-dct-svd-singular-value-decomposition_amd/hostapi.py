@@ -187,6 +187,30 @@ def _plane_layout(a: np.ndarray):
     return n, H, W, rs, ps
 
 
+def _p(a):
+    """an array's address as the ABI takes it; None (an output the caller does not want) stays None"""
+    return None if a is None else _vp(a.ctypes.data)
+
+
+def _f32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _dense(a: np.ndarray, dtype, ndim: int, what: str):
+    """a [H, W] (ndim 2) or [N, H, W] (ndim 3) input of the given dtype, made dense -> (array, H, W, min(H, W))"""
+    if a.dtype != dtype or a.ndim != ndim:
+        raise ValueError(what)
+    H, W = a.shape[-2:]
+    return np.ascontiguousarray(a), H, W, min(H, W)
+
+
+def _planes_of(a: np.ndarray, dtype, what: str):
+    """_plane_layout of a [H, W] / [N, H, W] input of the given dtype, which may be strided"""
+    if a.dtype != dtype:
+        raise ValueError(what)
+    return _plane_layout(a)
+
+
 class Context:
     """One device + one HIP stream (wm_ctx).  ``stream`` may be a raw
     hipStream_t handle (e.g. ``torch.cuda.current_stream().cuda_stream``)."""
@@ -243,12 +267,12 @@ class Context:
 
     def h2d(self, dptr: int, arr: np.ndarray):
         arr = np.ascontiguousarray(arr)
-        self._call("wm_memcpy_h2d", _vp(dptr), _vp(arr.ctypes.data), arr.nbytes)
+        self._call("wm_memcpy_h2d", _vp(dptr), _p(arr), arr.nbytes)
         self.sync()
 
     def d2h(self, arr: np.ndarray, dptr: int):
         assert arr.flags.c_contiguous
-        self._call("wm_memcpy_d2h", _vp(arr.ctypes.data), _vp(dptr), arr.nbytes)
+        self._call("wm_memcpy_d2h", _p(arr), _vp(dptr), arr.nbytes)
 
     def copy_mapped(self, dst: int, src: int, nbytes: int, n_workgroups: int = 0):
         """async copy kernel between device memory and mapped pinned host memory (either direction) on this stream"""
@@ -323,11 +347,9 @@ class Context:
                     want_yw: bool = False):
         """host uint8 [H,W] or [N,H,W]; sigma_w float32 [nby,nbx,8] (shared) or
         [N,nby,nbx,8].  Returns (stego uint8, sigma_c float32 [N?,nby,nbx,8], yw or None)."""
-        if host.dtype != np.uint8:
-            raise ValueError("host planes must be uint8")
-        n, H, W, rs, ps = _plane_layout(host)
+        n, H, W, rs, ps = _planes_of(host, np.uint8, "host planes must be uint8")
         nby, nbx = H // TILE, W // TILE
-        sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        sw = _f32(sigma_w)
         per_plane = sw.ndim == 4
         if sw.shape[-3:] != (nby, nbx, 8) or (per_plane and sw.shape[0] != n):
             raise ValueError(f"sigma_w shape {sw.shape} does not match {n}x{nby}x{nbx}x8")
@@ -336,129 +358,103 @@ class Context:
         yw = np.empty((n, H, W), np.float32) if want_yw else None
         # stego is dense; host may be strided -> densify so both share one layout
         hostc = np.ascontiguousarray(host.reshape(n, H, W))
-        self._call("wm_embed_tiles_u8", _vp(hostc.ctypes.data), _vp(sw.ctypes.data), _vp(stego.ctypes.data),
-                   _vp(sc.ctypes.data), _vp(yw.ctypes.data) if want_yw else None, n, H, W, W, H * W,
+        self._call("wm_embed_tiles_u8", _p(hostc), _p(sw), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W,
                    nby * nbx * 8 if per_plane else 0, float(alpha), int(K))
         if host.ndim == 2:
             return stego[0], sc[0], (yw[0] if want_yw else None)
         return stego, sc, yw
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
-        if planes.dtype != np.uint8:
-            raise ValueError("planes must be uint8")
-        n, H, W, rs, ps = _plane_layout(planes)
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
         s = np.empty((n, H // TILE, W // TILE, 8), np.float32)
-        self._call("wm_sigma_tiles_u8", _vp(planes.ctypes.data), _vp(s.ctypes.data), n, H, W, rs, ps)
+        self._call("wm_sigma_tiles_u8", _p(planes), _p(s), n, H, W, rs, ps)
         return s[0] if planes.ndim == 2 else s
 
     def svd_tiles(self, planes: np.ndarray):
         """float32 planes -> (U [..,nby,nbx,8,8], S [..,nby,nbx,8], Vt [..,nby,nbx,8,8])."""
-        if planes.dtype != np.float32:
-            raise ValueError("planes must be float32")
-        n, H, W, rs, ps = _plane_layout(planes)
+        n, H, W, rs, ps = _planes_of(planes, np.float32, "planes must be float32")
         nby, nbx = H // TILE, W // TILE
         U = np.empty((n, nby, nbx, 8, 8), np.float32)
         S = np.empty((n, nby, nbx, 8), np.float32)
         Vt = np.empty((n, nby, nbx, 8, 8), np.float32)
-        self._call("wm_svd_tiles_f32", _vp(planes.ctypes.data), _vp(U.ctypes.data), _vp(S.ctypes.data),
-                   _vp(Vt.ctypes.data), n, H, W, rs, ps)
+        self._call("wm_svd_tiles_f32", _p(planes), _p(U), _p(S), _p(Vt), n, H, W, rs, ps)
         if planes.ndim == 2:
             return U[0], S[0], Vt[0]
         return U, S, Vt
+
+    @staticmethod
+    def _sigma_c_tiles(sigma_c, n: int, nby: int, nbx: int) -> np.ndarray:
+        sc = _f32(sigma_c)
+        if sc.size != n * nby * nbx * 8:
+            raise ValueError(f"sigma_c has {sc.size} values, the planes need {n}x{nby}x{nbx}x8")
+        return sc.reshape(n, nby, nbx, 8)
 
     def extract_tiles(self, stego: np.ndarray, sigma_c: np.ndarray, Uw: np.ndarray, Vwt: np.ndarray,
                       alpha: float, K: int = 8, sum_planes: bool = False) -> np.ndarray:
         """Scrambled-watermark estimate per plane, float32 [n, H, W]; with ``sum_planes`` the planes
         are added on the device and only their sum [H, W] comes back (video extract averages frames)."""
-        if stego.dtype != np.uint8:
-            raise ValueError("stego planes must be uint8")
-        n, H, W, rs, ps = _plane_layout(stego)
+        n, H, W, rs, ps = _planes_of(stego, np.uint8, "stego planes must be uint8")
         nby, nbx = H // TILE, W // TILE
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32)
-        if sc.size != n * nby * nbx * 8:
-            raise ValueError(f"sigma_c has {sc.size} values, the planes need {n}x{nby}x{nbx}x8")
-        sc = sc.reshape(n, nby, nbx, 8)
-        Uw = np.ascontiguousarray(Uw, dtype=np.float32)
-        Vwt = np.ascontiguousarray(Vwt, dtype=np.float32)
+        sc = self._sigma_c_tiles(sigma_c, n, nby, nbx)
+        Uw = _f32(Uw); Vwt = _f32(Vwt)
         per_plane = Uw.ndim == 5
         if Uw.ndim not in (4, 5) or Uw.shape[-4:] != (nby, nbx, 8, 8) or Vwt.shape != Uw.shape \
                 or (per_plane and Uw.shape[0] != n):
             raise ValueError(f"Uw/Vwt shape {Uw.shape}/{Vwt.shape} does not match {n} plane(s) of {nby}x{nbx} tiles")
-        if sum_planes:
-            tot = np.empty((H, W), np.float32)
-            self._call("wm_extract_tiles_sum_u8", _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(Uw.ctypes.data),
-                       _vp(Vwt.ctypes.data), _vp(tot.ctypes.data), n, H, W, rs, ps,
-                       nby * nbx if per_plane else 0, float(alpha), int(K))
-            return tot
-        out = np.empty((n, H, W), np.float32)
-        self._call("wm_extract_tiles_u8", _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(Uw.ctypes.data),
-                   _vp(Vwt.ctypes.data), _vp(out.ctypes.data), n, H, W, rs, ps,
-                   nby * nbx if per_plane else 0, float(alpha), int(K))
-        return out[0] if stego.ndim == 2 else out
+        out = np.empty((H, W) if sum_planes else (n, H, W), np.float32)
+        self._call("wm_extract_tiles_sum_u8" if sum_planes else "wm_extract_tiles_u8", _p(stego), _p(sc), _p(Uw), _p(Vwt),
+                   _p(out), n, H, W, rs, ps, nby * nbx if per_plane else 0, float(alpha), int(K))
+        return out[0] if stego.ndim == 2 and not sum_planes else out
 
     def reconstruct_tiles(self, Uw: np.ndarray, sw_hat: np.ndarray, Vwt: np.ndarray, H: int, W: int):
-        Uw = np.ascontiguousarray(Uw, dtype=np.float32)
-        Vwt = np.ascontiguousarray(Vwt, dtype=np.float32)
-        sh = np.ascontiguousarray(sw_hat, dtype=np.float32)
+        Uw = _f32(Uw); Vwt = _f32(Vwt); sh = _f32(sw_hat)
         single = Uw.ndim == 4
         n = 1 if single else Uw.shape[0]
         nby, nbx = H // TILE, W // TILE
         if Uw.shape[-4:] != (nby, nbx, 8, 8) or Vwt.shape != Uw.shape or sh.size != n * nby * nbx * 8:
             raise ValueError("Uw / Vwt / sw_hat do not match the plane size")
         out = np.empty((n, H, W), np.float32)
-        self._call("wm_reconstruct_tiles", _vp(Uw.ctypes.data), _vp(sh.ctypes.data), _vp(Vwt.ctypes.data),
-                   _vp(out.ctypes.data), n, H, W)
+        self._call("wm_reconstruct_tiles", _p(Uw), _p(sh), _p(Vwt), _p(out), n, H, W)
         return out[0] if single else out
 
     def detect_tiles(self, stego: np.ndarray, sigma_c: np.ndarray, sigma_w: np.ndarray,
                      alpha: float) -> np.ndarray:
-        if stego.dtype != np.uint8:
-            raise ValueError("stego planes must be uint8")
-        n, H, W, rs, ps = _plane_layout(stego)
+        n, H, W, rs, ps = _planes_of(stego, np.uint8, "stego planes must be uint8")
         nby, nbx = H // TILE, W // TILE
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32)
-        if sc.size != n * nby * nbx * 8:
-            raise ValueError(f"sigma_c has {sc.size} values, the planes need {n}x{nby}x{nbx}x8")
-        sc = sc.reshape(n, nby, nbx, 8)
-        sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        sc = self._sigma_c_tiles(sigma_c, n, nby, nbx)
+        sw = _f32(sigma_w)
         per_plane = sw.ndim == 4
         if sw.ndim not in (3, 4) or sw.shape[-3:] != (nby, nbx, 8) or (per_plane and sw.shape[0] != n):
             raise ValueError(f"sigma_w shape {sw.shape} does not match {n} plane(s) of {nby}x{nbx} tiles")
         scores = np.zeros(n, np.float64)
-        self._call("wm_detect_tiles_u8", _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(sw.ctypes.data),
-                   _vp(scores.ctypes.data), n, H, W, rs, ps, nby * nbx * 8 if per_plane else 0, float(alpha))
+        self._call("wm_detect_tiles_u8", _p(stego), _p(sc), _p(sw), _p(scores), n, H, W, rs, ps,
+                   nby * nbx * 8 if per_plane else 0, float(alpha))
         return scores
 
-    # ---- full-frame mode (tile=None), one plane per call -----------------------
+    # ---- full-frame mode (tile=None): one plane per call, or [N, H, W] planes sharing every launch ------------------
+    # A one-plane method and its ``_planes`` twin prepare their arguments alike (_dense, then the plane's H, W, L) and
+    # differ in the entry point they call and in the leading axis of what they return.
+    def _embed_outputs(self, hosts: np.ndarray, sc_shape, want_yw: bool):
+        return np.empty_like(hosts), np.empty(sc_shape, np.float32), np.empty(hosts.shape, np.float32) if want_yw else None
+
     def ref_embed(self, host: np.ndarray, sigma_w: np.ndarray, alpha: float, K: int, want_yw: bool = False):
-        if host.dtype != np.uint8 or host.ndim != 2:
-            raise ValueError("host plane must be uint8 [H, W]")
-        host = np.ascontiguousarray(host)
-        H, W = host.shape
-        L = min(H, W)
-        sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        host, H, W, L = _dense(host, np.uint8, 2, "host plane must be uint8 [H, W]")
+        sw = _f32(sigma_w)
         if sw.shape != (L,):
             raise ValueError(f"sigma_w must have shape ({L},)")
-        stego = np.empty_like(host); sc = np.empty(L, np.float32)
-        yw = np.empty((H, W), np.float32) if want_yw else None
-        self._call("wm_ref_embed_u8", _vp(host.ctypes.data), _vp(sw.ctypes.data), _vp(stego.ctypes.data),
-                   _vp(sc.ctypes.data), _vp(yw.ctypes.data) if want_yw else None, H, W, W, float(alpha), int(K))
+        stego, sc, yw = self._embed_outputs(host, L, want_yw)
+        self._call("wm_ref_embed_u8", _p(host), _p(sw), _p(stego), _p(sc), _p(yw), H, W, W, float(alpha), int(K))
         return stego, sc, yw
 
     def ref_embed_planes(self, hosts: np.ndarray, sigma_w: np.ndarray, alpha: float, K: int, want_yw: bool = False):
         """hosts uint8 [N, H, W]; sigma_w [L] (shared) or [N, L].  All planes share every launch."""
-        if hosts.dtype != np.uint8 or hosts.ndim != 3:
-            raise ValueError("hosts must be uint8 [N, H, W]")
-        hosts = np.ascontiguousarray(hosts)
-        n, H, W = hosts.shape
-        L = min(H, W)
-        sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        hosts, H, W, L = _dense(hosts, np.uint8, 3, "hosts must be uint8 [N, H, W]")
+        n = hosts.shape[0]
+        sw = _f32(sigma_w)
         if sw.shape not in ((L,), (n, L)):
             raise ValueError(f"sigma_w must have shape ({L},) or ({n}, {L})")
-        stego = np.empty_like(hosts); sc = np.empty((n, L), np.float32)
-        yw = np.empty((n, H, W), np.float32) if want_yw else None
-        self._call("wm_ref_embed_planes_u8", _vp(hosts.ctypes.data), _vp(sw.ctypes.data), _vp(stego.ctypes.data),
-                   _vp(sc.ctypes.data), _vp(yw.ctypes.data) if want_yw else None, n, H, W, W, H * W,
+        stego, sc, yw = self._embed_outputs(hosts, (n, L), want_yw)
+        self._call("wm_ref_embed_planes_u8", _p(hosts), _p(sw), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W,
                    L if sw.ndim == 2 else 0, float(alpha), int(K))
         return stego, sc, yw
 
@@ -469,11 +465,8 @@ class Context:
         decomposes the host planes (single:172-173 are independent statements; one full-frame SVD leaves most of the chip
         idle).  Returns (stego, sigma_c, yw, the callable's second value); the callable's exception is re-raised here."""
         import threading
-        if hosts.dtype != np.uint8 or hosts.ndim != 3:
-            raise ValueError("hosts must be uint8 [N, H, W]")
-        hosts = np.ascontiguousarray(hosts)
-        n, H, W = hosts.shape
-        L = min(H, W)
+        hosts, H, W, L = _dense(hosts, np.uint8, 3, "hosts must be uint8 [N, H, W]")
+        n = hosts.shape[0]
         sw = np.zeros((n, L) if per_plane else (L,), np.float32)
         flag = _i(0)
         box = {}
@@ -492,12 +485,10 @@ class Context:
                 flag.value = -1
         t = threading.Thread(target=run, daemon=True)
         t.start()
-        stego = np.empty_like(hosts); sc = np.empty((n, L), np.float32)
-        yw = np.empty((n, H, W), np.float32) if want_yw else None
+        stego, sc, yw = self._embed_outputs(hosts, (n, L), want_yw)
         try:
-            self._call("wm_ref_embed_planes_u8_when", _vp(hosts.ctypes.data), _vp(sw.ctypes.data), C.byref(flag),
-                       _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(yw.ctypes.data) if want_yw else None, n, H, W, W, H * W,
-                       L if per_plane else 0, float(alpha), int(K))
+            self._call("wm_ref_embed_planes_u8_when", _p(hosts), _p(sw), C.byref(flag), _p(stego), _p(sc), _p(yw),
+                       n, H, W, W, H * W, L if per_plane else 0, float(alpha), int(K))
         except Exception:
             t.join()
             if "exc" in box:
@@ -518,123 +509,94 @@ class Context:
         return f.value, bool(h.value)
 
     def ref_sigma_planes(self, planes: np.ndarray) -> np.ndarray:
-        if planes.dtype != np.uint8 or planes.ndim != 3:
-            raise ValueError("planes must be uint8 [N, H, W]")
-        planes = np.ascontiguousarray(planes)
-        n, H, W = planes.shape
-        s = np.empty((n, min(H, W)), np.float32)
-        self._call("wm_ref_sigma_planes_u8", _vp(planes.ctypes.data), _vp(s.ctypes.data), n, H, W, W, H * W)
+        planes, H, W, L = _dense(planes, np.uint8, 3, "planes must be uint8 [N, H, W]")
+        n = planes.shape[0]
+        s = np.empty((n, L), np.float32)
+        self._call("wm_ref_sigma_planes_u8", _p(planes), _p(s), n, H, W, W, H * W)
         return s
 
     def ref_sigma(self, plane: np.ndarray) -> np.ndarray:
-        if plane.dtype != np.uint8 or plane.ndim != 2:
-            raise ValueError("plane must be uint8 [H, W]")
-        plane = np.ascontiguousarray(plane)
-        H, W = plane.shape
-        s = np.empty(min(H, W), np.float32)
-        self._call("wm_ref_sigma_u8", _vp(plane.ctypes.data), _vp(s.ctypes.data), H, W, W)
+        plane, H, W, L = _dense(plane, np.uint8, 2, "plane must be uint8 [H, W]")
+        s = np.empty(L, np.float32)
+        self._call("wm_ref_sigma_u8", _p(plane), _p(s), H, W, W)
         return s
 
     def ref_svd(self, plane: np.ndarray, apply_dct: bool = True):
-        if plane.dtype != np.float32 or plane.ndim != 2:
-            raise ValueError("plane must be float32 [H, W]")
-        plane = np.ascontiguousarray(plane)
-        H, W = plane.shape
-        L = min(H, W)
+        plane, H, W, L = _dense(plane, np.float32, 2, "plane must be float32 [H, W]")
         U = np.empty((H, L), np.float32); S = np.empty(L, np.float32); Vt = np.empty((L, W), np.float32)
-        self._call("wm_ref_svd_f32", _vp(plane.ctypes.data), _vp(U.ctypes.data), _vp(S.ctypes.data),
-                   _vp(Vt.ctypes.data), H, W, W, 1 if apply_dct else 0)
+        self._call("wm_ref_svd_f32", _p(plane), _p(U), _p(S), _p(Vt), H, W, W, 1 if apply_dct else 0)
         return U, S, Vt
 
     def ref_svd_planes(self, planes: np.ndarray, apply_dct: bool = True):
         """planes float32 [n, H, W] -> U [n, H, L], S [n, L], Vt [n, L, W]: the watermark-side SVDs of a colour watermark's
         three planes (single:128-134) as one batch."""
-        if planes.dtype != np.float32 or planes.ndim != 3:
-            raise ValueError("planes must be float32 [n, H, W]")
-        planes = np.ascontiguousarray(planes)
-        n, H, W = planes.shape
-        L = min(H, W)
+        planes, H, W, L = _dense(planes, np.float32, 3, "planes must be float32 [n, H, W]")
+        n = planes.shape[0]
         U = np.empty((n, H, L), np.float32); S = np.empty((n, L), np.float32); Vt = np.empty((n, L, W), np.float32)
-        self._call("wm_ref_svd_planes_f32", _vp(planes.ctypes.data), _vp(U.ctypes.data), _vp(S.ctypes.data),
-                   _vp(Vt.ctypes.data), n, H, W, W, H * W, 1 if apply_dct else 0)
+        self._call("wm_ref_svd_planes_f32", _p(planes), _p(U), _p(S), _p(Vt), n, H, W, W, H * W, 1 if apply_dct else 0)
         return U, S, Vt
 
-    def ref_extract(self, stego: np.ndarray, sigma_c, Uw, Vwt, alpha: float, K: int) -> np.ndarray:
-        if stego.dtype != np.uint8 or stego.ndim != 2:
-            raise ValueError("stego plane must be uint8 [H, W]")
-        stego = np.ascontiguousarray(stego)
-        H, W = stego.shape
+    @staticmethod
+    def _ref_factors(sigma_c, Uw, Vwt, sc_shape, H: int, W: int):
+        """sigma_c of the given shape and the factors of one H x W plane, dense float32"""
+        sc = _f32(sigma_c); Uw = _f32(Uw); Vwt = _f32(Vwt)
         L = min(H, W)
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32)
-        Uw = np.ascontiguousarray(Uw, dtype=np.float32); Vwt = np.ascontiguousarray(Vwt, dtype=np.float32)
-        if sc.shape != (L,) or Uw.shape != (H, L) or Vwt.shape != (L, W):
+        if sc.shape != sc_shape or Uw.shape != (H, L) or Vwt.shape != (L, W):
             raise ValueError("meta arrays do not match the plane size")
+        return sc, Uw, Vwt
+
+    def ref_extract(self, stego: np.ndarray, sigma_c, Uw, Vwt, alpha: float, K: int) -> np.ndarray:
+        stego, H, W, L = _dense(stego, np.uint8, 2, "stego plane must be uint8 [H, W]")
+        sc, Uw, Vwt = self._ref_factors(sigma_c, Uw, Vwt, (L,), H, W)
         out = np.empty((H, W), np.float32)
-        self._call("wm_ref_extract_u8", _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(Uw.ctypes.data),
-                   _vp(Vwt.ctypes.data), _vp(out.ctypes.data), H, W, W, float(alpha), int(K))
+        self._call("wm_ref_extract_u8", _p(stego), _p(sc), _p(Uw), _p(Vwt), _p(out), H, W, W, float(alpha), int(K))
         return out
 
     def ref_reconstruct(self, Uw, sw_hat, Vwt, H: int, W: int) -> np.ndarray:
         """single:214-218 with the estimates given: ``Uw[:L,:L] @ diag(sw_hat) @ Vwt[:L,:L]`` (L = len(sw_hat)) in the
         top-left corner of a zero H x W plane, then idct2.  Uw [H, min(H,W)], Vwt [min(H,W), W] as the meta holds them."""
         Lm = min(H, W)
-        Uw = np.ascontiguousarray(Uw, dtype=np.float32); Vwt = np.ascontiguousarray(Vwt, dtype=np.float32)
-        sh = np.ascontiguousarray(sw_hat, dtype=np.float32).reshape(-1)
+        Uw = _f32(Uw); Vwt = _f32(Vwt)
+        sh = _f32(sw_hat).reshape(-1)
         if Uw.shape != (H, Lm) or Vwt.shape != (Lm, W):
             raise ValueError(f"Uw {Uw.shape} / Vwt {Vwt.shape} are not the factors of a {H}x{W} plane")
         if sh.size > Lm:
             raise ValueError(f"{sh.size} estimates for a plane with {Lm} singular values")
         out = np.empty((H, W), np.float32)
-        self._call("wm_ref_reconstruct_f32", _vp(Uw.ctypes.data), _vp(sh.ctypes.data) if sh.size else _vp(out.ctypes.data),
-                   _vp(Vwt.ctypes.data), _vp(out.ctypes.data), H, W, int(sh.size))
+        self._call("wm_ref_reconstruct_f32", _p(Uw), _p(sh) if sh.size else _p(out), _p(Vwt), _p(out), H, W, int(sh.size))
         return out
 
     def ref_extract_planes(self, stegos: np.ndarray, sigma_c, Uw, Vwt, alpha: float, K: int) -> np.ndarray:
         """stegos uint8 [n, H, W] sharing one watermark decomposition; sigma_c [n, L]."""
-        if stegos.dtype != np.uint8 or stegos.ndim != 3:
-            raise ValueError("stego planes must be uint8 [n, H, W]")
-        stegos = np.ascontiguousarray(stegos)
-        n, H, W = stegos.shape
-        L = min(H, W)
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32)
-        Uw = np.ascontiguousarray(Uw, dtype=np.float32); Vwt = np.ascontiguousarray(Vwt, dtype=np.float32)
-        if sc.shape != (n, L) or Uw.shape != (H, L) or Vwt.shape != (L, W):
-            raise ValueError("meta arrays do not match the plane size")
+        stegos, H, W, L = _dense(stegos, np.uint8, 3, "stego planes must be uint8 [n, H, W]")
+        n = stegos.shape[0]
+        sc, Uw, Vwt = self._ref_factors(sigma_c, Uw, Vwt, (n, L), H, W)
         out = np.empty((n, H, W), np.float32)
-        self._call("wm_ref_extract_planes_u8", _vp(stegos.ctypes.data), _vp(sc.ctypes.data), _vp(Uw.ctypes.data),
-                   _vp(Vwt.ctypes.data), _vp(out.ctypes.data), n, H, W, W, H * W, float(alpha), int(K))
+        self._call("wm_ref_extract_planes_u8", _p(stegos), _p(sc), _p(Uw), _p(Vwt), _p(out), n, H, W, W, H * W,
+                   float(alpha), int(K))
         return out
 
     def ref_detect(self, stego: np.ndarray, sigma_c, sigma_w, alpha: float) -> float:
-        if stego.dtype != np.uint8 or stego.ndim != 2:
-            raise ValueError("stego plane must be uint8 [H, W]")
-        stego = np.ascontiguousarray(stego)
-        H, W = stego.shape
-        L = min(H, W)
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32); sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        stego, H, W, L = _dense(stego, np.uint8, 2, "stego plane must be uint8 [H, W]")
+        sc = _f32(sigma_c); sw = _f32(sigma_w)
         # the C side reads min(H, W) floats from each buffer; the reference would truncate to the
         # shortest of Sc / S_cw / Sw (single:299,311-313) - a meta that does not belong to this
         # stego is refused here instead of being read past its end
         if sc.shape != (L,) or sw.shape != (L,):
             raise ValueError(f"sigma_c {sc.shape} / sigma_w {sw.shape} do not match the plane's {L} singular values")
         score = C.c_double(0.0)
-        self._call("wm_ref_detect_u8", _vp(stego.ctypes.data), _vp(sc.ctypes.data), _vp(sw.ctypes.data),
-                   C.byref(score), H, W, W, float(alpha))
+        self._call("wm_ref_detect_u8", _p(stego), _p(sc), _p(sw), C.byref(score), H, W, W, float(alpha))
         return score.value
 
     def ref_detect_planes(self, stegos: np.ndarray, sigma_c, sigma_w, alpha: float) -> np.ndarray:
         """stegos uint8 [n, H, W] carrying one watermark; sigma_c [n, L], sigma_w [L] -> scores float64 [n]."""
-        if stegos.dtype != np.uint8 or stegos.ndim != 3:
-            raise ValueError("stego planes must be uint8 [n, H, W]")
-        stegos = np.ascontiguousarray(stegos)
-        n, H, W = stegos.shape
-        L = min(H, W)
-        sc = np.ascontiguousarray(sigma_c, dtype=np.float32); sw = np.ascontiguousarray(sigma_w, dtype=np.float32)
+        stegos, H, W, L = _dense(stegos, np.uint8, 3, "stego planes must be uint8 [n, H, W]")
+        n = stegos.shape[0]
+        sc = _f32(sigma_c); sw = _f32(sigma_w)
         if sc.shape != (n, L) or sw.shape != (L,):
             raise ValueError("meta arrays do not match the plane size")
         scores = np.empty(n, np.float64)
-        self._call("wm_ref_detect_planes_u8", _vp(stegos.ctypes.data), _vp(sc.ctypes.data), _vp(sw.ctypes.data),
-                   _vp(scores.ctypes.data), n, H, W, W, H * W, float(alpha))
+        self._call("wm_ref_detect_planes_u8", _p(stegos), _p(sc), _p(sw), _p(scores), n, H, W, W, H * W, float(alpha))
         return scores
 
     # ---- keyed scramble / unscramble on the device (single:66-80) ------------------
@@ -817,7 +779,7 @@ class Context:
         H, W = img.shape[:2]
         if code in (2, 3):
             out = np.empty((H, W), np.uint8)
-            self._call("wm_color_u8", code, _vp(img.ctypes.data), None, None, _vp(out.ctypes.data), H * W)
+            self._call("wm_color_u8", code, _p(img), None, None, _p(out), H * W)
             return out
         out = np.empty_like(img)
         pin = None
@@ -825,8 +787,8 @@ class Context:
             plane = np.ascontiguousarray(plane, dtype=np.uint8)
             if plane.shape != (H, W):
                 raise ValueError("plane must be [H, W]")
-            pin = _vp(plane.ctypes.data)
-        self._call("wm_color_u8", code, _vp(img.ctypes.data), pin, _vp(out.ctypes.data), None, H * W)
+            pin = _p(plane)
+        self._call("wm_color_u8", code, _p(img), pin, _p(out), None, H * W)
         return out
 
     def psnr(self, a: np.ndarray, b: np.ndarray) -> float:
@@ -834,7 +796,7 @@ class Context:
         if a.shape != b.shape:
             raise ValueError("shape mismatch")
         v = C.c_double(0.0)
-        self._call("wm_psnr_u8", _vp(a.ctypes.data), _vp(b.ctypes.data), a.size, C.byref(v))
+        self._call("wm_psnr_u8", _p(a), _p(b), a.size, C.byref(v))
         return v.value
 
     def ssim(self, img1: np.ndarray, img2: np.ndarray) -> float:
@@ -847,13 +809,13 @@ class Context:
         if x.shape != y.shape or x.ndim != 2:
             raise ValueError("planes must be [H, W] of equal shape")
         v = C.c_double(0.0)
-        self._call("wm_ssim", _vp(x.ctypes.data), _vp(y.ctypes.data), x.shape[0], x.shape[1], k1 | (k2 << 1), C.byref(v))
+        self._call("wm_ssim", _p(x), _p(y), x.shape[0], x.shape[1], k1 | (k2 << 1), C.byref(v))
         return v.value
 
     def normalize_u8(self, x: np.ndarray, normalize: bool = True) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)
         out = np.empty(x.shape, np.uint8)
-        self._call("wm_normalize_u8", _vp(x.ctypes.data), x.size, 1 if normalize else 0, _vp(out.ctypes.data))
+        self._call("wm_normalize_u8", _p(x), x.size, 1 if normalize else 0, _p(out))
         return out
 
     # ---- extract post-processing (NL-means, CLAHE, unsharp, Lab; include/wmhip.h) ----------------------------------
@@ -919,5 +881,5 @@ class Context:
         img = self._u8_image(img, (1, 3))
         out = np.empty_like(img)
         ch = 1 if img.ndim == 2 else 3
-        self._call("wm_enhance_extract_u8", _vp(img.ctypes.data), _vp(out.ctypes.data), img.shape[0], img.shape[1], ch)
+        self._call("wm_enhance_extract_u8", _p(img), _p(out), img.shape[0], img.shape[1], ch)
         return out

@@ -1,0 +1,208 @@
+"""The ``.npz`` meta of the drop-in and of the video functions: the one statement of its layout.
+
+Member names, their order in the file, what the HMAC covers and in which order (single:152-156, 182), how the nonce,
+the digest, ``kfrac``, ``k_floor`` and the tile size are read back, and the small argument rules the public functions
+share.  The reference's ``extract`` / ``detect`` read the full-frame image metas written through here, so a slip in this
+file is a file they cannot authenticate.  NumPy and hashlib only (through hostglue): nothing here touches the device.
+"""
+from __future__ import annotations
+
+import os
+from typing import Optional
+
+import numpy as np
+
+from . import hostglue as hg
+
+TILE = 8
+CHANNELS = "bgr"                                   # plane order of a colour meta (single:122)
+
+
+# ---- key names ----------------------------------------------------------------
+def s_key(n: str) -> str:
+    return "S" + n                                 # host singular values of channel n, single:157-166
+
+
+def uw_key(n: str) -> str:
+    return "UW" + n
+
+
+def vwt_key(n: str) -> str:
+    return "VW" + n + "t"
+
+
+def sw_key(n: str) -> str:
+    return "SW" + n
+
+
+_GRAY = ("Sc", "Uw", "Vwt", "Sw")
+_IMAGE_COMMON = ("payload_type", "shape", "alpha", "kfrac", "nonce", "tile", "k_floor")
+_VIDEO_COMMON = ("payload_type", "shape", "alpha", "kfrac", "frame_interval", "n_frames", "tile", "k_floor", "nonce")
+_BY_CHANNEL = tuple(f(n) for n in CHANNELS for f in (s_key, uw_key, vwt_key, sw_key))
+_BY_CHANNEL_THEN_S = tuple(f(n) for n in CHANNELS for f in (uw_key, vwt_key, sw_key)) + tuple(s_key(n) for n in CHANNELS)
+
+# mode -> member order in the file; a member a writer does not set is skipped
+_ORDER = {
+    "gray": ("mode",) + _GRAY + _IMAGE_COMMON + ("digest",),                                # single:183-189 (+ tile, k_floor)
+    "color": ("mode",) + _IMAGE_COMMON + _BY_CHANNEL + ("digest",),                         # single:157-166 (+ tile, k_floor)
+    "video_gray": ("mode", "payload_type") + _GRAY + _VIDEO_COMMON[1:] + ("digest",),
+    "video_color": ("mode",) + _VIDEO_COMMON + ("digest",) + _BY_CHANNEL,
+}
+_ORDER_FULL_FRAME = dict(_ORDER, color=("mode",) + _IMAGE_COMMON + _BY_CHANNEL_THEN_S + ("digest",))
+
+
+def is_color(meta) -> bool:
+    return str(meta["mode"]) not in ("gray", "video_gray")                 # single:196,293: whatever is not gray
+
+
+def hmac_parts(meta) -> list:
+    """The arrays the HMAC covers, in its order: Sc, Uw, Vwt (single:182) or Sb Sg Sr, UWb UWg UWr, VWbt VWgt VWrt
+    (single:152-156)."""
+    if is_color(meta):
+        return [meta[f(n)] for f in (s_key, uw_key, vwt_key) for n in CHANNELS]
+    return [meta["Sc"], meta["Uw"], meta["Vwt"]]
+
+
+# ---- writers ------------------------------------------------------------------
+def common_members(H: int, W: int, alpha: float, kfrac: float, nonce: bytes) -> dict:
+    return dict(payload_type="image", shape=np.array((H, W)), alpha=float(alpha), kfrac=float(kfrac),
+                nonce=np.frombuffer(nonce, dtype=np.uint8))
+
+
+def image_members(tile: Optional[int], k_floor: int) -> dict:
+    """Tile mode names its tile and floor; a full-frame image meta is exactly the reference's (keys of single:157-166,
+    183-189), with no extra unless k_floor differs from the literal 8 of single:174."""
+    if tile:
+        return dict(tile=np.int32(TILE), k_floor=np.int32(k_floor))
+    return dict(k_floor=np.int32(k_floor)) if k_floor != 8 else {}
+
+
+def video_members(frame_interval: int, n_frames: int, tile: Optional[int], k_floor: int) -> dict:
+    return dict(frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames), tile=np.int32(tile or 0),
+                k_floor=np.int32(k_floor))
+
+
+def gray_members(Sc, Uw, Vwt, Sw) -> dict:
+    return dict(Sc=Sc, Uw=Uw, Vwt=Vwt, Sw=Sw)                              # single:183-189
+
+
+def channel_members(S, UW, VWt, SW) -> dict:
+    """Each argument holds the three channels' arrays along its first axis (a stacked [3, ...] array or a list)."""
+    out = {}
+    for ch, n in enumerate(CHANNELS):                                      # single:157-166
+        out[s_key(n)] = S[ch]; out[uw_key(n)] = UW[ch]; out[vwt_key(n)] = VWt[ch]; out[sw_key(n)] = SW[ch]
+    return out
+
+
+def sealed(members: dict, tile: Optional[int], digest: bytes) -> dict:
+    """The meta as it goes to the file: the members (``mode`` among them) in their writer's order, with the digest."""
+    have = dict(members, digest=np.frombuffer(digest, dtype=np.uint8))
+    order = (_ORDER if tile else _ORDER_FULL_FRAME)[have["mode"]]
+    assert set(have) <= set(order), sorted(set(have) - set(order))
+    return {k: have[k] for k in order if k in have}
+
+
+# ---- readers ------------------------------------------------------------------
+def _bytes_of(x) -> bytes:
+    return bytes(bytearray(np.asarray(x).astype(np.uint8).tolist()))
+
+
+def nonce_of(meta) -> bytes:
+    return _bytes_of(meta["nonce"])
+
+
+def digest_of(meta) -> bytes:
+    return _bytes_of(meta["digest"])
+
+
+def kfrac_of(meta) -> float:
+    return float(meta["kfrac"]) if "kfrac" in meta else hg.K_FRAC_DEFAULT  # single:211
+
+
+def k_floor_of(meta) -> int:
+    return int(meta["k_floor"]) if "k_floor" in meta else 8
+
+
+def tile_of(meta) -> Optional[int]:
+    """Tile size a meta was written with: the explicit ``tile`` key (0: full-frame), else inferred from the
+    singular-value array (per-tile [nby, nbx, 8] against full-frame [L])."""
+    if "tile" in meta:
+        t = int(meta["tile"])
+        if t == 0:
+            return None
+        if t != TILE:
+            raise ValueError("tile must be 8 or None")
+        return TILE
+    s = meta["Sc"] if "Sc" in meta else meta[s_key(CHANNELS[0])]
+    return TILE if np.asarray(s).ndim == 3 else None
+
+
+def by_channel(meta, key_rule) -> list:
+    """[meta of b, of g, of r] for one of s_key / uw_key / vwt_key / sw_key."""
+    return [meta[key_rule(n)] for n in CHANNELS]
+
+
+def stacked(meta, key_rule) -> np.ndarray:
+    """The [3, ...] array of one of a colour meta's S / UW / VWt / SW."""
+    return np.stack(by_channel(meta, key_rule))
+
+
+_RULE_OF = dict(Sc=s_key, Uw=uw_key, Vwt=vwt_key, Sw=sw_key)              # a gray member's name -> its per-channel rule
+
+
+def per_plane(meta, *names) -> list:
+    """The named members (among Sc, Uw, Vwt, Sw - the gray names) plane by plane: one tuple for a gray meta, three for a
+    colour one.  Only the named members are read (an ``np.load`` handle inflates a member on every access)."""
+    if is_color(meta):
+        return list(zip(*(by_channel(meta, _RULE_OF[k]) for k in names)))
+    return [tuple(meta[k] for k in names)]
+
+
+def batched(meta, *names) -> tuple:
+    """The named members as one array each for all planes: a gray meta's own, a colour meta's stacked to [3, ...]."""
+    if is_color(meta):
+        return tuple(stacked(meta, _RULE_OF[k]) for k in names)
+    return tuple(meta[k] for k in names)
+
+
+def authentic(meta, key: bytes) -> bool:
+    """single:206-209, 244-247"""
+    return hg.digests_equal(hg.hmac_digest(key, hmac_parts(meta)), digest_of(meta))
+
+
+# ---- small rules --------------------------------------------------------------
+def k_of(L: int, kfrac: float, k_floor: int) -> int:
+    return min(L, max(int(k_floor), int(kfrac * L)))                       # single:174 (capped at L)
+
+
+NO_PASSWORD = {"embed": "Vui lòng nhập mật khẩu để nhúng.",               # single:115-116
+               "extract": "Vui lòng nhập mật khẩu để giải trích."}        # single:193-194
+WRONG_PASSWORD = "Sai mật khẩu hoặc meta không khớp."                      # single:208-209,246-247
+
+
+def check_password_type(password, what: str) -> None:
+    """The authoritative signatures (single:112-114,192) take the password as a string.  The legacy module of the
+    same name had ``extract(stego, meta, out, normalize=True)`` and ``embed(..., payload_type, text_data)`` without one
+    (core:85-92,203): a positional ``True`` from such a call site would otherwise be hashed as a password."""
+    if password is not None and not isinstance(password, str):
+        raise TypeError(f"password must be a str, got {type(password).__name__}: {what}(...) follows "
+                        "app_dct_svd_single.py's signature (password before normalize / kfrac), not the legacy "
+                        "dct_svd_core_secure.py one - pass password= and normalize= by keyword")
+
+
+def require_password(password, what: str) -> None:
+    if not password:
+        raise ValueError(NO_PASSWORD[what])
+
+
+def check_tile(tile) -> None:
+    if tile is not None and int(tile) != TILE:
+        raise ValueError("tile must be 8 or None")
+
+
+check_enhance = hg.check_enhance
+
+
+def out_name(path: str, suffix: str) -> str:
+    """single:148-149,178-179 (``_stego.png``), 225-226,278-279 (``_wm.png``)"""
+    return path if path.lower().endswith(".png") else os.path.splitext(path)[0] + suffix

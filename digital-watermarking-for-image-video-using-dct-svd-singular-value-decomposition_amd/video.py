@@ -20,6 +20,7 @@ Arrays of frames (``[N, H, W]`` uint8 luma) are accepted directly as well.
 """
 from __future__ import annotations
 
+import collections
 import os
 from typing import Iterator, Optional, Tuple
 
@@ -27,9 +28,10 @@ import numpy as np
 
 from . import hostapi
 from . import hostglue as hg
+from . import meta as M
 from . import sharding
 
-TILE = 8
+TILE = M.TILE
 
 
 # ---------------------------------------------------------------------------
@@ -107,18 +109,10 @@ def prepare_watermark(ctx: hostapi.Context, wm_bgr: np.ndarray, H: int, W: int, 
     return Uw, Sw, Vwt, idx
 
 
-def _k_of(tile: Optional[int], kfrac: float, k_floor: int, H: int, W: int) -> int:
-    """K = max(8, int(kfrac * L)) (single:137) with L = 8 per tile or min(H, W) per plane."""
-    L = tile if tile else min(H, W)
-    return min(L, max(int(k_floor), int(kfrac * L)))
-
-
-def embed_frames(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8,
-                 batch: int = 32, tile: Optional[int] = TILE):
-    """frames_y uint8 [N, H, W] -> (stego [N, H, W], Sc); one set of launches per batch.
-    tile=8: Sc [N, nby, nbx, 8] (K1); tile=None: Sc [N, min(H, W)] (batched full-plane SVDs)."""
+def _embed_frames_into(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int, batch: int,
+                       tile: Optional[int], stego: np.ndarray) -> np.ndarray:
+    """embed_frames with the stego frames written into ``stego`` ([N, H, W], may be strided); returns Sc."""
     n, H, W = frames_y.shape
-    stego = np.empty_like(frames_y)
     sc = np.empty((n, H // TILE, W // TILE, 8) if tile else (n, min(H, W)), np.float32)
     for b0 in range(0, n, batch):
         if tile:
@@ -126,7 +120,15 @@ def embed_frames(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alp
         else:
             s, c, _ = ctx.ref_embed_planes(frames_y[b0:b0 + batch], Sw, alpha, K)
         stego[b0:b0 + batch] = s; sc[b0:b0 + batch] = c
-    return stego, sc
+    return sc
+
+
+def embed_frames(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8,
+                 batch: int = 32, tile: Optional[int] = TILE):
+    """frames_y uint8 [N, H, W] -> (stego [N, H, W], Sc); one set of launches per batch.
+    tile=8: Sc [N, nby, nbx, 8] (K1); tile=None: Sc [N, min(H, W)] (batched full-plane SVDs)."""
+    stego = np.empty_like(frames_y)
+    return stego, _embed_frames_into(ctx, frames_y, Sw, alpha, K, batch, tile, stego)
 
 
 def extract_frames_mean(ctx: hostapi.Context, frames_y: np.ndarray, Sc: np.ndarray, Uw, Vwt, alpha: float,
@@ -162,146 +164,11 @@ def embed_frames_sharded(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndar
 
 
 # ---------------------------------------------------------------------------
-# file level (names of the reference's bytecode-only video module)
-# ---------------------------------------------------------------------------
-def _marked(n_frames: int, frame_interval: int) -> np.ndarray:
-    return np.arange(0, n_frames, max(1, int(frame_interval)))
-
-
-def embed_watermark_video(host_video_path: str, watermark_path: str, output_video_path: str,
-                          metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
-                          password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
-                          k_floor: int = 8, batch: int = 32, device: int = 0, tile: Optional[int] = TILE):
-    """Embed the watermark into the luma of every ``frame_interval``-th frame of a
-    .y4m video.  Returns (output_video_path, metadata_path, mean PSNR of marked frames).
-    tile=8: 8x8-block formulation (fast path); tile=None: one SVD per frame like the reference's
-    image embed (batched over the frames of a chunk; use a smaller ``batch``, e.g. 8)."""
-    if tile not in (TILE, None):
-        raise ValueError("tile must be 8 or None")
-    if not password:
-        raise ValueError("Vui lòng nhập mật khẩu để nhúng.")
-    ctx = hostapi.Context(device)
-    vid = Y4M(host_video_path)
-    try:
-        H, W = vid.H, vid.W
-        if nonce is None:
-            nonce = os.urandom(8)
-        key = hg.derive_key(password, nonce)
-        Uw, Sw, Vwt, _ = prepare_watermark(ctx, hg.read_image_bgr(watermark_path), H, W, key, tile)
-        K = _k_of(tile, kfrac, k_floor, H, W)
-        sc_all, psnrs, n_frames = [], [], 0
-        with open(output_video_path, "wb") as out:
-            out.write(vid.header_line)
-            pend = []          # (frame_line, y, chroma, marked)
-
-            def flush():
-                ys = [p[1] for p in pend if p[3]]
-                if ys:
-                    st, sc = embed_frames(ctx, np.stack(ys), Sw, alpha, K, batch, tile)
-                    sc_all.append(sc)
-                j = 0
-                for line, y, chroma, marked in pend:
-                    yy = y
-                    if marked:
-                        yy = st[j]; psnrs.append(hg.psnr(y, yy)); j += 1
-                    out.write(line); out.write(yy.tobytes()); out.write(chroma.tobytes())
-                pend.clear()
-
-            for line, y, chroma in vid:
-                pend.append((line, y.copy(), chroma.copy(), n_frames % max(1, frame_interval) == 0))
-                n_frames += 1
-                if len(pend) >= batch * max(1, frame_interval):
-                    flush()
-            flush()
-        Sc = np.concatenate(sc_all) if sc_all else np.zeros((0, H // TILE, W // TILE, 8) if tile else (0, min(H, W)), np.float32)
-        digest = hg.hmac_digest(key, [Sc, Uw, Vwt])
-        # uncompressed .npz: the per-frame singular values are float noise to zlib (ratio ~1.1) and compressing them was
-        # 80 % of this function's time (1.7 s for 64 frames of 1080p); np.load reads either form
-        np.savez(metadata_path, mode="video_gray", payload_type="image", Sc=Sc, Uw=Uw, Vwt=Vwt, Sw=Sw,
-                            shape=np.array((H, W)), alpha=float(alpha), kfrac=float(kfrac),
-                            frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames),
-                            tile=np.int32(tile or 0), k_floor=np.int32(k_floor),
-                            nonce=np.frombuffer(nonce, dtype=np.uint8), digest=np.frombuffer(digest, dtype=np.uint8))
-        return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0
-    finally:
-        vid.close(); ctx.close()
-
-
-def _load_video_meta(metadata_path: str):
-    data = np.load(metadata_path, allow_pickle=False)
-    if str(data["mode"]) != "video_gray":
-        raise ValueError("metadata was not written by embed_watermark_video")
-    return data
-
-
-def _meta_tile(data) -> Optional[int]:
-    return int(data["tile"]) or None
-
-
-def _marked_luma(stego_video_path: str, data) -> np.ndarray:
-    vid = Y4M(stego_video_path)
-    try:
-        fi = int(data["frame_interval"])
-        ys = [y.copy() for i, (_, y, _) in enumerate(vid) if i % max(1, fi) == 0]
-    finally:
-        vid.close()
-    n = data["Sc"].shape[0]
-    if len(ys) < n:
-        raise ValueError("video has fewer marked frames than the metadata")
-    return np.stack(ys[:n]) if n else np.zeros((0,) + tuple(map(int, data["shape"])), np.uint8)
-
-
-def extract_watermark_video(stego_video_path: str, metadata_path: str, output_image_path: str,
-                            password: str, normalize: bool = True, *, batch: int = 32, device: int = 0,
-                            enhance=False) -> str:
-    """Averaged multi-frame extraction -> watermark image (PNG).  ``enhance`` as in dct_svd_core_secure.extract."""
-    hg.check_enhance(enhance)
-    if not password:
-        raise ValueError("Vui lòng nhập mật khẩu để giải trích.")
-    data = _load_video_meta(metadata_path)
-    H, W = map(int, data["shape"])
-    nonce = bytes(bytearray(data["nonce"].astype(np.uint8).tolist()))
-    key = hg.derive_key(password, nonce)
-    if not hg.digests_equal(hg.hmac_digest(key, [data["Sc"], data["Uw"], data["Vwt"]]),
-                            bytes(bytearray(data["digest"].astype(np.uint8).tolist()))):
-        raise ValueError("Sai mật khẩu hoặc meta không khớp.")
-    ctx = hostapi.Context(device)
-    try:
-        ys = _marked_luma(stego_video_path, data)
-        tile = _meta_tile(data)
-        K = _k_of(tile, float(data["kfrac"]), int(data["k_floor"]), H, W)
-        wy_s = extract_frames_mean(ctx, ys, data["Sc"], data["Uw"], data["Vwt"], float(data["alpha"]), K, batch, tile)
-        img = ctx.unpermute_normalize_u8(wy_s, hg.permutation_index(H, W, key), normalize)   # single:74-80, 221-222 on the device
-        img = hg.apply_enhance(ctx, img, enhance)                                           # single:223-227
-    finally:
-        ctx.close()
-    if not output_image_path.lower().endswith(".png"):
-        output_image_path = os.path.splitext(output_image_path)[0] + "_wm.png"
-    if not hg.write_png(output_image_path, img, 1):
-        raise IOError("Ghi watermark thất bại.")
-    return output_image_path
-
-
-def detect_watermark_video(stego_video_path: str, metadata_path: str, thresh: float = 0.6, *,
-                           batch: int = 32, device: int = 0):
-    """(bool, mean score, per-frame scores) over the marked frames."""
-    data = _load_video_meta(metadata_path)
-    ctx = hostapi.Context(device)
-    try:
-        ys = _marked_luma(stego_video_path, data)
-        scores = detect_frames(ctx, ys, data["Sc"], data["Sw"], float(data["alpha"]), batch, _meta_tile(data))
-    finally:
-        ctx.close()
-    mean = float(scores.mean()) if scores.size else 0.0
-    return bool(mean >= thresh), mean, scores
-
-
-# ---------------------------------------------------------------------------
-# colour video (names of the reference's bytecode-only ``color_video_dct_svd`` module: ``embed_watermark_video_color`` /
-# ``extract_watermark_video_color``; its source is not in the tree, so the SHAPE is the colour image embed of single:121-166
-# put into the luma loop above: the colour watermark's B, G, R planes are decomposed ONCE, every marked frame's B, G, R planes
+# colour frames.  The reference's ``color_video_dct_svd`` module is bytecode-only too (``embed_watermark_video_color`` /
+# ``extract_watermark_video_color``); its source is not in the tree, so the SHAPE is the colour image embed of single:121-166
+# put into the luma loop: the colour watermark's B, G, R planes are decomposed ONCE, every marked frame's B, G, R planes
 # are embedded with them, per-frame host singular values per channel go to the metadata, extraction averages over the marked
-# frames per channel).  Container: 8-bit 4:4:4 ``.y4m`` (planes Y, Cb, Cr); the frames pass through OpenCV's fixed-point
+# frames per channel.  Container: 8-bit 4:4:4 ``.y4m`` (planes Y, Cb, Cr); the frames pass through OpenCV's fixed-point
 # YCrCb <-> BGR conversion on the device (``wm_color_u8``) on the way in and out, so - like any YUV container - the stored
 # stego differs from the embedded BGR planes by that conversion's rounding (a grey level or two per channel).  No audio remux.
 # ---------------------------------------------------------------------------
@@ -329,43 +196,63 @@ def prepare_watermark_color(ctx: hostapi.Context, wm_bgr: np.ndarray, H: int, W:
     return Uw, Sw, Vwt, idx
 
 
-_CH = "bgr"
-
-
 def embed_frames_color(ctx: hostapi.Context, planes: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8, batch: int = 8,
                        tile: Optional[int] = TILE):
     """planes uint8 [n, 3, H, W] (B, G, R of n frames), Sw [3, ...] -> (stego [n, 3, H, W], [Sb, Sg, Sr]): channel c of every
-    frame gets the watermark's channel c (single:139-152); one set of launches per channel and batch."""
+    frame gets the watermark's channel c (single:139-152); one set of launches per channel and batch.  (Any number of
+    channels: the luma loop passes [n, 1, H, W].)"""
     st = np.empty_like(planes)
-    sc = []
-    for ch in range(3):
-        s, c = embed_frames(ctx, np.ascontiguousarray(planes[:, ch]), Sw[ch], alpha, K, batch, tile)
-        st[:, ch] = s; sc.append(c)
+    sc = [_embed_frames_into(ctx, np.ascontiguousarray(planes[:, ch]), Sw[ch], alpha, K, batch, tile, st[:, ch])
+          for ch in range(planes.shape[1])]
     return st, sc
 
 
-def embed_watermark_video_color(host_video_path: str, watermark_path: str, output_video_path: str,
-                                metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
-                                password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
-                                k_floor: int = 8, batch: int = 8, device: int = 0, tile: Optional[int] = TILE):
-    """Embed a colour watermark into the B, G, R planes of every ``frame_interval``-th frame of a 4:4:4 .y4m video.
-    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' BGR planes)."""
-    if tile not in (TILE, None):
-        raise ValueError("tile must be 8 or None")
-    if not password:
-        raise ValueError("Vui lòng nhập mật khẩu để nhúng.")
+# ---------------------------------------------------------------------------
+# file level (names of the reference's bytecode-only video modules).  One loop, one reader, one extract and one detect,
+# over [n, C, H, W] planes; what differs between luma (C = 1) and 4:4:4 colour (C = 3) is the frame codec.
+# ---------------------------------------------------------------------------
+_Codec = collections.namedtuple("_Codec", "mode writer chroma prepare planes frame_bytes members")
+# luma: the luma plane IS the plane the hot path works on ([1, H, W]); write-back replaces y and keeps the chroma bytes
+_Luma = _Codec(
+    mode="video_gray", writer="embed_watermark_video", chroma=None,
+    prepare=lambda ctx, wm_bgr, H, W, key, tile: [x[None] for x in prepare_watermark(ctx, wm_bgr, H, W, key, tile)[:3]],
+    planes=lambda ctx, y, chroma, H, W: y[None],
+    frame_bytes=lambda ctx, planes, chroma: (planes[0].tobytes(), chroma.tobytes()),
+    members=lambda S, Uw, Vwt, Sw: M.gray_members(S[0], Uw[0], Vwt[0], Sw[0]))
+# 4:4:4 colour: the B, G, R planes of a frame ([3, H, W]); write-back converts the three stego planes to Y, Cb, Cr
+_Bgr444 = _Codec(
+    mode="video_color", writer="embed_watermark_video_color", chroma="444",
+    prepare=lambda ctx, wm_bgr, H, W, key, tile: prepare_watermark_color(ctx, wm_bgr, H, W, key, tile)[:3],
+    planes=_frame_to_bgr_planes,
+    frame_bytes=lambda ctx, planes, chroma: [p.tobytes() for p in _bgr_planes_to_frame(ctx, planes)],
+    members=M.channel_members)                                             # the colour image meta's key names (single:157-166)
+
+
+def _check_container(codec, vid: Y4M, refusal: str):
+    if codec.chroma and vid.chroma != codec.chroma:
+        raise ValueError(refusal)
+
+
+def _is_marked(i: int, frame_interval: int) -> bool:
+    return i % max(1, int(frame_interval)) == 0
+
+
+def _embed_video(codec, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
+                 password, nonce, kfrac, k_floor, batch, device, tile):
+    M.check_tile(tile)
+    M.require_password(password, "embed")
     ctx = hostapi.Context(device)
     vid = Y4M(host_video_path)
     try:
-        if vid.chroma != "444":
-            raise ValueError("embed_watermark_video_color needs an 8-bit 4:4:4 .y4m (C444): per-channel embedding needs full-resolution chroma")
+        _check_container(codec, vid, "embed_watermark_video_color needs an 8-bit 4:4:4 .y4m (C444): per-channel embedding "
+                                     "needs full-resolution chroma")
         H, W = vid.H, vid.W
         if nonce is None:
             nonce = os.urandom(8)
         key = hg.derive_key(password, nonce)
-        Uw, Sw, Vwt, _ = prepare_watermark_color(ctx, hg.read_image_bgr(watermark_path), H, W, key, tile)
-        K = _k_of(tile, kfrac, k_floor, H, W)
-        sc_all = [[], [], []]
+        Uw, Sw, Vwt = codec.prepare(ctx, hg.read_image_bgr(watermark_path), H, W, key, tile)
+        K = M.k_of(tile or min(H, W), kfrac, k_floor)                     # single:137, L = 8 per tile or min(H, W) per plane
+        sc_all = [[] for _ in Sw]
         psnrs, n_frames = [], 0
         with open(output_video_path, "wb") as out:
             out.write(vid.header_line)
@@ -374,112 +261,151 @@ def embed_watermark_video_color(host_video_path: str, watermark_path: str, outpu
             def flush():
                 marked = [p for p in pend if p[3]]
                 if marked:
-                    planes = np.stack([_frame_to_bgr_planes(ctx, p[1], p[2], H, W) for p in marked])     # [n, 3, H, W]
+                    planes = np.stack([codec.planes(ctx, p[1], p[2], H, W) for p in marked])     # [n, C, H, W]
                     st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile)
-                    for ch in range(3):
-                        sc_all[ch].append(sc[ch])
+                    for ch, c in enumerate(sc):
+                        sc_all[ch].append(c)
                     psnrs.extend(hg.psnr(planes[i], st[i]) for i in range(len(marked)))
                 j = 0
                 for line, y, chroma, is_marked in pend:
+                    out.write(line)
                     if is_marked:
-                        yy, cb, cr = _bgr_planes_to_frame(ctx, st[j]); j += 1
-                        out.write(line); out.write(yy.tobytes()); out.write(cb.tobytes()); out.write(cr.tobytes())
+                        out.writelines(codec.frame_bytes(ctx, st[j], chroma)); j += 1
                     else:
-                        out.write(line); out.write(y.tobytes()); out.write(chroma.tobytes())
+                        out.write(y.tobytes()); out.write(chroma.tobytes())
                 pend.clear()
 
             for line, y, chroma in vid:
-                pend.append((line, y.copy(), chroma.copy(), n_frames % max(1, frame_interval) == 0))
+                pend.append((line, y.copy(), chroma.copy(), _is_marked(n_frames, frame_interval)))
                 n_frames += 1
                 if len(pend) >= batch * max(1, frame_interval):
                     flush()
             flush()
         empty = np.zeros((0, H // TILE, W // TILE, 8) if tile else (0, min(H, W)), np.float32)
-        S = [np.concatenate(sc_all[ch]) if sc_all[ch] else empty for ch in range(3)]
-        digest = hg.hmac_digest(key, S + [Uw[ch] for ch in range(3)] + [Vwt[ch] for ch in range(3)])     # the coverage of single:160-161
-        meta = dict(mode="video_color", payload_type="image", shape=np.array((H, W)), alpha=float(alpha), kfrac=float(kfrac),
-                    frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames), tile=np.int32(tile or 0),
-                    k_floor=np.int32(k_floor), nonce=np.frombuffer(nonce, dtype=np.uint8), digest=np.frombuffer(digest, dtype=np.uint8))
-        for ch, n in enumerate(_CH):                     # the colour image meta's key names (single:157-166)
-            meta["S" + n] = S[ch]; meta["UW" + n] = Uw[ch]; meta["VW" + n + "t"] = Vwt[ch]; meta["SW" + n] = Sw[ch]
-        np.savez(metadata_path, **meta)
+        S = [np.concatenate(c) if c else empty for c in sc_all]
+        members = {"mode": codec.mode, **M.common_members(H, W, alpha, kfrac, nonce),
+                   **M.video_members(frame_interval, n_frames, tile, k_floor), **codec.members(S, Uw, Vwt, Sw)}
+        digest = hg.hmac_digest(key, M.hmac_parts(members))                # the coverage of single:152-156,182
+        # uncompressed .npz: the per-frame singular values are float noise to zlib (ratio ~1.1) and compressing them was
+        # 80 % of this function's time (1.7 s for 64 frames of 1080p); np.load reads either form
+        np.savez(metadata_path, **M.sealed(members, tile, digest))
         return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0
     finally:
         vid.close(); ctx.close()
 
 
-def _load_video_meta_color(metadata_path: str):
+def _load_video_meta(codec, metadata_path: str):
     data = np.load(metadata_path, allow_pickle=False)
-    if str(data["mode"]) != "video_color":
-        raise ValueError("metadata was not written by embed_watermark_video_color")
+    if str(data["mode"]) != codec.mode:
+        raise ValueError("metadata was not written by " + codec.writer)
     return data
 
 
-def _marked_bgr(ctx: hostapi.Context, stego_video_path: str, data) -> np.ndarray:
+def _marked_planes(codec, ctx: hostapi.Context, stego_video_path: str, data, n: int, C: int) -> np.ndarray:
+    """The first n marked frames' planes, uint8 [n, C, H, W]."""
     vid = Y4M(stego_video_path)
     try:
-        if vid.chroma != "444":
-            raise ValueError("a colour-watermarked video is 4:4:4")
-        fi = int(data["frame_interval"]); n = data["Sb"].shape[0]
+        _check_container(codec, vid, "a colour-watermarked video is 4:4:4")
+        fi = int(data["frame_interval"])
         H, W = vid.H, vid.W
         out = []
         for i, (_, y, chroma) in enumerate(vid):
-            if i % max(1, fi) == 0 and len(out) < n:
-                out.append(_frame_to_bgr_planes(ctx, y, chroma, H, W))
+            if _is_marked(i, fi) and len(out) < n:
+                out.append(codec.planes(ctx, y, chroma, H, W))
     finally:
         vid.close()
     if len(out) < n:
         raise ValueError("video has fewer marked frames than the metadata")
-    return np.stack(out) if out else np.zeros((0, 3) + tuple(map(int, data["shape"])), np.uint8)
+    return np.stack(out) if out else np.zeros((0, C) + tuple(map(int, data["shape"])), np.uint8)
+
+
+def _extract_video(codec, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance):
+    M.check_enhance(enhance)
+    M.require_password(password, "extract")
+    data = _load_video_meta(codec, metadata_path)
+    H, W = map(int, data["shape"])
+    key = hg.derive_key(password, M.nonce_of(data))
+    if not M.authentic(data, key):
+        raise ValueError(M.WRONG_PASSWORD)
+    ctx = hostapi.Context(device)
+    try:
+        factors = M.per_plane(data, "Sc", "Uw", "Vwt")
+        planes = _marked_planes(codec, ctx, stego_video_path, data, factors[0][0].shape[0], len(factors))
+        tile = M.tile_of(data)
+        K = M.k_of(tile or min(H, W), M.kfrac_of(data), M.k_floor_of(data))
+        idx = hg.permutation_index(H, W, key)
+        chans = []
+        for ch, (Sc, Uw, Vwt) in enumerate(factors):
+            w_s = extract_frames_mean(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Uw, Vwt, float(data["alpha"]), K, batch, tile)
+            chans.append(ctx.unpermute_normalize_u8(w_s, idx, normalize))                    # single:74-80, 221-222, 265-271 on the device
+        img = hg.apply_enhance(ctx, chans[0] if len(chans) == 1 else np.stack(chans, axis=-1), enhance)   # single:223-227, 275-277
+    finally:
+        ctx.close()
+    output_image_path = M.out_name(output_image_path, "_wm.png")
+    if not hg.write_png(output_image_path, img, 1):
+        raise IOError("Ghi watermark thất bại.")
+    return output_image_path
+
+
+def _detect_video(codec, stego_video_path, metadata_path, thresh, batch, device):
+    data = _load_video_meta(codec, metadata_path)
+    ctx = hostapi.Context(device)
+    try:
+        sigmas = M.per_plane(data, "Sc", "Sw")
+        planes = _marked_planes(codec, ctx, stego_video_path, data, sigmas[0][0].shape[0], len(sigmas))
+        tile = M.tile_of(data)
+        per_ch = [detect_frames(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Sw, float(data["alpha"]), batch, tile)
+                  for ch, (Sc, Sw) in enumerate(sigmas)]
+    finally:
+        ctx.close()
+    scores = per_ch[0] if len(per_ch) == 1 else (per_ch[0] + per_ch[1] + per_ch[2]) / 3.0      # single:317
+    mean = float(scores.mean()) if scores.size else 0.0
+    return bool(mean >= thresh), mean, scores
+
+
+def embed_watermark_video(host_video_path: str, watermark_path: str, output_video_path: str,
+                          metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
+                          password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
+                          k_floor: int = 8, batch: int = 32, device: int = 0, tile: Optional[int] = TILE):
+    """Embed the watermark into the luma of every ``frame_interval``-th frame of a
+    .y4m video.  Returns (output_video_path, metadata_path, mean PSNR of marked frames).
+    tile=8: 8x8-block formulation (fast path); tile=None: one SVD per frame like the reference's
+    image embed (batched over the frames of a chunk; use a smaller ``batch``, e.g. 8)."""
+    return _embed_video(_Luma, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
+                        password, nonce, kfrac, k_floor, batch, device, tile)
+
+
+def extract_watermark_video(stego_video_path: str, metadata_path: str, output_image_path: str,
+                            password: str, normalize: bool = True, *, batch: int = 32, device: int = 0,
+                            enhance=False) -> str:
+    """Averaged multi-frame extraction -> watermark image (PNG).  ``enhance`` as in dct_svd_core_secure.extract."""
+    return _extract_video(_Luma, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance)
+
+
+def detect_watermark_video(stego_video_path: str, metadata_path: str, thresh: float = 0.6, *,
+                           batch: int = 32, device: int = 0):
+    """(bool, mean score, per-frame scores) over the marked frames."""
+    return _detect_video(_Luma, stego_video_path, metadata_path, thresh, batch, device)
+
+
+def embed_watermark_video_color(host_video_path: str, watermark_path: str, output_video_path: str,
+                                metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
+                                password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
+                                k_floor: int = 8, batch: int = 8, device: int = 0, tile: Optional[int] = TILE):
+    """Embed a colour watermark into the B, G, R planes of every ``frame_interval``-th frame of a 4:4:4 .y4m video.
+    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' BGR planes)."""
+    return _embed_video(_Bgr444, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
+                        password, nonce, kfrac, k_floor, batch, device, tile)
 
 
 def extract_watermark_video_color(stego_video_path: str, metadata_path: str, output_image_path: str, password: str,
                                   normalize: bool = True, *, batch: int = 8, device: int = 0, enhance=False) -> str:
     """Averaged multi-frame extraction per channel -> colour watermark image (PNG).  ``enhance`` as in
     dct_svd_core_secure.extract."""
-    hg.check_enhance(enhance)
-    if not password:
-        raise ValueError("Vui lòng nhập mật khẩu để giải trích.")
-    data = _load_video_meta_color(metadata_path)
-    H, W = map(int, data["shape"])
-    nonce = bytes(bytearray(data["nonce"].astype(np.uint8).tolist()))
-    key = hg.derive_key(password, nonce)
-    parts = [data["S" + n] for n in _CH] + [data["UW" + n] for n in _CH] + [data["VW" + n + "t"] for n in _CH]
-    if not hg.digests_equal(hg.hmac_digest(key, parts), bytes(bytearray(data["digest"].astype(np.uint8).tolist()))):
-        raise ValueError("Sai mật khẩu hoặc meta không khớp.")
-    ctx = hostapi.Context(device)
-    try:
-        planes = _marked_bgr(ctx, stego_video_path, data)
-        tile = _meta_tile(data)
-        K = _k_of(tile, float(data["kfrac"]), int(data["k_floor"]), H, W)
-        idx = hg.permutation_index(H, W, key)
-        chans = []
-        for ch, n in enumerate(_CH):
-            w_s = extract_frames_mean(ctx, np.ascontiguousarray(planes[:, ch]), data["S" + n], data["UW" + n], data["VW" + n + "t"],
-                                      float(data["alpha"]), K, batch, tile)
-            chans.append(ctx.unpermute_normalize_u8(w_s, idx, normalize))                    # single:265-271 per channel
-        img = hg.apply_enhance(ctx, np.stack(chans, axis=-1), enhance)                     # single:275-277
-    finally:
-        ctx.close()
-    if not output_image_path.lower().endswith(".png"):
-        output_image_path = os.path.splitext(output_image_path)[0] + "_wm.png"
-    if not hg.write_png(output_image_path, img, 1):
-        raise IOError("Ghi watermark thất bại.")
-    return output_image_path
+    return _extract_video(_Bgr444, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance)
 
 
 def detect_watermark_video_color(stego_video_path: str, metadata_path: str, thresh: float = 0.6, *,
                                  batch: int = 8, device: int = 0):
     """(bool, mean score, per-frame scores): a frame's score is the mean of its three channels' NC (single:317)."""
-    data = _load_video_meta_color(metadata_path)
-    ctx = hostapi.Context(device)
-    try:
-        planes = _marked_bgr(ctx, stego_video_path, data)
-        tile = _meta_tile(data)
-        per_ch = [detect_frames(ctx, np.ascontiguousarray(planes[:, ch]), data["S" + n], data["SW" + n], float(data["alpha"]), batch, tile)
-                  for ch, n in enumerate(_CH)]
-    finally:
-        ctx.close()
-    scores = (per_ch[0] + per_ch[1] + per_ch[2]) / 3.0
-    mean = float(scores.mean()) if scores.size else 0.0
-    return bool(mean >= thresh), mean, scores
+    return _detect_video(_Bgr444, stego_video_path, metadata_path, thresh, batch, device)

@@ -1,5 +1,6 @@
 """The C-ABI library loads on a box without a GPU and exports every symbol
 include/wmhip.h declares (no compute calls here)."""
+import importlib
 import os
 import re
 
@@ -108,12 +109,13 @@ def test_meta_shapes_are_validated_before_the_c_abi(hostapi):
 def test_meta_tile_and_stego_size_are_checked():
     import dct_svd_core_secure as core
     mod = core.embed_arrays.__globals__
+    tile_of = importlib.import_module(core._impl.__package__ + ".meta").tile_of
     meta = {"tile": np.int32(16), "Sc": np.zeros((2, 2, 8), np.float32), "shape": np.array((16, 16))}
     with pytest.raises(ValueError, match="tile must be 8 or None"):
-        mod["_meta_tile"](meta)
-    assert mod["_meta_tile"]({"tile": np.int32(0), "Sc": np.zeros(4)}) is None
-    assert mod["_meta_tile"]({"tile": np.int32(8), "Sc": np.zeros(4)}) == 8
-    assert mod["_meta_tile"]({"Sc": np.zeros((2, 2, 8))}) == 8 and mod["_meta_tile"]({"Sb": np.zeros(16)}) is None
+        tile_of(meta)
+    assert tile_of({"tile": np.int32(0), "Sc": np.zeros(4)}) is None
+    assert tile_of({"tile": np.int32(8), "Sc": np.zeros(4)}) == 8
+    assert tile_of({"Sc": np.zeros((2, 2, 8))}) == 8 and tile_of({"Sb": np.zeros(16)}) is None
     with pytest.raises(ValueError, match="meta was written for"):
         mod["_check_stego_shape"](np.zeros((16, 24, 3), np.uint8), meta)
     mod["_check_stego_shape"](np.zeros((16, 16, 3), np.uint8), meta)
