@@ -413,7 +413,6 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
   jacobi_sweep_pk<0>(a, n2, notconv);
   jacobi_sweep_pk<0>(a, n2, notconv);
   int sweep = 2;
-#if !defined(WM_EXP_R1_SWEEPS)
   // The embed's third sweep carries no test either: no image or noise tile is done after three
   // sweeps at cos^2 <= 1e-7 (tools/skip_study.cpp: 0 of 19 200), so the earliest last sweep is the 4th.
   if (!SIGMA_ONLY) {
@@ -421,16 +420,12 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
     jacobi_sweep_pk<0>(a, n2, notconv);
     sweep = 3;
   }
-#endif
   bool more = true;
   while (more && sweep < JAC_MAX_SWEEPS) {
     if ((sweep & 1) == 0) col_norms2_pk(a, n2);
     notconv = false;
-#if !defined(WM_EXP_R1_SWEEPS)
     if (!SIGMA_ONLY && sweep >= 4) jacobi_sweep_pk<1, true>(a, n2, notconv);
-    else
-#endif
-    jacobi_sweep_pk<SIGMA_ONLY ? 2 : 1>(a, n2, notconv);
+    else jacobi_sweep_pk<SIGMA_ONLY ? 2 : 1>(a, n2, notconv);
     ++sweep;
     // a rank-deficient tile's null columns are rounding residue whose cosines never fall (and whose tracked norms
     // cancel to garbage): after JAC_DEFI_FROM sweeps such a lane no longer keeps its wave iterating (gen_jacobi_asm.py)

@@ -54,9 +54,6 @@ int grow(wm_ctx* ctx, void** buf, size_t* have, size_t bytes, const char* what) 
 namespace {
 
 constexpr int N_SUMS = 5;          // detect: sum a, b, ab, aa, bb
-constexpr unsigned FB_SUB = 64;    // embed: sub-lists per kind of flagged tile (one per lane of the fallback kernel's scan)
-constexpr unsigned FB_PAD = 32;    // ints between two sub-list counters: one 128-byte line each
-constexpr unsigned FB_KINDS = 4;   // 0 literal chain, 1 constant, 2 rank 1, 3 one small singular value (B kept in fb_b)
 
 // The iteration every tile kernel spends its time in (B = X V by one-sided Jacobi) is a generated,
 // hand-scheduled gfx950 stream with pinned registers (tools/gen_jacobi_asm.py); -DWM_NO_ASM_JACOBI
@@ -76,13 +73,9 @@ __device__ __forceinline__ int sigma_tile_dev(const wm::RawTile& raw, float (&s)
   // cosine c between two equal singular values moves them by c s_i / 2, so 1e-8 bounds the error at 5e-5 s_i;
   // 1e-6 measured 4.7e-4 s_1 on one tile of a 4K noise frame (profiles/r02m_sigma_skip.log), 1e-7 and 1e-8 leave
   // every value of four 4K frames where the full sweeps leave it (5e-6 s_1).
-#ifndef WM_SIGMA_SKIP2
-#define WM_SIGMA_SKIP2 1e-8f
-#endif
-#ifndef WM_SIGMA_SKIP_FROM
-#define WM_SIGMA_SKIP_FROM 2
-#endif
-  const unsigned long long more = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2_SIGMA, WM_SIGMA_SKIP2, 3, WM_SIGMA_SKIP_FROM);
+  constexpr float SIGMA_SKIP2 = 1e-8f;
+  constexpr int SIGMA_SKIP_FROM = 2;
+  const unsigned long long more = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2_SIGMA, SIGMA_SKIP2, 3, SIGMA_SKIP_FROM);
 #pragma unroll
   for (int i = 0; i < 8; ++i) s[i] = wm::fsqrt(n2[i]);
   return more ? -1 : 1;
@@ -94,20 +87,43 @@ __device__ __forceinline__ int sigma_tile_dev(const wm::RawTile& raw, float (&s)
 // ---------------------------------------------------------------------------
 // tile I/O (per lane)
 // ---------------------------------------------------------------------------
+// The one byte path: a little-endian word of 4 pixels, and the 8 pixels of a tile row as a pair of them.  ALIGNED
+// (pointers and strides multiples of 8) moves whole words; otherwise the word is put together from / taken apart into
+// single bytes, which the compiler is free to merge into unaligned word accesses where the target allows them.
 template <bool ALIGNED>
-__device__ __forceinline__ void load_tile_u8(const uint8_t* __restrict__ p, const size_t stride,
-                                             float (&a)[8][8]) {
+__device__ __forceinline__ uint32_t load_px4(const uint8_t* __restrict__ q) {
+  if (ALIGNED) return *reinterpret_cast<const uint32_t*>(q);
+  return q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
+}
+template <bool ALIGNED>
+__device__ __forceinline__ void store_px4(uint8_t* __restrict__ q, const uint32_t w) {
+  if (ALIGNED) { *reinterpret_cast<uint32_t*>(q) = w; return; }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = (uint8_t)(w >> (8 * i));
+}
+template <bool ALIGNED>
+__device__ __forceinline__ void load_px8(const uint8_t* __restrict__ q, uint32_t& lo, uint32_t& hi) {
+  if (ALIGNED) { const uint2 w = *reinterpret_cast<const uint2*>(q); lo = w.x; hi = w.y; }
+  else { lo = load_px4<false>(q); hi = load_px4<false>(q + 4); }
+}
+template <bool ALIGNED>
+__device__ __forceinline__ void store_px8(uint8_t* __restrict__ q, const uint32_t lo, const uint32_t hi) {
+  if (ALIGNED) *reinterpret_cast<uint2*>(q) = make_uint2(lo, hi);
+  else { store_px4<false>(q, lo); store_px4<false>(q + 4, hi); }
+}
+
+template <bool ALIGNED>
+__device__ __forceinline__ void load_raw(const uint8_t* __restrict__ p, const size_t stride, wm::RawTile& t) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r) load_px8<ALIGNED>(p + r * stride, t.lo[r], t.hi[r]);
+}
+
+template <bool ALIGNED>
+__device__ __forceinline__ void load_tile_u8(const uint8_t* __restrict__ p, const size_t stride, float (&a)[8][8]) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     uint32_t lo, hi;
-    if (ALIGNED) {
-      const uint2 w = *reinterpret_cast<const uint2*>(p + r * stride);
-      lo = w.x; hi = w.y;
-    } else {
-      const uint8_t* q = p + r * stride;
-      lo = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
-      hi = q[4] | (q[5] << 8) | (q[6] << 16) | ((uint32_t)q[7] << 24);
-    }
+    load_px8<ALIGNED>(p + r * stride, lo, hi);
     a[r][0] = (float)(lo & 0xffu); a[r][1] = (float)((lo >> 8) & 0xffu);
     a[r][2] = (float)((lo >> 16) & 0xffu); a[r][3] = (float)(lo >> 24);
     a[r][4] = (float)(hi & 0xffu); a[r][5] = (float)((hi >> 8) & 0xffu);
@@ -116,40 +132,14 @@ __device__ __forceinline__ void load_tile_u8(const uint8_t* __restrict__ p, cons
 }
 
 template <bool ALIGNED>
-__device__ __forceinline__ void store_tile_u8(uint8_t* __restrict__ p, const size_t stride,
-                                              const float (&a)[8][8]) {
+__device__ __forceinline__ void store_tile_u8(uint8_t* __restrict__ p, const size_t stride, const float (&a)[8][8]) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const uint32_t lo = wm::quant_u8(a[r][0]) | (wm::quant_u8(a[r][1]) << 8) |
                         (wm::quant_u8(a[r][2]) << 16) | (wm::quant_u8(a[r][3]) << 24);
     const uint32_t hi = wm::quant_u8(a[r][4]) | (wm::quant_u8(a[r][5]) << 8) |
                         (wm::quant_u8(a[r][6]) << 16) | (wm::quant_u8(a[r][7]) << 24);
-    if (ALIGNED) {
-      *reinterpret_cast<uint2*>(p + r * stride) = make_uint2(lo, hi);
-    } else {
-      uint8_t* q = p + r * stride;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        q[i] = (uint8_t)(lo >> (8 * i));
-        q[4 + i] = (uint8_t)(hi >> (8 * i));
-      }
-    }
-  }
-}
-
-template <bool ALIGNED>
-__device__ __forceinline__ void load_raw(const uint8_t* __restrict__ p, const size_t stride,
-                                         wm::RawTile& t) {
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    if (ALIGNED) {
-      const uint2 w = *reinterpret_cast<const uint2*>(p + r * stride);
-      t.lo[r] = w.x; t.hi[r] = w.y;
-    } else {
-      const uint8_t* q = p + r * stride;
-      t.lo[r] = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
-      t.hi[r] = q[4] | (q[5] << 8) | (q[6] << 16) | ((uint32_t)q[7] << 24);
-    }
+    store_px8<ALIGNED>(p + r * stride, lo, hi);
   }
 }
 
@@ -157,41 +147,12 @@ __device__ __forceinline__ void load_raw(const uint8_t* __restrict__ p, const si
 template <bool ALIGNED>
 __device__ __forceinline__ void load_words(const uint8_t* __restrict__ p, const size_t stride, uint32_t (&w)[8]) {
 #pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const uint8_t* q = p + r * stride;
-    if (ALIGNED) w[r] = *reinterpret_cast<const uint32_t*>(q);
-    else w[r] = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
-  }
+  for (int r = 0; r < 8; ++r) w[r] = load_px4<ALIGNED>(p + r * stride);
 }
 template <bool ALIGNED>
 __device__ __forceinline__ void store_words(uint8_t* __restrict__ p, const size_t stride, const uint32_t (&w)[8]) {
 #pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    uint8_t* q = p + r * stride;
-    if (ALIGNED) *reinterpret_cast<uint32_t*>(q) = w[r];
-    else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) q[i] = (uint8_t)(w[r] >> (8 * i));
-    }
-  }
-}
-
-template <bool ALIGNED>
-__device__ __forceinline__ void store_raw(uint8_t* __restrict__ p, const size_t stride,
-                                          const wm::RawTile& t) {
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    if (ALIGNED) {
-      *reinterpret_cast<uint2*>(p + r * stride) = make_uint2(t.lo[r], t.hi[r]);
-    } else {
-      uint8_t* q = p + r * stride;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        q[i] = (uint8_t)(t.lo[r] >> (8 * i));
-        q[4 + i] = (uint8_t)(t.hi[r] >> (8 * i));
-      }
-    }
-  }
+  for (int r = 0; r < 8; ++r) store_px4<ALIGNED>(p + r * stride, w[r]);
 }
 
 template <bool VEC>
@@ -237,6 +198,15 @@ struct Geom {
   size_t plane_stride;
 };
 
+// Where tile (ty, tx) of `plane` starts.  In a strided uint8 / float plane batch: `base` is the batch's pointer, or
+// (size_t)0 for the element offset itself (the embed kernels address host and stego with one offset) ...
+#define STRIDED_TILE(base, g, plane, ty, tx) \
+  ((base) + (plane) * (g).plane_stride + (size_t)(ty) * 8 * (g).row_stride + (size_t)(tx) * 8)
+// ... and in a dense [plane][H][W] float output (row stride g.W).
+#define DENSE_TILE(out, g, plane, ty, tx) ((out) + (plane) * (g).HW + (size_t)(ty) * 8 * (g).W + (size_t)(tx) * 8)
+// (Macros: a function's body is optimised on its own before it is inlined, which folds the tile row's * 8 into one stride
+// where a kernel shares it between both addresses, and the extract and embed kernels then compile to other code.)
+
 __device__ __forceinline__ bool tile_coords(const Geom& g, int& t, int& ty, int& tx) {
   t = blockIdx.x * WAVE + threadIdx.x;
   if (t >= g.n_tiles) return false;
@@ -252,18 +222,16 @@ __device__ __forceinline__ bool tile_coords(const Geom& g, int& t, int& ty, int&
 // shared inputs come from HBM once and are served to the other planes by that XCD's L2, instead
 // of once per plane (grid (groups, planes): 66 MB of factors re-fetched 32 times at 32 x 4K).
 constexpr unsigned N_XCD = 8;
+struct GroupPlane { unsigned grp; size_t plane; };
+__device__ __forceinline__ GroupPlane group_plane_planefast(const unsigned n_planes) {
+  const unsigned b = blockIdx.x, x = b % N_XCD, k = b / N_XCD;
+  return {x + N_XCD * (k / n_planes), k % n_planes};
+}
 __device__ __forceinline__ bool tile_coords_planefast(const Geom& g, const unsigned n_planes, int& t, int& ty,
                                                       int& tx, size_t& plane) {
-#if defined(WM_EXP_EXTRACT_OLDMAP)   // A/B only: the round-1 order (all tile groups of plane 0, then plane 1, ...)
-  const unsigned per_plane = gridDim.x / n_planes;
-  const unsigned grp = blockIdx.x % per_plane;
-  plane = blockIdx.x / per_plane;
-#else
-  const unsigned b = blockIdx.x, x = b % N_XCD, k = b / N_XCD;
-  const unsigned grp = x + N_XCD * (k / n_planes);
-  plane = k % n_planes;
-#endif
-  t = (int)(grp * WAVE + threadIdx.x);
+  const GroupPlane gp = group_plane_planefast(n_planes);
+  plane = gp.plane;
+  t = (int)(gp.grp * WAVE + threadIdx.x);
   if (t >= g.n_tiles) return false;
   ty = t / g.nbx;
   tx = t - ty * g.nbx;
@@ -278,12 +246,121 @@ inline dim3 tile_grid_planefast(const Geom& g, int n_planes) {
 // ---------------------------------------------------------------------------
 // K1  fused embed   (a1 a2 a3 a4 a5 a6 a7; sigma_c side output)
 // ---------------------------------------------------------------------------
-// Fast path: packed, V-free, pixel-domain (wm_tile_math.h identities (1),(2)).
-// Flat / rank-deficient tiles append their id to one of the flagged-tile lists in `fb_list` (see append_kind)
-// and are redone by k_embed_fallback.
-#ifndef WM_EMBED_WAVES
-#define WM_EMBED_WAVES 3
-#endif
+// Fast path (k_embed_tiles): packed, V-free, pixel-domain (wm_tile_math.h identities (1),(2)).  Flat / rank-deficient
+// tiles are left untouched there, appended to the flagged-tile lists and redone by k_embed_fallback (kinds 0-2) and
+// k_embed_one_small (kind 3).
+//
+// The flagged-tile lists.  A flagged tile's id is plane * n_tiles + t; its kind says how it is redone:
+//   0  the literal chain with orthonormal completion (wm::embed_tile_completed)
+//   1  constant tiles: closed form (wm::embed_tile_constant)
+//   2  rank-1 tiles that are not constant: closed form (wm::embed_tile_rank1)
+//   3  every other flagged tile - one singular value out of reach or rank 2 .. 6: completed from the fast kernel's B
+//      (wm::embed_tile_one_small / embed_tile_from_b), which is kept beside the id
+// Each kind is split into FB_SUB sub-lists with a counter of their own, and a wave of the fast kernel appends to sub-list
+// (blockIdx.x % FB_SUB), wave-aggregated: one atomic per wave and kind.  (One counter per kind serialised the whole launch
+// on content made of such tiles: 16 200 same-address atomics at ~12 ns each were 189 of the fast kernel's 189 us on an
+// all-flat 8 x 4K batch, HISTORY.md round 3.)  Three arrays hold them, sized by wm_embed_tiles_u8_dev:
+//   fb_list  3 * FB_SUB * fb_cap + FB_SUB * fb_cap3 ids.  Sub-list s of kind k < 3 starts at (k * FB_SUB + s) * fb_cap and
+//            cannot overflow: fb_cap is the tile count of all waves that map to one sub-list.  Sub-list s of kind 3 starts
+//            at 3 * FB_SUB * fb_cap + s * fb_cap3.
+//   fb_cnt   FB_KINDS * FB_SUB counters, FB_PAD ints (one 128-byte line) apart: sub-list s of kind k counts in
+//            fb_cnt[(k * FB_SUB + s) * FB_PAD].  Zeroed before every launch.
+//   fb_b     64 floats (B as 4 x 8 row pairs) per kind-3 slot: entry j of sub-list s at (s * fb_cap3 + j) * 64.
+// Kind 3 is the only one that can overflow (fb_cap3 = fb_cap / 16, at least 64: B costs 256 bytes per tile).  Its counter
+// still counts every tile that asked; a tile whose slot is >= fb_cap3 goes to kind 0 instead, and the readers clamp the
+// count to fb_cap3.
+constexpr unsigned FB_SUB = 64;    // sub-lists per kind (one per lane of the readers' scan)
+constexpr unsigned FB_PAD = 32;    // ints between two sub-list counters
+constexpr unsigned FB_KINDS = 4;
+constexpr int EMBED_WAVES = 3;     // waves per SIMD the launch bounds of k_embed_tiles ...
+constexpr int FALLBACK_WAVES = 2;  // ... and k_embed_fallback ask for
+
+__device__ __forceinline__ size_t fb_counter(const unsigned l) { return (size_t)l * FB_PAD; }      // of sub-list l = kind * FB_SUB + s
+
+// Writer: reserves entries of sub-list l = kind * FB_SUB + sub for the wave's flagged lanes with one atomic, then has each
+// flagged lane store(l, base, rank) its tile: entry base + rank of the sub-list is that lane's.  store says whether it took
+// the entry (kind 3 does not from fb_cap3 on); the result is true for the lanes whose tile is now listed.
+template <typename Store>
+__device__ __forceinline__ bool fb_reserve(int* __restrict__ fb_cnt, const unsigned kind, const unsigned sub, const bool flag,
+                                           const Store& store) {
+  const unsigned long long dmask = __builtin_amdgcn_ballot_w64(flag);
+  if (dmask == 0ull) return flag;      // (false)
+  const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const unsigned leader = (unsigned)__builtin_ctzll(dmask);
+  const unsigned l = kind * FB_SUB + sub;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(fb_cnt + fb_counter(l), (int)__builtin_popcountll(dmask));
+  base = __builtin_amdgcn_readlane(base, leader);
+  return flag && store(l, base, (unsigned)__builtin_popcountll(dmask & ((1ull << lane) - 1ull)));
+}
+
+// Readers: one tile per lane, a fixed grid striding a kind's items (the counts are only known on the device).  The
+// sub-lists' counts are scanned in the wave (lane l holds sub-list l); the sub-list that owns item `it` is found by a
+// 6-step search over the lanes' prefix sums.
+struct FlaggedTile {
+  size_t plane;
+  int t, ty, tx;
+  size_t off;      // of the tile in host / stego
+  size_t slot;     // of the entry within its kind (kind 3: in fb_b)
+};
+struct FbWalk {
+  const uint32_t* __restrict__ fb_list;
+  uint32_t fb_cap, fb_cap3;
+  int pre[FB_KINDS], total[FB_KINDS];
+
+  __device__ __forceinline__ FbWalk(const uint32_t* __restrict__ fb_list_, const int* __restrict__ fb_cnt,
+                                    const uint32_t fb_cap_, const uint32_t fb_cap3_)
+      : fb_list(fb_list_), fb_cap(fb_cap_), fb_cap3(fb_cap3_) {
+    static_assert(FB_SUB == WAVE, "one sub-list per lane");
+#pragma unroll
+    for (int k = 0; k < (int)FB_KINDS; ++k) {
+      int c = fb_cnt[fb_counter(k * FB_SUB + threadIdx.x)];
+      if (k == 3) c = min(c, (int)fb_cap3);
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < WAVE; o <<= 1) { const int v = __shfl_up(incl, o, WAVE); if ((int)threadIdx.x >= o) incl += v; }
+      pre[k] = incl - c;
+      total[k] = __shfl(incl, WAVE - 1, WAVE);
+    }
+  }
+  // The lane's tile of the wave's items it0 .. it0 + 63 of kind k (it0 < total[k], wave-uniform: the shuffles need every
+  // lane); false for the lanes past the last item.
+  __device__ __forceinline__ bool item(const int k, const int it0, const Geom& g, FlaggedTile& tl) const {
+    const int it = min(it0 + (int)threadIdx.x, total[k] - 1);
+    int sub = 0;
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) { const int p = __shfl(pre[k], sub + o, WAVE); if (p <= it) sub += o; }
+    const int j = it - __shfl(pre[k], sub, WAVE);
+    if (it0 + (int)threadIdx.x >= total[k]) return false;
+    tl.slot = (size_t)sub * (k == 3 ? fb_cap3 : fb_cap) + j;
+    const uint32_t id = fb_list[(size_t)k * FB_SUB * fb_cap + tl.slot];
+    tl.plane = id / (uint32_t)g.n_tiles;
+    tl.t = (int)(id % (uint32_t)g.n_tiles);
+    tl.ty = tl.t / g.nbx;
+    tl.tx = tl.t - tl.ty * g.nbx;
+    tl.off = STRIDED_TILE((size_t)0, g, tl.plane, tl.ty, tl.tx);
+    return true;
+  }
+};
+
+__device__ __forceinline__ void fill_alpha_k(const float alpha, const int K, float (&alpha_k)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) alpha_k[i] = (i < K) ? alpha : 0.0f;
+}
+
+// what a redone tile leaves: its Sc, its stego pixels and, with YW, the unquantised pixels
+template <bool ALIGNED, bool YW>
+__device__ __forceinline__ void finish_flagged(const Geom& g, const FlaggedTile& tl, float* __restrict__ sigma_c, uint8_t* stego,
+                                               float* __restrict__ yw, const float (&sc)[8], const float (&a)[8][8]) {
+  store_row8_f32<true>(sigma_c + (tl.plane * g.n_tiles + tl.t) * 8, sc);
+  store_tile_u8<ALIGNED>(stego + tl.off, g.row_stride, a);
+  if (YW) {
+    float* o = DENSE_TILE(yw, g, tl.plane, tl.ty, tl.tx);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) store_row8_f32<false>(o + (size_t)r * g.W, a[r]);
+  }
+}
+
 template <bool ALIGNED, bool YW>
 __device__ __forceinline__ void embed_group(
     const uint8_t* host, const float* __restrict__ sigma_w,
@@ -292,27 +369,13 @@ __device__ __forceinline__ void embed_group(
     int* __restrict__ status, uint32_t* __restrict__ fb_list, int* __restrict__ fb_cnt, const uint32_t fb_cap,
     float* __restrict__ fb_b, const uint32_t fb_cap3,
     const int t, const int ty, const int tx, const size_t plane) {
-  const size_t off = plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
-
-  // Flagged tiles are appended (wave-aggregated: one atomic per wave and kind) to one of three lists - 0: the literal
-  // chain, 1: constant tiles, 2: rank-1 tiles - each split into FB_SUB sub-lists with their own counters, a wave using
-  // sub-list (wave id % FB_SUB).  One counter per kind serialised the whole launch on content made of such tiles: 16 200
-  // same-address atomics at ~12 ns each were 189 of the fast kernel's 189 us on an all-flat 8 x 4K batch (round 3,
-  // gpurun_out/r03o).  Sub-list s of kind k: fb_list[(k * FB_SUB + s) * fb_cap ...], counter fb_cnt[(k * FB_SUB + s) * FB_PAD].
+  const size_t off = STRIDED_TILE((size_t)0, g, plane, ty, tx);
   const unsigned fb_sub = blockIdx.x % FB_SUB;
-  auto append_kind = [&](const bool flag, const int kind) {
-    const unsigned long long dmask = __builtin_amdgcn_ballot_w64(flag);
-    if (dmask == 0ull) return;
-    const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const unsigned leader = (unsigned)__builtin_ctzll(dmask);
-    const unsigned l = (unsigned)kind * FB_SUB + fb_sub;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(fb_cnt + (size_t)l * FB_PAD, (int)__builtin_popcountll(dmask));
-    base = __builtin_amdgcn_readlane(base, leader);
-    if (flag) {
-      const unsigned rank = (unsigned)__builtin_popcountll(dmask & ((1ull << lane) - 1ull));
+  auto append_kind = [&](const bool flag, const unsigned kind) {
+    fb_reserve(fb_cnt, kind, fb_sub, flag, [&](const unsigned l, const int base, const unsigned rank) {
       fb_list[(size_t)l * fb_cap + base + rank] = (uint32_t)(plane * g.n_tiles + t);
-    }
+      return true;
+    });
   };
   wm::v2f a[4][8];
   float n2[8];
@@ -323,14 +386,12 @@ __device__ __forceinline__ void embed_group(
     wm::RawTile raw;
     load_raw<ALIGNED>(host + off, g.row_stride, raw);
     // A wave of constant tiles only (letterbox bars, flat backgrounds) has nothing to iterate on: all of them are
-    // rank-deficient and go to the constant list, which k_embed_fallback finishes in closed form
-    // (wm::embed_tile_constant).  A constant tile in a mixed wave rides the iteration along and goes to the same list.
+    // rank-deficient and go to kind 1.  A constant tile in a mixed wave rides the iteration along and goes to the same list.
     // (the 16-word comparison only if some tile of the wave passes a two-word test: textured content pays 3 instructions)
     cst = false;
     if (__builtin_amdgcn_ballot_w64(raw.lo[0] == raw.hi[0] && raw.lo[0] == raw.hi[7]) != 0ull) cst = wm::raw_is_constant(raw);
-    // rank-1 tiles that are not constant (edges of flat rectangles, rules and their crossings): closed form as well
-    // (wm::embed_tile_rank1, third list).  The exact test (64 integer products) only runs if some tile of the wave passes
-    // three 2x2 minors: textured waves pay ~15 instructions.
+    // rank-1 tiles that are not constant (edges of flat rectangles, rules and their crossings) are kind 2.  The exact test
+    // (64 integer products) only runs if some tile of the wave passes three 2x2 minors: textured waves pay ~15 instructions.
     r1 = 0;
     if (__builtin_amdgcn_ballot_w64(!cst && wm::raw_rank1_pretest(raw)) != 0ull && !cst && wm::raw_is_rank1(raw)) r1 = 1;
     if (__builtin_amdgcn_ballot_w64(!cst && r1 == 0) == 0ull) {      // nothing in this wave needs the iteration
@@ -355,52 +416,32 @@ __device__ __forceinline__ void embed_group(
   {
     float sw[8], sc[8], alpha_k[8];
     load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) alpha_k[i] = (i < K) ? alpha : 0.0f;
+    fill_alpha_k(alpha, K, alpha_k);
     wm::embed_coeffs_pk(n2, sw, alpha_k, e, sc, deficient);
     deficient = deficient || cst || r1 != 0;   // (constant and rank-1 tiles always are: sigma_8 = 0)
     // flagged tiles are left untouched: stego may alias host (in-place embedding) and the
-    // fallback kernel must still read the original pixels; it also writes their Sc
+    // list kernels must still read the original pixels; they also write their Sc
     if (!deficient) store_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
   }
-  // Every other flagged tile - one singular value out of reach (noise / camera content) or rank 2 .. 6 (structured content) -
-  // is kind 3: k_embed_one_small completes it from THIS B (wm::embed_tile_one_small / embed_tile_from_b), no Jacobi with
-  // V.  B goes to fb_b (256 bytes per tile; kind 3's sub-lists hold fb_cap3 entries each, what does not fit takes the
-  // literal chain).
+  // kind 3 takes THIS B along, so that k_embed_one_small needs no Jacobi with V; a full sub-list sends the tile to kind 0
   bool one_small = deficient && !cst && r1 == 0;
-#if defined(WM_EXP_NO_ONE_SMALL)    // A/B only: everything flagged that is not constant / rank 1 takes the literal chain (round 2 behaviour)
-  one_small = false;
-#endif
-  {
-    const unsigned long long dmask = __builtin_amdgcn_ballot_w64(one_small);
-    if (dmask != 0ull) {
-      const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      const unsigned leader = (unsigned)__builtin_ctzll(dmask);
-      const unsigned l = 3u * FB_SUB + fb_sub;
-      int base = 0;
-      if (lane == leader) base = atomicAdd(fb_cnt + (size_t)l * FB_PAD, (int)__builtin_popcountll(dmask));
-      base = __builtin_amdgcn_readlane(base, leader);
-      if (one_small) {
-        const unsigned slot = (unsigned)base + (unsigned)__builtin_popcountll(dmask & ((1ull << lane) - 1ull));
-        if (slot < fb_cap3) {
-          const size_t pos = (size_t)fb_sub * fb_cap3 + slot;
-          fb_list[(size_t)3 * FB_SUB * fb_cap + pos] = (uint32_t)(plane * g.n_tiles + t);
-          wm::v2f* dstb = reinterpret_cast<wm::v2f*>(fb_b + pos * 64);
+  one_small = fb_reserve(fb_cnt, 3, fb_sub, one_small, [&](const unsigned, const int base, const unsigned rank) {
+    const unsigned j = (unsigned)base + rank;
+    if (j >= fb_cap3) return false;
+    const size_t slot = (size_t)fb_sub * fb_cap3 + j;
+    fb_list[(size_t)3 * FB_SUB * fb_cap + slot] = (uint32_t)(plane * g.n_tiles + t);
+    wm::v2f* dstb = reinterpret_cast<wm::v2f*>(fb_b + slot * 64);
 #pragma unroll
-          for (int rp = 0; rp < 4; ++rp)
+    for (int rp = 0; rp < 4; ++rp)
 #pragma unroll
-            for (int c = 0; c < 8; ++c) dstb[rp * 8 + c] = a[rp][c];
-        } else {
-          one_small = false;                        // sub-list full: the literal chain
-        }
-      }
-    }
-  }
+      for (int c = 0; c < 8; ++c) dstb[rp * 8 + c] = a[rp][c];
+    return true;
+  });
   append_kind(deficient && !cst && r1 == 0 && !one_small, 0);
   append_kind(cst, 1);
   append_kind(r1 != 0, 2);
   if (sweeps < 0) atomicOr(status, 1);
-  float* ywp = YW ? yw + plane * g.HW + (size_t)ty * 8 * g.W + (size_t)tx * 8 : nullptr;
+  float* ywp = YW ? DENSE_TILE(yw, g, plane, ty, tx) : nullptr;
 #pragma nounroll
   for (int half = 0; half < 2; ++half) {      // a real loop: one half's registers at a time
     uint32_t w[8], ow[8];
@@ -417,7 +458,7 @@ __device__ __forceinline__ void embed_group(
 // dynamic placement balances waves that need 4 against waves that need 5 sweeps, a fixed
 // stride does not.
 template <bool ALIGNED, bool YW>
-__global__ __launch_bounds__(WAVE, WM_EMBED_WAVES) void k_embed_tiles(
+__global__ __launch_bounds__(WAVE, EMBED_WAVES) void k_embed_tiles(
     const uint8_t* host, const float* __restrict__ sigma_w,
     uint8_t* stego, float* __restrict__ sigma_c, float* __restrict__ yw,
     const Geom g, const unsigned n_groups, const size_t sw_plane_stride,
@@ -432,111 +473,53 @@ __global__ __launch_bounds__(WAVE, WM_EMBED_WAVES) void k_embed_tiles(
                            t, ty, tx, (size_t)plane);
 }
 
-// The tiles listed by the fast kernel, one per lane, a fixed grid striding each list (the counts are only known on
-// the device): first the literal chain with orthonormal completion (wm::embed_tile_completed) for the front list,
-// then the closed form of the constant tiles (wm::embed_tile_constant) for the back list.
-#ifndef WM_FALLBACK_WAVES
-#define WM_FALLBACK_WAVES 2
-#endif
+// Kinds 0, 1 and 2 of the flagged-tile lists, one walk after the other.
 template <bool ALIGNED, bool YW>
-__global__ __launch_bounds__(WAVE, WM_FALLBACK_WAVES) void k_embed_fallback(
+__global__ __launch_bounds__(WAVE, FALLBACK_WAVES) void k_embed_fallback(
     const uint8_t* host, const float* __restrict__ sigma_w,
     uint8_t* stego, float* __restrict__ sigma_c, float* __restrict__ yw,
     const Geom g, const size_t sw_plane_stride, const float alpha, const int K,
     int* __restrict__ status, const uint32_t* __restrict__ fb_list, const int* __restrict__ fb_cnt, const uint32_t fb_cap,
     const float* __restrict__ fb_b, const uint32_t fb_cap3) {
   float alpha_k[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) alpha_k[i] = (i < K) ? alpha : 0.0f;
-  auto finish = [&](const size_t plane, const int t, const size_t off, const float (&sc)[8], float (&a)[8][8]) {
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    store_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
-    store_tile_u8<ALIGNED>(stego + off, g.row_stride, a);
-    if (YW) {
-      float* o = yw + plane * g.HW + (size_t)ty * 8 * g.W + (size_t)tx * 8;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) store_row8_f32<false>(o + (size_t)r * g.W, a[r]);
-    }
-  };
-  // item `it` of kind k: the sub-lists' counts are scanned in the wave (lane l holds sub-list l), the owning sub-list is
-  // found by a 6-step search over the lanes' prefix sums
-  static_assert(FB_SUB == WAVE, "one sub-list per lane");
-  int pre[FB_KINDS], total[FB_KINDS];
-#pragma unroll
-  for (int k = 0; k < (int)FB_KINDS; ++k) {
-    int c = fb_cnt[(size_t)(k * FB_SUB + threadIdx.x) * FB_PAD];
-    if (k == 3) c = min(c, (int)fb_cap3);           // what did not fit went to kind 0
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) { const int v = __shfl_up(incl, o, WAVE); if ((int)threadIdx.x >= o) incl += v; }
-    pre[k] = incl - c;
-    total[k] = __shfl(incl, WAVE - 1, WAVE);
-  }
-  auto locate = [&](const int k, const int it, int& sub, int& j) {      // `it` < total[k]
-    int s_ = 0;
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) { const int p_ = __shfl(pre[k], s_ + o, WAVE); if (p_ <= it) s_ += o; }
-    sub = s_; j = it - __shfl(pre[k], s_, WAVE);
-  };
-  auto item = [&](const int k, const int it) -> uint32_t {
-    int sub, j;
-    locate(k, it, sub, j);
-    return fb_list[(size_t)(k * FB_SUB + sub) * fb_cap + j];
-  };
-  const int count = total[0], n_const = total[1], n_rank1 = total[2];
-  for (int it0 = blockIdx.x * WAVE; it0 < count; it0 += gridDim.x * WAVE) {      // wave-uniform bounds: the shuffles need every lane
-    const int it = it0 + threadIdx.x;
-    const uint32_t id = item(0, min(it, count - 1));
-    if (it >= count) continue;
-    const size_t plane = id / (uint32_t)g.n_tiles;
-    const int t = (int)(id % (uint32_t)g.n_tiles);
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    const size_t off = plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
+  fill_alpha_k(alpha, K, alpha_k);
+  const FbWalk walk(fb_list, fb_cnt, fb_cap, fb_cap3);
+  for (int it0 = blockIdx.x * WAVE; it0 < walk.total[0]; it0 += gridDim.x * WAVE) {
+    FlaggedTile tl;
     float a[8][8], sw[8], sc[8];
-    load_tile_u8<ALIGNED>(host + off, g.row_stride, a);
-    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    if (!walk.item(0, it0, g, tl)) continue;
+    load_tile_u8<ALIGNED>(host + tl.off, g.row_stride, a);
+    load_row8_f32<true>(sigma_w + tl.plane * sw_plane_stride + (size_t)tl.t * 8, sw);
     if (wm::embed_tile_completed(a, sw, alpha_k, sc) < 0) atomicOr(status, 1);
-    finish(plane, t, off, sc, a);
+    finish_flagged<ALIGNED, YW>(g, tl, sigma_c, stego, yw, sc, a);
   }
-  for (int it0 = blockIdx.x * WAVE; it0 < n_const; it0 += gridDim.x * WAVE) {
-    const int it = it0 + threadIdx.x;
-    const uint32_t id = item(1, min(it, n_const - 1));
-    if (it >= n_const) continue;
-    const size_t plane = id / (uint32_t)g.n_tiles;
-    const int t = (int)(id % (uint32_t)g.n_tiles);
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    const size_t off = plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
+  for (int it0 = blockIdx.x * WAVE; it0 < walk.total[1]; it0 += gridDim.x * WAVE) {
+    FlaggedTile tl;
     float a[8][8], sw[8], sc[8];
-    const float v0 = (float)host[off];                    // every pixel of the tile has this value
-    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    if (!walk.item(1, it0, g, tl)) continue;
+    const float v0 = (float)host[tl.off];                    // every pixel of the tile has this value
+    load_row8_f32<true>(sigma_w + tl.plane * sw_plane_stride + (size_t)tl.t * 8, sw);
     // the table is a compile-time constant when the wave's tiles are all black or none of them is (bit-identical
     // to the general form, which adds 0 * the other table)
     const unsigned long long bm = __builtin_amdgcn_ballot_w64(v0 == 0.0f);
     if (bm == 0ull) wm::embed_tile_constant_t<1>(v0, sw, alpha_k, sc, a);
     else if (bm == __builtin_amdgcn_ballot_w64(true)) wm::embed_tile_constant_t<0>(v0, sw, alpha_k, sc, a);
     else wm::embed_tile_constant(v0, sw, alpha_k, sc, a);
-    finish(plane, t, off, sc, a);
+    finish_flagged<ALIGNED, YW>(g, tl, sigma_c, stego, yw, sc, a);
   }
-  for (int it0 = blockIdx.x * WAVE; it0 < n_rank1; it0 += gridDim.x * WAVE) {
-    const int it = it0 + threadIdx.x;
-    const uint32_t id = item(2, min(it, n_rank1 - 1));
-    if (it >= n_rank1) continue;
-    const size_t plane = id / (uint32_t)g.n_tiles;
-    const int t = (int)(id % (uint32_t)g.n_tiles);
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    const size_t off = plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
+  for (int it0 = blockIdx.x * WAVE; it0 < walk.total[2]; it0 += gridDim.x * WAVE) {
+    FlaggedTile tl;
     float a[8][8], sw[8], sc[8];
-    load_tile_u8<ALIGNED>(host + off, g.row_stride, a);
-    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    if (!walk.item(2, it0, g, tl)) continue;
+    load_tile_u8<ALIGNED>(host + tl.off, g.row_stride, a);
+    load_row8_f32<true>(sigma_w + tl.plane * sw_plane_stride + (size_t)tl.t * 8, sw);
     wm::embed_tile_rank1(a, sw, alpha_k, sc, a);
-    finish(plane, t, off, sc, a);
+    finish_flagged<ALIGNED, YW>(g, tl, sigma_c, stego, yw, sc, a);
   }
 }
 
-// Kind 3 of the flagged-tile lists (completed from the fast kernel's B: wm::embed_tile_one_small / embed_tile_from_b) in a
-// kernel of its own, one wave per SIMD: three 8 x 8 arrays and a float64 bilinear form need 314-362 registers; inside
-// k_embed_fallback they pushed the literal chain's 202-228 VGPRs into scratch.  Same list walk as k_embed_fallback (one
-// tile per lane, a fixed grid striding the list - the count is only known on the device).
+// Kind 3 of the flagged-tile lists in a kernel of its own, one wave per SIMD: three 8 x 8 arrays and a float64 bilinear
+// form need 314-362 registers; inside k_embed_fallback they pushed the literal chain's 202-228 VGPRs into scratch.
 template <bool ALIGNED, bool YW>
 __global__ __launch_bounds__(WAVE, 1) void k_embed_one_small(
     const uint8_t* host, const float* __restrict__ sigma_w,
@@ -545,63 +528,19 @@ __global__ __launch_bounds__(WAVE, 1) void k_embed_one_small(
     int* __restrict__ status, const uint32_t* __restrict__ fb_list, const int* __restrict__ fb_cnt, const uint32_t fb_cap,
     const float* __restrict__ fb_b, const uint32_t fb_cap3) {
   float alpha_k[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) alpha_k[i] = (i < K) ? alpha : 0.0f;
-  auto finish = [&](const size_t plane, const int t, const size_t off, const float (&sc)[8], float (&a)[8][8]) {
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    store_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
-    store_tile_u8<ALIGNED>(stego + off, g.row_stride, a);
-    if (YW) {
-      float* o = yw + plane * g.HW + (size_t)ty * 8 * g.W + (size_t)tx * 8;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) store_row8_f32<false>(o + (size_t)r * g.W, a[r]);
-    }
-  };
-  // item `it` of kind k: the sub-lists' counts are scanned in the wave (lane l holds sub-list l), the owning sub-list is
-  // found by a 6-step search over the lanes' prefix sums
-  static_assert(FB_SUB == WAVE, "one sub-list per lane");
-  int pre[FB_KINDS], total[FB_KINDS];
-#pragma unroll
-  for (int k = 0; k < (int)FB_KINDS; ++k) {
-    int c = fb_cnt[(size_t)(k * FB_SUB + threadIdx.x) * FB_PAD];
-    if (k == 3) c = min(c, (int)fb_cap3);           // what did not fit went to kind 0
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) { const int v = __shfl_up(incl, o, WAVE); if ((int)threadIdx.x >= o) incl += v; }
-    pre[k] = incl - c;
-    total[k] = __shfl(incl, WAVE - 1, WAVE);
-  }
-  auto locate = [&](const int k, const int it, int& sub, int& j) {      // `it` < total[k]
-    int s_ = 0;
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) { const int p_ = __shfl(pre[k], s_ + o, WAVE); if (p_ <= it) s_ += o; }
-    sub = s_; j = it - __shfl(pre[k], s_, WAVE);
-  };
-  auto item = [&](const int k, const int it) -> uint32_t {
-    int sub, j;
-    locate(k, it, sub, j);
-    return fb_list[(size_t)(k * FB_SUB + sub) * fb_cap + j];
-  };
-  const int n_small = total[3];
-  for (int it0 = blockIdx.x * WAVE; it0 < n_small; it0 += gridDim.x * WAVE) {
-    const int it = it0 + threadIdx.x;
-    int sub, j;
-    locate(3, min(it, n_small - 1), sub, j);
-    if (it >= n_small) continue;
-    const size_t pos = (size_t)sub * fb_cap3 + j;
-    const uint32_t id = fb_list[(size_t)3 * FB_SUB * fb_cap + pos];
-    const size_t plane = id / (uint32_t)g.n_tiles;
-    const int t = (int)(id % (uint32_t)g.n_tiles);
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
-    const size_t off = plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
+  fill_alpha_k(alpha, K, alpha_k);
+  const FbWalk walk(fb_list, fb_cnt, fb_cap, fb_cap3);
+  for (int it0 = blockIdx.x * WAVE; it0 < walk.total[3]; it0 += gridDim.x * WAVE) {
+    FlaggedTile tl;
+    if (!walk.item(3, it0, g, tl)) continue;
     float a[8][8], bb[8][8], sw[8], sc[8];
-    load_tile_u8<ALIGNED>(host + off, g.row_stride, a);
-    const wm::v2f* srcb = reinterpret_cast<const wm::v2f*>(fb_b + pos * 64);
+    load_tile_u8<ALIGNED>(host + tl.off, g.row_stride, a);
+    const wm::v2f* srcb = reinterpret_cast<const wm::v2f*>(fb_b + tl.slot * 64);
 #pragma unroll
     for (int rp = 0; rp < 4; ++rp)
 #pragma unroll
       for (int c = 0; c < 8; ++c) { const wm::v2f v = srcb[rp * 8 + c]; bb[2 * rp][c] = v[0]; bb[2 * rp + 1][c] = v[1]; }
-    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    load_row8_f32<true>(sigma_w + tl.plane * sw_plane_stride + (size_t)tl.t * 8, sw);
     float n6 = 0.0f, n0 = 0.0f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) { n6 = __builtin_fmaf(bb[r][6], bb[r][6], n6); n0 = __builtin_fmaf(bb[r][0], bb[r][0], n0); }
@@ -609,7 +548,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_embed_one_small(
     const bool one = n6 > wm::SIGMA_RATIO_MIN2 * n0;
     if (wm::wave_any(one)) { if (one) wm::embed_tile_one_small(a, bb, sw, alpha_k, sc, a); }
     if (wm::wave_any(!one)) { if (!one) wm::embed_tile_from_b(a, bb, sw, alpha_k, sc, a); }
-    finish(plane, t, off, sc, a);
+    finish_flagged<ALIGNED, YW>(g, tl, sigma_c, stego, yw, sc, a);
   }
 }
 
@@ -645,8 +584,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_sigma_tiles(const uint8_t* __restri
   const size_t plane = blockIdx.y;
   wm::RawTile raw;
   float s[8];
-  load_raw<ALIGNED>(planes + plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8,
-                    g.row_stride, raw);
+  load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
   if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
   store_row8_f32<true>(sigma + (plane * g.n_tiles + t) * 8, s);
 }
@@ -662,7 +600,7 @@ __global__ __launch_bounds__(WAVE, 2) void k_svd_tiles(const float* __restrict__
   int t, ty, tx;
   if (!tile_coords(g, t, ty, tx)) return;
   const size_t plane = blockIdx.y;
-  const float* p = planes + plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8;
+  const float* p = STRIDED_TILE(planes, g, plane, ty, tx);
   float a[8][8], s[8], vt[8][8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) load_row8_f32<VECF>(p + (size_t)r * g.row_stride, a[r]);
@@ -705,19 +643,17 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
   size_t plane;
   bool valid = true;
   if (MM) {
-    const unsigned b = blockIdx.x, x = b % N_XCD, k = b / N_XCD;
-    const unsigned grp = x + N_XCD * (k / n_planes);
-    plane = k % n_planes;
-    if ((size_t)grp * WAVE >= (size_t)g.n_tiles) return;               // wave-uniform: a padding group
-    t = (int)(grp * WAVE + threadIdx.x);
+    const GroupPlane gp = group_plane_planefast(n_planes);
+    plane = gp.plane;
+    if ((size_t)gp.grp * WAVE >= (size_t)g.n_tiles) return;               // wave-uniform: a padding group
+    t = (int)(gp.grp * WAVE + threadIdx.x);
     valid = t < g.n_tiles;
     t = valid ? t : g.n_tiles - 1;
     ty = t / g.nbx; tx = t - ty * g.nbx;
   } else if (!tile_coords_planefast(g, n_planes, t, ty, tx, plane)) return;
   wm::RawTile raw;
   float a[8][8], s[8], sc[8], keep[8];
-  load_raw<ALIGNED>(stego + plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8,
-                    g.row_stride, raw);
+  load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
   if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
   load_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
 #pragma unroll
@@ -728,7 +664,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
   load_mat_f32(Vwt + mi, vwt);
   if (PX) wm::extract_tile_px(s, sc, inv_alpha, keep, uw, vwt, a);
   else wm::extract_tile(s, sc, inv_alpha, keep, uw, vwt, a);
-  float* o = out + plane * g.HW + (size_t)ty * 8 * g.W + (size_t)tx * 8;
+  float* o = DENSE_TILE(out, g, plane, ty, tx);
   if (valid) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) store_row8_f32<VECF>(o + (size_t)r * g.W, a[r]);
@@ -743,9 +679,9 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
 #pragma unroll
     for (int o_ = 32; o_ > 0; o_ >>= 1) { ulo = min(ulo, (unsigned)__shfl_down(ulo, o_, WAVE)); uhi = max(uhi, (unsigned)__shfl_down(uhi, o_, WAVE)); }
     if (threadIdx.x == 0) {
-      const unsigned b = blockIdx.x, grp = b % N_XCD + N_XCD * ((b / N_XCD) / n_planes);
-      const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE;
-      mm[2 * (plane * groups + grp)] = ulo; mm[2 * (plane * groups + grp) + 1] = uhi;
+      // (the group is asked for again, not kept from above: scalar arithmetic, and nothing to hold across the tile's work)
+      const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE, pair = plane * groups + group_plane_planefast(n_planes).grp;
+      mm[2 * pair] = ulo; mm[2 * pair + 1] = uhi;
     }
   }
 }
@@ -793,7 +729,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_reconstruct_tiles(
   load_mat_f32(Uw + ti * 64, uw);
   load_mat_f32(Vwt + ti * 64, vwt);
   wm::extract_tile(sh, zero, 1.0f, one, uw, vwt, a);   // (sh - 0) * 1 * 1
-  float* o = out + plane * g.HW + (size_t)ty * 8 * g.W + (size_t)tx * 8;
+  float* o = DENSE_TILE(out, g, plane, ty, tx);
 #pragma unroll
   for (int r = 0; r < 8; ++r) store_row8_f32<VECF>(o + (size_t)r * g.W, a[r]);
 }
@@ -812,15 +748,13 @@ __global__ __launch_bounds__(WAVE, 3) void k_detect_tiles(
     const uint8_t* __restrict__ stego, const float* __restrict__ sigma_c,
     const float* __restrict__ sigma_w, double* __restrict__ partials, const Geom g,
     const size_t sw_plane_stride, const float inv_alpha, int* __restrict__ status) {
-  const int t = blockIdx.x * WAVE + threadIdx.x;
+  int t, ty, tx;
   const size_t plane = blockIdx.y;
   double acc[N_SUMS] = {0, 0, 0, 0, 0};
-  if (t < g.n_tiles) {
-    const int ty = t / g.nbx, tx = t - ty * g.nbx;
+  if (tile_coords(g, t, ty, tx)) {
     wm::RawTile raw;
     float s[8], sc[8], sw[8];
-    load_raw<ALIGNED>(stego + plane * g.plane_stride + (size_t)ty * 8 * g.row_stride + (size_t)tx * 8,
-                      g.row_stride, raw);
+    load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
     if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
     load_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
     load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
@@ -1085,11 +1019,11 @@ int wm_embed_tiles_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w
     const size_t n_all = (size_t)g.n_tiles * (size_t)n_planes;
     if (n_all > 0x7fffffffull) return set_err(WM_ERR_BADARG, "more than 2^31 tiles in one call");   // ids are uint32, the device-side count an int
     const size_t n_waves = (n_all + WAVE - 1) / WAVE;
-    // three kinds x FB_SUB sub-lists of fb_cap entries (a sub-list holds at most the tiles of the waves that hash to it),
-    // then the padded counters
+    // the flagged-tile lists (layout: above k_embed_tiles); a sub-list of kinds 0-2 holds at most the tiles of the waves that
+    // map to it
     const size_t cap = (n_work_sz + FB_SUB - 1) / FB_SUB * WAVE;
     if (cap > 0x7fffffffull) return set_err(WM_ERR_BADARG, "more than 2^31 tiles in one call");
-    // kind 3 keeps its tiles' B (256 bytes each): its sub-lists hold cap / 16 entries (>= 64), the rest takes the literal chain
+    // kind 3 keeps its tiles' B (256 bytes each): its sub-lists hold cap / 16 entries (>= 64), the rest goes to kind 0
     const size_t cap3 = std::max<size_t>(WAVE, cap / 16);
     const size_t n_cnt = (size_t)FB_KINDS * FB_SUB * FB_PAD;
     uint32_t* fb; int* fb_cnt; float* fb_b;

@@ -242,8 +242,8 @@ def test_one_small_singular_value_tiles_on_gpu(gpu_ctx):
     """Kind 3 of the flagged-tile lists (k_embed_one_small): tiles whose eighth singular value is below 1e-5 sigma_1 - what
     noise frames contain, 4 in 10 000 - are completed from the fast kernel's own B, both eighth vectors as orthogonal
     complements, their joint sign from a float64 bilinear form.  Near-singular FULL-rank tiles have unique singular
-    vectors: 1 LSB against float64 LAPACK (the literal chain they used to take was off by 3 LSB on the ones below
-    float32 resolution: tools/one_small_check.py); rank-7 tiles satisfy the reference's invariant; a plane made of rank-7
+    vectors: 1 LSB against float64 LAPACK, also on the ones below float32 resolution (S[7] < 1e-5 S[0], asserted
+    below), where the literal chain they used to take was off by 3 LSB; rank-7 tiles satisfy the reference's invariant; a plane made of rank-7
     tiles only overflows the kind's sub-lists into the literal chain and still satisfies it."""
     from test_host_harness import _one_small_tiles
     near, r7 = _one_small_tiles(n_want=40, seed=9)
@@ -383,6 +383,58 @@ def test_unaligned_and_strided_planes(gpu_ctx, hostapi):
         assert _rel_sigma(sc[p], ref["Sc"]) < SIGMA_RTOL
     mask = np.ones_like(big, bool); mask[:, 3:51, 5:77] = False
     assert np.all(out_big[mask] == 7)
+
+
+def test_unaligned_planes_with_flagged_tiles(gpu_ctx):
+    """The byte-wise embed kernels (fast, fallback and one-small, with and without the Yw output) on strided planes that
+    hold every kind of flagged tile: the planes of test_unaligned_and_strided_planes (3 x 48 x 72 at (3, 5) of a
+    3 x 70 x 101 buffer: 54 tiles, one partial wave per plane, sub-lists 0-2) filled with constant (also black),
+    equal-row, repeated-column and saturated-edge tiles, one-small-singular-value tiles and random tiles between them.
+    The aligned and the byte-wise kernels run the same arithmetic and differ in their loads and stores only, so strided
+    in / strided out (with Yw, without it) and strided in place give the bytes of the contiguous copy."""
+    import ctypes as C
+    from test_host_harness import _one_small_tiles
+    near, r7 = _one_small_tiles(n_want=6, seed=9)
+    special = near + r7
+    rng = np.random.default_rng(23)
+    big = rng.integers(0, 256, (3, 70, 101), dtype=np.uint8)
+    view = big[:, 3:3 + 48, 5:5 + 72]
+    n_special = 0
+    for p in range(3):
+        for k in range(54):
+            t = view[p, k // 9 * 8:k // 9 * 8 + 8, k % 9 * 8:k % 9 * 8 + 8]
+            if k % 3 == 0:
+                kind = (k // 3 + p) % 5
+                if kind == 0: t[:] = rng.integers(1, 256)
+                elif kind == 1: t[:] = rng.integers(0, 256, (1, 8))                 # rank 1: equal rows
+                elif kind == 2: t[:, 4:] = t[:, :4]                                  # repeated columns
+                elif kind == 3: t[:] = np.where(np.arange(8)[:, None] < 3, 255, 0)   # saturated edge
+                else: t[:] = 0
+            elif k % 3 == 1 and n_special < len(special) and k // 3 % 3 == p:
+                t[:] = special[n_special]; n_special += 1
+    assert n_special == len(special)
+    dense = np.ascontiguousarray(view)
+    rk = np.linalg.matrix_rank(dense.reshape(3, 6, 8, 9, 8).transpose(0, 1, 3, 2, 4).astype(np.float64))
+    assert (rk == 0).sum() >= 5 and (rk == 1).sum() >= 20 and ((rk > 1) & (rk < 8)).sum() >= 20 and (rk == 8).sum() >= 80
+    sw = np.sort(rng.uniform(1, 1500, (6, 9, 8)).astype(np.float32), axis=-1)[..., ::-1].copy()
+    stego, sc, yw = gpu_ctx.embed_tiles(dense, sw, 0.15, want_yw=True)
+    same = lambda a, b: a.tobytes() == b.tobytes()
+    vp = lambda a, off=0: C.c_void_p(a.ctypes.data + off)
+    off = 3 * 101 + 5
+    mask = np.ones_like(big, bool); mask[:, 3:51, 5:77] = False
+    for want_yw in (True, False):
+        out_big = np.full_like(big, 7)
+        sc_s = np.empty_like(sc); yw_s = np.empty_like(yw)
+        gpu_ctx._call("wm_embed_tiles_u8", vp(big, off), vp(sw), vp(out_big, off), vp(sc_s), vp(yw_s) if want_yw else None,
+                      3, 48, 72, 101, 70 * 101, 0, 0.15, 8)
+        assert same(np.ascontiguousarray(out_big[:, 3:51, 5:77]), stego) and same(sc_s, sc), want_yw
+        assert not want_yw or same(yw_s, yw)
+        assert np.all(out_big[mask] == 7), want_yw
+    buf = big.copy(); sc_s = np.empty_like(sc)
+    gpu_ctx._call("wm_embed_tiles_u8", vp(buf, off), vp(sw), vp(buf, off), vp(sc_s), None, 3, 48, 72, 101, 70 * 101, 0, 0.15, 8)
+    assert same(np.ascontiguousarray(buf[:, 3:51, 5:77]), stego) and same(sc_s, sc)
+    assert np.array_equal(buf[mask], big[mask])
+    gpu_ctx.check_status()
 
 
 def test_in_place_embed_with_deficient_tiles(gpu_ctx):
