@@ -144,14 +144,24 @@ constexpr int JAC_MAX_SWEEPS = 12;
 constexpr int JAC_DEFI_FROM = 6;     // sweeps after which a rank-deficient tile stops counting as "not converged"
 // Singular VALUES alone converge one order ahead of the vectors: after a sweep that saw
 // max cos c the columns are orthogonal to ~c^2 and |b_i| = s_i (1 + O(c^4)), so the
-// sigma-only kernels (extract, detect, K2) may stop at c < 3.2e-2 - their sigma error
-// stays at the float32 rounding floor (tools/conv_study.cpp: 8.6e-7 s_1 for every
-// threshold from 1e-7 to 1e-3) with 4.1 instead of 5.0 sweeps per wave.  The embed keeps
+// sigma-only kernels (extract, detect, K2) may stop well above the embed's threshold.  The embed keeps
 // JAC_CONV2: its reconstruction needs the VECTORS (B orthogonal to 1e-7).
-constexpr float JAC_CONV2_SIGMA = 1e-3f;
-// From the 5th sweep on the embed's sweeps test every pair before rotating it: by then 93 % of the
-// pair visits are below cos^2 = 1e-12 in all 64 tiles of a wave (tools/skip_study.cpp), i.e. the 5th
-// sweep is almost pure verification, and a skipped pair costs its dot product only.  1e-12 is
+// How far above is set by near-degenerate pairs, whose values move by c s_i / 2 where a separated pair's move by
+// c^2 s_i s_j^2 / gap: a cosine alone cannot tell them apart.  Behind the LQ prelude most waves end on their 3rd sweep, which
+// sits closer to the threshold than the 4th used to, and at cos^2 <= 1e-3 alone (the test before the prelude: 4.1 sweeps
+// per wave, every error at the float32 floor of 8.6e-7 s_1) 7 of 25 600 noise tiles come out above 2e-6 s_1, the worst
+// at 2.6e-5 - enough to move an extracted watermark pixel by 0.2 grey levels.  So a tested rotation also reports what
+// it did to the VALUES: w = |t g| is what it moves the two squared norms by (|g| for a degenerate pair, g^2 / gap for
+// a separated one), and a sweep is the last one only if no rotation of it had w > sqrt(JAC_MOVE2) s_1 s_p (w^2 >
+// JAC_MOVE2 n2[0] max(n2[p], n2[q])).  With that test next to it the cosine bound may be loose: at cos^2 <= 1e-2 and
+// JAC_MOVE2 = 1e-6 every tile of tools/conv_study.cpp 3 is at the floor (1.1e-6 s_1) with 3.2 sweeps per wave; the cosine
+// alone needs 3e-4 for that, at 3.5.  A sweep that passes JAC_CONV2 passes the move test too (w <= |g| <= 3.2e-4 s_p s_q):
+// the embed's iteration is unchanged by it.
+constexpr float JAC_CONV2_SIGMA = 1e-2f;
+constexpr float JAC_MOVE2 = 1e-6f;
+// From the 4th sweep on - the first that can be the last behind the LQ prelude - the embed's sweeps test every pair
+// before rotating it: a pair below cos^2 = 1e-12 in all 64 tiles of a wave is left alone and costs its dot product
+// only (tools/skip_study.cpp lq: profiles/r05_skip_study_lq.txt has the share of such pair visits per sweep).  1e-12 is
 // cos = 1e-6, an order above the float32 floor the full sweeps end at (1.2e-7): measured against the
 // round-1 kernel the stego differs by 1 LSB on 4.5e-6 of the pixels (profiles/r02_embed_variants.md).
 constexpr float JAC_SKIP2 = 1e-12f;
@@ -371,6 +381,7 @@ WM_HD void jacobi_rot_pk(v2f (&a)[4][8], float (&n2)[8], const int p, const int 
   const bool sw = tau > 0.0f;                    // de Rijk: larger column ends in p
   const float C = sw ? s0 : c0, Sn = sw ? c0 : s0;
   const float w = fabsf((s0 * rx) * g);          // |t * g|: the larger norm grows by it
+  if (CHECK) notconv = notconv || (w * w > (JAC_MOVE2 * fmaxf(al, be)) * n2[0]);
   n2[p] = fmaxf(al, be) + w;                     // (cancellation-free, unlike (al+be+-h)/2)
   n2[q] = fminf(al, be) - w;
   const v2f Cv = splat2(C), Sv = splat2(Sn);
@@ -402,19 +413,81 @@ WM_HD void jacobi_sweep_pk(v2f (&a)[4][8], float (&n2)[8], bool& notconv) {
     for (int q = p + 1; q < 8; ++q) jacobi_rot_pk<CHECK, SKIP>(a, n2, p, q, notconv);
 }
 
+// ---- LQ prelude: B0 = X Q ahead of the sweeps ----------------------------------------------------------------------
+// Householder LQ of the tile with greedy ROW pivoting, the reflectors applied from the right.  Step k = 0 .. 6: among the
+// rows not used yet the one with the largest |x[k:]|^2 is the pivot, H = I - vh vh^T with vh = (x + sign(x_k) |x| e_k)
+// sqrt(2 / v^T v) on columns k .. 7 zeroes its entries k+1 .. 7, and H is applied to all eight rows (used rows hold zeros
+// there).  B0's column Gram matrix is that of the row-pivoted R^T: R R^T, one QR-algorithm step further on than X^T X,
+// which costs the sweeps about one sweep (tools/conv_study.cpp; Jacobi on the columns of R itself would see X^T X again
+// and gain nothing).  The row permutation never has to be applied - row order does not enter a column Gram matrix - and
+// B0 = X * (orthogonal), so the sweeps still deliver B = X V and everything downstream of them is unchanged.
+// A wrong pivot (exact ties: the first row wins; cancellation in the downdated norms) only costs convergence; a zero
+// row gives vh = 0.  Same operations in the same order as lq_prelude() of tools/gen_jacobi_asm.py.
+WM_HD float fmax3(const float a, const float b, const float c) { return fmaxf(fmaxf(a, b), c); }
+WM_HD void lq_prelude_pk(v2f (&a)[4][8]) {
+  v2f rn[4];                                       // |row[k:]|^2, row r in rn[r >> 1][r & 1]; -1e30 once the row is used
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+#pragma unroll
+    for (int rp = 0; rp < 4; ++rp) rn[rp] = (c == 0) ? a[rp][c] * a[rp][c] : fma2(a[rp][c], a[rp][c], rn[rp]);
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    float m = fmax3(rn[0][0], rn[0][1], rn[1][0]);
+    const float m2 = fmax3(rn[1][1], rn[2][0], rn[2][1]);
+    m = fmaxf(fmax3(rn[3][0], rn[3][1], m), m2);
+    float x[8];
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const bool hit = rn[r >> 1][r & 1] == m;
+      const bool mine = hit && !found;             // first match wins: exactly one pivot row
+      found = found || hit;
+      rn[r >> 1][r & 1] = mine ? -1e30f : rn[r >> 1][r & 1];
+      if (r) {
+#pragma unroll
+        for (int c = k; c < 8; ++c) x[c] = mine ? a[r >> 1][c][r & 1] : (r == 1 ? a[0][c][0] : x[c]);
+      }
+    }
+    float t2 = x[7] * x[7];
+#pragma unroll
+    for (int c = 6; c > k; --c) t2 = ffma(x[c], x[c], t2);                  // |x[k+1:]|^2
+    const float nx2 = ffma(x[k], x[k], t2);
+    const float nrm = copysignf(nx2 * frsq(fmaxf(1e-36f, nx2)), x[k]);      // sign(x_k) |x|, 0 for a zero row
+    const float vk = x[k] + nrm;                                            // no cancellation
+    const float sb = frsq(fmaxf(1e-36f, 0.5f * ffma(vk, vk, t2)));          // sqrt(2 / v^T v)
+    x[k] = vk;
+#pragma unroll
+    for (int c = k; c < 8; ++c) x[c] *= sb;
+    v2f w[4];                                                               // W = A vh
+#pragma unroll
+    for (int c = k; c < 8; ++c)
+#pragma unroll
+      for (int rp = 0; rp < 4; ++rp) w[rp] = (c == k) ? splat2(x[c]) * a[rp][c] : fma2(splat2(x[c]), a[rp][c], w[rp]);
+#pragma unroll
+    for (int c = k; c < 8; ++c)
+#pragma unroll
+      for (int rp = 0; rp < 4; ++rp) a[rp][c] = fma2(splat2(x[c]), -w[rp], a[rp][c]);
+    if (k < 6) {
+#pragma unroll
+      for (int rp = 0; rp < 4; ++rp) rn[rp] = fma2(-a[rp][k], a[rp][k], rn[rp]);   // trailing norms lose column k
+    }
+  }
+}
+
 template <bool SIGMA_ONLY = false>
 WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
-  // Sweeps 1 and 2 carry no convergence test (a sweep can only be the last one if
-  // it tested every pair, so these two are never last; on image tiles the earliest
-  // last sweep is the 4th).  Column norms are recomputed before odd sweeps and
+  // The sweeps run on B0 = X Q (LQ prelude above).  Sweeps 1 and 2 carry no convergence test (a sweep can only be the
+  // last one if it tested every pair, so these two are never last).  Column norms are recomputed before odd sweeps and
   // tracked through the even ones.
+  lq_prelude_pk(a);
   bool notconv = false;
   col_norms2_pk(a, n2);
   jacobi_sweep_pk<0>(a, n2, notconv);
   jacobi_sweep_pk<0>(a, n2, notconv);
   int sweep = 2;
-  // The embed's third sweep carries no test either: no image or noise tile is done after three
-  // sweeps at cos^2 <= 1e-7 (tools/skip_study.cpp: 0 of 19 200), so the earliest last sweep is the 4th.
+  // The embed's third sweep carries no test either: behind the prelude no image or noise tile is done after three
+  // sweeps at cos^2 <= 1e-7 (tools/skip_study.cpp), so the earliest last sweep is the 4th - and that one already tests
+  // every pair before rotating it (JAC_SKIP2), as every later one does.
   if (!SIGMA_ONLY) {
     col_norms2_pk(a, n2);
     jacobi_sweep_pk<0>(a, n2, notconv);
@@ -424,8 +497,8 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
   while (more && sweep < JAC_MAX_SWEEPS) {
     if ((sweep & 1) == 0) col_norms2_pk(a, n2);
     notconv = false;
-    if (!SIGMA_ONLY && sweep >= 4) jacobi_sweep_pk<1, true>(a, n2, notconv);
-    else jacobi_sweep_pk<SIGMA_ONLY ? 2 : 1>(a, n2, notconv);
+    if (!SIGMA_ONLY) jacobi_sweep_pk<1, true>(a, n2, notconv);
+    else jacobi_sweep_pk<2>(a, n2, notconv);
     ++sweep;
     // a rank-deficient tile's null columns are rounding residue whose cosines never fall (and whose tracked norms
     // cancel to garbage): after JAC_DEFI_FROM sweeps such a lane no longer keeps its wave iterating (gen_jacobi_asm.py)

@@ -67,12 +67,14 @@ __device__ __forceinline__ int sigma_tile_dev(const wm::RawTile& raw, float (&s)
 #if !defined(WM_NO_ASM_JACOBI)
   wm::v2f a[4][8];
   float n2[8];
-  // sigma only: test from the 3rd sweep on at cos^2 <= 1e-3 (the values are an order ahead of the vectors); from the
-  // same sweep on a pair that is below cos^2 = 1e-8 in every tile of the wave is left alone (a third of the 4th
-  // sweep's pair visits, tools/skip_study.cpp).  The threshold is set by the near-degenerate pairs: a residual
-  // cosine c between two equal singular values moves them by c s_i / 2, so 1e-8 bounds the error at 5e-5 s_i;
-  // 1e-6 measured 4.7e-4 s_1 on one tile of a 4K noise frame (profiles/r02m_sigma_skip.log), 1e-7 and 1e-8 leave
-  // every value of four 4K frames where the full sweeps leave it (5e-6 s_1).
+  // sigma only, behind the LQ prelude (B0 = X Q, wm_tile_math.h: about one sweep fewer): test from the 3rd sweep on, a
+  // sweep being the last one if it saw no pair above cos^2 = JAC_CONV2_SIGMA and no rotation that moved a squared value
+  // by more than sqrt(JAC_MOVE2) s_1 s_p (the stream's own test; wm_tile_math.h) - four noise waves in five end there,
+  // the rest after the 4th (tools/conv_study.cpp 3); from the same sweep on a pair that is below cos^2 = 1e-8 in every tile of the wave is
+  // left alone (a third of the 3rd sweep's pair visits and 98 % of the 4th's, tools/skip_study.cpp lq).  The threshold
+  // is set by the near-degenerate pairs: a residual cosine c between two equal singular values moves them by c s_i / 2,
+  // so 1e-8 bounds the error at 5e-5 s_i; 1e-6 measured 4.7e-4 s_1 on one tile of a 4K noise frame
+  // (profiles/r02m_sigma_skip.log), 1e-7 and 1e-8 leave every value where the full sweeps leave it.
   constexpr float SIGMA_SKIP2 = 1e-8f;
   constexpr int SIGMA_SKIP_FROM = 2;
   const unsigned long long more = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2_SIGMA, SIGMA_SKIP2, 3, SIGMA_SKIP_FROM);
@@ -400,8 +402,9 @@ __device__ __forceinline__ void embed_group(
       return;
     }
 #if !defined(WM_NO_ASM_JACOBI)
-    // sweeps 1-3 run untested, the 4th is the first that can be the last, pairs are skipped from the 5th on
-    sweeps = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2, wm::JAC_SKIP2, 4, 4) ? -1 : 1;
+    // behind the LQ prelude: sweeps 1-3 run untested, the 4th is the first that can be the last (no wave of the study
+    // passes the test after three, tools/skip_study.cpp lq) and already skips the pairs that are below JAC_SKIP2
+    sweeps = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2, wm::JAC_SKIP2, 4, 3) ? -1 : 1;
 #else
     sweeps = wm::embed_jacobi_pk(raw, a, n2);
 #endif

@@ -1,0 +1,146 @@
+"""A/B of the tile kernels of TWO builds of libwmhip.so in ONE process on one device (no torch): embed and extract
+(pixel-domain factors, what bench.py runs) at the bench shape, the variants interleaved round by round, HIP events on
+each context's stream.  Prints per variant the median over the rounds and the spread (max - min) of the round values,
+and the parity of b against a (stego LSB differences, Sc relative to sigma_1, extracted watermark).
+
+    python tools/ab_tile_libs.py --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so [--content natural]
+
+Development aid; bench.py is the contract benchmark."""
+import argparse
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+api = importlib.import_module(
+    "digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd.hostapi")
+
+
+class LibContext(api.Context):
+    """a Context on an explicitly loaded library"""
+
+    def __init__(self, lib):
+        self.lib = lib
+        h = C.c_void_p()
+        assert lib.wm_create(0, None, C.byref(h)) == 0
+        self._h = h
+        self.device = 0
+
+
+def make_frames(content, F, H, W, rng):
+    if content == "noise":
+        return rng.integers(0, 256, (F, H, W), dtype=np.uint8)
+    low = rng.uniform(20, 235, (F, H // 16 + 2, W // 16 + 2)).astype(np.float32)     # quick_bench.py's "natural"
+    up = np.kron(low, np.ones((16, 16), np.float32))[:, 8:8 + H, 8:8 + W]
+    for ax in (1, 2):
+        c = np.cumsum(up, axis=ax)
+        up = (np.take(c, np.arange(16, c.shape[ax]), axis=ax) - np.take(c, np.arange(0, c.shape[ax] - 16), axis=ax)) / 16
+        pad = [(0, 0)] * 3; pad[ax] = (8, 8); up = np.pad(up, pad, mode="edge")
+    return np.clip(up + rng.normal(0, 2.0, up.shape), 0, 255).astype(np.uint8)
+
+
+class Side:
+    def __init__(self, path, host, wys, alpha):
+        self.ctx = ctx = LibContext(api.load_library(path))
+        F, H, W = host.shape
+        self.dims = (F, H, W)
+        self.alpha = alpha
+        nt = (H // 8) * (W // 8)
+        self.d_host = ctx.malloc(host.nbytes); ctx.h2d(self.d_host, host)
+        self.d_stego = ctx.malloc(host.nbytes)
+        d_wys = ctx.malloc(wys.nbytes); ctx.h2d(d_wys, wys)
+        d_U = ctx.malloc(nt * 256); d_V = ctx.malloc(nt * 256)
+        self.d_S = ctx.malloc(nt * 32)
+        self.d_Ux = ctx.malloc(nt * 256); self.d_Vx = ctx.malloc(nt * 256)
+        self.d_sc = ctx.malloc(F * nt * 32)
+        self.d_out = ctx.malloc(F * H * W * 4)
+        ctx.svd_tiles_f32_dev(d_wys, d_U, self.d_S, d_V, 1, H, W, W, H * W)
+        ctx.tile_factors_to_pixel_dev(d_U, d_V, self.d_Ux, self.d_Vx, nt)
+        self.embed(); self.extract(); ctx.sync()
+
+    def embed(self):
+        F, H, W = self.dims
+        self.ctx.embed_tiles_u8_dev(self.d_host, self.d_S, self.d_stego, self.d_sc, None, F, H, W, W, H * W, 0, self.alpha, 8)
+
+    def extract(self):
+        F, H, W = self.dims
+        self.ctx.extract_tiles_px_u8_dev(self.d_stego, self.d_sc, self.d_Ux, self.d_Vx, self.d_out, F, H, W, W, H * W, 0,
+                                         self.alpha, 8)
+
+    def time_us(self, fn, launches):
+        self.ctx.sync()
+        self.ctx.event_record(0)
+        for _ in range(launches):
+            fn()
+        self.ctx.event_record(1)
+        self.ctx.sync()
+        return self.ctx.event_elapsed_ms(0, 1) * 1e3 / launches
+
+    def results(self):
+        F, H, W = self.dims
+        nt = (H // 8) * (W // 8)
+        st = np.empty((F, H, W), np.uint8); sc = np.empty((F, nt, 8), np.float32); out = np.empty((F, H, W), np.float32)
+        self.ctx.sync()
+        self.ctx.d2h(st, self.d_stego); self.ctx.d2h(sc, self.d_sc); self.ctx.d2h(out, self.d_out)
+        self.ctx.sync()
+        self.ctx.check_status()
+        return st, sc, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--a", required=True, help="libwmhip.so of the baseline")
+    ap.add_argument("--b", required=True, help="libwmhip.so of the variant")
+    ap.add_argument("--frames", type=int, default=32)
+    ap.add_argument("--H", type=int, default=2160)
+    ap.add_argument("--W", type=int, default=3840)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--warmup-rounds", type=int, default=2, help="rounds run first and left out (clocks settle)")
+    ap.add_argument("--alpha", type=float, default=0.15)
+    ap.add_argument("--content", default="noise", choices=["noise", "natural"])
+    a = ap.parse_args()
+    rng = np.random.default_rng(1234)
+    host = np.ascontiguousarray(make_frames(a.content, a.frames, a.H, a.W, rng))
+    wys = rng.integers(0, 256, (a.H, a.W)).astype(np.float32)
+    sides = {"a": Side(a.a, host, wys, a.alpha), "b": Side(a.b, host, wys, a.alpha)}
+    t = {(k, w): [] for k in sides for w in ("embed", "extract")}
+    for r in range(-a.warmup_rounds, a.rounds):
+        for k in (("a", "b") if r % 2 == 0 else ("b", "a")):
+            s = sides[k]
+            te, tx = s.time_us(s.embed, a.launches), s.time_us(s.extract, a.launches)
+            if r >= 0:
+                t[k, "embed"].append(te); t[k, "extract"].append(tx)
+        if r < 0:
+            continue
+        print("round %d  " % r + "  ".join(f"{k}.{w} {t[k, w][-1]:8.1f}" for k in "ab" for w in ("embed", "extract")), flush=True)
+    print(f"content={a.content}, {a.frames} frames {a.W}x{a.H}, {a.rounds} rounds x {a.launches} launches, us per launch")
+    for w in ("embed", "extract"):
+        ma, mb = np.median(t["a", w]), np.median(t["b", w])
+        spread = max(np.ptp(t["a", w]), np.ptp(t["b", w]))
+        print(f"{w:8s} a {ma:9.1f}  b {mb:9.1f}  delta {100 * (mb / ma - 1):+6.2f} %  ({ma - mb:+.1f} us; round-to-round spread "
+              f"{spread:.1f} us, delta / spread {abs(ma - mb) / max(spread, 1e-9):.1f})")
+    (st_a, sc_a, w_a), (st_b, sc_b, w_b) = sides["a"].results(), sides["b"].results()
+    d = np.abs(st_a.astype(np.int16) - st_b.astype(np.int16))
+    print(f"parity b vs a: stego max {int(d.max())} LSB on {float((d != 0).mean()):.2e} of the pixels, "
+          f"Sc max {float(np.max(np.abs(sc_a - sc_b) / np.maximum(sc_a[..., :1], 1.0))):.2e} sigma_1, "
+          f"extract max |diff| {float(np.max(np.abs(w_a - w_b))):.3e} (values up to {float(np.max(np.abs(w_a))):.1f})")
+    # the sigma-only kernel of both builds on IDENTICAL input (a's stego)
+    F, H, W = host.shape
+    sig = {}
+    sides["b"].ctx.h2d(sides["b"].d_host, st_a)
+    for k, s in sides.items():
+        s.ctx.sigma_tiles_u8_dev(s.d_stego if k == "a" else s.d_host, s.d_sc, F, H, W, W, H * W)
+        sig[k] = np.empty_like(sc_a); s.ctx.sync(); s.ctx.d2h(sig[k], s.d_sc); s.ctx.sync(); s.ctx.check_status()
+    rel = np.abs(sig["a"] - sig["b"]) / np.maximum(sig["a"][..., :1], 1.0)
+    print(f"sigma-only kernel on the same stego: max |b - a| {float(rel.max()):.2e} sigma_1, tiles above 2e-6: "
+          f"{int((rel.max(axis=-1) > 2e-6).sum())} of {rel.shape[0] * rel.shape[1]}, above 1e-5: {int((rel.max(axis=-1) > 1e-5).sum())}")
+    for s in sides.values():
+        s.ctx.close()
+
+
+if __name__ == "__main__":
+    main()

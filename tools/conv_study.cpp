@@ -1,7 +1,10 @@
 // Development study (host build): how the Jacobi stopping threshold trades sweeps for
 // accuracy on 8x8 uint8 tiles, with the wave-uniform termination of the kernels emulated
 // (64 consecutive tiles sweep in lock-step until none of them saw cos^2 > T).
-//   g++ -O2 -o tools/bin/conv_study tools/conv_study.cpp && tools/bin/conv_study
+//   g++ -O2 -o tools/bin/conv_study tools/conv_study.cpp && tools/bin/conv_study [3 [move2 [waves [seed]]]]
+// (argument 3: the sweeps run behind the LQ prelude, lq_prelude_pk - what the kernels do since round 5;
+//  move2 > 0: a sweep is the last one only if, besides cos^2 <= T, no rotation of it moved the squared norms by w with
+//  w^2 > move2 n2[0] max(n2[p], n2[q]) - the second stopping test of jacobi_rot_pk, JAC_MOVE2)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,14 +13,18 @@
 #include "../digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd/csrc/wm_tile_math.h"
 using namespace wm;
 
-// jacobi_rot_pk with the largest cos^2 it saw reported instead of a fixed threshold test
-static void rot(v2f (&a)[4][8], float (&n2)[8], int p, int q, float& maxc2) {
+// jacobi_rot_pk with the largest cos^2 and the largest norm move w^2 / (n2[0] max(al, be)) it saw reported instead of
+// fixed threshold tests
+static void rot(v2f (&a)[4][8], float (&n2)[8], int p, int q, float& maxc2, float& maxmv) {
   v2f gv = a[0][p] * a[0][q];
   for (int rp = 1; rp < 4; ++rp) gv = fma2(a[rp][p], a[rp][q], gv);
   const float g = gv[0] + gv[1];
   const float al = n2[p], be = n2[q];
   const float c2 = g * g / fmaxf(al * be, 1e-30f);
   if (c2 > maxc2) maxc2 = c2;
+  const float ta = fabsf(be - al) + 1e-18f, ih = frsq(ffma(g + g, g + g, ta * ta)), rx = frsq(ffma(0.5f * ta, ih, 0.5f));
+  const float w = fabsf((((g * ih) * rx) * rx) * g), mv = w * w / fmaxf(fmaxf(al, be) * n2[0], 1e-30f);
+  if (mv > maxmv) maxmv = mv;
   bool dummy = false;
   jacobi_rot_pk<0>(a, n2, p, q, dummy);
 }
@@ -40,11 +47,20 @@ static void svd_f64(const double (&x)[8][8], double (&s)[8]) {
 }
 
 int main(int argc, char** argv) {
-  const int NW = 400;   // waves of 64 tiles
-  const char* kinds[] = {"noise", "natural"};
-  const float thr[] = {1e-7f, 1e-6f, 1e-5f, 1e-4f, 1e-3f};
-  for (int kind = 0; kind < 2; ++kind) {
-    srand(1234);
+  const float MOVE2 = argc > 2 ? (float)atof(argv[2]) : 0.0f;
+  const int NW = argc > 3 ? atoi(argv[3]) : 400;   // waves of 64 tiles
+  // quantised: a smooth tile after a JPEG-like round trip (8x8 DCT, luminance table at quality 50, rounded back to 8 bits);
+  // posterised: the natural tile at 16 grey levels.  Both are rich in repeated rows, rank-deficient tiles and
+  // near-degenerate pairs - what compressed or banded content feeds the kernels.
+  const char* kinds[] = {"noise", "natural", "quantised", "posterised"};
+  static const int QT[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+  double Cm[8][8];
+  for (int u = 0; u < 8; ++u) for (int x = 0; x < 8; ++x) Cm[u][x] = (u ? 0.5 : sqrt(0.125)) * cos((2 * x + 1) * u * M_PI / 16);
+  const float thr[] = {1e-7f, 1e-6f, 1e-5f, 1e-4f, 3e-4f, 1e-3f, 1e-2f};
+  for (int kind = 0; kind < 4; ++kind) {
+    srand(argc > 4 ? atoi(argv[4]) : 1234);
     std::vector<uint8_t> px((size_t)NW * 64 * 64);
     for (int t = 0; t < NW * 64; ++t) {
       const double b0 = 20 + rand() % 200, gx = (rand() % 200 - 100) / 25.0, gy = (rand() % 200 - 100) / 25.0, cxy = (rand() % 200 - 100) / 400.0;
@@ -52,11 +68,27 @@ int main(int argc, char** argv) {
         double v;
         if (kind == 0) v = rand() % 256;
         else { double n = 0; for (int k = 0; k < 4; ++k) n += (rand() % 1000) / 1000.0 - 0.5; v = b0 + gx * c + gy * r + cxy * r * c + 3.5 * n; }
+        if (kind == 3) v = 16 * floor(v / 16) + 8;
         px[(size_t)t * 64 + r * 8 + c] = (uint8_t)fmin(fmax(v, 0.0), 255.0);
+      }
+      if (kind == 2) {
+        uint8_t* P = &px[(size_t)t * 64];
+        double X[8][8], D[8][8];
+        for (int u = 0; u < 8; ++u) for (int v = 0; v < 8; ++v) {
+          double d = 0;
+          for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) d += Cm[u][r] * Cm[v][c] * (P[r * 8 + c] - 128.0);
+          D[u][v] = QT[u * 8 + v] * nearbyint(d / QT[u * 8 + v]);
+        }
+        for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) {
+          double d = 0;
+          for (int u = 0; u < 8; ++u) for (int v = 0; v < 8; ++v) d += Cm[u][r] * Cm[v][c] * D[u][v];
+          X[r][c] = d + 128.0;
+        }
+        for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) P[r * 8 + c] = (uint8_t)fmin(fmax(nearbyint(X[r][c]), 0.0), 255.0);
       }
     }
     for (float T : thr) {
-      double sum_sweeps = 0, max_err = 0, sum_err = 0, max_cos = 0, sum_tile_sweeps = 0; long nerr = 0;
+      double sum_sweeps = 0, max_err = 0, sum_err = 0, max_cos = 0, sum_tile_sweeps = 0; long nerr = 0, above = 0;
       int hist[16] = {0};
       for (int w = 0; w < NW; ++w) {
         static v2f a[64][4][8]; static float n2[64][8];
@@ -66,6 +98,7 @@ int main(int argc, char** argv) {
             v2f v = {(float)px[((size_t)w * 64 + l) * 64 + (2 * rp) * 8 + c], (float)px[((size_t)w * 64 + l) * 64 + (2 * rp + 1) * 8 + c]};
             a[l][rp][c] = v;
           }
+          if (argc > 1 && atoi(argv[1]) == 3) lq_prelude_pk(a[l]);   // B0 = X Q: row-pivoted Householder LQ from the right
           col_norms2_pk(a[l], n2[l]); tile_done[l] = 0;
           if (argc > 1 && atoi(argv[1]) == 1) {      // experiment: columns sorted by norm (descending) before the first sweep
             int ord[8]; for (int c = 0; c < 8; ++c) ord[c] = c;
@@ -88,11 +121,13 @@ int main(int argc, char** argv) {
           more = false;
           for (int l = 0; l < 64; ++l) {
             if (sweep >= 2 && (sweep & 1) == 0) col_norms2_pk(a[l], n2[l]);
-            float m = 0;
-            for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) rot(a[l], n2[l], p, q, m);
-            if (sweep >= 2 && m > T) more = true;
-            if (!(m > T) && !tile_done[l]) tile_done[l] = sweep + 1;
-            if (m > T) tile_done[l] = 0;
+            float m = 0, mv = 0;
+            for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) rot(a[l], n2[l], p, q, m, mv);
+            bool bad = m > T || (MOVE2 > 0 && mv > MOVE2);
+            if (sweep + 1 >= JAC_DEFI_FROM && !(n2[l][7] > SIGMA_RATIO_MIN2 * n2[l][0])) bad = false;   // the rank-deficient exit of jacobi_cols_pk
+            if (sweep >= 2 && bad) more = true;
+            if (!bad && !tile_done[l]) tile_done[l] = sweep + 1;
+            if (bad) tile_done[l] = 0;
           }
           if (sweep < 2) more = true;
           ++sweep;
@@ -104,16 +139,16 @@ int main(int argc, char** argv) {
           double x[8][8], s[8];
           for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) x[r][c] = px[((size_t)w * 64 + l) * 64 + r * 8 + c];
           svd_f64(x, s);
-          for (int i = 0; i < 8; ++i) { const double e = fabs(sqrt((double)n2[l][i]) - s[i]) / s[0]; max_err = std::max(max_err, e); sum_err += e; ++nerr; }
+          for (int i = 0; i < 8; ++i) { const double e = fabs(sqrt((double)n2[l][i]) - s[i]) / s[0]; max_err = std::max(max_err, e); sum_err += e; ++nerr; above += e > 2e-6; }
           for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) {
             double g = 0; for (int rp = 0; rp < 4; ++rp) g += (double)a[l][rp][p][0] * a[l][rp][q][0] + (double)a[l][rp][p][1] * a[l][rp][q][1];
             max_cos = std::max(max_cos, fabs(g) / sqrt((double)n2[l][p] * n2[l][q] + 1e-300));
           }
         }
       }
-      printf("%-8s T=%.0e  wave sweeps avg %.3f [3:%d 4:%d 5:%d 6:%d 7+:%d]  per-tile avg %.3f  sigma err/s1 max %.2e mean %.2e  final max cos %.2e\n",
+      printf("%-8s T=%.0e  wave sweeps avg %.3f [3:%d 4:%d 5:%d 6:%d 7+:%d]  per-tile avg %.3f  sigma err/s1 max %.2e mean %.2e above 2e-6: %ld  final max cos %.2e\n",
              kinds[kind], T, sum_sweeps / NW, hist[3], hist[4], hist[5], hist[6], hist[7] + hist[8] + hist[9] + hist[10] + hist[11] + hist[12],
-             sum_tile_sweeps / (NW * 64.0), max_err, sum_err / nerr, max_cos);
+             sum_tile_sweeps / (NW * 64.0), max_err, sum_err / nerr, above, max_cos);
     }
   }
   return 0;

@@ -15,8 +15,10 @@ import gen_jacobi_asm as G
 F = np.float32
 
 
-def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128):
-    """Runs the stream on n lanes; returns (vector registers [n_vregs, n], more mask, sweeps)."""
+def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128, stats=None, stop_at=None):
+    """Runs the stream on n lanes; returns (vector registers [n_vregs, n], more mask, sweeps).  stats (a dict) receives
+    the executed VALU instructions of the wave: "pk" (v_pk_*), "trans" (v_rsq) and "valu" (the rest).  stop_at: a label
+    at which the run ends (the registers as they are there)."""
     v = np.zeros((n_vregs, n), F)
     if v_init:
         for r_, val in v_init.items():
@@ -86,8 +88,13 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128):
         ln = lines[pc]
         pc += 1
         if ln.endswith(":"):
+            if stop_at is not None and ln[:-1] == stop_at:
+                break
             continue
         mn, rest = ln.split(None, 1)
+        if stats is not None and mn.startswith("v_"):
+            kind_ = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith("v_rsq") else "valu"
+            stats[kind_] = stats.get(kind_, 0) + 1
         opnds = [o.strip() for o in re.split(r"\s+(?:op_sel|neg_)", rest)[0].split(",")]
         with np.errstate(all="ignore"):
             if mn.startswith("v_cvt_f32_ubyte"):
@@ -118,6 +125,16 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128):
                 op = mn[2:5]
                 r = {"mul": a * b, "add": a + b, "sub": a - b, "max": np.maximum(a, b), "min": np.minimum(a, b)}[op]
                 wr(int(opnds[0][1:]), r.astype(F))
+            elif mn == "v_max3_f32":
+                a, b, c = (src(o) for o in opnds[1:4])
+                wr(int(opnds[0][1:]), np.maximum(np.maximum(a, b), c))
+            elif mn == "v_bfi_b32":                                  # (s0 & s1) | (~s0 & s2), bitwise
+                a, b, c = (np.ascontiguousarray(src(o)).view(np.uint32) for o in opnds[1:4])
+                wr(int(opnds[0][1:]), ((a & b) | (~a & c)).view(F))
+            elif mn == "v_cmp_eq_f32_e64":                           # VOP3: the lane mask goes to an SGPR pair
+                s[opnds[0]] = (src(opnds[1]) == src(opnds[2])) & ex
+            elif mn == "v_cndmask_b32_e64":
+                wr(int(opnds[0][1:]), np.where(s[opnds[3]], src(opnds[2]), src(opnds[1])))
             elif mn == "v_fma_f32":
                 a, b, c = (src(o).astype(np.float64) for o in opnds[1:4])
                 wr(int(opnds[0][1:]), (a * b + c).astype(F))
@@ -152,6 +169,11 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128):
                     ex = val.copy()
                 else:
                     s[opnds[0]] = val
+            elif mn == "s_andn2_b64":
+                s[opnds[0]] = s[opnds[1]] & ~s[opnds[2]]
+                scc = bool(np.any(s[opnds[0]]))
+            elif mn == "s_cmp_lg_u32":
+                scc = sval(opnds[0]) != sval(opnds[1])
             elif mn == "s_or_b64":
                 get = lambda t_: vcc if t_ == "vcc" else s[t_]
                 s[opnds[0]] = get(opnds[1]) | get(opnds[2])
@@ -211,14 +233,35 @@ def _unpack(v, base, n):
     return a
 
 
-def run(raw_tiles: np.ndarray, conv2: float, skip2: float, min_sweeps: int, skip_from: int):
-    """raw_tiles uint8 [n, 8, 8] -> (a [n, 4, 8, 2] float32, n2 [n, 8], more mask (bool [n]), sweeps)."""
+_STREAM = {}
+
+
+def _stream(move_test=True, lq=True):
+    if (move_test, lq) not in _STREAM:
+        _STREAM[move_test, lq] = G.build(move_test, lq)
+    return _STREAM[move_test, lq]
+
+
+def run(raw_tiles: np.ndarray, conv2: float, skip2: float, min_sweeps: int, skip_from: int, lq: int = 1, stats=None,
+        move_test=True):
+    """raw_tiles uint8 [n, 8, 8] -> (a [n, 4, 8, 2] float32, n2 [n, 8], more mask (bool [n]), sweeps).
+    lq=0: the stream without the LQ prelude (gen_jacobi_asm.build(lq=False), the baseline); stats: see _interp; move_test=False: the stream that stops on cos^2
+    alone (gen_jacobi_asm.build(False): the iteration before the prelude)."""
     n = raw_tiles.shape[0]
     lo, hi = _pack_words(raw_tiles)
     named = {"%[conv]": F(conv2), "%[skip]": F(skip2), "%[minsw]": int(min_sweeps), "%[skipfrom]": int(skip_from)}
-    v, more, sweeps = _interp(G.build(), n, named, lo, hi)
+    v, more, sweeps = _interp(_stream(move_test, bool(lq)), n, named, lo, hi, stats=stats)
     n2 = np.stack([v[G.N0 + c] for c in range(8)], axis=1)
     return _unpack(v, G.A0, n), n2, more, sweeps
+
+
+def run_prelude(raw_tiles: np.ndarray):
+    """B0 = X Q as the LQ prelude leaves it (a [n, 4, 8, 2] float32), before the first sweep."""
+    n = raw_tiles.shape[0]
+    lo, hi = _pack_words(raw_tiles)
+    named = {"%[conv]": F(0), "%[skip]": F(0), "%[minsw]": 0, "%[skipfrom]": 0}
+    v, _, _ = _interp(_stream(), n, named, lo, hi, stop_at=".Lwmj_lqdone_%=")
+    return _unpack(v, G.A0, n)
 
 
 def run_v(tiles_f32: np.ndarray, conv2: float):
@@ -245,7 +288,7 @@ if __name__ == "__main__":
     tiles[0] = (yy + xx) % 2 * 255
     tiles[1] = 9
     tiles[2] = 0
-    for conv, skip, mn, sf in ((1e-7, 1e-12, 4, 4), (1e-3, 0.0, 3, 1 << 20)):
+    for conv, skip, mn, sf in ((1e-7, 1e-12, 4, 3), (1e-2, 1e-8, 3, 2)):      # embed, sigma-only (csrc/wmhip.hip)
         a, n2, more, sw = run(tiles, conv, skip, mn, sf)
         ref = np.linalg.svd(tiles.astype(np.float64), compute_uv=False)
         err = np.abs(np.sqrt(np.maximum(n2, 0)) - ref) / ref[:, :1].clip(1)

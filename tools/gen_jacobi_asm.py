@@ -17,7 +17,11 @@ does not already satisfy them (it never needs to inside a rotation).
 
 Same arithmetic as jacobi_rot_pk (two-rsq angle, de Rijk swap, cancellation-free norm update, wave-uniform
 skip of a pair that is below the skip threshold in all 64 tiles), same pair order (row-cyclic), same sweep
-control (norms recomputed before odd sweeps, convergence test on cos^2, sweep bound 12).
+control (norms recomputed before odd sweeps, convergence test on cos^2 and on the norm move w = |t g|, sweep bound 12).
+
+Ahead of the first sweep the stream runs the LQ prelude (lq_prelude: B0 = X Q, Householder LQ with greedy row
+pivoting applied from the right - about one sweep fewer).  build(lq=False) is the stream without it: never compiled into
+a kernel, only interpreted (tools/emu_jacobi_asm.py) as the baseline the prelude is measured against.
 
 A second stream, csrc/wm_jacobi_v_gfx950.inc (build_v), is jacobi_cols_pk_v: the same rotation applied to the
 stacked rows of B and V (v[40:103], v[104:167]), every pair tested and rotated, a converged lane leaving the
@@ -30,6 +34,7 @@ import struct
 import sys
 
 MAX_SWEEPS = 12
+MOVE2 = 1e-6          # JAC_MOVE2 of wm_tile_math.h
 
 
 class Lay:
@@ -67,7 +72,9 @@ A0, N0, T = LAY.A0, LAY.N0, LAY.T
 LAY_V = Lay(40, 168, 184, v0=104, vn0=176)
 # SGPRs (clobbered): mask, sweep counter, constants
 M, SW, EPS, CONV, SKIPC, MINSW, SKIPFROM = "s[80:81]", "s82", "s83", "s84", "s85", "s86", "s87"
-TMPM, NOSKIP, TMPS = "s[88:89]", "s[90:91]", "s92"
+TMPM, NOSKIP, TMPS = "s[88:89]", "s[90:91]", "s98"
+LQ_STEPS = 7            # reflectors of the LQ prelude (5 / 6 / 7: 4.45 / 4.30 / 4.15 embed sweeps per wave on noise tiles)
+LQ_T, LQ_FOUND, LQ_M = "s[92:93]", "s[94:95]", "s[96:97]"   # LQ prelude: compare result, rows matched so far, this row's one-hot
 DEFI_FROM = 6           # from this many sweeps on, a lane whose tile is rank deficient no longer keeps its wave iterating
 SAVE = "s[88:89]"       # with-V stream: the caller's exec mask (TMPM / NOSKIP are unused there)
 
@@ -89,6 +96,9 @@ class Stream:
             return {op}
         if op == "vcc":
             return {"vcc"}
+        if op.startswith("s["):
+            a, b = op[2:-1].split(":")
+            return {f"s{i}" for i in range(int(a), int(b) + 1)}
         return set()
 
     def emit(self, text, kind="valu", reads_vcc=False):
@@ -111,7 +121,7 @@ class Stream:
                 continue
             if k in ("pk", "trans") and d < 2:
                 need = max(need, 2 - d)
-            if k == "vcmp" and "vcc" in (w & read) and mn.startswith("v_") and d < 3:
+            if k == "vcmp" and mn.startswith("v_") and d < 3:      # (w & read) holds vcc or the compare's SGPR pair
                 need = max(need, 3 - d)
         if need:
             self.lines.append(f"s_nop {need - 1}")
@@ -119,7 +129,7 @@ class Stream:
                 self.hist.append(("nop", set()))
         k = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith("v_rsq") else "vcmp" if mn.startswith("v_cmp") else "valu"
         self.lines.append(text)
-        self.hist.append((k, self.regs(dst) | ({"vcc"} if k == "vcmp" else set())))
+        self.hist.append((k, self.regs(dst) | ({"vcc"} if k == "vcmp" and dst == "vcc" else set())))
 
     def nops(self):
         return sum(1 for ln in self.lines if ln.startswith("s_nop"))
@@ -142,10 +152,10 @@ def col_norms(st, L=LAY, of_v=False):
             st.emit(f"v_add_f32_e32 {L.N(c0 + i, nb)}, v{lo}, v{int(lo) + 1}")
 
 
-def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False):
+def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False, move_test=True):
     """One Jacobi rotation of columns p < q (jacobi_rot_pk<CHECK, SKIP>); plain: no convergence test, no skip
     (the sweeps that can never be the last one); with_v: tested, never skipped, V's columns rotated too
-    (jacobi_rot_pk_v<1>)."""
+    (jacobi_rot_pk_v<1>); move_test: the tested rotation also reports a norm move above MOVE2."""
     A, N = L.A, L.N
     GV, T1, T2, CS, T3, GVl, GVh, C, S = L.GV, L.T1, L.T2, L.CS, L.T3, L.GVl, L.GVh, L.C, L.S
     g, gg, ab, tau, ta, t1, ih, x = L.g, L.gg, L.ab, L.tau, L.ta, L.t1, L.ih, L.x
@@ -194,6 +204,14 @@ def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False):
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {g}")                          # ... w = t g  (|w| below)
     if not plain:
         st.emit(f"v_min_f32_e32 {ta}, {Np}, {Nq}")
+    if not plain and not with_v and move_test:
+        # notconv |= w^2 > move2 max(al, be) n2[0]: the rotation moved a squared singular value by more than
+        # sqrt(move2) s_1 s_p (w is |g| for a near-degenerate pair, g^2 / gap for a separated one)
+        st.emit(f"v_mul_f32_e32 {x}, {gg}, {gg}")
+        st.emit(f"v_mul_f32_e32 {ih}, {f32_literal(MOVE2)}, {ab}")
+        st.emit(f"v_mul_f32_e32 {ih}, {ih}, {N(0)}")
+        st.emit(f"v_cmp_gt_f32_e32 vcc, {x}, {ih}")
+        st.emit(f"s_or_b64 {M}, {M}, vcc", kind="salu")
     st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")                       # larger norm grows by |t g|
     st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
     # columns: a_p <- C a_p + S a_q ; a_q <- C a_q - S a_p   (C, S broadcast from the halves of CS by op_sel)
@@ -214,11 +232,91 @@ def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False):
         st.hist.append(("nop", set()))       # a taken branch lands here: nothing before it may be assumed
 
 
+def f32_literal(x):
+    return f"0x{struct.unpack('<I', struct.pack('<f', x))[0]:08x}"
+
+
+def lq_prelude(st, L=LAY):
+    """B0 = X Q: Householder LQ of the tile with greedy row pivoting, reflectors applied from the RIGHT (lq_prelude_pk of
+    wm_tile_math.h).  Step k = 0 .. 6: the row not yet used with the largest |x[k:]|^2 is the pivot; the reflector
+    H = I - vh vh^T (vh = (x + sign(x_k) |x| e_k) sqrt(2 / v^T v), columns k .. 7) zeroes its entries k+1 .. 7 and is
+    applied to all eight rows.  The column Gram matrix of B0 is that of the row-pivoted R^T - one QR-algorithm step
+    further on than X's - and the row permutation never has to be applied.  B0 = X * (orthogonal), so everything
+    downstream of the sweeps is unchanged.  A wrong pivot (ties, cancellation in the downdated norms) only costs
+    convergence; a zero row gives vh = 0.
+    Registers, all free before the first sweep: vh / the selected row in v[N0 : N0+7] (column c in half c & 1 of pair
+    c >> 1), W = A vh in v[T : T+7], the trailing row norms in v[T+8 : T+15] (row r in v[T+8+r]); scalars of a step in
+    W's registers before W is formed.  The one-hot row masks are made exclusive on the scalar unit (first match wins)
+    and read by v_cndmask from SGPRs the SALU wrote."""
+    e = st.emit
+    X = lambda c: f"v{L.N0 + c}"
+    XP = lambda c: f"v[{L.N0 + 2 * (c >> 1)}:{L.N0 + 2 * (c >> 1) + 1}]"
+    W = lambda rp: f"v[{L.T + 2 * rp}:{L.T + 2 * rp + 1}]"
+    RNP = lambda rp: f"v[{L.T + 8 + 2 * rp}:{L.T + 9 + 2 * rp}]"
+    RN = lambda r: f"v{L.T + 8 + r}"
+    row = lambda r, c: L.Alo(r >> 1, c) if (r & 1) == 0 else L.Ahi(r >> 1, c)
+    m, neg, t2, nx2, rr, nrm, vk, sb = (f"v{L.T + i}" for i in range(8))
+    tiny = f32_literal(1e-36)
+    for c in range(8):                                   # |row|^2 of all eight rows: four packed chains
+        for rp in range(4):
+            e(f"v_pk_mul_f32 {RNP(rp)}, {L.A(rp, c)}, {L.A(rp, c)}" if c == 0 else
+              f"v_pk_fma_f32 {RNP(rp)}, {L.A(rp, c)}, {L.A(rp, c)}, {RNP(rp)}")
+    for k in range(LQ_STEPS):
+        cols = range(k, 8)
+        e(f"v_max3_f32 {m}, {RN(0)}, {RN(1)}, {RN(2)}")
+        e(f"v_max3_f32 {neg}, {RN(3)}, {RN(4)}, {RN(5)}")
+        e(f"v_max3_f32 {m}, {RN(6)}, {RN(7)}, {m}")
+        e(f"s_mov_b64 {LQ_FOUND}, 0", kind="salu")
+        e(f"v_max_f32_e32 {m}, {m}, {neg}")
+        e(f"v_mov_b32_e32 {neg}, {f32_literal(-1e30)}")   # a used row never wins again
+        for r in range(8):
+            e(f"v_cmp_eq_f32_e64 {LQ_T}, {RN(r)}, {m}")
+            e(f"s_andn2_b64 {LQ_M}, {LQ_T}, {LQ_FOUND}", kind="salu")
+            e(f"s_or_b64 {LQ_FOUND}, {LQ_FOUND}, {LQ_T}", kind="salu")
+            if r < 7:                                    # (row 7's own mark: below, where it keeps v_rsq and its use apart)
+                e(f"v_cndmask_b32_e64 {RN(r)}, {RN(r)}, {neg}, {LQ_M}")
+            if r:
+                for c in cols:                           # x = the pivot row's entries k .. 7 (row 0 unless another matched)
+                    e(f"v_cndmask_b32_e64 {X(c)}, {row(0, c) if r == 1 else X(c)}, {row(r, c)}, {LQ_M}")
+        e(f"v_mul_f32_e32 {t2}, {X(7)}, {X(7)}")
+        for c in range(6, k, -1):
+            e(f"v_fma_f32 {t2}, {X(c)}, {X(c)}, {t2}")    # |x[k+1:]|^2
+        e(f"v_fma_f32 {nx2}, {X(k)}, {X(k)}, {t2}")
+        e(f"v_max_f32_e32 {rr}, {tiny}, {nx2}")
+        e(f"v_rsq_f32_e32 {rr}, {rr}")
+        e(f"v_mov_b32_e32 {vk}, 0x7fffffff")
+        e(f"v_mul_f32_e32 {nrm}, {nx2}, {rr}")            # |x| (0 for a zero row)
+        e(f"v_bfi_b32 {nrm}, {vk}, {nrm}, {X(k)}")        # sign(x_k) |x|
+        e(f"v_add_f32_e32 {vk}, {X(k)}, {nrm}")           # v_k = x_k + sign(x_k) |x|: no cancellation
+        e(f"v_fma_f32 {t2}, {vk}, {vk}, {t2}")            # v^T v
+        e(f"v_mul_f32_e32 {t2}, 0.5, {t2}")
+        e(f"v_max_f32_e32 {t2}, {tiny}, {t2}")
+        e(f"v_rsq_f32_e32 {sb}, {t2}")                    # sqrt(2 / v^T v)
+        e(f"v_cndmask_b32_e64 {RN(7)}, {RN(7)}, {neg}, {LQ_M}")   # row 7 used, if it is the pivot ({LQ_M} is still its one-hot)
+        for c in cols:
+            e(f"v_mul_f32_e32 {X(c)}, {vk if c == k else X(c)}, {sb}")      # vh
+        for c in cols:                                   # W = A vh (both rows of a pair at once)
+            h = c & 1
+            for rp in range(4):
+                e(f"v_pk_mul_f32 {W(rp)}, {XP(c)}, {L.A(rp, c)} op_sel:[{h},0] op_sel_hi:[{h},1]" if c == k else
+                  f"v_pk_fma_f32 {W(rp)}, {XP(c)}, {L.A(rp, c)}, {W(rp)} op_sel:[{h},0,0] op_sel_hi:[{h},1,1]")
+        for c in cols:                                   # A <- A - W vh^T
+            h = c & 1
+            for rp in range(4):
+                e(f"v_pk_fma_f32 {L.A(rp, c)}, {XP(c)}, {W(rp)}, {L.A(rp, c)} op_sel:[{h},0,0] op_sel_hi:[{h},1,1] "
+                  f"neg_lo:[0,1,0] neg_hi:[0,1,0]")
+        if k < LQ_STEPS - 1:
+            for rp in range(4):                          # trailing norms lose column k
+                e(f"v_pk_fma_f32 {RNP(rp)}, {L.A(rp, k)}, {L.A(rp, k)}, {RNP(rp)} neg_lo:[1,0,0] neg_hi:[1,0,0]")
+
+
 def eps_literal():
     return struct.unpack("<I", struct.pack("<f", 1e-18))[0]  # keeps 0/0 out; its square (1e-36) is a normal float
 
 
-def build():
+def build(move_test=True, lq=True):
+    """lq=False: no LQ prelude; move_test=False: the tested sweeps stop on cos^2 alone, as they did before the LQ prelude (what the emulator
+    measures the prelude against); the committed stream is build()."""
     st = Stream()
     e = st.emit
     Alo, Ahi = LAY.Alo, LAY.Ahi
@@ -234,6 +332,10 @@ def build():
             src = f"%[lo{r}]" if c < 4 else f"%[hi{r}]"
             dst = Alo(r >> 1, c) if (r & 1) == 0 else Ahi(r >> 1, c)
             e(f"v_cvt_f32_ubyte{c & 3}_e32 {dst}, {src}")
+    if lq:
+        lq_prelude(st)
+    e(".Lwmj_lqdone_%=:", kind="label")
+    st.hist.append(("nop", set()))
     e(".Lwmj_sweep_%=:", kind="label")
     e(f"s_mov_b64 {M}, 0", kind="salu")
     e(f"s_bitcmp1_b32 {SW}, 0", kind="salu")                 # norms are recomputed before odd-numbered sweeps
@@ -256,7 +358,7 @@ def build():
     k = 0
     for p in range(7):
         for q in range(p + 1, 8):
-            rotation(st, p, q, k)
+            rotation(st, p, q, k, move_test=move_test)
             k += 1
     e(".Lwmj_swept_%=:", kind="label")
     st.hist.append(("nop", set()))
@@ -328,8 +430,11 @@ def build_v():
 HEADER = """// GENERATED by tools/gen_jacobi_asm.py - do not edit.  The packed one-sided Jacobi of the tile kernels
 // (raw_to_pk + jacobi_cols_pk + final col_norms2_pk of wm_tile_math.h) as one gfx950 instruction stream with
 // pinned registers: B = X V in v[40:103] (a[rp][c] = v[40 + 2 (8 rp + c)] : rows 2 rp, 2 rp + 1),
-// |b_c|^2 in v[104:111], temporaries v[112:127], control in s[80:92].  {n_inst} instructions, {n_nop} s_nop.
-//   conv2:     a sweep that saw no pair with cos^2 > conv2 in any tile of the wave is the last one
+// |b_c|^2 in v[104:111], temporaries v[112:127], control in s[80:98].  {n_inst} instructions, {n_nop} s_nop.
+// The sweeps run on B0 = X Q, the row-pivoted Householder LQ of the tile applied from the right (its column Gram
+// matrix is one QR-algorithm step further on: about one sweep fewer); B stays X * orthogonal.
+//   conv2:     a sweep that saw no pair with cos^2 > conv2 in any tile of the wave, and no rotation that moved the two
+//              squared norms by w with w^2 > {move2:g} n2[0] max(n2[p], n2[q]) (JAC_MOVE2), is the last one
 //   skip2:     from sweep `skip_from` (0-based) on, a pair below skip2 in every tile of the wave is left alone
 //   min_sweeps: sweeps that run regardless of the test (the first ones never pass it)
 // Returns the wave's not-converged mask after the last sweep (non-zero only when the bound of {max_sw} is hit).
@@ -367,7 +472,7 @@ def n_instructions(st):
 
 def render():
     st = build()
-    body = HEADER.format(n_inst=n_instructions(st), n_nop=st.nops(), max_sw=MAX_SWEEPS)
+    body = HEADER.format(n_inst=n_instructions(st), n_nop=st.nops(), max_sw=MAX_SWEEPS, move2=MOVE2)
     for ln in st.lines:
         body += f'      "{ln}\\n\\t"\n'
     outs = []
@@ -380,7 +485,7 @@ def render():
     outs.append('[more] "=&s"(more)')
     ins = [f'[lo{r}] "v"(lo[{r}])' for r in range(8)] + [f'[hi{r}] "v"(hi[{r}])' for r in range(8)]
     ins += ['[conv] "s"(conv2)', '[skip] "s"(skip2)', '[minsw] "s"(min_sweeps)', '[skipfrom] "s"(skip_from)']
-    clob = [f'"v{i}"' for i in range(T, 128)] + [f'"s{i}"' for i in range(80, 93)] + ['"vcc"', '"scc"']
+    clob = [f'"v{i}"' for i in range(T, 128)] + [f'"s{i}"' for i in range(80, 99)] + ['"vcc"', '"scc"']
     body += "      : " + ",\n        ".join(outs) + "\n"
     body += "      : " + ",\n        ".join(ins) + "\n"
     body += "      : " + ", ".join(clob) + ");\n  return more;\n}\n"

@@ -1,7 +1,8 @@
 // Development study (host build): for every sweep of the packed one-sided Jacobi, how many column pairs
 // are below a cos^2 threshold in ALL 64 tiles of a wave at the moment the pair is visited - i.e. how much a
 // wave-uniform "leave this pair alone" test can save (embed-kernel diet).
-//   g++ -O2 -o tools/bin/skip_study tools/skip_study.cpp && tools/bin/skip_study
+//   g++ -O2 -o tools/bin/skip_study tools/skip_study.cpp && tools/bin/skip_study [lq]
+// (argument lq: the sweeps run behind the LQ prelude, lq_prelude_pk)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,7 +11,8 @@
 #include "../digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd/csrc/wm_tile_math.h"
 using namespace wm;
 
-int main() {
+int main(int argc, char**) {
+  const bool lq = argc > 1;
   const int NW = 300, NS = 6;
   const char* kinds[] = {"noise", "natural"};
   const float thr[] = {1e-13f, 1e-12f, 1e-11f, 1e-10f, 1e-8f, 1e-7f, 1e-6f, 1e-5f, 1e-4f, 1e-3f};
@@ -36,6 +38,7 @@ int main() {
           v2f v = {(float)px[((size_t)w * 64 + l) * 64 + (2 * rp) * 8 + c], (float)px[((size_t)w * 64 + l) * 64 + (2 * rp + 1) * 8 + c]};
           a[l][rp][c] = v;
         }
+        if (lq) lq_prelude_pk(a[l]);
         col_norms2_pk(a[l], n2[l]);
       }
       for (int s = 0; s < NS; ++s) {
@@ -64,7 +67,7 @@ int main() {
     }
     printf("== %s: fraction of (wave, pair) visits whose cos^2 is below T in all 64 tiles | fraction of WAVES whose whole sweep is below T | fraction of TILES\n", kinds[kind]);
     printf("   T:      "); for (int k = 0; k < NT; ++k) printf(" %7.0e", thr[k]); printf("\n");
-    for (int s = 2; s < NS; ++s) {
+    for (int s = 1; s < NS; ++s) {
       printf("sweep %d pair:", s + 1); for (int k = 0; k < NT; ++k) printf(" %7.3f", below[s][k] / (NW * 28.0)); printf("\n");
       printf("        wave:"); for (int k = 0; k < NT; ++k) printf(" %7.3f", wavemax[s][k] / NW); printf("\n");
       printf("        tile:"); for (int k = 0; k < NT; ++k) printf(" %7.3f", lanebelow[s][k] / (NW * 64.0)); printf("\n");
