@@ -37,10 +37,7 @@ namespace {
 
 constexpr int RB = 32;        // rows per Jacobi block
 constexpr int RP = 2 * RB;    // rows per block pair
-#ifndef WM_GRAM_CC
-#define WM_GRAM_CC 128
-#endif
-constexpr int GRAM_CC = WM_GRAM_CC;  // columns per Gram partial (128 or 256)
+constexpr int GRAM_CC = 128;  // columns per Gram partial
 constexpr int MAX_SWEEPS = 40;
 constexpr int FULL_INNER_SWEEPS = 0;   // outer sweeps whose every step runs the full 63-step inner schedule
 constexpr float CONV_COS = 2e-5f;   // float32 Gram entries resolve cos down to ~eps*sqrt(M)
@@ -50,13 +47,111 @@ constexpr float CONV_COS_SIGMA = 2e-4f;
 constexpr float SKIP_FRACTION = 0.25f;    // a block pair below this fraction of the (embed) stopping cosine is left alone
 constexpr double RESIDUE_RHO = 10.0;      // |A0 b_i^T| / |b_i|^2 above this: b_i is not a singular direction at all
 constexpr double T_SWITCH = 200.0;        // |A0 b_i^T| / |b_i| is used for s_i >= T_SWITCH * (residual cosine) * s_max
-constexpr int HIER_F16_DEFAULT = 3;         // two-level scheme, split-f16 operands on the f16 matrix pipe: bit 0 Gram tiles (k_hgram_h), bit 1 rotation products (k_happly_h); WM_RF_HIER_F16 overrides
+constexpr int HIER_F16_DEFAULT = 3;         // two-level scheme, split-f16 operands on the f16 matrix pipe: bit 0 Gram tiles (k_hgram_t<true>), bit 1 rotation products (k_happly_h); WM_RF_HIER_F16 overrides
 constexpr int HIER_MIN_PLANES = 20;         // ... with the f32 kernels
 constexpr int HIER_MIN_PLANES_F16 = 3;      // planes per call from which the two-level scheme is the default when its split-f16 kernels apply        // planes per call from which the two-level scheme (wm_ref_hier.inc) is the default
 constexpr int DEFAULT_QUEUES = 2;         // plane groups of a batched Jacobi, each on its own HIP queue
 constexpr double DRIFT_TOL = 1e-2;        // |T[:, i]| / |b_i|^2 may differ from 1 by the scale drift, not more
 constexpr double NULL_ROW_RATIO = 1e-5;   // rows below this fraction of |A|_F do not take part in the convergence test
 constexpr double NULL_RATIO = 1e-6;   // embed: singular directions below this fraction of s_1 get no watermark energy
+
+// ---------------------------------------------------------------------------
+// Tile vocabulary of the full-frame kernels (this file and wm_ref_hier.inc): every rule below is stated here, once.
+// Functions where the kernels compile to the same code with them; the four macros (capitals) are the rules that hipcc
+// optimises on their own before it inlines them, after which a kernel's instruction stream comes out different.
+// ---------------------------------------------------------------------------
+typedef float v16f __attribute__((ext_vector_type(16)));     // the accumulator of one 32 x 32 MFMA tile
+typedef float f2v __attribute__((ext_vector_type(2)));
+typedef _Float16 h8_t __attribute__((ext_vector_type(8)));    // one lane's operand of v_mfma_f32_32x32x16_f16: 8 consecutive k
+typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+
+// Accumulator register v of lane (j, h = lane / 32) holds row ACC_ROW(v, h, base) of the 32 x 32 tile (column j); base: the tile's
+// first row in whatever it is a tile of (added first: as a function, or with the base added last, the sum is associated
+// differently and the address arithmetic of k_sgemm, k_hgemm and k_hupdate comes out in another order).
+#define ACC_ROW(v, h, base) ((base) + 8 * ((v) / 4) + 4 * (h) + ((v) % 4))
+
+// row (or column) r of a block pair's 64 -> row of the enclosing matrix whose blocks la, lb the pair is made of
+__device__ __forceinline__ constexpr int pair_row(const int r, const int la, const int lb) { return (r < RB) ? la * RB + r : lb * RB + r - RB; }
+
+// A unit of a stage of the two-level scheme: two blocks (local indices la, lb of the super-pair) that are rotated against each
+// other, or an idle pair that only keeps k_hupdate's pairing complete (R = I); -1: no such unit at this stage.
+constexpr int UNIT_NONE = -1;
+__host__ __device__ constexpr int unit_make(const int la, const int lb, const bool real) { return la | (lb << 8) | (real ? 1 << 16 : 0); }
+__host__ __device__ constexpr int unit_la(const int e) { return e & 0xff; }
+__host__ __device__ constexpr int unit_lb(const int e) { return (e >> 8) & 0xff; }
+// (as a function: other code in k_happly_h's stage prologue)
+#define UNIT_ROTATES(e) ((e) >= 0 && (((e) >> 16) & 1))
+
+// XCD-aware orders.  Workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share an L2 - observed placement, speed
+// only), so id -> (xcd = id % 8, q = id / 8).
+//  * groups (Gram kernels): `per` consecutive q on ONE XCD are the workgroups w of one (super-pair, split, plane) group - they
+//    read the same row panels and meet in that XCD's L2.  Returns the group, which lies beyond the grid's nsp * KS * nz for
+//    the workgroups that pad the launch to a multiple of 8 groups.
+__device__ __forceinline__ int xcd_group(const int id, const int per, int& w) {
+  const int xcd = id & 7, q = id >> 3;
+  w = q % per;
+  return (q / per) * 8 + xcd;
+}
+__device__ __forceinline__ void group_decode(const int grp, const int nsp, const int KS, int& sp, int& ks, int& zl) {
+  sp = grp % nsp; ks = (grp / nsp) % KS; zl = grp / (nsp * KS);
+}
+//  * tasks (apply kernels): the ntask tasks in contiguous ranges, XCD x takes [ntask x / 8, ntask (x + 1) / 8) - a super-pair's
+//    rotations serve all of its strips from one or two L2s.  Returns the task; at or beyond `end` this workgroup has none.
+//  (Plain arithmetic, the early return stays with the kernel: a helper that returns "no work" compiles to another prologue.)
+__device__ __forceinline__ int xcd_task(const unsigned id, const int ntask, int& end) {
+  const int xcd = id & 7, q = id >> 3;
+  const int x0 = (int)((long)ntask * xcd / 8);
+  end = (int)((long)ntask * (xcd + 1) / 8);
+  return x0 + q;
+}
+
+// Of the 16-byte load v of columns col .. col + 3 of a row of M columns, what lies behind the row's end is zeroed.  (The load
+// itself may run past M: every row of Aug has its identity part and padding behind it.  k_hgemm's operands are dense matrices
+// with nothing behind a row, so its load4 does not load what this masks - a bounded load, not a fourth copy of this mask.)
+// (as a function, by value or by reference: other register assignments in k_hgram_h3 and k_hgram_t<true>)
+#define MASK_TAIL4(v, col, M) \
+  do { if ((col) + 3 >= (M)) { if ((col) >= (M)) (v).x = 0.0f; if ((col) + 1 >= (M)) (v).y = 0.0f; if ((col) + 2 >= (M)) (v).z = 0.0f; (v).w = 0.0f; } } while (0)
+
+// The three hi / lo splits of an f32 value for the f16 matrix pipe.  They differ in what happens to
+// the low part, and so in their bits - they are kept apart on purpose:
+//  * split4_f16     x = hi + lo, lo = f16(x - hi) UNSCALED.  k_hgram_t<true>, k_hgram_h3, k_hgemm: Gram entries only steer the
+//                   rotations and the finalisation's operands are pre-scaled into [~1, 3e4), so losing lo where it is an f16
+//                   denormal (|x| < 0.125) costs < 2^-22 of the products, and the accumulator needs no rescaling.
+//  * split4_scaled  x = hi + lo' / 2048, lo' = f16((x - hi) * 2048).  k_happly_h's strip image, staged and written back every
+//                   stage: the rows themselves live in this form, so lo' keeps 22 significant bits down to |x| ~ 3e-8 (f16
+//                   subnormals are kept by the conversion and honoured by the matrix pipe: tools/ubench_f16_denorm.hip); the
+//                   cross products go to a second accumulator that is scaled by 2^-11 at the end.
+//  * SPLIT1_FLUSHED the scaled rule for ONE value with hi flushed to 0 below f16's normal range (6.2e-5): k_rf_inner's packed
+//                   rotation for k_happly_h.  Such an entry sits wholly in lo' instead of in a subnormal hi; the matrix pipe
+//                   would take the subnormal as well, but dropping the flush changes R's bits, so it stays.
+__device__ __forceinline__ void split4_f16(const float4 v, uint2& hi, uint2& lo) {
+  const h2_t a = {(_Float16)v.x, (_Float16)v.y}, b = {(_Float16)v.z, (_Float16)v.w};
+  const h2_t la = {(_Float16)(v.x - (float)a[0]), (_Float16)(v.y - (float)a[1])};
+  const h2_t lb = {(_Float16)(v.z - (float)b[0]), (_Float16)(v.w - (float)b[1])};
+  hi = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
+  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
+}
+// (six VALU instructions per two values: packed f32 subtract and scale)
+__device__ __forceinline__ void split4_scaled(const float x0, const float x1, const float x2, const float x3, h4_t& hi, h4_t& lo) {
+  const f2v a = {x0, x1}, b = {x2, x3};
+  const h2_t ha = __builtin_convertvector(a, h2_t), hb = __builtin_convertvector(b, h2_t);
+  const f2v ra = (a - __builtin_convertvector(ha, f2v)) * 2048.0f, rb = (b - __builtin_convertvector(hb, f2v)) * 2048.0f;
+  const h2_t la = __builtin_convertvector(ra, h2_t), lb = __builtin_convertvector(rb, h2_t);
+  hi = h4_t{ha[0], ha[1], hb[0], hb[1]};
+  lo = h4_t{la[0], la[1], lb[0], lb[1]};
+}
+// (as a function: k_rf_inner's stores of the packed R in another order)
+#define SPLIT1_FLUSHED(v, hi, lo) \
+  do { const _Float16 h_ = fabsf(v) < 6.2e-5f ? (_Float16)0.0f : (_Float16)(v); (hi) = h_; (lo) = (_Float16)(((v) - (float)h_) * 2048.0f); } while (0)
+
+// acc += a b^T from split operands: hi hi, hi lo, lo hi (lo lo is below 2^-22 of the product).  k_happly_h issues the same three
+// with the two cross products in an accumulator of their own (its lo' is scaled); k_hgemm drops the third where A has no lo.
+__device__ __forceinline__ void mfma3_f16(const h8_t ah, const h8_t al, const h8_t bh, const h8_t bl, v16f& acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+}
 
 // ---------------------------------------------------------------------------
 // generic row-major SGEMM:  C = alpha * op(A) op(B) + beta * C  on MFMA
@@ -66,8 +161,6 @@ constexpr double NULL_RATIO = 1e-6;   // embed: singular directions below this f
 // loads issued before this step's 16 MFMAs.  Plain-library-GEMM shaped work of the full-frame
 // mode (DCT as two GEMMs, T = A0 B^T, U diag V^T products).
 // ---------------------------------------------------------------------------
-typedef float v16f_s __attribute__((ext_vector_type(16)));
-
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256) void k_sgemm(const int M, const int N, const int K, const float alpha,
                                               const float* __restrict__ A, const int lda, const size_t sA,
@@ -116,7 +209,7 @@ __global__ __launch_bounds__(256) void k_sgemm(const int M, const int N, const i
   // C one by one, round-to-nearest: tools/mfma_round_probe.hip) and the step sums are added up by the VALU.  One long
   // chain loses every term that follows a dominant one below that term's ulp - the DC coefficient of a DCT plane
   // leads its row by 2^11 - which made sigma_1 of the watermark-side SVD 5e-6 (1080p) to 4e-5 (8K) low.
-  v16f_s acc = {0};
+  v16f acc = {0};
   fetch(0);
   int buf = 0;
   for (int k0 = 0; k0 < K; k0 += KS, buf ^= 1) {
@@ -125,7 +218,7 @@ __global__ __launch_bounds__(256) void k_sgemm(const int M, const int N, const i
     __syncthreads();                    // double-buffered LDS: one barrier per K step
     const float* pa = &As[buf][m0 + j][h];
     const float* pb = &Bs[buf][h][n0 + j];
-    v16f_s part = {0};
+    v16f part = {0};
 #pragma unroll
     for (int kk = 0; kk < KS / 2; ++kk)
       part = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk], pb[2 * kk * 65], part, 0, 0, 0);
@@ -135,7 +228,7 @@ __global__ __launch_bounds__(256) void k_sgemm(const int M, const int N, const i
   if (gn < N) {
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int gm = bm + m0 + 8 * (v / 4) + 4 * h + (v % 4);
+      const int gm = ACC_ROW(v, h, bm + m0);
       if (gm < M) {
         float* c = C + (size_t)gm * ldc + gn;
         *c = (beta == 0.0f) ? alpha * acc[v] : __builtin_fmaf(beta, *c, alpha * acc[v]);
@@ -190,7 +283,6 @@ __global__ void k_rf_load(const T* __restrict__ src, const size_t src_stride, co
 // X[i0 + lane%32][k + lane/32] of a wave hit 32 distinct banks twice), wave w owns the 32 x 32
 // quadrant (w >> 1, w & 1) of the Gram matrix and issues 64 v_mfma_f32_32x32x2_f32 whose A and B
 // operands both come from X (D = X_I X_J^T).
-typedef float v16f_g __attribute__((ext_vector_type(16)));
 constexpr int GP = GRAM_CC + 1;
 constexpr int GRAM_PART = 3 * RB * RB;      // floats per (pair, chunk) partial: the quadrants (I,I), (I,J), (J,J)
 
@@ -215,7 +307,7 @@ __global__ __launch_bounds__(256) void k_rf_gram(const float* __restrict__ aug, 
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int r = r0 + RSTEP * i;
-      const int grow = (r < RB) ? pr.x * RB + r : pr.y * RB + (r - RB);
+      const int grow = pair_row(r, pr.x, pr.y);
       v[i] = aug[(size_t)grow * ld + gcc];
     }
 #pragma unroll
@@ -228,15 +320,14 @@ __global__ __launch_bounds__(256) void k_rf_gram(const float* __restrict__ aug, 
   const int i0 = (wv >> 1) * 32, j0 = (wv & 1) * 32;
   const float* ra = &Xs[i0 + j][h];
   const float* rb = &Xs[j0 + j][h];
-  v16f_g acc = {0};
+  v16f acc = {0};
 #pragma unroll 16
   for (int kk = 0; kk < GRAM_CC / 2; ++kk)
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[2 * kk], rb[2 * kk], acc, 0, 0, 0);
   float* out = partials + ((size_t)p * nch + ch) * GRAM_PART + (wv == 3 ? 2 : wv) * (RB * RB);
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = 8 * (v / 4) + 4 * h + (v % 4);
-    out[row * RB + j] = acc[v];
+    out[ACC_ROW(v, h, 0) * RB + j] = acc[v];
   }
 }
 
@@ -272,14 +363,10 @@ __device__ __forceinline__ int rr_elem(const int pos, const int step) {
 // Two-level (super-block) scheme, see "hierarchical block Jacobi" further down: a super-pair is at most HSB
 // 32-row blocks (HN rows); its Gram matrix G_s and accumulated rotation Q_s are HN x HN arrays (pitch HN) in
 // global memory, and a stage rotates HU disjoint block pairs ("units") of it.
-typedef float f2v __attribute__((ext_vector_type(2)));
 constexpr int HSB = 12;
 constexpr int HN = HSB * RB;
 constexpr int HU = HSB / 2;
-#ifndef WM_INNER_NT
-#define WM_INNER_NT 512
-#endif
-constexpr int INNER_NT = WM_INNER_NT;
+constexpr int INNER_NT = 512;
 constexpr int INNER_NW = INNER_NT / 64;
 constexpr int INNER_KR = INNER_NT / 32;        // row pairs a thread column covers per pass (stride between a thread's row pairs)
 constexpr int INNER_NB = 32 / INNER_KR;        // 2x2 blocks of G per thread
@@ -299,15 +386,6 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
   __shared__ float R[RP][RP + 1];
   __shared__ float red[INNER_NW];
   const int t = threadIdx.x, p = blockIdx.x;
-#if defined(WM_POISON_LDS)     // diagnostic: every word of the kernel's LDS starts as a NaN - a read of a word the kernel never wrote shows in the results
-  for (int i = threadIdx.x; i < 2 * RP * (RP + 1); i += INNER_NT) (&GG[0][0][0])[i] = __int_as_float(0x7fc00000);
-  for (int i = threadIdx.x; i < RP * (RP + 1); i += INNER_NT) (&R[0][0])[i] = __int_as_float(0x7fc00000);
-  if (threadIdx.x < INNER_NW) red[threadIdx.x] = __int_as_float(0x7fc00000);
-  __syncthreads();
-#endif
-#if defined(WM_INNER_DIAG)     // diagnostic build only (tools/): where one inner solve spends its cycles
-  unsigned long long st0 = __builtin_amdgcn_s_memtime(), st1 = 0, st2 = 0, st3 = 0;
-#endif
   partials += (size_t)blockIdx.z * gridDim.x * nch * GRAM_PART;
   Rout += (size_t)blockIdx.z * gridDim.x * RP * RP;
   maxcos_bits += blockIdx.z;
@@ -318,8 +396,8 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
   float* gs = nullptr;
   if (h_units) {
     const int unit = h_units[p];
-    if (unit < 0 || !((unit >> 16) & 1)) return;   // no such unit in this super-pair at this stage / an idle pair
-    la = unit & 0xff; lb = (unit >> 8) & 0xff;
+    if (!UNIT_ROTATES(unit)) return;               // no such unit in this super-pair at this stage / an idle pair
+    la = unit_la(unit); lb = unit_lb(unit);
     gs = h_Gs + ((size_t)blockIdx.z * h_nsp + p / HU) * HN * HN;
   }
   const float* src = partials + (size_t)p * nch * GRAM_PART;
@@ -336,8 +414,7 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
   if (h_units) {
     for (int f = t; f < RP * RP / 4; f += INNER_NT) {
       const int r = f >> 4, c4 = (f & 15) * 4;
-      const int gr = (r < RB) ? la * RB + r : lb * RB + r - RB;
-      const int gc = (c4 < RB) ? la * RB + c4 : lb * RB + c4 - RB;
+      const int gr = pair_row(r, la, lb), gc = pair_row(c4, la, lb);
       const float4 v = *reinterpret_cast<const float4*>(gs + (size_t)gr * HN + gc);
       G[r][c4] = v.x; G[r][c4 + 1] = v.y; G[r][c4 + 2] = v.z; G[r][c4 + 3] = v.w;
       if (!cross_only) {
@@ -384,9 +461,6 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
     }
   }
   __syncthreads();
-#if defined(WM_INNER_DIAG)
-  st1 = __builtin_amdgcn_s_memtime();
-#endif
   // largest cosine between two rows of the pair, from the sums still in registers and the diagonal in LDS
   float mx = 0.0f;
   if (h_units) {
@@ -439,22 +513,19 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
   float* rpk = h_Rpk ? h_Rpk + ((size_t)blockIdx.z * gridDim.x + p) * RP * RP : nullptr;
   auto pk_index = [](const int r, const int c) { return (((c >> 5) * 8 + (r >> 3)) * 64 + (c & 31) + 32 * (r & 1)) * 4 + ((r >> 1) & 3); };
   // h_f16: the same 16 KB as split f16 for k_happly_h (v_mfma_f32_32x32x16_f16: lane (i, kg) holds 8 consecutive k):
-  // R[k][c] = hi + lo' / 2048 with hi = f16(R) (0 below f16's normal range), lo' = f16((R - hi) * 2048);
+  // R[k][c] = hi + lo' / 2048 (SPLIT1_FLUSHED);
   // half index ((c / 32 * 4 + k / 16) * 64 + c % 32 + 32 * (k / 8 % 2)) * 8 + k % 8, hi in the first 4096 halfs, lo' behind
   auto put_r = [&](const int r, const int c, const float v) {
     if (!h_f16) { rpk[pk_index(r, c)] = v; return; }
     _Float16* hp = reinterpret_cast<_Float16*>(rpk);
     const int idx = (((c >> 5) * 4 + (r >> 4)) * 64 + (c & 31) + 32 * ((r >> 3) & 1)) * 8 + (r & 7);
-    const _Float16 hi = fabsf(v) < 6.2e-5f ? (_Float16)0.0f : (_Float16)v;
-    hp[idx] = hi;
-    hp[RP * RP + idx] = (_Float16)((v - (float)hi) * 2048.0f);
+    SPLIT1_FLUSHED(v, hp[idx], hp[RP * RP + idx]);
   };
   // two-level scheme: the rotated Gram matrix (pitch RP + 1 in LDS) goes back into G_s
   auto writeback = [&](const float* gf) {
     for (int f = t; f < RP * RP / 4; f += INNER_NT) {
       const int r = f >> 4, c4 = (f & 15) * 4;
-      const int gr = (r < RB) ? la * RB + r : lb * RB + r - RB;
-      const int gc = (c4 < RB) ? la * RB + c4 : lb * RB + c4 - RB;
+      const int gr = pair_row(r, la, lb), gc = pair_row(c4, la, lb);
       const float* q = gf + r * (RP + 1) + c4;
       *reinterpret_cast<float4*>(gs + (size_t)gr * HN + gc) = make_float4(q[0], q[1], q[2], q[3]);
     }
@@ -468,16 +539,9 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
   const int wv_s = __builtin_amdgcn_readfirstlane(t >> 6);
   const bool hi = (t & 32) != 0;
   const int kr = 2 * wv_s + (hi ? 1 : 0);
-  const int n_inner = cross_only ? RB : RP - 1;
-#if defined(WM_INNER_DIAG)
-  st2 = __builtin_amdgcn_s_memtime();
-#endif
+  const int n_inner = cross_only ? RB : RP - 1;           // (RP - 1 where it is used: hipcc compiles the step loop differently for a literal bound)
   float* out = Rout + (size_t)p * RP * RP;
-#if defined(WM_INNER_R_LDS)      // A/B only: R through LDS on every step (the round-2a kernel)
-  if (false) {
-#else
   if (cross_only) {
-#endif
     // Cross-block schedule (32 steps; every step of a sweep but the first): block-I row k meets block-J row
     // (k + step) mod 32.  R never touches LDS here: thread (kr, k2) keeps R[r][k2] (its block-I column, fixed) and
     // R[r][32 + (k2 + step) mod 32] (the block-J column of its current pair) for its rows r = kr + KR j in
@@ -509,23 +573,13 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
       rp_[i] = (kr + INNER_KR * i) * PITCH;                // row p1 (fixed)
       rq_[i] = (RB + kr + INNER_KR * i) * PITCH;           // row q1 (moves one row down per step, wraps to row 32)
     }
-#if defined(WM_INNER_DIAG)
-    int diag_step = 0;
-#endif
     auto one_step = [&](const float* __restrict__ Gs, float* __restrict__ Gd) {
-#if defined(WM_INNER_DIAG)
-      const unsigned long long d0 = __builtin_amdgcn_s_memtime();
-#endif
       const float app = Gs[dp], aqq = Gs[dq], apq = Gs[k2 * PITCH + cq];
       float g[INNER_NB][4];
 #pragma unroll
       for (int i = 0; i < INNER_NB; ++i) {
         g[i][0] = Gs[rp_[i] + k2]; g[i][1] = Gs[rp_[i] + cq]; g[i][2] = Gs[rq_[i] + k2]; g[i][3] = Gs[rq_[i] + cq];
       }
-#if defined(WM_INNER_DIAG)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const unsigned long long d1 = __builtin_amdgcn_s_memtime();
-#endif
       const float tau = aqq - app, g2 = apq + apq;
       const float ta = fabsf(tau) + 1e-18f;
       const float ih = __builtin_amdgcn_rsqf(fmaf(g2, g2, ta * ta));
@@ -564,25 +618,12 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
       dq = wc ? RB * (PITCH + 1) : dq + (PITCH + 1);
 #pragma unroll
       for (int i = 0; i < INNER_NB; ++i) rq_[i] = (rq_[i] == (RP - 1) * PITCH) ? RB * PITCH : rq_[i] + PITCH;
-#if defined(WM_INNER_DIAG)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const unsigned long long d2 = __builtin_amdgcn_s_memtime();
-#endif
       __syncthreads();
-#if defined(WM_INNER_DIAG)
-      if (diag_step++ == 7 && t == 0 && p == 1 && blockIdx.z == 0) {
-        const unsigned long long d3 = __builtin_amdgcn_s_memtime();
-        printf("inner step diag: reads %llu  angle+update+writes+bpermute %llu  barrier %llu cycles\n", d1 - d0, d2 - d1, d3 - d2);
-      }
-#endif
     };
     for (int it = 0; it < RB / 2; ++it) {      // G starts in buffer 0 and is back there after an even number of steps
       one_step(gbuf0, gbuf1);
       one_step(gbuf1, gbuf0);
     }
-#if defined(WM_INNER_DIAG)
-    st3 = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
     for (int j = 0; j < 2 * INNER_NB; ++j) {
       const int r = kr + INNER_KR * j;
@@ -592,28 +633,19 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
       if (rpk) { put_r(r, k2, ri[j]); put_r(r, RB + k2, rj[j]); }
     }
     if (h_units) writeback(gbuf0);             // 32 steps: the result is back in buffer 0, behind the last step's barrier
-#if defined(WM_INNER_DIAG)
-    __syncthreads();
-    if (t == 0 && p == 1 && blockIdx.z == 0) {
-      const unsigned long long st4 = __builtin_amdgcn_s_memtime();
-      printf("inner diag (cross, R in registers): load %llu maxcos %llu loop %llu (%llu per step) store %llu cycles\n", st1 - st0,
-             st2 - st1, st3 - st2, (st3 - st2) / 32ull, st4 - st3);
-    }
-#endif
     return;
   }
+  // not cross_only from here on: the full 63-step round-robin schedule over the pair's 64 rows, R through LDS
   for (int step = 0; step < n_inner; ++step) {
     float (*Gn)[RP + 1] = GG[(step + 1) & 1];
-    // ---- indices of this step's pairs (cross_only: block-I row k with block-J row (k + step) mod 32) ----
-    const int a2 = cross_only ? k2 : rr_elem(k2, step);
-    const int b2 = cross_only ? RB + ((k2 + step) & (RB - 1)) : rr_elem(RP - 1 - k2, step);
+    // ---- indices of this step's pairs ----
+    const int a2 = rr_elem(k2, step), b2 = rr_elem(RP - 1 - k2, step);
     const int p2 = min(a2, b2), q2 = max(a2, b2);
     int p1[INNER_NB], q1[INNER_NB];
 #pragma unroll
     for (int i = 0; i < INNER_NB; ++i) {
       const int k1 = kr + INNER_KR * i;
-      const int a1 = cross_only ? k1 : rr_elem(k1, step);
-      const int b1 = cross_only ? RB + ((k1 + step) & (RB - 1)) : rr_elem(RP - 1 - k1, step);
+      const int a1 = rr_elem(k1, step), b1 = rr_elem(RP - 1 - k1, step);
       p1[i] = min(a1, b1); q1[i] = max(a1, b1);
     }
     // ---- every LDS read of the step, issued before the angle arithmetic ----
@@ -666,22 +698,11 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
     __syncthreads();
     G = Gn;
   }
-#if defined(WM_INNER_DIAG)
-  st3 = __builtin_amdgcn_s_memtime();
-#endif
   for (int e = t; e < RP * RP; e += INNER_NT) {
     out[h_units ? pk_index(e >> 6, e & 63) : e] = R[e >> 6][e & 63];
     if (rpk) put_r(e >> 6, e & 63, R[e >> 6][e & 63]);
   }
   if (h_units) writeback(&G[0][0]);
-#if defined(WM_INNER_DIAG)
-  __syncthreads();
-  if (t == 0 && p == 1 && blockIdx.z == 0) {
-    const unsigned long long st4 = __builtin_amdgcn_s_memtime();
-    printf("inner diag: load %llu maxcos %llu loop %llu (%d steps, %llu per step) store %llu cycles\n", st1 - st0, st2 - st1,
-           st3 - st2, n_inner, (st3 - st2) / (unsigned long long)n_inner, st4 - st3);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -694,8 +715,6 @@ __global__ __launch_bounds__(INNER_NT) void k_rf_inner(const float* __restrict__
 // load), takes the A operands R[2m + h][i0 + j] from the LDS copy of R, and accumulates both row
 // halves (i0 = 0, 32) in 2 x 16 accumulator registers: 64 MFMAs per block, no LDS traffic for X,
 // in place (the block is fully in registers before the first store).
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(256) void k_rf_apply(float* __restrict__ aug, const size_t aug_plane_stride,
                                                  const int ld, const int ncols, const int blocks_per_wave,
                                                  const int2* __restrict__ pairs, const float* __restrict__ Rall,
@@ -741,7 +760,7 @@ __global__ __launch_bounds__(256) void k_rf_apply(float* __restrict__ aug, const
       float* oy = aug + (size_t)(pr.y * RB) * ld + col;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int i = 8 * (v / 4) + 4 * h + (v % 4);     // accumulator register v, lane half h -> output row
+        const int i = ACC_ROW(v, h, 0);
         ox[(size_t)i * ld] = acc0[v];
         oy[(size_t)i * ld] = acc1[v];
       }
@@ -943,7 +962,7 @@ struct RefPlan {
 // the start of the call that uses them: tests switch WM_RF_HIER*, WM_RF_QUEUES, WM_RF_HGRAM3 and WM_RF_FINAL_F16 between
 // calls on one context - except the three marked "process", which keep what the first call saw.
 struct RefKnobs {
-  int apply_tiles, full_sweeps, queues, hier, hier_f16, hier_sb, hgram3, hdbg;
+  int apply_tiles, full_sweeps, queues, hier, hier_f16, hier_sb, hgram3;
   float conv_sigma;
   bool drift_cal, debug_drift, final_f16;
 };
@@ -966,7 +985,6 @@ RefKnobs ref_knobs() {
   k.hier_sb = num("WM_RF_HIER_SB", 6);                          // 2, 4 or 6 blocks per super-block
   if (k.hier_sb != 2 && k.hier_sb != 4 && k.hier_sb != 6) k.hier_sb = 6;
   k.hgram3 = flag("WM_RF_HGRAM3");                              // 0 / 1: never / always k_hgram_h3 where it applies; unset: where it fills the chip
-  k.hdbg = num("WM_RF_HDBG", 0);                                // debug bits handed to k_hgram and (from bit 4) k_happly
   k.final_f16 = flag("WM_RF_FINAL_F16") != 0;                   // 0 keeps the finalisation's large products in f32
   return k;
 }
@@ -1209,16 +1227,16 @@ int hier_sweep(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiRun& r
       const bool use_h3 = r.gram_f16 && npmax == 3 && h3;     // (its column splits weigh more: every split writes the whole upper triangle - 2.0 against 0.25: +2 % at 64 and 128 planes)
       const int KS = hier_ks(nsp, nz, use_h3 ? 1 : npmax, nchunk, hw.KS, use_h3 ? 2.0 : 0.25), cps = (nchunk + KS - 1) / KS;
       const int ngrp = nsp * KS * nz;               // (super-pair, split, plane) groups of npmax workgroups, dealt over the XCDs
-      // Gram tiles on the f16 matrix pipe with split operands (k_hgram_h; WM_RF_HIER_F16=0: the f32 form)
+      // Gram tiles on the f16 matrix pipe with split operands (k_hgram_t<true>; WM_RF_HIER_F16=0: the f32 instance)
       if (use_h3)                                     // three panels: the rows fetched once per chunk (k_hgram_h3)
         hipLaunchKernelGGL(k_hgram_h3, dim3(((ngrp + 7) / 8) * 8), dim3(H3_NT), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
                            par, KS, cps, nz);
       else if (r.gram_f16)
-        hipLaunchKernelGGL(k_hgram_h, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
+        hipLaunchKernelGGL(k_hgram_t<true>, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
                            par, KS, cps, npmax, nz);
       else
-        hipLaunchKernelGGL(k_hgram, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
-                           par, KS, cps, npmax, nz, r.k.hdbg);
+        hipLaunchKernelGGL(k_hgram_t<false>, dim3(((ngrp + 7) / 8) * 8 * npmax), dim3(512), 0, st, aug, p.aug_ps, p.ld, p.M, sup, nsp,
+                           par, KS, cps, npmax, nz);
       hipLaunchKernelGGL(k_hreduce, dim3(HSB * (HSB + 1) / 2, nsp, nz), dim3(256), 0, st, par, sup, nsp, KS, Gs, anyrot);
       constexpr int NG = HU * (HU - 1) / 2;
       const int T = ht->T[s1];
@@ -1234,10 +1252,10 @@ int hier_sweep(wm_ctx* ctx, const RefPlan& p, const RefWs& w, const JacobiRun& r
       const int ntask = nsp * nz * ((r.ncols + 63) / 64);
       if (r.apply_f16)
         hipLaunchKernelGGL((k_happly_h<64>), dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)2 * 64 * HA_CP * 2, st, aug, p.aug_ps, p.ld,
-                           r.ncols, sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, r.k.hdbg >> 4);
+                           r.ncols, sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot);
       else
         hipLaunchKernelGGL(k_happly, dim3(8 * ((ntask + 7) / 8)), dim3(64 * ht->nmax), (size_t)n32 * 65 * 4, st, aug, p.aug_ps, p.ld, r.ncols,
-                           sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot, r.k.hdbg >> 4);
+                           sup, nsp, nz, un0, T, Rpk, skipT, rpk_stage, skip_stage, anyrot);
     }
   return WM_OK;
 }

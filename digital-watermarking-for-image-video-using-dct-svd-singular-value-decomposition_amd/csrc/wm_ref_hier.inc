@@ -4,7 +4,7 @@
 // times per step, 99 passes per sweep at 1080p, and runs at the memory system's speed (profiles/r04_a_fullframe_*).
 // Here the 32-row blocks are grouped into SUPER-BLOCKS of up to 6; a level-1 tournament step pairs super-blocks, and
 // for each super-pair (n <= 12 blocks, <= 384 rows X_s):
-//   1. k_hgram + k_hreduce   G_s = X_s X_s^T  (one read of the rows, 128 x 128 MFMA tiles, split over column ranges)
+//   1. k_hgram_t + k_hreduce  G_s = X_s X_s^T  (one read of the rows, 128 x 128 MFMA tiles, split over column ranges)
 //   2. stages of a sub-tournament among the n blocks (all of them in the first step of a sweep, the bipartite
 //      cross pairs afterwards): k_rf_inner reads each block pair's 64 x 64 Gram matrix straight out of G_s, solves it
 //      and writes the rotated diagonal block back (and R, also in the order k_happly consumes it); k_hupdate keeps the
@@ -28,7 +28,7 @@ __device__ __forceinline__ int hg_tile_i(const int tile) { return (tile == 0 || 
 __device__ __forceinline__ int hg_tile_j(const int tile) { return tile == 0 ? 0 : tile <= 2 ? 1 : 2; }
 __device__ __forceinline__ int hg_tile_of(const int ti, const int tj) { return tj == 0 ? 0 : tj == 1 ? 1 + ti : 3 + ti; }
 
-typedef float v16f_h __attribute__((ext_vector_type(16)));
+constexpr int CU_LDS_BYTES = 160 * 1024;      // LDS of one CU (gfx950)
 
 // ---------------------------------------------------------------------------
 // partial[z][sp][tile][ks] = X_a X_b^T over the column range of split ks; X_a / X_b = 128-row panels of super-pair sp.
@@ -39,21 +39,53 @@ typedef float v16f_h __attribute__((ext_vector_type(16)));
 // load (a CU takes 5 - 10 B/clk from beyond L2), so the first version - one 128 x 128 tile per 256-thread workgroup,
 // 1 152 staged rows per group - spent 7 000 of a chunk's 12 000 cycles issuing its loads; here a chunk's loads are 4 per
 // thread for 64 MFMAs per wave, spread over the MFMA steps.
-// LDS image k-major ([k][row], pitch 257: operand reads of 32 consecutive rows are conflict-free), double-buffered.
+// One matrix-core chain per workgroup column range (<= a few hundred columns); k_hreduce adds the ranges on the VALU, so the
+// accumulation is two-level like the flat kernel's.
+// F16 selects the LDS image, the stash and the MFMA group; everything else is one skeleton:
+//  * f32 (float inputs, WM_RF_HIER_F16 bit 0 clear): image k-major ([k][row], pitch 257: operand reads of 32 consecutive rows
+//    are conflict-free), v_mfma_f32_32x32x2_f32, the next chunk's loads one every four MFMA steps;
+//  * split f16 (the default for uint8 planes): x = hi + lo (split4_f16; 22 significant bits together), X_a X_b^T ~ hi hi^T +
+//    hi lo^T + lo hi^T accumulated in f32 - three v_mfma_f32_32x32x16_f16 (32 cycles, 16 values of k each) where the f32 form
+//    issues eight v_mfma_f32_32x32x2_f32 (64 cycles, 2 values of k each): 5.3 x fewer matrix-pipe cycles.  What is dropped
+//    (lo lo^T, and lo itself for |x| < 0.125 where it is an f16 denormal) is below 2^-22 of the products' magnitude: the Gram
+//    entries only steer the rotations, and every row entry is bounded by 255 sqrt(L) < 65 504 (f16's range) up to 8K planes
+//    because the rotations are orthogonal.  Rows are converted once, while they are staged: the image is row-major f16
+//    ([row][k], pitch 40 halfs = 80 bytes: a lane's 16-byte operand reads are conflict-free), two loads per MFMA step.
+// Both images are double-buffered (one barrier per chunk).
+// Reproducibility: ONE workgroup of the f16 form per CU, enforced by its LDS footprint (84.5 KB with the padding rows): with
+// two of them co-resident (a single-image form, 40 KB each, was 2 % faster) G_s differed from run to run at 1080p - sigma off
+// by up to 7e-5 sigma_1, 13 or 14 sweeps - although they share no LDS and write disjoint partial sums; neither an extra
+// barrier per chunk nor 96 instead of 126 VGPRs changed that, one workgroup per CU is bit-reproducible (HISTORY.md).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void k_hgram(const float* __restrict__ aug, const size_t aug_ps, const int ld, const int M,
-                                              const HSuper* __restrict__ supers, const int nsp, float* __restrict__ partials,
-                                              const int KS, const int cps, const int npmax, const int nz, const int dbg) {
-  __shared__ float S[2][HG_KC][2 * HG_T + 1];
+constexpr int HG_HP = 40;                     // halfs per row of the f16 image (32 + 8 of padding)
+constexpr int HG_NB = 2;                      // LDS images in flight
+constexpr int HG_PADROWS = 8;                 // rows of the f16 image that only hold its footprint above half a CU's LDS
+
+template <bool F16>
+__global__ __launch_bounds__(512, 1) void k_hgram_t(const float* __restrict__ aug, const size_t aug_ps, const int ld, const int M,
+                                                    const HSuper* __restrict__ supers, const int nsp, float* __restrict__ partials,
+                                                    const int KS, const int cps, const int npmax, const int nz) {
+  // the image of the instance's form (the other form's arrays shrink to one unused element and take no LDS)
+  __shared__ float S[F16 ? 1 : HG_NB][F16 ? 1 : HG_KC][F16 ? 1 : 2 * HG_T + 1];
+  __shared__ __attribute__((aligned(16))) _Float16 Sh[F16 ? HG_NB : 1][F16 ? 2 * HG_T + HG_PADROWS : 1][F16 ? HG_HP : 8];
+  __shared__ __attribute__((aligned(16))) _Float16 Sl[F16 ? HG_NB : 1][F16 ? 2 * HG_T + HG_PADROWS : 1][F16 ? HG_HP : 8];
+  static_assert(!F16 || (sizeof(Sh) + sizeof(Sl) == 84480 && 2 * (sizeof(Sh) + sizeof(Sl)) > CU_LDS_BYTES),
+                "two workgroups of the f16 form must not fit one CU: co-resident they are not bit-reproducible");
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, j = lane & 31, h = lane >> 5;
-  // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share an L2 - observed placement,
-  // speed only), so id -> (xcd = id % 8, q = id / 8): the workgroups of one (super-pair, plane, split) - which read
-  // the same row panels - are consecutive on ONE XCD and meet in its L2.
-  const int id = blockIdx.x, xcd = id & 7, q = id >> 3;
-  const int w = q % npmax, grp = (q / npmax) * 8 + xcd;
-  const int ngrp = nsp * KS * nz;
-  if (grp >= ngrp) return;
-  const int sp = grp % nsp, ks = (grp / nsp) % KS, zl = grp / (nsp * KS);
+  int w, sp, ks, zl;
+  const int grp = xcd_group(blockIdx.x, npmax, w);
+  if (grp >= nsp * KS * nz) return;
+  group_decode(grp, nsp, KS, sp, ks, zl);
+  // the block numbers of this thread's rows, fetched together with the super-pair's size (panel pb = (w + 1) % np is w + 1 or 0:
+  // both candidates are read) - one round trip to L2 in front of the row loads instead of two
+  const int bsel = (t >> 8);             // rows (t >> 3) + 64 i of a panel lie in block 4 panel + (t >> 8) + 2 i
+  int blk_a[2], blk_b1[2], blk_b0[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    blk_a[i] = supers[sp].blk[min(4 * w + bsel + 2 * i, HSB - 1)];
+    blk_b1[i] = supers[sp].blk[min(4 * (w + 1) + bsel + 2 * i, HSB - 1)];
+    blk_b0[i] = supers[sp].blk[bsel + 2 * i];
+  }
   const int n = supers[sp].n, n32 = n * RB;
   const int np = (n32 + HG_T - 1) / HG_T;                  // panels of this super-pair
   if (w >= np) return;
@@ -67,52 +99,78 @@ __global__ __launch_bounds__(512) void k_hgram(const float* __restrict__ aug, co
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = (t >> 3) + 64 * (i & 1), lr = HG_T * (i < 2 ? pa : pb) + r;
-    rowp[i] = ((i < 2 || second) && lr < n32) ? aug + (size_t)(supers[sp].blk[lr >> 5] * RB + (lr & 31)) * ld : nullptr;
+    const int bk = i < 2 ? blk_a[i & 1] : (pb == 0 ? blk_b0[i & 1] : blk_b1[i & 1]);
+    rowp[i] = ((i < 2 || second) && lr < n32) ? aug + (size_t)(bk * RB + (lr & 31)) * ld : nullptr;
   }
   const int cq = 4 * (t & 7);
   float4 rr[4];
   auto fetch1 = [&](const int c, const int i) {            // one of the 4 loads of chunk c
     const int col = c * HG_KC + cq;                        // col + 3 < ld always (ld >= M + 64)
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (rowp[i] && !(dbg & 2)) v = *reinterpret_cast<const float4*>(rowp[i] + col);
-    if (col + 3 >= M) { if (col >= M) v.x = 0.0f; if (col + 1 >= M) v.y = 0.0f; if (col + 2 >= M) v.z = 0.0f; v.w = 0.0f; }
+    if (rowp[i]) v = *reinterpret_cast<const float4*>(rowp[i] + col);
+    MASK_TAIL4(v, col, M);
     rr[i] = v;
   };
   auto stash = [&](const int buf) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = (t >> 3) + 64 * i;
-      S[buf][cq][r] = rr[i].x; S[buf][cq + 1][r] = rr[i].y; S[buf][cq + 2][r] = rr[i].z; S[buf][cq + 3][r] = rr[i].w;
+      if constexpr (F16) {
+        uint2 hi, lo;
+        split4_f16(rr[i], hi, lo);
+        *reinterpret_cast<uint2*>(&Sh[buf][r][cq]) = hi;
+        *reinterpret_cast<uint2*>(&Sl[buf][r][cq]) = lo;
+      } else {
+        S[buf][cq][r] = rr[i].x; S[buf][cq + 1][r] = rr[i].y; S[buf][cq + 2][r] = rr[i].z; S[buf][cq + 3][r] = rr[i].w;
+      }
     }
   };
   const int tsel = wv >> 2, wi = (wv >> 1) & 1, wj = wv & 1;
   const bool idle = (tsel == 0 && wi == 1 && wj == 0) || (tsel == 1 && !second);   // mirrored quadrant of the diagonal tile / no second tile
-  // One matrix-core chain per workgroup column range (<= a few hundred columns); k_hreduce adds the ranges on the VALU, so the
-  // accumulation is two-level like the flat kernel's.
-  v16f_h acc[2][2];
+  v16f acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = v16f_h{0};
+    for (int b = 0; b < 2; ++b) acc[a][b] = v16f{0};
   if (c_begin < c_end) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) fetch1(c_begin, i);
   }
   int buf = 0;
-  for (int c = c_begin; c < c_end; ++c, buf ^= 1) {
+  for (int c = c_begin; c < c_end; ++c, buf = (buf + 1) % HG_NB) {
     stash(buf);
     const bool more = c + 1 < c_end;
-    if (more && (idle || (dbg & 1))) {
+    if (more && idle) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) fetch1(c + 1, i);
     }
     __syncthreads();
-    if (!idle && !(dbg & 1)) {
+    if (idle) continue;
+    // the next chunk's loads are spread over this chunk's MFMA steps
+    if constexpr (F16) {
+      const int ra = 64 * wi + j, rb = HG_T * tsel + 64 * wj + j;
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {                 // two MFMA steps of 16 values of k; lane half h takes 8 of them
+        if (more) { fetch1(c + 1, 2 * s2); fetch1(c + 1, 2 * s2 + 1); }
+        h8_t ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+          ah[x] = *reinterpret_cast<const h8_t*>(&Sh[buf][ra + 32 * x][16 * s2 + 8 * h]);
+          al[x] = *reinterpret_cast<const h8_t*>(&Sl[buf][ra + 32 * x][16 * s2 + 8 * h]);
+          bh[x] = *reinterpret_cast<const h8_t*>(&Sh[buf][rb + 32 * x][16 * s2 + 8 * h]);
+          bl[x] = *reinterpret_cast<const h8_t*>(&Sl[buf][rb + 32 * x][16 * s2 + 8 * h]);
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) mfma3_f16(ah[a], al[a], bh[b], bl[b], acc[a][b]);
+      }
+    } else {
       const float* pA = &S[buf][h][64 * wi + j];
       const float* pB = &S[buf][h][HG_T * tsel + 64 * wj + j];
 #pragma unroll
       for (int kk = 0; kk < HG_KC / 2; ++kk) {
-        if (more && (kk & 3) == 0) fetch1(c + 1, kk >> 2);                   // the next chunk's loads, one every four MFMA steps
+        if (more && (kk & 3) == 0) fetch1(c + 1, kk >> 2);
         const float a0 = pA[2 * kk * (2 * HG_T + 1)], a1 = pA[2 * kk * (2 * HG_T + 1) + 32];
         const float b0 = pB[2 * kk * (2 * HG_T + 1)], b1 = pB[2 * kk * (2 * HG_T + 1) + 32];
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
@@ -133,174 +191,19 @@ __global__ __launch_bounds__(512) void k_hgram(const float* __restrict__ aug, co
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int row = 64 * wi + 32 * a + 8 * (v / 4) + 4 * h + (v % 4), col = 64 * wj + 32 * b + j;
+        const int row = ACC_ROW(v, h, 64 * wi + 32 * a), col = 64 * wj + 32 * b + j;
         out[tr ? col * HG_T + row : row * HG_T + col] = acc[a][b][v];
       }
 }
 
 // ---------------------------------------------------------------------------
-// The same Gram tiles on the f16 matrix pipe with split operands: x = hi + lo, hi = f16(x), lo = f16(x - hi) (22 significant
-// bits together), X_a X_b^T ~ hi hi^T + hi lo^T + lo hi^T accumulated in f32 - three v_mfma_f32_32x32x16_f16 (32 cycles, 16
-// values of k each) where the f32 form issues eight v_mfma_f32_32x32x2_f32 (64 cycles, 2 values of k each): 5.3 x fewer
-// matrix-pipe cycles.  What is dropped (lo lo^T, and lo itself for |x| < 0.125 where it is an f16 denormal) is below 2^-22
-// of the products' magnitude: the Gram entries only steer the rotations, and every row entry is bounded by 255 sqrt(L) <
-// 65 504 (f16's range) up to 8K planes because the rotations are orthogonal.  Rows are converted once, while they are staged:
-// the LDS image is row-major f16 ([row][k], pitch 40 halfs = 80 bytes: a lane's 16-byte operand reads are conflict-free).
-// ---------------------------------------------------------------------------
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split4_f16(const float4 v, uint2& hi, uint2& lo) {
-  const h2_t a = {(_Float16)v.x, (_Float16)v.y}, b = {(_Float16)v.z, (_Float16)v.w};
-  const h2_t la = {(_Float16)(v.x - (float)a[0]), (_Float16)(v.y - (float)a[1])};
-  const h2_t lb = {(_Float16)(v.z - (float)b[0]), (_Float16)(v.w - (float)b[1])};
-  hi = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
-  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
-
-constexpr int HG_HP = 40;                     // halfs per row of the f16 image (32 + 8 of padding)
-#ifndef WM_HGRAM_BUFS
-#define WM_HGRAM_BUFS 2                       // LDS images in flight (2 = double-buffered, one barrier per chunk)
-#endif
-// One workgroup of this kernel per CU, enforced by its LDS footprint (84.5 KB with the padding rows): with two of them
-// co-resident (the single-image form, 40 KB each, was 2 % faster) G_s differed from run to run at 1080p - sigma off by up to
-// 7e-5 sigma_1, 13 or 14 sweeps - although they share no LDS and write disjoint partial sums; neither an extra barrier per
-// chunk nor 96 instead of 126 VGPRs changed that, one workgroup per CU is bit-reproducible (tools/README.md, HISTORY.md).
-#ifndef WM_HGRAM_PADROWS
-#define WM_HGRAM_PADROWS 8
-#endif
-constexpr int HG_NB = WM_HGRAM_BUFS;
-
-#ifndef WM_HGRAM_LB
-#define WM_HGRAM_LB (3 - HG_NB)
-#endif
-__global__ __launch_bounds__(512, WM_HGRAM_LB) void k_hgram_h(const float* __restrict__ aug, const size_t aug_ps, const int ld, const int M,
-                                                const HSuper* __restrict__ supers, const int nsp, float* __restrict__ partials,
-                                                const int KS, const int cps, const int npmax, const int nz) {
-  __shared__ __attribute__((aligned(16))) _Float16 Sh[HG_NB][2 * HG_T + WM_HGRAM_PADROWS][HG_HP];
-  __shared__ __attribute__((aligned(16))) _Float16 Sl[HG_NB][2 * HG_T + WM_HGRAM_PADROWS][HG_HP];
-#if defined(WM_POISON_LDS)
-  for (int i = threadIdx.x; i < HG_NB * (2 * HG_T + WM_HGRAM_PADROWS) * HG_HP; i += 512) { (&Sh[0][0][0])[i] = __builtin_bit_cast(_Float16, (unsigned short)0x7e00); (&Sl[0][0][0])[i] = __builtin_bit_cast(_Float16, (unsigned short)0x7e00); }
-  __syncthreads();
-#endif
-  const int t = threadIdx.x, wv = t >> 6, lane = t & 63, j = lane & 31, h = lane >> 5;
-  const int id = blockIdx.x, xcd = id & 7, q = id >> 3;     // XCD-aware order, as in k_hgram
-  const int w = q % npmax, grp = (q / npmax) * 8 + xcd;
-  const int ngrp = nsp * KS * nz;
-  if (grp >= ngrp) return;
-  const int sp = grp % nsp, ks = (grp / nsp) % KS, zl = grp / (nsp * KS);
-  // the block numbers of this thread's rows, fetched together with the super-pair's size (panel pb = (w + 1) % np is w + 1 or 0:
-  // both candidates are read) - one round trip to L2 in front of the row loads instead of two
-  const int bsel = (t >> 8);             // rows (t >> 3) + 64 i of a panel lie in block 4 panel + (t >> 8) + 2 i
-  int blk_a[2], blk_b1[2], blk_b0[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    blk_a[i] = supers[sp].blk[min(4 * w + bsel + 2 * i, HSB - 1)];
-    blk_b1[i] = supers[sp].blk[min(4 * (w + 1) + bsel + 2 * i, HSB - 1)];
-    blk_b0[i] = supers[sp].blk[bsel + 2 * i];
-  }
-  const int n = supers[sp].n, n32 = n * RB;
-  const int np = (n32 + HG_T - 1) / HG_T;
-  if (w >= np) return;
-  const int pa = w, pb = (w + 1) % np;
-  const bool second = np == 3 || (np == 2 && w == 0);
-  aug += (size_t)zl * aug_ps;
-  const int nchunk = (M + HG_KC - 1) / HG_KC;
-  const int c_begin = ks * cps, c_end = min(nchunk, c_begin + cps);
-  const float* rowp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (t >> 3) + 64 * (i & 1), lr = HG_T * (i < 2 ? pa : pb) + r;
-    const int bk = i < 2 ? blk_a[i & 1] : (pb == 0 ? blk_b0[i & 1] : blk_b1[i & 1]);
-    rowp[i] = ((i < 2 || second) && lr < n32) ? aug + (size_t)(bk * RB + (lr & 31)) * ld : nullptr;
-  }
-  const int cq = 4 * (t & 7);
-  float4 rr[4];
-  auto fetch1 = [&](const int c, const int i) {
-    const int col = c * HG_KC + cq;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (rowp[i]) v = *reinterpret_cast<const float4*>(rowp[i] + col);
-    if (col + 3 >= M) { if (col >= M) v.x = 0.0f; if (col + 1 >= M) v.y = 0.0f; if (col + 2 >= M) v.z = 0.0f; v.w = 0.0f; }
-    rr[i] = v;
-  };
-  auto stash = [&](const int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = (t >> 3) + 64 * i;
-      uint2 hi, lo;
-      split4_f16(rr[i], hi, lo);
-      *reinterpret_cast<uint2*>(&Sh[buf][r][cq]) = hi;
-      *reinterpret_cast<uint2*>(&Sl[buf][r][cq]) = lo;
-    }
-  };
-  const int tsel = wv >> 2, wi = (wv >> 1) & 1, wj = wv & 1;
-  const bool idle = (tsel == 0 && wi == 1 && wj == 0) || (tsel == 1 && !second);
-  v16f_h acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = v16f_h{0};
-  if (c_begin < c_end) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fetch1(c_begin, i);
-  }
-  int buf = 0;
-  for (int c = c_begin; c < c_end; ++c, buf = (buf + 1) % HG_NB) {
-    if (HG_NB == 1 && c > c_begin) __syncthreads();      // single image: the previous chunk's operand reads are done
-    stash(buf);
-    const bool more = c + 1 < c_end;
-    if (more && idle) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fetch1(c + 1, i);
-    }
-    __syncthreads();
-    if (!idle) {
-      const int ra = 64 * wi + j, rb = HG_T * tsel + 64 * wj + j;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {                 // two MFMA steps of 16 values of k; lane half h takes 8 of them
-        if (more) { fetch1(c + 1, 2 * s2); fetch1(c + 1, 2 * s2 + 1); }
-        h8_t ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-          ah[x] = *reinterpret_cast<const h8_t*>(&Sh[buf][ra + 32 * x][16 * s2 + 8 * h]);
-          al[x] = *reinterpret_cast<const h8_t*>(&Sl[buf][ra + 32 * x][16 * s2 + 8 * h]);
-          bh[x] = *reinterpret_cast<const h8_t*>(&Sh[buf][rb + 32 * x][16 * s2 + 8 * h]);
-          bl[x] = *reinterpret_cast<const h8_t*>(&Sl[buf][rb + 32 * x][16 * s2 + 8 * h]);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bh[b], acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bl[b], acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[a], bh[b], acc[a][b], 0, 0, 0);
-          }
-      }
-    }
-  }
-  if (idle) return;
-  const int ta = tsel == 0 ? pa : min(pa, pb), tb = tsel == 0 ? pa : max(pa, pb);
-  const bool tr = tsel == 1 && pa > pb;
-  float* out = partials + ((((size_t)zl * nsp + sp) * HG_TILES + hg_tile_of(ta, tb)) * KS + ks) * (HG_T * HG_T);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = 64 * wi + 32 * a + 8 * (v / 4) + 4 * h + (v % 4), col = 64 * wj + 32 * b + j;
-        out[tr ? col * HG_T + row : row * HG_T + col] = acc[a][b][v];
-      }
-}
-
-// ---------------------------------------------------------------------------
-// k_hgram_h for super-pairs of three panels (more than 256 rows): ONE workgroup per (super-pair, plane, split) stages all
+// The split-f16 Gram tiles for super-pairs of three panels (more than 256 rows): ONE workgroup per (super-pair, plane, split) stages all
 // <= 384 rows of a 32-column chunk once and computes the whole upper triangle of G_s from them - 78 blocks of 32 x 32, six or
 // seven per wave (768 threads), each one accumulator tile.  The two-panel form loads every panel twice (three workgroups x 256
 // rows for the same six tiles) and is bound by what a CU can fetch (10 B/clk): here the rows are fetched once.
 // LDS: the split image [384][40] halfs x 2 (hi, lo), double-buffered: 123 KB - one workgroup per CU (see the note on
-// reproducibility above k_hgram_h).  A wave's blocks are consecutive in row-major order, so most of them share their row block
-// (the A operand is re-read only when it changes).  Same partial-sum layout as k_hgram_h (k_hreduce reads either).
+// reproducibility above k_hgram_t).  A wave's blocks are consecutive in row-major order, so most of them share their row block
+// (the A operand is re-read only when it changes).  Same partial-sum layout as k_hgram_t (k_hreduce reads either).
 // ---------------------------------------------------------------------------
 constexpr int H3_NT = 768, H3_NW = H3_NT / 64, H3_TASKS = HSB * (HSB + 1) / 2, H3_TPW = (H3_TASKS + H3_NW - 1) / H3_NW;
 
@@ -309,11 +212,12 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
                                                    const int KS, const int cps, const int nz) {
   __shared__ __attribute__((aligned(16))) _Float16 Sh[2][HN][HG_HP];
   __shared__ __attribute__((aligned(16))) _Float16 Sl[2][HN][HG_HP];
+  static_assert(sizeof(Sh) + sizeof(Sl) == 122880 && 2 * (sizeof(Sh) + sizeof(Sl)) > CU_LDS_BYTES, "one workgroup per CU, like k_hgram_t<true>");
   const int t = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, j = lane & 31, h = lane >> 5;
-  const int id = blockIdx.x, xcd = id & 7, q = id >> 3;
-  const int grp = q * 8 + xcd, ngrp = nsp * KS * nz;
-  if (grp >= ngrp) return;
-  const int sp = grp % nsp, ks = (grp / nsp) % KS, zl = grp / (nsp * KS);
+  int w, sp, ks, zl;                     // (one workgroup per group: w = 0)
+  const int grp = xcd_group(blockIdx.x, 1, w);
+  if (grp >= nsp * KS * nz) return;
+  group_decode(grp, nsp, KS, sp, ks, zl);
   // this thread's four rows of the image, (t >> 3) + 96 i: their block numbers fetched together with the super-pair's size
   int blk[4];
 #pragma unroll
@@ -334,7 +238,7 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
     const int col = c * HG_KC + cq;
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (rowo[i] >= 0) v = *reinterpret_cast<const float4*>(aug + (size_t)rowo[i] + col);
-    if (col + 3 >= M) { if (col >= M) v.x = 0.0f; if (col + 1 >= M) v.y = 0.0f; if (col + 2 >= M) v.z = 0.0f; v.w = 0.0f; }
+    MASK_TAIL4(v, col, M);
     rr[i] = v;
   };
   auto stash = [&](const int buf) {
@@ -360,9 +264,9 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
       if (++bc == HSB) { ++br; bc = br; }
     }
   }
-  v16f_h acc[H3_TPW];
+  v16f acc[H3_TPW];
 #pragma unroll
-  for (int k = 0; k < H3_TPW; ++k) acc[k] = v16f_h{0};
+  for (int k = 0; k < H3_TPW; ++k) acc[k] = v16f{0};
   if (c_begin < c_end) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) fetch1(c_begin, i);
@@ -390,9 +294,7 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
         }
         const h8_t bh = *reinterpret_cast<const h8_t*>(&Sh[buf][32 * cb[k] + j][16 * s2 + 8 * h]);
         const h8_t bl = *reinterpret_cast<const h8_t*>(&Sl[buf][32 * cb[k] + j][16 * s2 + 8 * h]);
-        acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[k], 0, 0, 0);
-        acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[k], 0, 0, 0);
-        acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[k], 0, 0, 0);
+        mfma3_f16(ah, al, bh, bl, acc[k]);
       }
     }
   }
@@ -402,12 +304,12 @@ __global__ __launch_bounds__(H3_NT) void k_hgram_h3(const float* __restrict__ au
     if (k >= cnt || cb[k] >= n) continue;
     float* out = base + (size_t)hg_tile_of(rb[k] / 4, cb[k] / 4) * KS * (HG_T * HG_T) + ((rb[k] % 4) * 32) * HG_T + (cb[k] % 4) * 32;
 #pragma unroll
-    for (int v = 0; v < 16; ++v) out[(8 * (v / 4) + 4 * h + (v % 4)) * HG_T + j] = acc[k][v];
+    for (int v = 0; v < 16; ++v) out[ACC_ROW(v, h, 0) * HG_T + j] = acc[k][v];
   }
 }
 
 // ---------------------------------------------------------------------------
-// The finalisation's two large products on the f16 matrix pipe, operands split like k_hgram_h's (x = hi + lo):
+// The finalisation's two large products on the f16 matrix pipe, operands split like the Gram kernels' (split4_f16):
 //   C[M][N] (+)= alpha A[M][K] op(B),   op(B) = B[N][K]^T (TB) or B[K][N],   batched over grid.z.
 //   T = A0 B^T   (single:172's U and sigma measured on the input, fetch_norms_t): A0 holds the uint8 samples - exact in f16,
 //                no lo part (A_EXACT: two products per tile step instead of three);
@@ -499,11 +401,11 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
     }
   };
   const int wi = wv >> 1, wj = wv & 1;
-  v16f_h acc[2][2];
+  v16f acc[2][2];
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = v16f_h{0};
+    for (int y = 0; y < 2; ++y) acc[x][y] = v16f{0};
   fetch(0);
   for (int k0 = 0; k0 < K; k0 += KC) {
     if (k0 > 0) __syncthreads();         // the previous chunk's operand reads are done
@@ -524,9 +426,11 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
       for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int y = 0; y < 2; ++y) {
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], bh[y], acc[x][y], 0, 0, 0);
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], bl[y], acc[x][y], 0, 0, 0);
-          if (!A_EXACT) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[x], bh[y], acc[x][y], 0, 0, 0);
+          if (!A_EXACT) mfma3_f16(ah[x], al[x], bh[y], bl[y], acc[x][y]);
+          else {                           // A has no lo part
+            acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], bh[y], acc[x][y], 0, 0, 0);
+            acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], bl[y], acc[x][y], 0, 0, 0);
+          }
         }
     }
   }
@@ -539,7 +443,7 @@ __global__ __launch_bounds__(256) void k_hgemm(const int M, const int N, const i
       if (gn >= N) continue;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int gm = bm + 64 * wi + 32 * x + 8 * (v / 4) + 4 * h + (v % 4);
+        const int gm = ACC_ROW(v, h, bm + 64 * wi + 32 * x);
         if (gm < M) {
           float* c = C + (size_t)gm * ldc + gn;
           *c = accumulate ? *c + az * acc[x][y][v] : az * acc[x][y][v];
@@ -558,10 +462,6 @@ inline bool hgemm_ok(const void* A, int lda, const void* B, int ldb) {
 __global__ __launch_bounds__(256) void k_hreduce(const float* __restrict__ partials, const HSuper* __restrict__ supers, const int nsp,
                                                 const int KS, float* __restrict__ Gs, int* __restrict__ anyrot) {
   __shared__ float Ts[32][33];
-#if defined(WM_POISON_LDS)
-  for (int i = threadIdx.x; i < 32 * 33; i += 256) (&Ts[0][0])[i] = __int_as_float(0x7fc00000);
-  __syncthreads();
-#endif
   const int sp = blockIdx.y, z = blockIdx.z, t = threadIdx.x;
   const int nb = supers[sp].n;
   if (blockIdx.x == 0 && t == 0) anyrot[(size_t)z * nsp + sp] = 0;
@@ -604,14 +504,7 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
                                                 const float* __restrict__ Rall, const int* __restrict__ skip,
                                                 float* __restrict__ Gs) {
   __shared__ float Bm[RP][RP + 1];       // the block, then T = R_p^T B: 16.6 KB, so that a stage's <= 945 workgroups are resident at once
-#if defined(WM_POISON_LDS)
-  for (int i = threadIdx.x; i < RP * (RP + 1); i += 256) (&Bm[0][0])[i] = __int_as_float(0x7fc00000);
-  __syncthreads();
-#endif
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, j = lane & 31, h = lane >> 5;
-#if defined(WM_HUPD_DIAG)
-  const unsigned long long d0 = __builtin_amdgcn_s_memtime();
-#endif
   const int sp = blockIdx.y, z = blockIdx.z;
   const int* un = units + sp * HU;
   const size_t zs = (size_t)z * nsp + sp;
@@ -623,18 +516,15 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
   const int nu = supers[sp].n / 2, ep = un[up], eq = un[uq], skp = skip[zs * HU + up], skq = skip[zs * HU + uq];
   if (uq >= nu) return;
   if (ep < 0 || eq < 0) return;          // this super-pair has no such stage
-  const bool rot_p = ((ep >> 16) & 1) && !skp;
-  const bool rot_q = ((eq >> 16) & 1) && !skq;
+  const bool rot_p = UNIT_ROTATES(ep) && !skp;
+  const bool rot_q = UNIT_ROTATES(eq) && !skq;
   if (!rot_p && !rot_q) return;
-#if defined(WM_HUPD_DIAG)
-  const unsigned long long d1 = __builtin_amdgcn_s_memtime();
-#endif
-  const int pa = ep & 0xff, pb = (ep >> 8) & 0xff, qa = eq & 0xff, qb = (eq >> 8) & 0xff;
+  const int pa = unit_la(ep), pb = unit_lb(ep), qa = unit_la(eq), qb = unit_lb(eq);
   float* mat = Gs + zs * HN * HN;
   const int wi = wv >> 1, wj = wv & 1, i0 = wi * 32, c0 = wj * 32;
   // element (r, c) of the 64 x 64 block lives at row rmap(r), column cmap(c) of the matrix
-  auto rmap = [&](const int r) { return (r < RB) ? pa * RB + r : pb * RB + r - RB; };
-  auto cmap = [&](const int c) { return (c < RB) ? qa * RB + c : qb * RB + c - RB; };
+  auto rmap = [&](const int r) { return pair_row(r, pa, pb); };
+  auto cmap = [&](const int c) { return pair_row(c, qa, qb); };
   // The rotations are MFMA operands straight from k_rf_inner's packed copy (R[2 kk + h][32 hf + j] at ((hf * 8 + kk / 4) * 64 + lane) * 4
   // + kk % 4): the A operand of the left product is R_p's half wi, the B operand of the right product R_q's half wj - eight 16-byte
   // loads each, no LDS.
@@ -656,12 +546,8 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
     Bm[r][c4] = v.x; Bm[r][c4 + 1] = v.y; Bm[r][c4 + 2] = v.z; Bm[r][c4 + 3] = v.w;
   }
   __syncthreads();
-#if defined(WM_HUPD_DIAG)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned long long d2 = __builtin_amdgcn_s_memtime();
-#endif
   // two accumulation chains per product (even / odd steps): a dependent MFMA issues 64 cycles after its predecessor
-  v16f_h acc = {0}, acc2 = {0};
+  v16f acc = {0}, acc2 = {0};
   if (rot_p) {                           // T[i][c] = sum_k R_p[k][i] B[k][c]
 #pragma unroll
     for (int kk = 0; kk < RP / 2; kk += 2) {
@@ -672,15 +558,12 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
     if (rot_q) {
       __syncthreads();                   // every wave has read B
 #pragma unroll
-      for (int v = 0; v < 16; ++v) Bm[i0 + 8 * (v / 4) + 4 * h + (v % 4)][c0 + j] = acc[v];
+      for (int v = 0; v < 16; ++v) Bm[ACC_ROW(v, h, i0)][c0 + j] = acc[v];
       __syncthreads();
     }
   }
-#if defined(WM_HUPD_DIAG)
-  const unsigned long long d3 = __builtin_amdgcn_s_memtime();
-#endif
   if (rot_q) {                           // out[r][i] = sum_c T[r][c] R_q[c][i]
-    acc = v16f_h{0}; acc2 = v16f_h{0};
+    acc = v16f{0}; acc2 = v16f{0};
 #pragma unroll
     for (int kk = 0; kk < RP / 2; kk += 2) {
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Bm[i0 + j][2 * kk + h], bq[kk], acc, 0, 0, 0);
@@ -688,15 +571,12 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
     }
     acc += acc2;
   }
-#if defined(WM_HUPD_DIAG)
-  const unsigned long long d4 = __builtin_amdgcn_s_memtime();
-#endif
   // the block, and its mirror image G[q][p] = (G[p][q])^T (which keeps G_s exactly symmetric): back through the LDS tile, so that both
   // go out as 16-byte pieces of 256-byte row segments (straight from the accumulators the mirror image was 32 scattered 4-byte stores
   // per lane: 6 400 of the workgroup's 18 600 cycles)
   __syncthreads();                       // every wave has read the tile
 #pragma unroll
-  for (int v = 0; v < 16; ++v) Bm[i0 + 8 * (v / 4) + 4 * h + (v % 4)][c0 + j] = acc[v];
+  for (int v = 0; v < 16; ++v) Bm[ACC_ROW(v, h, i0)][c0 + j] = acc[v];
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -704,13 +584,6 @@ __global__ __launch_bounds__(256, 4) void k_hupdate(const int* __restrict__ unit
     *reinterpret_cast<float4*>(mat + (size_t)rmap(a) * HN + cmap(b4)) = make_float4(Bm[a][b4], Bm[a][b4 + 1], Bm[a][b4 + 2], Bm[a][b4 + 3]);
     *reinterpret_cast<float4*>(mat + (size_t)cmap(a) * HN + rmap(b4)) = make_float4(Bm[b4][a], Bm[b4 + 1][a], Bm[b4 + 2][a], Bm[b4 + 3][a]);
   }
-#if defined(WM_HUPD_DIAG)
-  if (t == 0 && blockIdx.x == 3 && blockIdx.y == 1 && blockIdx.z == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long d5 = __builtin_amdgcn_s_memtime();
-    printf("hupdate diag: prologue %llu loads+stage %llu product1 %llu product2 %llu stores %llu cycles (rot %d %d)\n", d1 - d0, d2 - d1, d3 - d2, d4 - d3, d5 - d4, (int)rot_p, (int)rot_q);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -732,27 +605,25 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
                                                     const HSuper* __restrict__ supers, const int nsp, const int nz,
                                                     const int* __restrict__ units, const int T, const float* __restrict__ Rpk,
                                                     const int* __restrict__ skipT, const size_t rpk_stage, const size_t skip_stage,
-                                                    const int* __restrict__ anyrot, const int dbg) {
+                                                    const int* __restrict__ anyrot) {
   extern __shared__ float Xs[];          // [n32][65]
   const int t = threadIdx.x, nthr = blockDim.x, wv = t >> 6, lane = t & 63, j = lane & 31, h = lane >> 5;
   const int nstrips = (ncols + 63) / 64;
   const int ntask = nsp * nz * nstrips;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int x0 = (int)((long)ntask * xcd / 8), x1 = (int)((long)ntask * (xcd + 1) / 8);
-  const int tk = x0 + q;
-  if (tk >= x1) return;
+  int tk_end;
+  const int tk = xcd_task(blockIdx.x, ntask, tk_end);
+  if (tk >= tk_end) return;
   const int g = tk / nstrips, sp = g % nsp, z = g / nsp, c0 = (tk % nstrips) * 64;      // g = z * nsp + sp
   const int n = supers[sp].n;
   if (n == 0 || !anyrot[g]) return;      // no such super-pair / every pair of every stage was already diagonal
   const int n32 = n * RB;
   aug += (size_t)z * aug_ps;
-  if (!(dbg & 2))
-    for (int f = t; f < n32 * 16; f += nthr) {
-      const int r = f >> 4, c4 = (f & 15) * 4;
-      const float4 v = *reinterpret_cast<const float4*>(aug + (size_t)(supers[sp].blk[r >> 5] * RB + (r & 31)) * ld + c0 + c4);   // within the row: ld >= ncols rounded up to 64
-      float* d = Xs + r * 65 + c4;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
+  for (int f = t; f < n32 * 16; f += nthr) {
+    const int r = f >> 4, c4 = (f & 15) * 4;
+    const float4 v = *reinterpret_cast<const float4*>(aug + (size_t)(supers[sp].blk[r >> 5] * RB + (r & 31)) * ld + c0 + c4);   // within the row: ld >= ncols rounded up to 64
+    float* d = Xs + r * 65 + c4;
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  }
   const int u = wv >> 1, hf = wv & 1;    // this wave's unit and which of its two blocks it produces
   const bool wave_on = 2 * u < n;        // (waves beyond the super-pair's units only keep the barriers company)
   // a stage's operands: the unit's entry, whether it rotates, and - if so - R_u's 32 steps for this wave's 32 output rows
@@ -762,7 +633,7 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
     e = -1;
     if (!wave_on || st >= T) return;
     const int ent = units[((size_t)st * nsp + sp) * HU + u];
-    if (ent < 0 || !((ent >> 16) & 1) || skipT[(size_t)st * skip_stage + (size_t)g * HU + u]) return;
+    if (!UNIT_ROTATES(ent) || skipT[(size_t)st * skip_stage + (size_t)g * HU + u]) return;
     e = ent;
     const float4* rp = reinterpret_cast<const float4*>(Rpk + (size_t)st * rpk_stage + ((size_t)g * HU + u) * RP * RP) + (hf * 8) * 64 + lane;
 #pragma unroll
@@ -773,10 +644,10 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
   };
   fetch_stage(0, e_cur, a_cur);
   __syncthreads();
-  for (int st = 0; st < ((dbg & 1) ? 0 : T); ++st) {
+  for (int st = 0; st < T; ++st) {
     fetch_stage(st + 1, e_nxt, a_nxt);
-    v16f_h acc0 = {0}, acc1 = {0};
-    const int la = e_cur & 0xff, lb = (e_cur >> 8) & 0xff;
+    v16f acc0 = {0}, acc1 = {0};
+    const int la = unit_la(e_cur), lb = unit_lb(e_cur);
     if (e_cur >= 0) {
       const float* xa = Xs + (la * RB + h) * 65 + j;        // k < 32: row la * 32 + k;  k >= 32: row lb * 32 + k - 32
       const float* xb = Xs + (lb * RB + h) * 65 + j;
@@ -796,7 +667,7 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
       float* o = Xs + ((hf ? lb : la) * RB) * 65 + j;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int i = 8 * (v / 4) + 4 * h + (v % 4);
+        const int i = ACC_ROW(v, h, 0);
         o[i * 65] = acc0[v]; o[i * 65 + 32] = acc1[v];
       }
     }
@@ -805,7 +676,6 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
 #pragma unroll
     for (int kk = 0; kk < 32; ++kk) a_cur[kk] = a_nxt[kk];
   }
-  if (dbg & 4) return;
   for (int f = t; f < n32 * 16; f += nthr) {
     const int r = f >> 4, c4 = (f & 15) * 4;
     const float* d = Xs + r * 65 + c4;
@@ -817,9 +687,9 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
 }
 
 // ---------------------------------------------------------------------------
-// k_happly on the f16 matrix pipe with split operands (see k_hgram_h).  The strip's LDS image IS the split form: two f16
+// k_happly on the f16 matrix pipe with split operands (see k_hgram_t).  The strip's LDS image IS the split form: two f16
 // planes [column][row] (k-contiguous for the B operand: a lane's 8 consecutive rows are one 16-byte read; pitch HA_CP halfs),
-// x = hi + lo' / 2048 with hi = f16(x) (0 below f16's normal range) and lo' = f16((x - hi) * 2048) - 22 significant bits, so
+// x = hi + lo' / 2048 (split4_scaled) - 22 significant bits, so
 // what a stage writes back is the f32 result rounded to 2^-23 relative (an f32 product chain of 64 terms rounds more).
 // Per stage a wave issues 24 v_mfma_f32_32x32x16_f16 (R_hi X_hi into one accumulator pair, R_hi X_lo' + R_lo' X_hi into a
 // second that is scaled by 2^-11 at the end) instead of 64 v_mfma_f32_32x32x2_f32: 768 matrix-pipe cycles instead of 4 096.
@@ -828,37 +698,21 @@ __global__ __launch_bounds__(64 * HSB) void k_happly(float* __restrict__ aug, co
 // ---------------------------------------------------------------------------
 constexpr int HA_CP = HN + 8;                 // halfs per column of the split image: 784 bytes = 196 dwords = 4 mod 64: 16-byte reads of 16 lanes are conflict-free
 
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef float f2_t __attribute__((ext_vector_type(2)));
-
-// Four values -> packed hi and lo' halfs.  v_cvt_pk_f16_f32 rounds to nearest even and keeps f16 subnormals, and the f16 matrix
-// instructions honour subnormal operands (tools/ubench_f16_denorm.hip), so no magnitude guard is needed: hi + lo' / 2048
-// reproduces x to 2^-22 |x| down to |x| ~ 3e-8.  Six VALU instructions per two values (packed f32 subtract and scale).
-__device__ __forceinline__ void split4_scaled(const float x0, const float x1, const float x2, const float x3, h4_t& hi, h4_t& lo) {
-  const f2_t a = {x0, x1}, b = {x2, x3};
-  const h2_t ha = __builtin_convertvector(a, h2_t), hb = __builtin_convertvector(b, h2_t);
-  const f2_t ra = (a - __builtin_convertvector(ha, f2_t)) * 2048.0f, rb = (b - __builtin_convertvector(hb, f2_t)) * 2048.0f;
-  const h2_t la = __builtin_convertvector(ra, h2_t), lb = __builtin_convertvector(rb, h2_t);
-  hi = h4_t{ha[0], ha[1], hb[0], hb[1]};
-  lo = h4_t{la[0], la[1], lb[0], lb[1]};
-}
-
 template <int SW>                      // strip width in columns: 64 (100 KB of LDS, one workgroup per CU)
 __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, const size_t aug_ps, const int ld, const int ncols,
                                                       const HSuper* __restrict__ supers, const int nsp, const int nz,
                                                       const int* __restrict__ units, const int T, const float* __restrict__ Rpk,
                                                       const int* __restrict__ skipT, const size_t rpk_stage, const size_t skip_stage,
-                                                      const int* __restrict__ anyrot, const int dbg) {
+                                                      const int* __restrict__ anyrot) {
   constexpr int NT = SW / 32;                          // 32-column tiles per wave
   extern __shared__ __attribute__((aligned(16))) _Float16 Xh[];          // [SW columns][HA_CP], then the lo' plane
   _Float16* const Xl = Xh + SW * HA_CP;
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, j = lane & 31, h = lane >> 5;
   const int nstrips = (ncols + SW - 1) / SW;
   const int ntask = nsp * nz * nstrips;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int x0 = (int)((long)ntask * xcd / 8), x1 = (int)((long)ntask * (xcd + 1) / 8);
-  const int tk = x0 + q;
-  if (tk >= x1) return;
+  int tk_end;
+  const int tk = xcd_task(blockIdx.x, ntask, tk_end);
+  if (tk >= tk_end) return;
   const int g = tk / nstrips, sp = g % nsp, z = g / nsp, c0 = (tk % nstrips) * SW;      // g = z * nsp + sp
   // (the words this workgroup's first loads depend on, fetched together: the super-pair's size, whether any of its pairs
   // rotated, and this wave's block)
@@ -872,18 +726,13 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
   // every stage's unit entries of this (plane, super-pair), with the skip flags folded in: read once, here - fetched stage by
   // stage they were two dependent L2 round trips in front of every stage's barrier (3 000 of a stage's 7 500 cycles)
   __shared__ int s_ent[HT_MAX][HU];
-#if defined(WM_POISON_LDS)
-  for (int i = threadIdx.x; i < 2 * SW * HA_CP; i += blockDim.x) Xh[i] = __builtin_bit_cast(_Float16, (unsigned short)0x7e00);
-  for (int i = threadIdx.x; i < HT_MAX * HU; i += blockDim.x) (&s_ent[0][0])[i] = 0x7fffffff;
-  __syncthreads();
-#endif
   if (t < T * HU) {
     const int st = t / HU, uu = t % HU;
     const int ent = units[((size_t)st * nsp + sp) * HU + uu], sk = skipT[(size_t)st * skip_stage + (size_t)g * HU + uu];
-    s_ent[st][uu] = (ent < 0 || !((ent >> 16) & 1) || sk) ? -1 : ent;
+    s_ent[st][uu] = (!UNIT_ROTATES(ent) || sk) ? UNIT_NONE : ent;
   }
   const int ti = lane & 7, tm = lane >> 3;
-  if (wv < n && !(dbg & 2)) {
+  if (wv < n) {
     const float* src = aug + (size_t)(myblk * RB + 4 * ti) * ld + c0 + 4 * tm;     // within the row: ld >= ncols rounded up to 64
     float4 v[NT][4];
 #pragma unroll
@@ -915,7 +764,7 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
     if (st == 0) {                       // (before the first barrier: straight from the tables, under the staging loads)
       ent = units[(size_t)sp * HU + u];
       const int sk = skipT[(size_t)g * HU + u];
-      if (ent < 0 || !((ent >> 16) & 1) || sk) ent = -1;
+      if (!UNIT_ROTATES(ent) || sk) ent = UNIT_NONE;
     } else ent = s_ent[st][u];
     if (ent < 0) return;
     e = ent;
@@ -924,10 +773,10 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
     for (int s2 = 0; s2 < 4; ++s2) { ah[s2] = rp[s2 * 64]; al[s2] = rp[RP * RP / 8 + s2 * 64]; }
   };
   // One 32-column tile's products of a stage (accumulators pa: hi hi, pb: the two cross products, x 2^11), and its write-back.
-  auto mfma_tile = [&](const int tl, const int e, const h8_t* ah, const h8_t* al, v16f_h& pa, v16f_h& pb) {
-    pa = v16f_h{0}; pb = v16f_h{0};
-    if (e < 0 || (dbg & 16)) return;
-    const int la = e & 0xff, lb = (e >> 8) & 0xff;
+  auto mfma_tile = [&](const int tl, const int e, const h8_t* ah, const h8_t* al, v16f& pa, v16f& pb) {
+    pa = v16f{0}; pb = v16f{0};
+    if (e < 0) return;
+    const int la = unit_la(e), lb = unit_lb(e);
     const _Float16* xhc = Xh + (32 * tl + j) * HA_CP; const _Float16* xlc = Xl + (32 * tl + j) * HA_CP;
 #pragma unroll
     for (int s2 = 0; s2 < 4; ++s2) {
@@ -940,11 +789,11 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
       pb = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s2], xh, pb, 0, 0, 0);
     }
   };
-  auto wb_tile = [&](const int tl, const int e, const v16f_h& pa, const v16f_h& pb) {
-    if (e < 0 || (dbg & 8)) return;
-    // accumulator register v of lane (j, h) is row 8 (v / 4) + 4 h + v % 4 of the block, column j: four consecutive rows per
-    // quad = four consecutive halfs of the column-major image
-    const int rb0 = (hf ? (e >> 8) & 0xff : e & 0xff) * RB + 4 * h;
+  auto wb_tile = [&](const int tl, const int e, const v16f& pa, const v16f& pb) {
+    if (e < 0) return;
+    // ACC_ROW: the registers 4 qd .. + 3 of a lane are four consecutive rows from row 8 qd + 4 h on = four consecutive halfs of
+    // the column-major image
+    const int rb0 = (hf ? unit_lb(e) : unit_la(e)) * RB + ACC_ROW(0, h, 0);
     _Float16* ch = Xh + (32 * tl + j) * HA_CP + rb0; _Float16* cl = Xl + (32 * tl + j) * HA_CP + rb0;
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
@@ -963,7 +812,7 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
   static_assert(NT == 2, "the stage pipeline alternates between two 32-column tiles");
   fetch_stage(0, e0, ah0, al0);
   __syncthreads();
-  v16f_h pa0, pb0, pa1, pb1;
+  v16f pa0, pb0, pa1, pb1;
   mfma_tile(0, e0, ah0, al0, pa0, pb0);
   // one stage: A = its operands (resident), B = the next stage's (fetched here, first used after the second barrier)
   const bool vfirst = ((wv >> 2) & 1) != 0;
@@ -980,13 +829,12 @@ __global__ __launch_bounds__(64 * HSB) void k_happly_h(float* __restrict__ aug, 
     if (vfirst) { wb_tile(1, eA, pa1, pb1); mfma_tile(0, eB, ahB, alB, pa0, pb0); }
     else { mfma_tile(0, eB, ahB, alB, pa0, pb0); wb_tile(1, eA, pa1, pb1); }
   };
-  const int Tn = (dbg & 1) ? 0 : T;
-  for (int st = 0; st < Tn; st += 2) {
+  for (int st = 0; st < T; st += 2) {
     stage(st, e0, ah0, al0, e1, ah1, al1);
-    if (st + 1 < Tn) stage(st + 1, e1, ah1, al1, e0, ah0, al0);
+    if (st + 1 < T) stage(st + 1, e1, ah1, al1, e0, ah0, al0);
   }
   __syncthreads();
-  if (wv < n && !(dbg & 4)) {            // the image back to f32 rows: the staging's pieces in reverse
+  if (wv < n) {                          // the image back to f32 rows: the staging's pieces in reverse
     float* dst = aug + (size_t)(myblk * RB + 4 * ti) * ld + c0 + 4 * tm;
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl) {
@@ -1022,7 +870,7 @@ struct HierTab {
   std::vector<int> T;            // stages of super-step s1
   std::vector<int> stage_off;    // first stage of super-step s1 in d_units
   HSuper* d_super;               // [nsteps1][nsp]
-  int* d_units;                  // [stages][nsp][HU]: la | lb << 8 | real << 16, or -1
+  int* d_units;                  // [stages][nsp][HU]: unit_make(la, lb, real), or UNIT_NONE
 };
 
 void round_robin(int m, std::vector<std::vector<std::pair<int, int>>>& steps) {      // m even
@@ -1092,33 +940,33 @@ int get_hier(wm_ctx* ctx, const int nbk, const int sb, const HierTab** out) {
         std::vector<std::vector<std::pair<int, int>>> l2;
         round_robin(su.n, l2);
         for (auto& stage : l2) {
-          std::array<int, HU> row; row.fill(-1);
+          std::array<int, HU> row; row.fill(UNIT_NONE);
           for (size_t u = 0; u < stage.size(); ++u)
-            row[u] = std::min(stage[u].first, stage[u].second) | (std::max(stage[u].first, stage[u].second) << 8) | (1 << 16);
+            row[u] = unit_make(std::min(stage[u].first, stage[u].second), std::max(stage[u].first, stage[u].second), true);
           st[k].push_back(row);
         }
       } else {                                       // the na x nb cross pairs: the smaller side meets the larger one cyclically
         const int big = std::max(na, nb), small = std::min(na, nb);
         for (int tt = 0; tt < big; ++tt) {
-          std::array<int, HU> row; row.fill(-1);
+          std::array<int, HU> row; row.fill(UNIT_NONE);
           std::vector<char> used(su.n, 0);
           int u = 0;
           for (int i = 0; i < small; ++i) {
             const int jb = (i + tt) % big;
             const int la = na >= nb ? jb : i, lb = na >= nb ? na + i : na + jb;     // local indices: A first, then B
-            row[u++] = la | (lb << 8) | (1 << 16);
+            row[u++] = unit_make(la, lb, true);
             used[la] = used[lb] = 1;
           }
           int pend = -1;                             // idle blocks in pairs (their count is even): R = I
           for (int b2 = 0; b2 < su.n; ++b2)
-            if (!used[b2]) { if (pend < 0) pend = b2; else { row[u++] = pend | (b2 << 8); pend = -1; } }
+            if (!used[b2]) { if (pend < 0) pend = b2; else { row[u++] = unit_make(pend, b2, false); pend = -1; } }
           st[k].push_back(row);
         }
       }
       Tmax = std::max(Tmax, (int)st[k].size());
     }
     ht->T[s1] = Tmax; ht->stage_off[s1] = (int)(units.size() / ((size_t)ht->nsp * HU));
-    {   // what the kernels issue for this super-step (k_hgram: 3 of a diagonal tile's 4 quadrants; k_happly: a 64 x 64 rotation per
+    {   // what the kernels issue for this super-step (k_hgram_t: 3 of a diagonal tile's 4 quadrants; k_happly: a 64 x 64 rotation per
         // rotated unit, stage and column; k_hupdate: two 64^3 products per unit pair and stage but the last)
       double fg = 0.0, fa = 0.0, fs = 0.0;
       for (int k = 0; k < ht->nsp; ++k) {
@@ -1128,7 +976,7 @@ int get_hier(wm_ctx* ctx, const int nbk, const int sb, const HierTab** out) {
         fg += 2.0 * quads * 64 * 64;
         const int nu = nb / 2;
         int real_units = 0;                          // k_happly: one 64 x 64 rotation per rotated unit and stage, per column
-        for (auto& row : st[k]) for (int u2 = 0; u2 < HU; ++u2) if (row[u2] >= 0 && ((row[u2] >> 16) & 1)) ++real_units;
+        for (auto& row : st[k]) for (int u2 = 0; u2 < HU; ++u2) if (UNIT_ROTATES(row[u2])) ++real_units;
         fa += 2.0 * real_units * RP * RP;
         fs += (double)(st[k].size() > 0 ? st[k].size() - 1 : 0) * (nu * (nu - 1) / 2 * 2) * 2.0 * RP * RP * RP;
       }
@@ -1136,7 +984,7 @@ int get_hier(wm_ctx* ctx, const int nbk, const int sb, const HierTab** out) {
     }
     for (int tt = 0; tt < Tmax; ++tt)
       for (int k = 0; k < ht->nsp; ++k)
-        for (int u = 0; u < HU; ++u) units.push_back(tt < (int)st[k].size() ? st[k][tt][u] : -1);
+        for (int u = 0; u < HU; ++u) units.push_back(tt < (int)st[k].size() ? st[k][tt][u] : UNIT_NONE);
   }
   const size_t b_sup = pad256(supers.size() * sizeof(HSuper)), b_un = units.size() * sizeof(int);
   void* dev = nullptr;

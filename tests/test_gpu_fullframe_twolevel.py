@@ -78,6 +78,37 @@ def test_two_level_against_lapack_and_the_flat_tournament(gpu_ctx, monkeypatch, 
     gpu_ctx.check_status()
 
 
+_OFF_GRID = [(H, W, f16, h3) for H, W in [(64, 97), (128, 130), (320, 323), (97, 64)] for f16 in (3, 0)
+             for h3 in ((0, 1) if (H, W) == (320, 323) else (None,))]
+
+
+@pytest.mark.parametrize("H,W,f16,hgram3", _OFF_GRID)
+def test_two_level_row_lengths_off_the_float4_grid(gpu_ctx, monkeypatch, H, W, f16, hgram3):
+    """Row lengths M = 1, 2, 3 (mod 4): the last 16-byte load of a row is masked element by element (every other shape of the
+    suite has M = 0 (mod 4)).  One panel (64 rows), two, three (ten blocks: a 6 + 4 super-pair, with both Gram kernels) and a
+    transposed plane; the module's bars against float64 LAPACK and the flat tournament, and two runs bit for bit."""
+    monkeypatch.setenv("WM_RF_HIER_F16", str(f16))
+    if hgram3 is None:
+        monkeypatch.delenv("WM_RF_HGRAM3", raising=False)
+    else:
+        monkeypatch.setenv("WM_RF_HGRAM3", str(hgram3))
+    planes = _planes(2, H, W)
+    ref = np.stack([np.linalg.svd(p.astype(np.float64), compute_uv=False) for p in planes])
+    monkeypatch.setenv("WM_RF_HIER", "0")
+    s_flat = gpu_ctx.ref_sigma_planes(planes)
+    assert gpu_ctx.ref_last_flops()[1] is False
+    monkeypatch.setenv("WM_RF_HIER", "1")
+    a = gpu_ctx.ref_sigma_planes(planes)
+    assert gpu_ctx.ref_last_flops()[1] is True
+    b = gpu_ctx.ref_sigma_planes(planes)
+    print(f"off-grid {H}x{W} f16={f16} hgram3={hgram3}: vs LAPACK {np.max(np.abs(a - ref) / ref[:, :1]):.2e}, "
+          f"vs flat {np.max(np.abs(a - s_flat) / ref[:, :1]):.2e} sigma_1")
+    assert np.max(np.abs(a - ref) / ref[:, :1]) < 2e-6
+    assert np.max(np.abs(a - s_flat) / ref[:, :1]) < 1e-6
+    assert a.tobytes() == b.tobytes()
+    gpu_ctx.check_status()
+
+
 def test_two_level_is_deterministic_and_batch_independent(gpu_ctx):
     """Bit for bit: the same plane alone, twice, and inside a batch (fixed summation orders, no float atomics)."""
     planes = _planes(3, 256, 384, seed=11)

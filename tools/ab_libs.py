@@ -1,14 +1,24 @@
-"""A/B of the tile kernels of TWO builds of libwmhip.so in ONE process on one device (no torch): embed and extract
-(pixel-domain factors, what bench.py runs) at the bench shape, the variants interleaved round by round, HIP events on
-each context's stream.  Prints per variant the median over the rounds and the spread (max - min) of the round values,
-and the parity of b against a (stego LSB differences, Sc relative to sigma_1, extracted watermark).
+"""A/B of TWO builds of libwmhip.so in ONE process on one device (no torch).
 
-    python tools/ab_tile_libs.py --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so [--content natural]
+Tile kernels (default): embed and extract (pixel-domain factors, what bench.py runs) at the bench shape, the variants
+interleaved round by round, HIP events on each context's stream.  Prints per variant the median over the rounds and the
+spread (max - min) of the round values, and the parity of b against a (stego LSB differences, Sc relative to sigma_1,
+extracted watermark).
+
+    python tools/ab_libs.py --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so [--content natural]
+
+Full-frame mode (--ref): the BYTES of both builds' singular values, embed (stego, Sc), watermark-side SVD (U, S, Vt),
+extract and detect on seeded planes, under every combination of WM_RF_HIER, WM_RF_HIER_F16, WM_RF_HGRAM3 and
+WM_RF_FINAL_F16 (read by the library on every call).  Extract and detect of both builds get a's stego and factors, so a
+difference is that call's own.  The mode is deterministic, so any differing byte is a change of behaviour.
+
+    python tools/ab_libs.py --ref --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so
 
 Development aid; bench.py is the contract benchmark."""
 import argparse
 import ctypes as C
 import importlib
+import itertools
 import os
 import sys
 
@@ -90,8 +100,55 @@ class Side:
         return st, sc, out
 
 
+def seeded_planes(B, H, W, seed=5):
+    """tests/test_gpu_fullframe_twolevel.py's planes: noise, from three planes on a smooth and a half-empty one as well"""
+    rng = np.random.default_rng(seed)
+    planes = rng.integers(0, 256, (B, H, W), dtype=np.uint8)
+    if B >= 3:
+        planes[1] = (np.outer(np.linspace(0, 200, H), np.ones(W)) + 20 * np.sin(np.arange(W) / 9.0)[None, :]).astype(np.uint8)
+        planes[2, :, W // 2:] = 0
+    return planes
+
+
+def ref_bits(path_a, path_b, alpha=0.15):
+    ctx = {"a": LibContext(api.load_library(path_a)), "b": LibContext(api.load_library(path_b))}
+    inputs = [("3x320x480", seeded_planes(3, 320, 480)), ("2x832x900", seeded_planes(2, 832, 900)),
+              ("3x1080x1920", np.random.default_rng(21).integers(0, 256, (3, 1080, 1920), dtype=np.uint8))]
+    inputs += [(f"2x{H}x{W}", seeded_planes(2, H, W)) for H, W in ((64, 97), (128, 130), (320, 323), (97, 64))]
+    n_diff = n_cmp = 0
+    for hier, f16, h3, fin in itertools.product((0, 1), (3, 1, 0), (0, 1), (1, 0)):
+        os.environ.update(WM_RF_HIER=str(hier), WM_RF_HIER_F16=str(f16), WM_RF_HGRAM3=str(h3), WM_RF_FINAL_F16=str(fin))
+        for name, planes in inputs:
+            _, H, W = planes.shape
+            K = int(0.6 * min(H, W))
+            wm = np.random.default_rng(H * 10000 + W).integers(0, 256, (1, H, W)).astype(np.float32)
+            got = {}
+            for k, c in ctx.items():
+                U, S, Vt = c.ref_svd_planes(wm, apply_dct=True)
+                got[k] = {"sigma": c.ref_sigma_planes(planes), "U": U, "S": S, "Vt": Vt}
+                got[k]["two_level"] = c.ref_last_flops()[1]
+            for k, c in ctx.items():            # the same watermark factors (a's) for both builds from here on
+                emb = c.ref_embed_planes(planes, got["a"]["S"][0], alpha, K)
+                got[k]["stego"], got[k]["Sc"] = emb[0], emb[1]
+            ga = got["a"]
+            for k, c in ctx.items():
+                got[k]["extract"] = c.ref_extract_planes(ga["stego"], ga["Sc"], ga["U"][0], ga["Vt"][0], alpha, K)
+                got[k]["detect"] = c.ref_detect_planes(ga["stego"], ga["Sc"], ga["S"][0], alpha)
+                c.check_status()
+            keys = ("sigma", "stego", "Sc", "U", "S", "Vt", "extract", "detect")
+            diff = [q for q in keys if np.asarray(got["a"][q]).tobytes() != np.asarray(got["b"][q]).tobytes()]
+            n_cmp += len(keys); n_diff += len(diff)
+            print(f"HIER={hier} HIER_F16={f16} HGRAM3={h3} FINAL_F16={fin}  {name:12s} sigma two-level={got['a']['two_level']}:  "
+                  + ("all %d results equal bytes" % len(keys) if not diff else "DIFFERENT: " + ", ".join(diff)), flush=True)
+    print(f"{n_cmp} results compared, {n_diff} differ")
+    for c in ctx.values():
+        c.close()
+    return 1 if n_diff else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ref", action="store_true", help="full-frame mode: compare the bytes of both builds' results")
     ap.add_argument("--a", required=True, help="libwmhip.so of the baseline")
     ap.add_argument("--b", required=True, help="libwmhip.so of the variant")
     ap.add_argument("--frames", type=int, default=32)
@@ -103,6 +160,8 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.15)
     ap.add_argument("--content", default="noise", choices=["noise", "natural"])
     a = ap.parse_args()
+    if a.ref:
+        sys.exit(ref_bits(a.a, a.b, a.alpha))
     rng = np.random.default_rng(1234)
     host = np.ascontiguousarray(make_frames(a.content, a.frames, a.H, a.W, rng))
     wys = rng.integers(0, 256, (a.H, a.W)).astype(np.float32)
