@@ -182,6 +182,123 @@ __global__ __launch_bounds__(256) void k_color(const uint8_t* __restrict__ in3, 
   }
 }
 
+// ---- planar frame codec: stored Y, Cb, Cr frames (chroma subsampled SX x SY) <-> planar B, G, R ----------------
+// The colour video functions' container side (video.py): a YUV4MPEG2 frame is Y [H][W], Cb [ch][cw], Cr [ch][cw] packed,
+// ch x cw = ceil(H / SY) x ceil(W / SX); the hot path works on B, G, R planes.
+//   decode: chroma sample (r / SY, c / SX) serves pixel (r, c) (replication), then ycc2bgr per pixel;
+//   encode: bgr2ycc per pixel, Y as is, Cb / Cr the half-up integer mean over the pixels of the block that exist.
+// One work item is one chroma block row of PX pixels (SY luma rows): its chroma is read (or written) once and serves every
+// luma row it covers.  VEC: PX = 16, every access is one 16-byte (Y, B, G, R, full-resolution chroma) or 8-byte
+// (subsampled chroma) piece, a wave's lanes side by side in the row; it needs W % 16 == 0 and 16-byte aligned bases.
+// !VEC: PX = SX, byte accesses, any W, H and alignment; the same values.  Everything is planar on both sides, so the lanes'
+// pieces are contiguous as they are: no LDS staging.  The frame index is blockIdx.y.
+enum ChromaDir { YUV_TO_BGR = 0, BGR_TO_YUV = 1 };
+
+// n (<= PX) consecutive bytes of a row, one value per pixel
+template <int PX, bool VEC>
+__device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, const int n, uint32_t (&v)[PX]) {
+  if constexpr (VEC) {
+    uint32_t w[PX / 4];
+    // The empty asm takes the whole piece at once: without it hipcc (ROCm 7.2) splits an encode's 16-byte read into two
+    // global_load_dwordx2 some 150 instructions apart, so that a wave's load touches every line twice
+    if constexpr (PX == 16) {
+      const uint4 q = *reinterpret_cast<const uint4*>(p);
+      w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+      asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
+    } else {
+      const uint2 q = *reinterpret_cast<const uint2*>(p);
+      w[0] = q.x; w[1] = q.y;
+      asm volatile("" : "+v"(w[0]), "+v"(w[1]));
+    }
+#pragma unroll
+    for (int i = 0; i < PX; ++i) v[i] = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+  } else {
+#pragma unroll
+    for (int i = 0; i < PX; ++i) v[i] = i < n ? (uint32_t)p[i] : 0u;
+  }
+}
+template <int PX, bool VEC>
+__device__ __forceinline__ void store_px(uint8_t* __restrict__ p, const int n, const uint32_t (&v)[PX]) {
+  if constexpr (VEC) {
+    uint32_t w[PX / 4];
+#pragma unroll
+    for (int i = 0; i < PX / 4; ++i) w[i] = v[4 * i] | (v[4 * i + 1] << 8) | (v[4 * i + 2] << 16) | (v[4 * i + 3] << 24);
+    if constexpr (PX == 16) *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    else *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < PX; ++i) if (i < n) p[i] = (uint8_t)v[i];
+  }
+}
+
+template <int DIR, int SX, int SY, bool VEC>
+__global__ __launch_bounds__(256) void k_frame_codec(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int n_frames,
+                                                    const int H, const int W, const size_t frame_stride) {
+  constexpr int PX = VEC ? 16 : SX, NC = PX / SX;          // pixels and chroma samples of an item's row piece
+  const int cw = (W + SX - 1) / SX, ch = (H + SY - 1) / SY;
+  const int cols = VEC ? W / 16 : cw;                      // items per chroma row
+  const size_t ysz = (size_t)H * W, csz = (size_t)ch * cw, items = (size_t)ch * cols;
+  for (int fr = blockIdx.y; fr < n_frames; fr += gridDim.y) {
+    const size_t f_off = (size_t)fr * frame_stride, p_off = (size_t)fr * 3 * ysz;
+    for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (size_t)gridDim.x * blockDim.x) {
+      const int crow = (int)(it / cols), col = (int)(it - (size_t)crow * cols);
+      const int x0 = col * PX, nx = min(PX, W - x0), nc = (nx + SX - 1) / SX;
+      const int rows = min(SY, H - crow * SY);             // luma rows of this chroma row that exist
+      const size_t c_at = ysz + (size_t)crow * cw + (size_t)col * NC;     // the item's Cb samples within a frame; Cr: + csz
+      if constexpr (DIR == YUV_TO_BGR) {
+        const uint8_t* f = in + f_off;
+        uint8_t* pl = out + p_off;
+        uint32_t cb[NC], cr[NC];
+        load_px<NC, VEC>(f + c_at, nc, cb);
+        load_px<NC, VEC>(f + c_at + csz, nc, cr);
+#pragma unroll
+        for (int j = 0; j < SY; ++j) {
+          if (j >= rows) break;
+          const size_t at = (size_t)(crow * SY + j) * W + x0;
+          uint32_t y[PX], b[PX], g[PX], r[PX];
+          load_px<PX, VEC>(f + at, nx, y);
+#pragma unroll
+          for (int px = 0; px < PX; ++px) ycc2bgr(y[px], cr[px / SX], cb[px / SX], b[px], g[px], r[px]);
+          store_px<PX, VEC>(pl + at, nx, b);
+          store_px<PX, VEC>(pl + ysz + at, nx, g);
+          store_px<PX, VEC>(pl + 2 * ysz + at, nx, r);
+        }
+      } else {
+        const uint8_t* pl = in + p_off;
+        uint8_t* f = out + f_off;
+        uint32_t scb[NC], scr[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) scb[c] = scr[c] = 0;
+#pragma unroll
+        for (int j = 0; j < SY; ++j) {
+          if (j >= rows) break;
+          const size_t at = (size_t)(crow * SY + j) * W + x0;
+          uint32_t y[PX], b[PX], g[PX], r[PX];
+          load_px<PX, VEC>(pl + at, nx, b);
+          load_px<PX, VEC>(pl + ysz + at, nx, g);
+          load_px<PX, VEC>(pl + 2 * ysz + at, nx, r);
+#pragma unroll
+          for (int px = 0; px < PX; ++px) {
+            uint32_t cr1, cb1;
+            bgr2ycc(b[px], g[px], r[px], y[px], cr1, cb1);
+            if (VEC || px < nx) { scb[px / SX] += cb1; scr[px / SX] += cr1; }
+          }
+          store_px<PX, VEC>(f + at, nx, y);
+        }
+        // mean over the cnt = 1, 2 or 4 pixels of the block that exist, half up: (2 sum + cnt) / (2 cnt)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const int lg = (rows == 2) + (min(SX, nx - c * SX) == 2);
+          scb[c] = (2 * scb[c] + (1u << lg)) >> (1 + lg);
+          scr[c] = (2 * scr[c] + (1u << lg)) >> (1 + lg);
+        }
+        store_px<NC, VEC>(f + c_at, nc, scb);
+        store_px<NC, VEC>(f + c_at + csz, nc, scr);
+      }
+    }
+  }
+}
+
 // ---- PSNR: sum of squared differences of two uint8 buffers ------------------------
 __global__ __launch_bounds__(256) void k_sqdiff_u8(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                                   const size_t n, unsigned long long* __restrict__ out) {
@@ -513,6 +630,79 @@ int color_dispatch(wm_ctx* ctx, int op, const uint8_t* in3, const uint8_t* plane
   return WM_OK;
 }
 
+template <int DIR, int SX, int SY>
+void launch_frame_codec(wm_ctx* ctx, const bool vec, const uint8_t* in, uint8_t* out, int n_frames, int H, int W, size_t frame_stride) {
+  const size_t ch = (size_t)(H + SY - 1) / SY, cols = vec ? (size_t)W / 16 : (size_t)(W + SX - 1) / SX;
+  const dim3 grid(grid_for(ch * cols), (unsigned)min(n_frames, 65535)), block(256);
+  if (vec) hipLaunchKernelGGL((k_frame_codec<DIR, SX, SY, true>), grid, block, 0, ctx->stream, in, out, n_frames, H, W, frame_stride);
+  else hipLaunchKernelGGL((k_frame_codec<DIR, SX, SY, false>), grid, block, 0, ctx->stream, in, out, n_frames, H, W, frame_stride);
+}
+
+bool sub_ok(int sx, int sy) { return (sx == 1 && sy == 1) || (sx == 2 && (sy == 1 || sy == 2)); }
+size_t frame_bytes(int H, int W, int sx, int sy) {
+  return (size_t)H * W + 2 * ((size_t)(H + sy - 1) / sy) * ((size_t)(W + sx - 1) / sx);
+}
+
+// the argument rules both forms share; *fsz = bytes of a frame, 0 when there is nothing to do (an empty batch or plane)
+int frame_codec_args(wm_ctx* ctx, const uint8_t* frames, const uint8_t* planes, int n_frames, int H, int W, int sx, int sy,
+                     size_t frame_stride, size_t* fsz) {
+  *fsz = 0;
+  WM_TRY(wmi::use_ctx(ctx));
+  if (n_frames < 0 || H < 0 || W < 0) return set_err(WM_ERR_BADARG, "n_frames, H and W must not be negative");
+  if (!sub_ok(sx, sy)) return set_err(WM_ERR_BADARG, "chroma subsampling must be 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0)");
+  if (n_frames == 0 || H == 0 || W == 0) return WM_OK;
+  if (!frames || !planes) return set_err(WM_ERR_BADARG, "NULL argument");
+  const size_t b = frame_bytes(H, W, sx, sy);
+  if (frame_stride < b) return set_err(WM_ERR_BADARG, "frame_stride is smaller than a frame");
+  const uintptr_t f0 = (uintptr_t)frames, p0 = (uintptr_t)planes;
+  if (f0 < p0 + (size_t)n_frames * 3 * H * W && p0 < f0 + (size_t)(n_frames - 1) * frame_stride + b)
+    return set_err(WM_ERR_BADARG, "the frame codec cannot run in place: frames and planes overlap");
+  *fsz = b;
+  return WM_OK;
+}
+
+// DIR == YUV_TO_BGR: in = frames, out = planes; BGR_TO_YUV: in = planes, out = frames (device pointers)
+template <int DIR>
+int frame_codec_dispatch(wm_ctx* ctx, const uint8_t* in, uint8_t* out, int n_frames, int H, int W, int sx, int sy, size_t frame_stride) {
+  const uint8_t *frames = DIR == YUV_TO_BGR ? in : out, *planes = DIR == YUV_TO_BGR ? out : in;
+  size_t fsz;
+  WM_TRY(frame_codec_args(ctx, frames, planes, n_frames, H, W, sx, sy, frame_stride, &fsz));
+  if (!fsz) return WM_OK;
+  const uintptr_t f0 = (uintptr_t)frames, p0 = (uintptr_t)planes;
+  const bool vec = W % 16 == 0 && ((f0 | p0) & 15u) == 0 && (n_frames == 1 || frame_stride % 16 == 0);
+  if (sx == 1) launch_frame_codec<DIR, 1, 1>(ctx, vec, in, out, n_frames, H, W, frame_stride);
+  else if (sy == 1) launch_frame_codec<DIR, 2, 1>(ctx, vec, in, out, n_frames, H, W, frame_stride);
+  else launch_frame_codec<DIR, 2, 2>(ctx, vec, in, out, n_frames, H, W, frame_stride);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// host-pointer form: one H2D, one launch, one D2H, one sync for the whole batch.  Host frames lie frame_stride apart; the
+// device copy is packed (a 2-D copy skips the gaps in both directions, so an encode leaves them untouched)
+template <int DIR>
+int frame_codec_host(wm_ctx* ctx, const uint8_t* in, uint8_t* out, int n_frames, int H, int W, int sx, int sy, size_t frame_stride) {
+  const uint8_t *frames = DIR == YUV_TO_BGR ? in : out, *planes = DIR == YUV_TO_BGR ? out : in;
+  size_t fsz;
+  WM_TRY(frame_codec_args(ctx, frames, planes, n_frames, H, W, sx, sy, frame_stride, &fsz));
+  if (!fsz) return WM_OK;
+  const size_t psz = (size_t)n_frames * 3 * H * W;
+  uint8_t *d_frames, *d_planes;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_frames = cv.take<uint8_t>((size_t)n_frames * fsz); d_planes = cv.take<uint8_t>(psz);
+  }));
+  if (DIR == YUV_TO_BGR) {
+    WM_HIP(hipMemcpy2DAsync(d_frames, fsz, in, frame_stride, fsz, (size_t)n_frames, hipMemcpyHostToDevice, ctx->stream));
+    WM_TRY(frame_codec_dispatch<DIR>(ctx, d_frames, d_planes, n_frames, H, W, sx, sy, fsz));
+    WM_HIP(hipMemcpyAsync(out, d_planes, psz, hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    WM_HIP(hipMemcpyAsync(d_planes, in, psz, hipMemcpyHostToDevice, ctx->stream));
+    WM_TRY(frame_codec_dispatch<DIR>(ctx, d_planes, d_frames, n_frames, H, W, sx, sy, fsz));
+    WM_HIP(hipMemcpy2DAsync(out, frame_stride, d_frames, fsz, fsz, (size_t)n_frames, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  WM_HIP(hipStreamSynchronize(ctx->stream));
+  return WM_OK;
+}
+
 GaussTaps make_taps() {     // cv2.getGaussianKernel(11, 1.5)
   GaussTaps g;
   double s = 0, v[11];
@@ -563,6 +753,16 @@ int wm_bgr_to_y_u8_dev(wm_ctx* ctx, const uint8_t* bgr, uint8_t* y, size_t n_px)
 int wm_replace_y_u8_dev(wm_ctx* ctx, const uint8_t* bgr, const uint8_t* y_new, uint8_t* bgr_out, size_t n_px) {
   if ((!y_new || !bgr_out) && n_px) return set_err(WM_ERR_BADARG, "NULL argument");
   return color_dispatch(ctx, Y_INTO_YCC_TO_BGR, bgr, y_new, bgr_out, nullptr, n_px);
+}
+
+// stored Y, Cb, Cr frames <-> planar B, G, R (k_frame_codec)
+int wm_yuv_frames_to_bgr_planes_u8_dev(wm_ctx* ctx, const uint8_t* frames, uint8_t* planes, int n_frames, int H, int W,
+                                       int sub_x, int sub_y, size_t frame_stride) {
+  return frame_codec_dispatch<YUV_TO_BGR>(ctx, frames, planes, n_frames, H, W, sub_x, sub_y, frame_stride);
+}
+int wm_bgr_planes_to_yuv_frames_u8_dev(wm_ctx* ctx, const uint8_t* planes, uint8_t* frames, int n_frames, int H, int W,
+                                       int sub_x, int sub_y, size_t frame_stride) {
+  return frame_codec_dispatch<BGR_TO_YUV>(ctx, planes, frames, n_frames, H, W, sub_x, sub_y, frame_stride);
 }
 
 // sum of squared differences (device scalar, exact integer); psnr = 20 log10(255 / sqrt(ssd / n))
@@ -691,6 +891,15 @@ int wm_color_u8(wm_ctx* ctx, int op, const uint8_t* in3, const uint8_t* plane_in
   }
   WM_HIP(hipStreamSynchronize(ctx->stream));
   return WM_OK;
+}
+
+int wm_yuv_frames_to_bgr_planes_u8(wm_ctx* ctx, const uint8_t* frames, uint8_t* planes, int n_frames, int H, int W,
+                                   int sub_x, int sub_y, size_t frame_stride) {
+  return frame_codec_host<YUV_TO_BGR>(ctx, frames, planes, n_frames, H, W, sub_x, sub_y, frame_stride);
+}
+int wm_bgr_planes_to_yuv_frames_u8(wm_ctx* ctx, const uint8_t* planes, uint8_t* frames, int n_frames, int H, int W,
+                                   int sub_x, int sub_y, size_t frame_stride) {
+  return frame_codec_host<BGR_TO_YUV>(ctx, planes, frames, n_frames, H, W, sub_x, sub_y, frame_stride);
 }
 
 int wm_psnr_u8(wm_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, double* psnr_out) {

@@ -107,6 +107,10 @@ SIGNATURES = {
     "wm_unpermute_normalize_u8_dev": [_vp, _vp, _vp, _vp, _sz, _i, _i],
     "wm_permute_u8_f32_routed_dev": [_vp, _vp, _vp, _vp, _sz, _i],
     "wm_extract_unscrambled_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _i, _i],
+    "wm_yuv_frames_to_bgr_planes_u8_dev": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz],
+    "wm_bgr_planes_to_yuv_frames_u8_dev": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz],
+    "wm_yuv_frames_to_bgr_planes_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz],
+    "wm_bgr_planes_to_yuv_frames_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz],
     "wm_color_u8": [_vp, _i, _vp, _vp, _vp, _vp, _sz],
     "wm_psnr_u8": [_vp, _vp, _vp, _sz, C.POINTER(C.c_double)],
     "wm_ssim": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_double)],
@@ -789,6 +793,62 @@ class Context:
                 raise ValueError("plane must be [H, W]")
             pin = _p(plane)
         self._call("wm_color_u8", code, _p(img), pin, _p(out), None, H * W)
+        return out
+
+    # ---- frame codec: stored Y, Cb, Cr frames (chroma subsampled sub = (sx, sy)) <-> planar B, G, R ----------------
+    @staticmethod
+    def frame_bytes(H: int, W: int, sub) -> int:
+        """bytes of one stored frame: Y [H, W], then Cb and Cr [ceil(H / sy), ceil(W / sx)]"""
+        sx, sy = sub
+        return H * W + 2 * (-(-H // sy)) * (-(-W // sx))
+
+    def yuv_frames_to_bgr_planes_u8_dev(self, frames, planes, n_frames, H, W, sub, frame_stride):
+        self._call("wm_yuv_frames_to_bgr_planes_u8_dev", _vp(frames), _vp(planes), n_frames, H, W, int(sub[0]), int(sub[1]),
+                   frame_stride)
+
+    def bgr_planes_to_yuv_frames_u8_dev(self, planes, frames, n_frames, H, W, sub, frame_stride):
+        self._call("wm_bgr_planes_to_yuv_frames_u8_dev", _vp(planes), _vp(frames), n_frames, H, W, int(sub[0]), int(sub[1]),
+                   frame_stride)
+
+    @staticmethod
+    def _frames_layout(frames: np.ndarray, fsz: int) -> int:
+        """frame_stride in bytes of uint8 [n, fsz] frames whose rows may lie further apart than fsz"""
+        if frames.dtype != np.uint8 or frames.ndim != 2 or frames.shape[1] != fsz:
+            raise ValueError(f"frames must be uint8 [n, {fsz}]")
+        n = frames.shape[0]
+        if n * fsz == 0:                           # nothing is addressed (NumPy gives an empty array arbitrary strides)
+            return fsz
+        if fsz > 1 and frames.strides[1] != 1:
+            raise ValueError("a frame's bytes must be contiguous")
+        if n > 1 and frames.strides[0] < fsz:
+            raise ValueError("frames overlap")
+        return frames.strides[0] if n > 1 else fsz
+
+    def yuv_frames_to_bgr_planes(self, frames: np.ndarray, H: int, W: int, sub) -> np.ndarray:
+        """frames uint8 [n, H*W + 2*ch*cw] (Y, Cb, Cr planes of each frame, packed) -> B, G, R planes uint8 [n, 3, H, W]:
+        chroma replicated to full resolution, OpenCV's 8-bit YCrCb2BGR per pixel.  One upload, launch and download."""
+        fsz = self.frame_bytes(H, W, sub)
+        stride = self._frames_layout(frames, fsz)
+        planes = np.empty((frames.shape[0], 3, H, W), np.uint8)
+        self._call("wm_yuv_frames_to_bgr_planes_u8", _p(frames), _p(planes), frames.shape[0], H, W, int(sub[0]), int(sub[1]),
+                   stride)
+        return planes
+
+    def bgr_planes_to_yuv_frames(self, planes: np.ndarray, sub, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """B, G, R planes uint8 [n, 3, H, W] -> stored frames uint8 [n, H*W + 2*ch*cw]: OpenCV's 8-bit BGR2YCrCb per pixel,
+        Cb and Cr averaged over each sx x sy block (half up; edge blocks over the pixels that exist).  ``out``: frames to
+        write into, which may lie further apart than a frame (the bytes between them are left alone)."""
+        if planes.dtype != np.uint8 or planes.ndim != 4 or planes.shape[1] != 3:
+            raise ValueError("planes must be uint8 [n, 3, H, W]")
+        planes = np.ascontiguousarray(planes)
+        n, _, H, W = planes.shape
+        fsz = self.frame_bytes(H, W, sub)
+        if out is None:
+            out = np.empty((n, fsz), np.uint8)
+        elif out.shape[0] != n:
+            raise ValueError(f"out must hold {n} frames")
+        stride = self._frames_layout(out, fsz)
+        self._call("wm_bgr_planes_to_yuv_frames_u8", _p(planes), _p(out), n, H, W, int(sub[0]), int(sub[1]), stride)
         return out
 
     def psnr(self, a: np.ndarray, b: np.ndarray) -> float:

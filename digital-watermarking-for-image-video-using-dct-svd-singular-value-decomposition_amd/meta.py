@@ -38,6 +38,8 @@ def sw_key(n: str) -> str:
 _GRAY = ("Sc", "Uw", "Vwt", "Sw")
 _IMAGE_COMMON = ("payload_type", "shape", "alpha", "kfrac", "nonce", "tile", "k_floor")
 _VIDEO_COMMON = ("payload_type", "shape", "alpha", "kfrac", "frame_interval", "n_frames", "tile", "k_floor", "nonce")
+# a colour video meta written from a subsampled container names it ("420" / "422") directly after n_frames
+_VIDEO_COLOR_COMMON = tuple(x for k in _VIDEO_COMMON for x in ((k, "chroma") if k == "n_frames" else (k,)))
 _BY_CHANNEL = tuple(f(n) for n in CHANNELS for f in (s_key, uw_key, vwt_key, sw_key))
 _BY_CHANNEL_THEN_S = tuple(f(n) for n in CHANNELS for f in (uw_key, vwt_key, sw_key)) + tuple(s_key(n) for n in CHANNELS)
 
@@ -46,7 +48,7 @@ _ORDER = {
     "gray": ("mode",) + _GRAY + _IMAGE_COMMON + ("digest",),                                # single:183-189 (+ tile, k_floor)
     "color": ("mode",) + _IMAGE_COMMON + _BY_CHANNEL + ("digest",),                         # single:157-166 (+ tile, k_floor)
     "video_gray": ("mode", "payload_type") + _GRAY + _VIDEO_COMMON[1:] + ("digest",),
-    "video_color": ("mode",) + _VIDEO_COMMON + ("digest",) + _BY_CHANNEL,
+    "video_color": ("mode",) + _VIDEO_COLOR_COMMON + ("digest",) + _BY_CHANNEL,
 }
 _ORDER_FULL_FRAME = dict(_ORDER, color=("mode",) + _IMAGE_COMMON + _BY_CHANNEL_THEN_S + ("digest",))
 
@@ -94,6 +96,23 @@ def channel_members(S, UW, VWt, SW) -> dict:
     return out
 
 
+# 8-bit Y4M chroma tags -> chroma format (the tag without its siting suffix)
+_CHROMA_FORMAT = {"420": "420", "420jpeg": "420", "420mpeg2": "420", "420paldv": "420", "422": "422", "444": "444"}
+
+
+def chroma_format(container_tag: str) -> str:
+    """A Y4M chroma tag with its siting suffix stripped: "420jpeg" -> "420".  Any other tag ("mono", "420p10",
+    "444alpha") is no 8-bit three-plane format and stands for itself."""
+    return _CHROMA_FORMAT.get(container_tag, container_tag)
+
+
+def chroma_members(container_tag: str) -> dict:
+    """The chroma format of the subsampled container a colour video was written to; a 4:4:4 meta has no such member and
+    stays what it was."""
+    fmt = chroma_format(container_tag)
+    return {} if fmt == "444" else dict(chroma=fmt)
+
+
 def sealed(members: dict, tile: Optional[int], digest: bytes) -> dict:
     """The meta as it goes to the file: the members (``mode`` among them) in their writer's order, with the digest."""
     have = dict(members, digest=np.frombuffer(digest, dtype=np.uint8))
@@ -135,6 +154,11 @@ def tile_of(meta) -> Optional[int]:
         return TILE
     s = meta["Sc"] if "Sc" in meta else meta[s_key(CHANNELS[0])]
     return TILE if np.asarray(s).ndim == 3 else None
+
+
+def chroma_of(meta) -> str:
+    """Chroma format of the container a colour video meta was written for: its ``chroma`` member, else 4:4:4."""
+    return str(meta["chroma"]) if "chroma" in meta else "444"
 
 
 def by_channel(meta, key_rule) -> list:

@@ -171,6 +171,15 @@ def embed_frames_sharded(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndar
 # frames per channel.  Container: 8-bit 4:4:4 ``.y4m`` (planes Y, Cb, Cr); the frames pass through OpenCV's fixed-point
 # YCrCb <-> BGR conversion on the device (``wm_color_u8``) on the way in and out, so - like any YUV container - the stored
 # stego differs from the embedded BGR planes by that conversion's rounding (a grey level or two per channel).  No audio remux.
+#
+# 4:2:0 (``C420``, ``C420jpeg``, ``C420mpeg2``, ``C420paldv``) and 4:2:2 (``C422``) containers, ``subsampling="box"``: the
+# chroma planes are ceil(H / sy) x ceil(W / sx).  On the way in every pixel takes the chroma sample of its block (replication),
+# then the same YCrCb -> BGR conversion; on the way out BGR -> YCrCb, Y stored as is, Cb and Cr each the mean over the pixels
+# of their sx x sy block that lie inside the plane, rounded half up in integers ((2 sum + cnt) // (2 cnt), cnt 1, 2 or 4).
+# Averaging replicated chroma gives it back exactly, so a frame the embed did not change keeps its chroma bytes.  The
+# siting the tag names (jpeg: centred, mpeg2: co-sited left, paldv) travels in the copied header line and is otherwise
+# ignored: one filter for all of them.  Both directions run on the device for all marked frames of a flush in one call
+# (``wm_yuv_frames_to_bgr_planes_u8`` / ``wm_bgr_planes_to_yuv_frames_u8``), planar on both sides.
 # ---------------------------------------------------------------------------
 def _frame_to_bgr_planes(ctx: hostapi.Context, y: np.ndarray, chroma: np.ndarray, H: int, W: int) -> np.ndarray:
     cb = chroma[:H * W].reshape(H, W); cr = chroma[H * W:].reshape(H, W)
@@ -209,28 +218,60 @@ def embed_frames_color(ctx: hostapi.Context, planes: np.ndarray, Sw: np.ndarray,
 
 # ---------------------------------------------------------------------------
 # file level (names of the reference's bytecode-only video modules).  One loop, one reader, one extract and one detect,
-# over [n, C, H, W] planes; what differs between luma (C = 1) and 4:4:4 colour (C = 3) is the frame codec.
+# over [n, C, H, W] planes; what differs between luma (C = 1), 4:4:4 colour and subsampled colour (C = 3) is the frame codec:
+#   planes(ctx, [(y, chroma), ...], H, W) -> [n, C, H, W]      frame_bytes(ctx, stego [n, C, H, W], [chroma, ...]) -> per frame,
+#   the byte strings that follow its FRAME line.  Both take all marked frames of a flush.
 # ---------------------------------------------------------------------------
 _Codec = collections.namedtuple("_Codec", "mode writer chroma prepare planes frame_bytes members")
 # luma: the luma plane IS the plane the hot path works on ([1, H, W]); write-back replaces y and keeps the chroma bytes
 _Luma = _Codec(
     mode="video_gray", writer="embed_watermark_video", chroma=None,
     prepare=lambda ctx, wm_bgr, H, W, key, tile: [x[None] for x in prepare_watermark(ctx, wm_bgr, H, W, key, tile)[:3]],
-    planes=lambda ctx, y, chroma, H, W: y[None],
-    frame_bytes=lambda ctx, planes, chroma: (planes[0].tobytes(), chroma.tobytes()),
+    planes=lambda ctx, frames, H, W: np.stack([y[None] for y, _ in frames]),
+    frame_bytes=lambda ctx, st, chromas: [(p[0].tobytes(), c.tobytes()) for p, c in zip(st, chromas)],
     members=lambda S, Uw, Vwt, Sw: M.gray_members(S[0], Uw[0], Vwt[0], Sw[0]))
 # 4:4:4 colour: the B, G, R planes of a frame ([3, H, W]); write-back converts the three stego planes to Y, Cb, Cr
 _Bgr444 = _Codec(
     mode="video_color", writer="embed_watermark_video_color", chroma="444",
     prepare=lambda ctx, wm_bgr, H, W, key, tile: prepare_watermark_color(ctx, wm_bgr, H, W, key, tile)[:3],
-    planes=_frame_to_bgr_planes,
-    frame_bytes=lambda ctx, planes, chroma: [p.tobytes() for p in _bgr_planes_to_frame(ctx, planes)],
+    planes=lambda ctx, frames, H, W: np.stack([_frame_to_bgr_planes(ctx, y, chroma, H, W) for y, chroma in frames]),
+    frame_bytes=lambda ctx, st, chromas: [[p.tobytes() for p in _bgr_planes_to_frame(ctx, planes)] for planes in st],
     members=M.channel_members)                                             # the colour image meta's key names (single:157-166)
 
 
-def _check_container(codec, vid: Y4M, refusal: str):
-    if codec.chroma and vid.chroma != codec.chroma:
+def _bgr_subsampled(tag: str) -> _Codec:
+    """Colour on a 4:2:0 / 4:2:2 container (tag as in the header, e.g. "420jpeg"): the B, G, R planes of all marked frames of
+    a flush come from, and go back to, the stored frames through the device's frame codec, one call each way."""
+    sub = _CHROMA_DIV[tag]
+
+    def planes(ctx, frames, H, W):
+        packed = np.empty((len(frames), ctx.frame_bytes(H, W, sub)), np.uint8)
+        for f, (y, chroma) in zip(packed, frames):
+            f[:H * W] = y.ravel(); f[H * W:] = chroma
+        return ctx.yuv_frames_to_bgr_planes(packed, H, W, sub)
+
+    return _Bgr444._replace(
+        chroma=tag, planes=planes,
+        frame_bytes=lambda ctx, st, chromas: [(f.tobytes(),) for f in ctx.bgr_planes_to_yuv_frames(st, sub)],
+        members=lambda *arrays: dict(M.channel_members(*arrays), **M.chroma_members(tag)))
+
+
+SUBSAMPLING = ("refuse", "box")
+
+
+def _check_subsampling(subsampling) -> None:
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of {SUBSAMPLING}, got {subsampling!r}")
+
+
+def _container_codec(codec, vid: Y4M, accept, refusal: str) -> _Codec:
+    """The codec that reads and writes this container, for a caller that takes the chroma formats ``accept`` (siting
+    suffix stripped: "444", "420", "422").  The luma codec takes every container."""
+    if not codec.chroma:
+        return codec
+    if M.chroma_format(vid.chroma) not in accept:
         raise ValueError(refusal)
+    return codec if vid.chroma == codec.chroma else _bgr_subsampled(vid.chroma)
 
 
 def _is_marked(i: int, frame_interval: int) -> bool:
@@ -238,14 +279,16 @@ def _is_marked(i: int, frame_interval: int) -> bool:
 
 
 def _embed_video(codec, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
-                 password, nonce, kfrac, k_floor, batch, device, tile):
+                 password, nonce, kfrac, k_floor, batch, device, tile, subsampling="refuse"):
     M.check_tile(tile)
     M.require_password(password, "embed")
+    _check_subsampling(subsampling)
     ctx = hostapi.Context(device)
     vid = Y4M(host_video_path)
     try:
-        _check_container(codec, vid, "embed_watermark_video_color needs an 8-bit 4:4:4 .y4m (C444): per-channel embedding "
-                                     "needs full-resolution chroma")
+        codec = _container_codec(codec, vid, ("444", "420", "422") if subsampling == "box" else ("444",),
+                                 "embed_watermark_video_color needs an 8-bit 4:4:4 .y4m (C444): per-channel embedding "
+                                 "needs full-resolution chroma")
         H, W = vid.H, vid.W
         if nonce is None:
             nonce = os.urandom(8)
@@ -261,16 +304,17 @@ def _embed_video(codec, host_video_path, watermark_path, output_video_path, meta
             def flush():
                 marked = [p for p in pend if p[3]]
                 if marked:
-                    planes = np.stack([codec.planes(ctx, p[1], p[2], H, W) for p in marked])     # [n, C, H, W]
+                    planes = codec.planes(ctx, [p[1:3] for p in marked], H, W)                   # [n, C, H, W]
                     st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile)
                     for ch, c in enumerate(sc):
                         sc_all[ch].append(c)
                     psnrs.extend(hg.psnr(planes[i], st[i]) for i in range(len(marked)))
+                    stored = codec.frame_bytes(ctx, st, [p[2] for p in marked])
                 j = 0
                 for line, y, chroma, is_marked in pend:
                     out.write(line)
                     if is_marked:
-                        out.writelines(codec.frame_bytes(ctx, st[j], chroma)); j += 1
+                        out.writelines(stored[j]); j += 1
                     else:
                         out.write(y.tobytes()); out.write(chroma.tobytes())
                 pend.clear()
@@ -301,22 +345,29 @@ def _load_video_meta(codec, metadata_path: str):
     return data
 
 
-def _marked_planes(codec, ctx: hostapi.Context, stego_video_path: str, data, n: int, C: int) -> np.ndarray:
-    """The first n marked frames' planes, uint8 [n, C, H, W]."""
+def _marked_planes(codec, ctx: hostapi.Context, stego_video_path: str, data, n: int, C: int, batch: int) -> np.ndarray:
+    """The first n marked frames' planes, uint8 [n, C, H, W], decoded ``batch`` frames at a time.  The container must be what
+    the meta was written for: a colour meta's ``chroma`` member, 4:4:4 when it has none."""
     vid = Y4M(stego_video_path)
     try:
-        _check_container(codec, vid, "a colour-watermarked video is 4:4:4")
+        want = M.chroma_of(data)
+        codec = _container_codec(codec, vid, (want,), "a colour-watermarked video is 4:4:4" if want == "444" else
+                                 f"the metadata was written for a C{want} video, this one is C{vid.chroma}")
         fi = int(data["frame_interval"])
         H, W = vid.H, vid.W
-        out = []
+        out, pend, seen = [], [], 0
         for i, (_, y, chroma) in enumerate(vid):
-            if _is_marked(i, fi) and len(out) < n:
-                out.append(codec.planes(ctx, y, chroma, H, W))
+            if _is_marked(i, fi) and seen < n:
+                pend.append((y, chroma)); seen += 1
+                if len(pend) >= batch:
+                    out.append(codec.planes(ctx, pend, H, W)); pend = []
+        if pend:
+            out.append(codec.planes(ctx, pend, H, W))
     finally:
         vid.close()
-    if len(out) < n:
+    if seen < n:
         raise ValueError("video has fewer marked frames than the metadata")
-    return np.stack(out) if out else np.zeros((0, C) + tuple(map(int, data["shape"])), np.uint8)
+    return np.concatenate(out) if out else np.zeros((0, C) + tuple(map(int, data["shape"])), np.uint8)
 
 
 def _extract_video(codec, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance):
@@ -330,7 +381,7 @@ def _extract_video(codec, stego_video_path, metadata_path, output_image_path, pa
     ctx = hostapi.Context(device)
     try:
         factors = M.per_plane(data, "Sc", "Uw", "Vwt")
-        planes = _marked_planes(codec, ctx, stego_video_path, data, factors[0][0].shape[0], len(factors))
+        planes = _marked_planes(codec, ctx, stego_video_path, data, factors[0][0].shape[0], len(factors), batch)
         tile = M.tile_of(data)
         K = M.k_of(tile or min(H, W), M.kfrac_of(data), M.k_floor_of(data))
         idx = hg.permutation_index(H, W, key)
@@ -352,7 +403,7 @@ def _detect_video(codec, stego_video_path, metadata_path, thresh, batch, device)
     ctx = hostapi.Context(device)
     try:
         sigmas = M.per_plane(data, "Sc", "Sw")
-        planes = _marked_planes(codec, ctx, stego_video_path, data, sigmas[0][0].shape[0], len(sigmas))
+        planes = _marked_planes(codec, ctx, stego_video_path, data, sigmas[0][0].shape[0], len(sigmas), batch)
         tile = M.tile_of(data)
         per_ch = [detect_frames(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Sw, float(data["alpha"]), batch, tile)
                   for ch, (Sc, Sw) in enumerate(sigmas)]
@@ -391,11 +442,17 @@ def detect_watermark_video(stego_video_path: str, metadata_path: str, thresh: fl
 def embed_watermark_video_color(host_video_path: str, watermark_path: str, output_video_path: str,
                                 metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
                                 password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
-                                k_floor: int = 8, batch: int = 8, device: int = 0, tile: Optional[int] = TILE):
-    """Embed a colour watermark into the B, G, R planes of every ``frame_interval``-th frame of a 4:4:4 .y4m video.
-    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' BGR planes)."""
+                                k_floor: int = 8, batch: int = 8, device: int = 0, tile: Optional[int] = TILE,
+                                subsampling: str = "refuse"):
+    """Embed a colour watermark into the B, G, R planes of every ``frame_interval``-th frame of a .y4m video.
+    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' BGR planes).
+    ``subsampling``: what to do with a container whose chroma is subsampled.  "refuse" (default): only 4:4:4 (C444) is
+    taken.  "box": 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv) and 4:2:2 (C422) are taken too - chroma is replicated to
+    full resolution on the way in and box-averaged (half up) on the way out; the siting a C420* tag names is carried
+    through in the header and otherwise ignored, one filter serves all of them.  The meta then names the chroma format
+    and extract / detect read the same kind of container with nothing but the meta and the password."""
     return _embed_video(_Bgr444, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
-                        password, nonce, kfrac, k_floor, batch, device, tile)
+                        password, nonce, kfrac, k_floor, batch, device, tile, subsampling)
 
 
 def extract_watermark_video_color(stego_video_path: str, metadata_path: str, output_image_path: str, password: str,

@@ -349,6 +349,28 @@ int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float
 /* the scramble direction through the same route (single:66-72, 124-126): dst[p][i] = (float) src[p][idx[i]], uint8 planes
  * in, float32 out; values identical to wm_permute_u8_f32_dev */
 int wm_permute_u8_f32_routed_dev(wm_ctx* ctx, const uint8_t* src, const wm_route* route, float* dst, size_t n, int n_planes);
+/* The frame codec of the colour video functions: stored planar Y, Cb, Cr frames <-> planar B, G, R, a whole batch of
+ * frames per launch.  Replaces, per frame, the host-side np.stack / cvtColor(YCrCb2BGR) / moveaxis chain (and its
+ * reverse) that wraps single:21-30's conversion around a 4:4:4 frame, and adds the chroma resampling a 4:2:0 or 4:2:2
+ * container needs, which the reference (cv2.VideoCapture hands it BGR) never sees.
+ *   frames  [n_frames] frames of Y [H][W], Cb [ch][cw], Cr [ch][cw] (the YUV4MPEG2 frame layout, packed), frame_stride
+ *           BYTES apart (>= H*W + 2*ch*cw); ch x cw = ceil(H / sub_y) x ceil(W / sub_x)
+ *   planes  [n_frames][3][H][W] contiguous, B, G, R
+ *   sub_x, sub_y   1, 1 (4:4:4), 2, 1 (4:2:2) or 2, 2 (4:2:0); chroma siting is not modelled
+ * to_bgr: every pixel (r, c) takes chroma sample (r / sub_y, c / sub_x) (replication) through YCrCb2BGR.  to_yuv: every
+ * pixel through BGR2YCrCb; Y as is; Cb, Cr the mean over the block's pixels inside the plane, rounded half up in integers.
+ * sub 1, 1 gives wm_ycrcb_to_bgr_u8_dev / wm_bgr_to_ycrcb_u8_dev on the interleaved form, bit for bit.  Any H, W >= 1 and
+ * any alignment; W % 16 == 0 with 16-byte aligned bases (and frame_stride) takes 16-byte accesses.  Never in place. */
+int wm_yuv_frames_to_bgr_planes_u8_dev(wm_ctx* ctx, const uint8_t* frames, uint8_t* planes, int n_frames, int H, int W,
+                                       int sub_x, int sub_y, size_t frame_stride);
+int wm_bgr_planes_to_yuv_frames_u8_dev(wm_ctx* ctx, const uint8_t* planes, uint8_t* frames, int n_frames, int H, int W,
+                                       int sub_x, int sub_y, size_t frame_stride);
+/* the same on host memory: one upload, one launch, one download and one synchronise per call; bytes between the frames
+ * (frame_stride > a frame) are neither read nor written */
+int wm_yuv_frames_to_bgr_planes_u8(wm_ctx* ctx, const uint8_t* frames, uint8_t* planes, int n_frames, int H, int W,
+                                   int sub_x, int sub_y, size_t frame_stride);
+int wm_bgr_planes_to_yuv_frames_u8(wm_ctx* ctx, const uint8_t* planes, uint8_t* frames, int n_frames, int H, int W,
+                                   int sub_x, int sub_y, size_t frame_stride);
 /* host-pointer conveniences; op: 0 BGR->YCrCb, 1 YCrCb->BGR, 2 BGR->gray plane, 3 BGR->Y plane,
  * 4 replace Y (plane_in) and return BGR */
 int wm_color_u8(wm_ctx* ctx, int op, const uint8_t* in3, const uint8_t* plane_in, uint8_t* out3,
