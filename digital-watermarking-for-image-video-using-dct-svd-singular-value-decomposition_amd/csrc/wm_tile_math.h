@@ -1289,4 +1289,41 @@ WM_HD void extract_tile_px(const float (&s_cw)[8], const float (&sc)[8], const f
     }
 }
 
+// ---- texture-masked strength ("Texture-masked strength") ----------
+// A tile's gain is a function of its COVER singular values alone, so embed, extract and detect agree on it with no side
+// information beyond the Sc every tile-mode meta already holds.  r = sqrt(s_2^2 + .. + s_8^2) is what the best rank-1 fit
+// of the tile leaves over (Frobenius units over 64 pixels); g = clamp((r - lo) / (hi - lo), 0, 1), all in float32, the
+// squares summed in index order by fused multiply-adds.  The embed adds alpha * G * sigma_w with G = (1, g, .., g): the leading
+// component (the brightness shift every tile shares) stays uniform.  sqrtf and the division are the correctly rounded ones
+// (not v_sqrt_f32 / frcp, which are good to an ulp), so this function gives the same g for the same float32 sc on host and
+// device, and a tile on the edge of `cut` is carried by both or by neither.  (A restatement that sums the squares in another
+// order, as NumPy does, can differ in the last bit of r.)
+WM_HD float mask_gain(const float (&sc)[8], const float lo, const float hi) {
+  float r2 = 0.0f;
+#pragma unroll
+  for (int i = 1; i < 8; ++i) r2 = ffma(sc[i], sc[i], r2);
+  const float g = (sqrtf(r2) - lo) / (hi - lo);
+  return fminf(fmaxf(g, 0.0f), 1.0f);
+}
+
+// a tile carries its i >= 2 values iff g >= cut (0 < cut <= 1, so a carried tile has g > 0)
+WM_HD bool mask_carried(const float g, const float cut) { return g >= cut; }
+
+// G o sigma_w: what the unchanged embed is fed for a masked tile
+WM_HD void mask_sigma_w(const float g, float (&sw)[8]) {
+#pragma unroll
+  for (int i = 1; i < 8; ++i) sw[i] *= g;
+}
+
+// The extract's keep[] with the rule folded in: 1 for the leading value, 1 / g for the others of a carried tile, 0 for
+// those of a tile that is not carried, and 0 from K on.  Returns whether the tile is carried.
+WM_HD bool mask_keep(const float (&sc)[8], const float lo, const float hi, const float cut, const int K, float (&keep)[8]) {
+  const float g = mask_gain(sc, lo, hi);
+  const bool carried = mask_carried(g, cut);
+  const float inv_g = carried ? 1.0f / g : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) keep[i] = (i < K) ? (i == 0 ? 1.0f : inv_g) : 0.0f;
+  return carried;
+}
+
 }  // namespace wm

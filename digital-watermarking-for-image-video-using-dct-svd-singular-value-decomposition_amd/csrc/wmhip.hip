@@ -592,6 +592,30 @@ __global__ __launch_bounds__(WAVE, 3) void k_sigma_tiles(const uint8_t* __restri
   store_row8_f32<true>(sigma + (plane * g.n_tiles + t) * 8, s);
 }
 
+// K2 + the masked embed's gain (wm_tile_math.h, mask_gain): the tile's cover singular values -> g, and G o sigma_w of the
+// tile to a dense [plane][tile][8] array that the unchanged embed launches are then fed with a per-plane stride; with
+// `gain`, g itself to [plane][tile].  sigma_w may be shared by the planes (sw_plane_stride 0); without sw_eff only g is left.
+template <bool ALIGNED>
+__global__ __launch_bounds__(WAVE, 3) void k_mask_sigma_w(const uint8_t* __restrict__ planes, const float* __restrict__ sigma_w,
+                                                      float* __restrict__ sw_eff, float* __restrict__ gain, const Geom g,
+                                                      const size_t sw_plane_stride, const float lo, const float hi,
+                                                      int* __restrict__ status) {
+  int t, ty, tx;
+  if (!tile_coords(g, t, ty, tx)) return;
+  const size_t plane = blockIdx.y;
+  wm::RawTile raw;
+  float s[8], sw[8];
+  load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
+  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
+  const float gn = wm::mask_gain(s, lo, hi);
+  if (sw_eff) {
+    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    wm::mask_sigma_w(gn, sw);
+    store_row8_f32<true>(sw_eff + (plane * g.n_tiles + t) * 8, sw);
+  }
+  if (gain) gain[plane * g.n_tiles + t] = gn;
+}
+
 // ---------------------------------------------------------------------------
 // K3  full SVD of float tiles (watermark side)
 // ---------------------------------------------------------------------------
@@ -636,12 +660,15 @@ __global__ __launch_bounds__(WAVE, 2) void k_svd_tiles(const float* __restrict__
 // MM: the wave also leaves the {min, max} of its 4 096 outputs (order-preserving uint form) in mm[plane][tile group]: the
 // min-max pass of the normalise that follows the unscramble (single:221) costs nothing extra then.  Lanes past the last tile
 // of a partial wave recompute the last tile (every lane takes part in the reduction) and store nothing.
-template <bool ALIGNED, bool VECF, bool PX, bool MM>
+// MASK: the texture-masked rule (wm_tile_math.h, mask_keep) folded into keep[] - 1 / g and the carried test from the sc
+// that is in registers anyway.  A template flag: the unmasked forms compile to what they were.
+struct MaskParams { float lo, hi, cut; };
+template <bool ALIGNED, bool VECF, bool PX, bool MM, bool MASK>
 __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
     const uint8_t* __restrict__ stego, const float* __restrict__ sigma_c,
     const float* __restrict__ Uw, const float* __restrict__ Vwt, float* __restrict__ out,
     const Geom g, const unsigned n_planes, const size_t uv_plane_stride, const float inv_alpha, const int K,
-    int* __restrict__ status, unsigned* __restrict__ mm) {
+    int* __restrict__ status, unsigned* __restrict__ mm, const MaskParams mk) {
   int t, ty, tx;
   size_t plane;
   bool valid = true;
@@ -659,8 +686,11 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
   load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
   if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
   load_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
+  if (MASK) wm::mask_keep(sc, mk.lo, mk.hi, mk.cut, K, keep);
+  else {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) keep[i] = (i < K) ? 1.0f : 0.0f;
+    for (int i = 0; i < 8; ++i) keep[i] = (i < K) ? 1.0f : 0.0f;
+  }
   float uw[8][8], vwt[8][8];
   const size_t mi = (plane * uv_plane_stride + (size_t)t) * 64;
   load_mat_f32(Uw + mi, uw);
@@ -746,14 +776,17 @@ __device__ __forceinline__ double wave_sum(double x) {
   return x;
 }
 
-template <bool ALIGNED>
+// MASK: the texture-masked rule - the five sums run over the leading value of every tile and the other seven of carried
+// tiles only, those scaled by 1 / g (wm_tile_math.h, mask_keep with K = 8); a sixth partial counts the values taken.
+template <bool ALIGNED, bool MASK>
 __global__ __launch_bounds__(WAVE, 3) void k_detect_tiles(
     const uint8_t* __restrict__ stego, const float* __restrict__ sigma_c,
     const float* __restrict__ sigma_w, double* __restrict__ partials, const Geom g,
-    const size_t sw_plane_stride, const float inv_alpha, int* __restrict__ status) {
+    const size_t sw_plane_stride, const float inv_alpha, int* __restrict__ status, const MaskParams mk) {
+  constexpr int NS = N_SUMS + (MASK ? 1 : 0);
   int t, ty, tx;
   const size_t plane = blockIdx.y;
-  double acc[N_SUMS] = {0, 0, 0, 0, 0};
+  double acc[NS] = {};
   if (tile_coords(g, t, ty, tx)) {
     wm::RawTile raw;
     float s[8], sc[8], sw[8];
@@ -761,44 +794,61 @@ __global__ __launch_bounds__(WAVE, 3) void k_detect_tiles(
     if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
     load_row8_f32<true>(sigma_c + (plane * g.n_tiles + t) * 8, sc);
     load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+    if (MASK) {
+      float keep[8];
+      const bool carried = wm::mask_keep(sc, mk.lo, mk.hi, mk.cut, 8, keep);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const double x = (double)sw[i];
-      const double y = (double)((s[i] - sc[i]) * inv_alpha);
-      acc[0] += x; acc[1] += y; acc[2] += x * y; acc[3] += x * x; acc[4] += y * y;
+      for (int i = 0; i < 8; ++i) {
+        if (i > 0 && !carried) continue;
+        const double x = (double)sw[i];
+        const double y = (double)((s[i] - sc[i]) * inv_alpha * keep[i]);
+        acc[0] += x; acc[1] += y; acc[2] += x * y; acc[3] += x * x; acc[4] += y * y;
+      }
+      acc[N_SUMS] = carried ? 8.0 : 1.0;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const double x = (double)sw[i];
+        const double y = (double)((s[i] - sc[i]) * inv_alpha);
+        acc[0] += x; acc[1] += y; acc[2] += x * y; acc[3] += x * x; acc[4] += y * y;
+      }
     }
   }
 #pragma unroll
-  for (int k = 0; k < N_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < NS; ++k) acc[k] = wave_sum(acc[k]);
   if (threadIdx.x == 0) {
-    double* o = partials + (plane * gridDim.x + blockIdx.x) * N_SUMS;
+    double* o = partials + (plane * gridDim.x + blockIdx.x) * NS;
 #pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) o[k] = acc[k];
+    for (int k = 0; k < NS; ++k) o[k] = acc[k];
   }
 }
 
+// MASK: the number of values comes from the sixth partial sum instead of n_vals
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_detect_finalize(const double* __restrict__ partials,
                                                         double* __restrict__ scores,
-                                                        const int n_waves, const double n_vals) {
-  __shared__ double sm[4][N_SUMS];
+                                                        const int n_waves, double n_vals) {
+  constexpr int NS = N_SUMS + (MASK ? 1 : 0);
+  __shared__ double sm[4][NS];
   const size_t plane = blockIdx.x;
-  double acc[N_SUMS] = {0, 0, 0, 0, 0};
+  double acc[NS] = {};
   for (int w = threadIdx.x; w < n_waves; w += blockDim.x) {
-    const double* p = partials + (plane * n_waves + w) * N_SUMS;
+    const double* p = partials + (plane * n_waves + w) * NS;
 #pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) acc[k] += p[k];
+    for (int k = 0; k < NS; ++k) acc[k] += p[k];
   }
 #pragma unroll
-  for (int k = 0; k < N_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < NS; ++k) acc[k] = wave_sum(acc[k]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) sm[threadIdx.x >> 6][k] = acc[k];
+    for (int k = 0; k < NS; ++k) sm[threadIdx.x >> 6][k] = acc[k];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double s[N_SUMS];
+    double s[NS];
 #pragma unroll
-    for (int k = 0; k < N_SUMS; ++k) s[k] = sm[0][k] + sm[1][k] + sm[2][k] + sm[3][k];
+    for (int k = 0; k < NS; ++k) s[k] = sm[0][k] + sm[1][k] + sm[2][k] + sm[3][k];
+    if (MASK) n_vals = s[N_SUMS];
     double score = 0.0;
     if (n_vals > 0) {
       // _nc (single:284-289): mean-removed correlation, +1e-8 in the denominator
@@ -848,6 +898,13 @@ inline bool f32_vec_ok(const void* p, size_t row_stride_elems, size_t plane_stri
 
 inline dim3 tile_grid(const Geom& g, int n_planes) {
   return dim3((unsigned)((g.n_tiles + WAVE - 1) / WAVE), (unsigned)n_planes, 1);
+}
+
+// the texture-masked rule's parameters (include/wmhip.h): 0 <= lo < hi, both finite; 0 < cut <= 1
+int check_mask(const float lo, const float hi, const float cut) {
+  if (!(isfinite(lo) && isfinite(hi) && lo >= 0.0f && lo < hi)) return set_err(WM_ERR_BADARG, "mask needs finite 0 <= lo < hi");
+  if (!(cut > 0.0f && cut <= 1.0f)) return set_err(WM_ERR_BADARG, "mask needs 0 < cut <= 1");
+  return WM_OK;
 }
 
 }  // namespace
@@ -916,6 +973,7 @@ int wm_destroy(wm_ctx* ctx) {
   if (ctx->ref_ws2) (void)hipFree(ctx->ref_ws2);
   if (ctx->route_tmp) (void)hipFree(ctx->route_tmp);
   if (ctx->extract_f32) (void)hipFree(ctx->extract_f32);
+  if (ctx->mask_sw) (void)hipFree(ctx->mask_sw);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) if (ctx->pair_tab[i]) (void)hipFree(ctx->pair_tab[i]);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) {
     if (ctx->hier_dev[i]) (void)hipFree(ctx->hier_dev[i]);
@@ -1078,6 +1136,50 @@ int wm_sigma_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, float* sigma, int 
   return WM_OK;
 }
 
+// ---- K2 + gain, masked K1 ----------------------------------------------------
+int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                                 int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float lo, float hi) {
+  WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_mask(lo, hi, 1.0f));
+  const Geom g = make_geom(H, W, row_stride, plane_stride);
+  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
+  if (!sigma_w != !sigma_w_eff) return set_err(WM_ERR_BADARG, "sigma_w and sigma_w_eff go together");
+  if (!sigma_w_eff && !gain) return set_err(WM_ERR_BADARG, "neither sigma_w_eff nor gain is asked for");
+  if ((((uintptr_t)sigma_w | (uintptr_t)sigma_w_eff) & 15u) || (sigma_w_plane_stride & 3u))
+    return set_err(WM_ERR_BADARG, "sigma_w / sigma_w_eff is not 16-byte aligned");
+  if (((uintptr_t)gain & 3u)) return set_err(WM_ERR_BADARG, "gain is not 4-byte aligned");
+  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+  with_bools([&](auto A) {
+    hipLaunchKernelGGL((k_mask_sigma_w<A.value>), grid, block, 0, ctx->stream, planes, sigma_w, sigma_w_eff, gain, g,
+                       sigma_w_plane_stride, lo, hi, ctx->d_status);
+  }, u8_aligned(planes, planes, row_stride, plane_stride));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// k_mask_sigma_w, then the unchanged embed launches fed G o sigma_w with a per-plane stride.  The sigma pass reads the host
+// planes before anything writes (one stream), so stego may alias host.  G o sigma_w lives in a grow-only buffer of the context.
+int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
+                                 float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi) {
+  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_mask(lo, hi, 1.0f));
+  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
+  if (K < 0 || K > 8) return set_err(WM_ERR_BADARG, "K must be in 0..8");
+  const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
+  float* eff = nullptr;
+  if (n_planes > 0 && nt8 > 0) {
+    if (!sigma_w || !sigma_c) return set_err(WM_ERR_BADARG, "sigma_w / sigma_c is NULL");
+    WM_TRY(staged(ctx, &ctx->mask_sw, &ctx->mask_sw_bytes, "masked sigma_w", [&](Carve& cv) {
+      eff = cv.take<float>((size_t)n_planes * nt8);
+    }));
+    WM_TRY(wm_mask_sigma_w_tiles_u8_dev(ctx, host, sigma_w, eff, nullptr, n_planes, H, W, row_stride, plane_stride,
+                                        sigma_w_plane_stride, lo, hi));
+  }
+  return wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, alpha, K);
+}
+
 // ---- K3 --------------------------------------------------------------------
 int wm_svd_tiles_f32_dev(wm_ctx* ctx, const float* planes, float* U, float* S, float* Vt,
                          int n_planes, int H, int W, int row_stride, size_t plane_stride) {
@@ -1097,8 +1199,10 @@ int wm_svd_tiles_f32_dev(wm_ctx* ctx, const float* planes, float* U, float* S, f
 // ---- K2+K4 -----------------------------------------------------------------
 static int extract_tiles_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
                              const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
-                             size_t plane_stride, size_t uv_plane_stride, float alpha, int K, bool px, unsigned* mm = nullptr) {
+                             size_t plane_stride, size_t uv_plane_stride, float alpha, int K, bool px, unsigned* mm = nullptr,
+                             const MaskParams* mask = nullptr) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  if (mask) WM_TRY(check_mask(mask->lo, mask->hi, mask->cut));
   if (!out) return set_err(WM_ERR_BADARG, "out is NULL");
   if (K < 0 || K > 8) return set_err(WM_ERR_BADARG, "K must be in 0..8");
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
@@ -1116,10 +1220,11 @@ static int extract_tiles_dev(wm_ctx* ctx, const uint8_t* stego, const float* sig
   if ((((size_t)g.n_tiles + WAVE - 1) / WAVE + N_XCD) * (size_t)n_planes > 0x7fffffffull)
     return set_err(WM_ERR_BADARG, "more than 2^31 tile groups in one call");
   const dim3 grid = tile_grid_planefast(g, n_planes), block(WAVE);
-  with_bools([&](auto P, auto A, auto V, auto M) {
-    hipLaunchKernelGGL((k_extract_tiles<A.value, V.value, P.value, M.value>), grid, block, 0, ctx->stream, stego, sigma_c, Uw, Vwt,
-                       out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm);
-  }, px, al, vf, mm != nullptr);
+  const MaskParams mk = mask ? *mask : MaskParams{0.0f, 1.0f, 1.0f};
+  with_bools([&](auto P, auto A, auto V, auto M, auto T) {
+    hipLaunchKernelGGL((k_extract_tiles<A.value, V.value, P.value, M.value, T.value>), grid, block, 0, ctx->stream, stego, sigma_c,
+                       Uw, Vwt, out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm, mk);
+  }, px, al, vf, mm != nullptr, mask != nullptr);
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1138,11 +1243,28 @@ int wm_extract_tiles_px_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* s
                            uv_plane_stride, alpha, K, true);
 }
 
+int wm_extract_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                   const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
+                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return extract_tiles_dev(ctx, stego, sigma_c, Uw, Vwt, out, n_planes, H, W, row_stride, plane_stride,
+                           uv_plane_stride, alpha, K, false, nullptr, &mk);
+}
+
+int wm_extract_tiles_px_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Ux,
+                                      const float* Vxt, float* out, int n_planes, int H, int W, int row_stride,
+                                      size_t plane_stride, size_t uv_plane_stride, float alpha, int K, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return extract_tiles_dev(ctx, stego, sigma_c, Ux, Vxt, out, n_planes, H, W, row_stride, plane_stride,
+                           uv_plane_stride, alpha, K, true, nullptr, &mk);
+}
+
 // single:203-222 per plane in one call: sigma + rank-8 product (K2+K4) -> routed unscramble -> min-max normalise -> uint8.
 // The float estimate lives in a grow-only buffer of the context; the min / max come out of the extract kernel itself.
-int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw, const float* Vwt,
-                                  const wm_route* route, uint8_t* out, int n_planes, int H, int W, int row_stride,
-                                  size_t plane_stride, size_t uv_plane_stride, float alpha, int K, int px, int do_norm) {
+static int extract_unscrambled_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw, const float* Vwt,
+                                   const wm_route* route, uint8_t* out, int n_planes, int H, int W, int row_stride,
+                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K, int px, int do_norm,
+                                   const MaskParams* mask) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   if (!out || !route) return set_err(WM_ERR_BADARG, "out / route is NULL");
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
@@ -1156,10 +1278,26 @@ int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float
   }));
   const bool use_mm = do_norm && g.n_tiles > 0;
   WM_TRY(extract_tiles_dev(ctx, stego, sigma_c, Uw, Vwt, w, n_planes, H, W, row_stride, plane_stride, uv_plane_stride, alpha, K,
-                           px != 0, use_mm ? mm : nullptr));
+                           px != 0, use_mm ? mm : nullptr, mask));
   // pixels outside the tile grid (H % 8, W % 8) are zeros of the estimate: they take part in the min / max
   return wmi::route_unpermute_normalize(ctx, w, route, out, n, n_planes, do_norm, use_mm ? mm : nullptr, (unsigned)groups,
                                         ((H % 8) || (W % 8)) ? 1 : 0);
+}
+
+int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw, const float* Vwt,
+                                  const wm_route* route, uint8_t* out, int n_planes, int H, int W, int row_stride,
+                                  size_t plane_stride, size_t uv_plane_stride, float alpha, int K, int px, int do_norm) {
+  return extract_unscrambled_dev(ctx, stego, sigma_c, Uw, Vwt, route, out, n_planes, H, W, row_stride, plane_stride,
+                                 uv_plane_stride, alpha, K, px, do_norm, nullptr);
+}
+
+int wm_extract_unscrambled_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                         const float* Vwt, const wm_route* route, uint8_t* out, int n_planes, int H, int W,
+                                         int row_stride, size_t plane_stride, size_t uv_plane_stride, float alpha, int K, int px,
+                                         int do_norm, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return extract_unscrambled_dev(ctx, stego, sigma_c, Uw, Vwt, route, out, n_planes, H, W, row_stride, plane_stride,
+                                 uv_plane_stride, alpha, K, px, do_norm, &mk);
 }
 
 int wm_tile_factors_to_pixel_dev(wm_ctx* ctx, const float* Uw, const float* Vwt, float* Ux, float* Vxt,
@@ -1197,11 +1335,14 @@ int wm_reconstruct_tiles_dev(wm_ctx* ctx, const float* Uw, const float* sw_hat, 
 }
 
 // ---- K2+K5 -----------------------------------------------------------------
-int wm_detect_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c,
-                           const float* sigma_w, double* scores, int n_planes, int H, int W,
-                           int row_stride, size_t plane_stride, size_t sigma_w_plane_stride,
-                           float alpha) {
+static int detect_tiles_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c,
+                            const float* sigma_w, double* scores, int n_planes, int H, int W,
+                            int row_stride, size_t plane_stride, size_t sigma_w_plane_stride,
+                            float alpha, const MaskParams* mask) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  if (mask) WM_TRY(check_mask(mask->lo, mask->hi, mask->cut));
+  const int ns = N_SUMS + (mask ? 1 : 0);
+  const MaskParams mk = mask ? *mask : MaskParams{0.0f, 1.0f, 1.0f};
   if (!scores) return set_err(WM_ERR_BADARG, "scores is NULL");
   if (n_planes == 0) return WM_OK;
   const Geom g = make_geom(H, W, row_stride, plane_stride);
@@ -1211,19 +1352,37 @@ int wm_detect_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma
         (sigma_w_plane_stride & 3u))
       return set_err(WM_ERR_BADARG, "sigma_c/sigma_w is NULL or not 16-byte aligned");
     WM_TRY(grow(ctx, &ctx->partials, &ctx->partials_bytes,
-                (size_t)n_planes * n_waves * N_SUMS * sizeof(double), "detect partial sums"));
+                (size_t)n_planes * n_waves * ns * sizeof(double), "detect partial sums"));
     const float inv_alpha = 1.0f / fmaxf(alpha, 1e-8f);
     const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-    with_bools([&](auto A) {
-      hipLaunchKernelGGL((k_detect_tiles<A.value>), grid, block, 0, ctx->stream, stego, sigma_c, sigma_w,
-                         (double*)ctx->partials, g, sigma_w_plane_stride, inv_alpha, ctx->d_status);
-    }, u8_aligned(stego, stego, row_stride, plane_stride));
+    with_bools([&](auto A, auto T) {
+      hipLaunchKernelGGL((k_detect_tiles<A.value, T.value>), grid, block, 0, ctx->stream, stego, sigma_c, sigma_w,
+                         (double*)ctx->partials, g, sigma_w_plane_stride, inv_alpha, ctx->d_status, mk);
+    }, u8_aligned(stego, stego, row_stride, plane_stride), mask != nullptr);
     WM_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_detect_finalize, dim3((unsigned)n_planes), dim3(256), 0, ctx->stream,
-                     (const double*)ctx->partials, scores, n_waves, (double)g.n_tiles * 8.0);
+  with_bools([&](auto T) {
+    hipLaunchKernelGGL((k_detect_finalize<T.value>), dim3((unsigned)n_planes), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->partials, scores, n_waves, (double)g.n_tiles * 8.0);
+  }, mask != nullptr && g.n_tiles > 0);
   WM_HIP(hipGetLastError());
   return WM_OK;
+}
+
+int wm_detect_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c,
+                           const float* sigma_w, double* scores, int n_planes, int H, int W,
+                           int row_stride, size_t plane_stride, size_t sigma_w_plane_stride,
+                           float alpha) {
+  return detect_tiles_dev(ctx, stego, sigma_c, sigma_w, scores, n_planes, H, W, row_stride, plane_stride,
+                          sigma_w_plane_stride, alpha, nullptr);
+}
+
+int wm_detect_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                                  double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                  size_t sigma_w_plane_stride, float alpha, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return detect_tiles_dev(ctx, stego, sigma_c, sigma_w, scores, n_planes, H, W, row_stride, plane_stride,
+                          sigma_w_plane_stride, alpha, &mk);
 }
 
 // ===========================================================================
@@ -1231,9 +1390,9 @@ int wm_detect_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma
 // without their own device allocator; the throughput path is *_dev.
 // ===========================================================================
 
-int wm_embed_tiles_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego,
-                      float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
-                      size_t plane_stride, size_t sigma_w_plane_stride, float alpha, int K) {
+static int embed_tiles_host(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego,
+                            float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                            size_t plane_stride, size_t sigma_w_plane_stride, float alpha, int K, const MaskParams* mask) {
   WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
   if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
@@ -1256,11 +1415,54 @@ int wm_embed_tiles_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, ui
   if (stego != host) WM_HIP(hipMemcpyAsync(d_stego, stego, span, hipMemcpyHostToDevice, ctx->stream));
   else d_stego = d_host;
   if (nt) WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_embed_tiles_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride,
-                               plane_stride, sigma_w_plane_stride, alpha, K));
+  if (mask) WM_TRY(wm_embed_tiles_masked_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride,
+                                                plane_stride, sigma_w_plane_stride, alpha, K, mask->lo, mask->hi));
+  else WM_TRY(wm_embed_tiles_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride,
+                                    plane_stride, sigma_w_plane_stride, alpha, K));
   WM_HIP(hipMemcpyAsync(stego, d_stego, span, hipMemcpyDeviceToHost, ctx->stream));
   if (nt) WM_HIP(hipMemcpyAsync(sigma_c, d_sc, n_sc * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (yw) WM_HIP(hipMemcpyAsync(yw, d_yw, n_yw * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return wm_check_status(ctx);
+}
+
+int wm_embed_tiles_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego,
+                      float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                      size_t plane_stride, size_t sigma_w_plane_stride, float alpha, int K) {
+  return embed_tiles_host(ctx, host, sigma_w, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride,
+                          sigma_w_plane_stride, alpha, K, nullptr);
+}
+
+int wm_embed_tiles_masked_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego,
+                             float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                             size_t plane_stride, size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi) {
+  const MaskParams mk{lo, hi, 1.0f};
+  return embed_tiles_host(ctx, host, sigma_w, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride,
+                          sigma_w_plane_stride, alpha, K, &mk);
+}
+
+int wm_mask_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                             int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                             size_t sigma_w_plane_stride, float lo, float hi) {
+  WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  if (n_planes == 0 || nt == 0) return WM_OK;
+  if (!sigma_w != !sigma_w_eff) return set_err(WM_ERR_BADARG, "sigma_w and sigma_w_eff go together");
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
+  const size_t n_eff = (size_t)n_planes * nt * 8, n_g = (size_t)n_planes * nt;
+  uint8_t* d_p; float *d_sw, *d_eff, *d_g;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_sw = sigma_w ? cv.take<float>(n_sw) : nullptr;
+    d_eff = sigma_w ? cv.take<float>(n_eff) : nullptr;
+    d_g = gain ? cv.take<float>(n_g) : nullptr;
+  }));
+  WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
+  if (sigma_w) WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
+  WM_TRY(wm_mask_sigma_w_tiles_u8_dev(ctx, d_p, d_sw, d_eff, d_g, n_planes, H, W, row_stride, plane_stride,
+                                      sigma_w_plane_stride, lo, hi));
+  if (sigma_w) WM_HIP(hipMemcpyAsync(sigma_w_eff, d_eff, n_eff * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (gain) WM_HIP(hipMemcpyAsync(gain, d_g, n_g * 4, hipMemcpyDeviceToHost, ctx->stream));
   return wm_check_status(ctx);
 }
 
@@ -1308,7 +1510,8 @@ int wm_svd_tiles_f32(wm_ctx* ctx, const float* planes, float* U, float* S, float
 
 static int extract_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
                               const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
-                              size_t plane_stride, size_t uv_plane_stride, float alpha, int K, bool sum_planes) {
+                              size_t plane_stride, size_t uv_plane_stride, float alpha, int K, bool sum_planes,
+                              const MaskParams* mask = nullptr) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   if (!out) return set_err(WM_ERR_BADARG, "out is NULL");
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
@@ -1333,8 +1536,10 @@ static int extract_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* si
     WM_HIP(hipMemcpyAsync(d_U, Uw, n_uv * 4, hipMemcpyHostToDevice, ctx->stream));
     WM_HIP(hipMemcpyAsync(d_V, Vwt, n_uv * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  WM_TRY(wm_extract_tiles_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
-                                 uv_plane_stride, alpha, K));
+  if (mask) WM_TRY(wm_extract_tiles_masked_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
+                                                  uv_plane_stride, alpha, K, mask->lo, mask->hi, mask->cut));
+  else WM_TRY(wm_extract_tiles_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
+                                      uv_plane_stride, alpha, K));
   if (sum_planes) {
     const size_t g = (hw + 255) / 256;
     hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, ctx->stream, d_o, hw, n_planes, d_sum);
@@ -1358,6 +1563,22 @@ int wm_extract_tiles_sum_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigm
                             size_t plane_stride, size_t uv_plane_stride, float alpha, int K) {
   return extract_tiles_host(ctx, stego, sigma_c, Uw, Vwt, out_sum, n_planes, H, W, row_stride, plane_stride,
                             uv_plane_stride, alpha, K, true);
+}
+
+int wm_extract_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                               const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
+                               size_t plane_stride, size_t uv_plane_stride, float alpha, int K, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return extract_tiles_host(ctx, stego, sigma_c, Uw, Vwt, out, n_planes, H, W, row_stride, plane_stride,
+                            uv_plane_stride, alpha, K, false, &mk);
+}
+
+int wm_extract_tiles_sum_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                   const float* Vwt, float* out_sum, int n_planes, int H, int W, int row_stride,
+                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return extract_tiles_host(ctx, stego, sigma_c, Uw, Vwt, out_sum, n_planes, H, W, row_stride, plane_stride,
+                            uv_plane_stride, alpha, K, true, &mk);
 }
 
 int wm_reconstruct_tiles(wm_ctx* ctx, const float* Uw, const float* sw_hat, const float* Vwt,
@@ -1388,9 +1609,9 @@ int wm_reconstruct_tiles(wm_ctx* ctx, const float* Uw, const float* sw_hat, cons
   return WM_OK;
 }
 
-int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
-                       double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
-                       size_t sigma_w_plane_stride, float alpha) {
+static int detect_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                             double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                             size_t sigma_w_plane_stride, float alpha, const MaskParams* mask) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   if (!scores) return set_err(WM_ERR_BADARG, "scores is NULL");
   if (n_planes == 0) return WM_OK;
@@ -1411,10 +1632,27 @@ int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, 
     WM_HIP(hipMemcpyAsync(d_sc, sigma_c, n_sc * 4, hipMemcpyHostToDevice, ctx->stream));
     WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  WM_TRY(wm_detect_tiles_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
-                                sigma_w_plane_stride, alpha));
+  if (mask) WM_TRY(wm_detect_tiles_masked_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
+                                                 sigma_w_plane_stride, alpha, mask->lo, mask->hi, mask->cut));
+  else WM_TRY(wm_detect_tiles_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
+                                     sigma_w_plane_stride, alpha));
   WM_HIP(hipMemcpyAsync(scores, d_scores, (size_t)n_planes * 8, hipMemcpyDeviceToHost, ctx->stream));
   return wm_check_status(ctx);
+}
+
+int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                       double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                       size_t sigma_w_plane_stride, float alpha) {
+  return detect_tiles_host(ctx, stego, sigma_c, sigma_w, scores, n_planes, H, W, row_stride, plane_stride,
+                           sigma_w_plane_stride, alpha, nullptr);
+}
+
+int wm_detect_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                              double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                              size_t sigma_w_plane_stride, float alpha, float lo, float hi, float cut) {
+  const MaskParams mk{lo, hi, cut};
+  return detect_tiles_host(ctx, stego, sigma_c, sigma_w, scores, n_planes, H, W, row_stride, plane_stride,
+                           sigma_w_plane_stride, alpha, &mk);
 }
 
 }  // extern "C"

@@ -20,6 +20,12 @@ defaults where the reference has a behaviour:
   k_floor  the literal 8 of ``K = max(8, int(kfrac*L))`` (single:174); at
            tile=8 the formula is 8 for every kfrac, so a mid-band sweep sets
            k_floor < 8.
+  strength "uniform" (default): every tile adds alpha * sigma_w.  "masked" (tile
+           mode only): a per-tile gain from the cover's own singular values
+           scales all but the leading component ("Texture-masked
+           strength"), so flat tiles stay clean; ``mask=(lo, hi, cut)`` are the
+           rule's parameters.  The meta then carries ``mask`` and extract /
+           detect take the rule from it.  Colour: one gain per channel plane.
   nonce    inject the 8-byte nonce (reference: ``os.urandom(8)``, single:119).
   device   HIP device index.
 
@@ -117,15 +123,15 @@ def _mode_of(meta):
     return _Color if M.is_color(meta) else _Gray                           # single:196,293
 
 
-def _embed_tiles(ctx, mode, hosts, wm, idx, alpha, K):
+def _embed_tiles(ctx, mode, hosts, wm, idx, alpha, K, mask=None):
     """tile=8: -> (stego planes, Sc, Yw or None, (U, S, Vt) of the watermark), every array with the planes' own rank."""
     wms = ctx.permute_planes(mode.wm_planes(ctx, wm), idx)                 # single:123-126,170-171 (index pass on the device)
     U, S, Vt = ctx.svd_tiles(wms)                                          # single:131-134,173
-    stego, Sc, Yw = ctx.embed_tiles(hosts, S, alpha, K, want_yw=mode.want_yw)   # single:127-147,172-177
+    stego, Sc, Yw = ctx.embed_tiles(hosts, S, alpha, K, want_yw=mode.want_yw, mask=mask)   # single:127-147,172-177
     return stego, Sc, Yw, (U, S, Vt)
 
 
-def _embed_fullframe(ctx, mode, hosts, wm, idx, alpha, K):
+def _embed_fullframe(ctx, mode, hosts, wm, idx, alpha, K, mask=None):
     """tile=None.  single:123-134 / 170-173: the scrambled watermark planes, their DCTs and SVDs (colour: as ONE batch) on the
     companion context and a worker thread, under the host planes' own decomposition (the two do not depend on each other
     until single:139's S + alpha * Sw)."""
@@ -143,11 +149,13 @@ def _embed_fullframe(ctx, mode, hosts, wm, idx, alpha, K):
 
 def embed_arrays(cover: np.ndarray, wm: np.ndarray, password: str, nonce: bytes,
                  alpha: float = 0.1, color: bool = False, kfrac: float = K_FRAC_DEFAULT,
-                 tile: Optional[int] = TILE, k_floor: int = 8, device: int = 0) -> dict:
+                 tile: Optional[int] = TILE, k_floor: int = 8, device: int = 0, *, strength: str = "uniform",
+                 mask=M.MASK_DEFAULT) -> dict:
     """cover, wm: BGR uint8.  Returns dict(stego BGR uint8, meta dict, psnr, ssim)."""
     M.check_password_type(password, "embed")
     M.require_password(password, "embed")                                  # single:115-116
     M.check_tile(tile)
+    mask = M.check_strength(strength, mask, tile)                          # None: uniform
     ctx = _ctx(device)
     H, W = cover.shape[:2]
     wm = hg.resize_area_cached(wm, W, H)                                   # single:118
@@ -156,9 +164,9 @@ def embed_arrays(cover: np.ndarray, wm: np.ndarray, password: str, nonce: bytes,
     mode = _Color if color else _Gray
     K = M.k_of(TILE if tile else min(H, W), kfrac, k_floor)                # single:174
     hosts = mode.planes_in(ctx, cover)
-    stego_p, Sc, Yw, (U, S, Vt) = (_embed_tiles if tile else _embed_fullframe)(ctx, mode, hosts, wm, idx, alpha, K)
+    stego_p, Sc, Yw, (U, S, Vt) = (_embed_tiles if tile else _embed_fullframe)(ctx, mode, hosts, wm, idx, alpha, K, mask)
     members = {"mode": mode.name, **M.common_members(H, W, alpha, kfrac, nonce), **M.image_members(tile, k_floor),
-               **mode.members(Sc, U, Vt, S)}
+               **M.mask_members(mask), **mode.members(Sc, U, Vt, S)}
     # single:152-156,182 (39 MB for a 1080p colour cover: 16 ms), under the colour conversion / interleave and the metrics
     dg = _Later(lambda: hg.hmac_digest(key, M.hmac_parts(members)))
     stego = mode.planes_out(ctx, cover, stego_p)
@@ -267,7 +275,8 @@ def _extract_checked(stego, meta, mode, alpha, kfrac, k_floor, H, W, key, normal
     if tile is not None:
         Sc, U, Vt = M.batched(meta, "Sc", "Uw", "Vwt")
         # single:205-222 / 233-274 in one device-resident chain: sigma -> rank-8 product -> unscramble -> normalise -> uint8
-        return mode.wm_out(ctx.extract_tiles_unscrambled_u8(planes, Sc, U, Vt, alpha, M.k_of(TILE, kfrac, k_floor), idx, normalize))
+        return mode.wm_out(ctx.extract_tiles_unscrambled_u8(planes, Sc, U, Vt, alpha, M.k_of(TILE, kfrac, k_floor), idx, normalize,
+                                                            mask=M.mask_of(meta)))
     if planes.ndim == 2 and _same_size(stego, meta):
         # gray, the meta's own size: sigma_hat and the product inside the library
         (Sc, Uw, Vwt), = M.per_plane(meta, "Sc", "Uw", "Vwt")
@@ -288,7 +297,7 @@ def detect_arrays(stego: np.ndarray, meta, thresh: float = 0.6, device: int = 0)
     planes = mode.planes_in(ctx, stego)                                    # single:296,303
     if tile is not None:
         Sc, Sw = M.batched(meta, "Sc", "Sw")
-        nc = ctx.detect_tiles(planes, Sc, Sw, alpha)                       # single:297-301,304-316
+        nc = ctx.detect_tiles(planes, Sc, Sw, alpha, mask=M.mask_of(meta)) # single:297-301,304-316
     elif planes.ndim == 2 and _same_size(stego, meta):
         nc = [ctx.ref_detect(planes, meta["Sc"], meta["Sw"], alpha)]       # single:297-301, NC inside the library
     else:
@@ -305,18 +314,20 @@ def detect_arrays(stego: np.ndarray, meta, thresh: float = 0.6, device: int = 0)
 def embed(cover_path: str, wm_source: str, out_path: str, meta_path: str,
           alpha: float = 0.1, color: bool = False, password: Optional[str] = None,
           kfrac: float = K_FRAC_DEFAULT, *, tile: Optional[int] = TILE, k_floor: int = 8,
-          nonce: Optional[bytes] = None, device: int = 0, compress_meta: bool = True):
+          nonce: Optional[bytes] = None, device: int = 0, compress_meta: bool = True, strength: str = "uniform",
+          mask=M.MASK_DEFAULT):
     """single:112-190.  Returns (out_path, meta_path, psnr, ssim).  ``compress_meta=False`` writes the .npz
     uncompressed (np.load - and the reference's extract / detect - read either form; tests/test_gpu_reference_files.py runs
     the reference program on both): the tile-mode factors are
     float noise to zlib, and compressing the 70 MB of a 4K cover costs ten times the rest of the call."""
     M.check_password_type(password, "embed")
     M.require_password(password, "embed")
+    M.check_strength(strength, mask, tile)                                 # refused before anything is read
     cover = hg.read_image_bgr(cover_path)                                  # single:117
     wm = hg.read_image_bgr(wm_source)                                      # single:118
     if nonce is None:
         nonce = os.urandom(8)                                              # single:119
-    r = embed_arrays(cover, wm, password, nonce, alpha, color, kfrac, tile, k_floor, device)
+    r = embed_arrays(cover, wm, password, nonce, alpha, color, kfrac, tile, k_floor, device, strength=strength, mask=mask)
     out_path = M.out_name(out_path, "_stego.png")                          # single:148-149,178-179
     if not hg.write_png(out_path, r["stego"], 0):                          # single:150,180
         raise IOError("Ghi stego thất bại.")

@@ -73,6 +73,18 @@ SIGNATURES = {
     "wm_reconstruct_tiles": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i],
     "wm_detect_tiles_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
     "wm_detect_tiles_u8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    # texture-masked strength: the unmasked argument lists with (lo, hi) or (lo, hi, cut) appended
+    "wm_mask_sigma_w_tiles_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f],
+    "wm_mask_sigma_w_tiles_u8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f],
+    "wm_embed_tiles_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f],
+    "wm_embed_tiles_masked_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f],
+    "wm_extract_tiles_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f, _f],
+    "wm_extract_tiles_px_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f, _f],
+    "wm_extract_tiles_masked_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f, _f],
+    "wm_extract_tiles_sum_masked_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _f, _f, _f],
+    "wm_extract_unscrambled_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _i, _i, _f, _f, _f],
+    "wm_detect_tiles_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f, _f, _f],
+    "wm_detect_tiles_masked_u8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f, _f, _f],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -208,6 +220,26 @@ def _dense(a: np.ndarray, dtype, ndim: int, what: str):
     return np.ascontiguousarray(a), H, W, min(H, W)
 
 
+def check_mask(mask) -> tuple:
+    """The texture-masked rule's (lo, hi, cut) as floats, checked on the host as the library checks them
+    (include/wmhip.h): 0 <= lo < hi, both finite, 0 < cut <= 1."""
+    try:
+        lo, hi, cut = (float(x) for x in mask)
+    except (TypeError, ValueError):
+        raise ValueError("mask must be (lo, hi, cut)") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo < hi):
+        raise ValueError(f"mask needs finite 0 <= lo < hi, got lo={lo}, hi={hi}")
+    if not (0.0 < cut <= 1.0):                                             # (NaN fails both comparisons)
+        raise ValueError(f"mask needs 0 < cut <= 1, got {cut}")
+    return lo, hi, cut
+
+
+def _mask_args(mask) -> tuple:
+    """() for uniform strength (mask None), else the checked (lo, hi, cut) the masked entry points take after the
+    unmasked arguments."""
+    return () if mask is None else check_mask(mask)
+
+
 def _planes_of(a: np.ndarray, dtype, what: str):
     """_plane_layout of a [H, W] / [N, H, W] input of the given dtype, which may be strided"""
     if a.dtype != dtype:
@@ -300,6 +332,19 @@ class Context:
                    _vp(yw) if yw else None, n_planes, H, W, row_stride, plane_stride,
                    sigma_w_plane_stride, alpha, K)
 
+    def embed_tiles_masked_u8_dev(self, host, sigma_w, stego, sigma_c, yw, n_planes, H, W, row_stride,
+                                  plane_stride, sigma_w_plane_stride, alpha, K, lo, hi):
+        """embed_tiles_u8_dev with texture-masked strength (include/wmhip.h)."""
+        self._call("wm_embed_tiles_masked_u8_dev", _vp(host), _vp(sigma_w), _vp(stego), _vp(sigma_c),
+                   _vp(yw) if yw else None, n_planes, H, W, row_stride, plane_stride,
+                   sigma_w_plane_stride, alpha, K, lo, hi)
+
+    def mask_sigma_w_tiles_u8_dev(self, planes, sigma_w, sigma_w_eff, gain, n_planes, H, W, row_stride, plane_stride,
+                                  sigma_w_plane_stride, lo, hi):
+        self._call("wm_mask_sigma_w_tiles_u8_dev", _vp(planes), _vp(sigma_w) if sigma_w else None,
+                   _vp(sigma_w_eff) if sigma_w_eff else None, _vp(gain) if gain else None,
+                   n_planes, H, W, row_stride, plane_stride, sigma_w_plane_stride, lo, hi)
+
     def sigma_tiles_u8_dev(self, planes, sigma, n_planes, H, W, row_stride, plane_stride):
         self._call("wm_sigma_tiles_u8_dev", _vp(planes), _vp(sigma), n_planes, H, W, row_stride, plane_stride)
 
@@ -348,9 +393,12 @@ class Context:
 
     # ---- NumPy (host-buffer) entry points --------------------------------
     def embed_tiles(self, host: np.ndarray, sigma_w: np.ndarray, alpha: float, K: int = 8,
-                    want_yw: bool = False):
+                    want_yw: bool = False, mask=None):
         """host uint8 [H,W] or [N,H,W]; sigma_w float32 [nby,nbx,8] (shared) or
-        [N,nby,nbx,8].  Returns (stego uint8, sigma_c float32 [N?,nby,nbx,8], yw or None)."""
+        [N,nby,nbx,8].  Returns (stego uint8, sigma_c float32 [N?,nby,nbx,8], yw or None).
+        ``mask=(lo, hi, cut)``: texture-masked strength (include/wmhip.h) - every tile adds alpha * G * sigma_w with
+        G = (1, g, .., g) and g from its own cover singular values; ``cut`` plays no part in the embed."""
+        m = _mask_args(mask)
         n, H, W, rs, ps = _planes_of(host, np.uint8, "host planes must be uint8")
         nby, nbx = H // TILE, W // TILE
         sw = _f32(sigma_w)
@@ -362,11 +410,21 @@ class Context:
         yw = np.empty((n, H, W), np.float32) if want_yw else None
         # stego is dense; host may be strided -> densify so both share one layout
         hostc = np.ascontiguousarray(host.reshape(n, H, W))
-        self._call("wm_embed_tiles_u8", _p(hostc), _p(sw), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W,
-                   nby * nbx * 8 if per_plane else 0, float(alpha), int(K))
+        self._call("wm_embed_tiles_masked_u8" if m else "wm_embed_tiles_u8", _p(hostc), _p(sw), _p(stego), _p(sc), _p(yw),
+                   n, H, W, W, H * W, nby * nbx * 8 if per_plane else 0, float(alpha), int(K), *m[:2])
         if host.ndim == 2:
             return stego[0], sc[0], (yw[0] if want_yw else None)
         return stego, sc, yw
+
+    def mask_gain_tiles(self, planes: np.ndarray, lo: float, hi: float) -> np.ndarray:
+        """The masked rule's gain g of every tile of uint8 planes [H,W] / [N,H,W] -> float32 [N?, nby, nbx], from the
+        device's own singular values (what a masked embed of these planes uses)."""
+        lo, hi, _ = _mask_args((lo, hi, 1.0))
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        nby, nbx = H // TILE, W // TILE
+        g = np.empty((n, nby, nbx), np.float32)
+        self._call("wm_mask_sigma_w_tiles_u8", _p(planes), None, None, _p(g), n, H, W, rs, ps, 0, lo, hi)
+        return g[0] if planes.ndim == 2 else g
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
@@ -394,9 +452,11 @@ class Context:
         return sc.reshape(n, nby, nbx, 8)
 
     def extract_tiles(self, stego: np.ndarray, sigma_c: np.ndarray, Uw: np.ndarray, Vwt: np.ndarray,
-                      alpha: float, K: int = 8, sum_planes: bool = False) -> np.ndarray:
+                      alpha: float, K: int = 8, sum_planes: bool = False, mask=None) -> np.ndarray:
         """Scrambled-watermark estimate per plane, float32 [n, H, W]; with ``sum_planes`` the planes
-        are added on the device and only their sum [H, W] comes back (video extract averages frames)."""
+        are added on the device and only their sum [H, W] comes back (video extract averages frames).
+        ``mask=(lo, hi, cut)``: the masked rule's extract (include/wmhip.h), g taken from sigma_c."""
+        m = _mask_args(mask)
         n, H, W, rs, ps = _planes_of(stego, np.uint8, "stego planes must be uint8")
         nby, nbx = H // TILE, W // TILE
         sc = self._sigma_c_tiles(sigma_c, n, nby, nbx)
@@ -406,8 +466,9 @@ class Context:
                 or (per_plane and Uw.shape[0] != n):
             raise ValueError(f"Uw/Vwt shape {Uw.shape}/{Vwt.shape} does not match {n} plane(s) of {nby}x{nbx} tiles")
         out = np.empty((H, W) if sum_planes else (n, H, W), np.float32)
-        self._call("wm_extract_tiles_sum_u8" if sum_planes else "wm_extract_tiles_u8", _p(stego), _p(sc), _p(Uw), _p(Vwt),
-                   _p(out), n, H, W, rs, ps, nby * nbx if per_plane else 0, float(alpha), int(K))
+        name = ("wm_extract_tiles_sum" if sum_planes else "wm_extract_tiles") + ("_masked_u8" if m else "_u8")
+        self._call(name, _p(stego), _p(sc), _p(Uw), _p(Vwt), _p(out), n, H, W, rs, ps, nby * nbx if per_plane else 0,
+                   float(alpha), int(K), *m)
         return out[0] if stego.ndim == 2 and not sum_planes else out
 
     def reconstruct_tiles(self, Uw: np.ndarray, sw_hat: np.ndarray, Vwt: np.ndarray, H: int, W: int):
@@ -422,7 +483,9 @@ class Context:
         return out[0] if single else out
 
     def detect_tiles(self, stego: np.ndarray, sigma_c: np.ndarray, sigma_w: np.ndarray,
-                     alpha: float) -> np.ndarray:
+                     alpha: float, mask=None) -> np.ndarray:
+        """NC score per plane, float64 [n].  ``mask=(lo, hi, cut)``: over the values the masked rule takes."""
+        m = _mask_args(mask)
         n, H, W, rs, ps = _planes_of(stego, np.uint8, "stego planes must be uint8")
         nby, nbx = H // TILE, W // TILE
         sc = self._sigma_c_tiles(sigma_c, n, nby, nbx)
@@ -431,8 +494,8 @@ class Context:
         if sw.ndim not in (3, 4) or sw.shape[-3:] != (nby, nbx, 8) or (per_plane and sw.shape[0] != n):
             raise ValueError(f"sigma_w shape {sw.shape} does not match {n} plane(s) of {nby}x{nbx} tiles")
         scores = np.zeros(n, np.float64)
-        self._call("wm_detect_tiles_u8", _p(stego), _p(sc), _p(sw), _p(scores), n, H, W, rs, ps,
-                   nby * nbx * 8 if per_plane else 0, float(alpha))
+        self._call("wm_detect_tiles_masked_u8" if m else "wm_detect_tiles_u8", _p(stego), _p(sc), _p(sw), _p(scores),
+                   n, H, W, rs, ps, nby * nbx * 8 if per_plane else 0, float(alpha), *m)
         return scores
 
     # ---- full-frame mode (tile=None): one plane per call, or [N, H, W] planes sharing every launch ------------------
@@ -732,9 +795,10 @@ class Context:
         return out
 
     def extract_tiles_unscrambled_u8(self, stego: np.ndarray, sigma_c: np.ndarray, Uw: np.ndarray, Vwt: np.ndarray,
-                                     alpha: float, K: int, idx: np.ndarray, normalize: bool = True) -> np.ndarray:
+                                     alpha: float, K: int, idx: np.ndarray, normalize: bool = True, mask=None) -> np.ndarray:
         """extract_tiles + unpermute + normalise without the float plane ever leaving the device
-        (single:204-222 / 232-274): uint8 stego planes in, uint8 watermark planes out."""
+        (single:204-222 / 232-274): uint8 stego planes in, uint8 watermark planes out.  ``mask`` as in extract_tiles."""
+        m = _mask_args(mask)
         if stego.dtype != np.uint8:
             raise ValueError("stego planes must be uint8")
         single = stego.ndim == 2
@@ -754,13 +818,14 @@ class Context:
         try:
             self.h2d(d_st, st); self.h2d(d_sc, sc); self.h2d(d_u, Uw); self.h2d(d_v, Vwt)
             if route is not None:          # one call: extract kernel (with its min / max) -> routed unscramble -> uint8
-                self._call("wm_extract_unscrambled_u8_dev", _vp(d_st), _vp(d_sc), _vp(d_u), _vp(d_v), _vp(route), _vp(d_w),
-                           n, H, W, W, H * W, nby * nbx if per_plane else 0, float(alpha), int(K), 0, 1 if normalize else 0)
+                self._call("wm_extract_unscrambled_masked_u8_dev" if m else "wm_extract_unscrambled_u8_dev", _vp(d_st), _vp(d_sc),
+                           _vp(d_u), _vp(d_v), _vp(route), _vp(d_w), n, H, W, W, H * W, nby * nbx if per_plane else 0,
+                           float(alpha), int(K), 0, 1 if normalize else 0, *m)
                 out = np.empty((n, H, W), np.uint8)
                 self.d2h(out, d_w)
-            else:
-                self.extract_tiles_u8_dev(d_st, d_sc, d_u, d_v, d_w, n, H, W, W, H * W, nby * nbx if per_plane else 0,
-                                          float(alpha), int(K))
+            else:                          # no route (an empty plane, or more pixels than one addresses): the two steps apart
+                self._call("wm_extract_tiles_masked_u8_dev" if m else "wm_extract_tiles_u8_dev", _vp(d_st), _vp(d_sc), _vp(d_u),
+                           _vp(d_v), _vp(d_w), n, H, W, W, H * W, nby * nbx if per_plane else 0, float(alpha), int(K), *m)
                 out = self._unpermute_normalize_dev(d_w, n, H, W, idx, normalize)
             # the *_dev entry points only set the sticky status bit; without this a Jacobi that hit its sweep
             # bound would hand back a watermark silently and surface in some later, unrelated call (DESIGN 5:

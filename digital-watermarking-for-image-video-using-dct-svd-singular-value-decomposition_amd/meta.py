@@ -3,7 +3,8 @@
 Member names, their order in the file, what the HMAC covers and in which order (single:152-156, 182), how the nonce,
 the digest, ``kfrac``, ``k_floor`` and the tile size are read back, and the small argument rules the public functions
 share.  The reference's ``extract`` / ``detect`` read the full-frame image metas written through here, so a slip in this
-file is a file they cannot authenticate.  NumPy and hashlib only (through hostglue): nothing here touches the device.
+file is a file they cannot authenticate.  NumPy and hashlib only (through hostglue; hostapi for the one statement of the
+masked rule's parameter check, which loads nothing): nothing here touches the device.
 """
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import hostapi
 from . import hostglue as hg
 
 TILE = 8
@@ -36,8 +38,10 @@ def sw_key(n: str) -> str:
 
 
 _GRAY = ("Sc", "Uw", "Vwt", "Sw")
-_IMAGE_COMMON = ("payload_type", "shape", "alpha", "kfrac", "nonce", "tile", "k_floor")
-_VIDEO_COMMON = ("payload_type", "shape", "alpha", "kfrac", "frame_interval", "n_frames", "tile", "k_floor", "nonce")
+# ``mask``: float32 (lo, hi, cut) of a tile-mode meta written with texture-masked strength, directly after k_floor; a meta
+# written without masking has no such member
+_IMAGE_COMMON = ("payload_type", "shape", "alpha", "kfrac", "nonce", "tile", "k_floor", "mask")
+_VIDEO_COMMON = ("payload_type", "shape", "alpha", "kfrac", "frame_interval", "n_frames", "tile", "k_floor", "mask", "nonce")
 # a colour video meta written from a subsampled container names it ("420" / "422") directly after n_frames
 _VIDEO_COLOR_COMMON = tuple(x for k in _VIDEO_COMMON for x in ((k, "chroma") if k == "n_frames" else (k,)))
 _BY_CHANNEL = tuple(f(n) for n in CHANNELS for f in (s_key, uw_key, vwt_key, sw_key))
@@ -82,6 +86,12 @@ def image_members(tile: Optional[int], k_floor: int) -> dict:
 def video_members(frame_interval: int, n_frames: int, tile: Optional[int], k_floor: int) -> dict:
     return dict(frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames), tile=np.int32(tile or 0),
                 k_floor=np.int32(k_floor))
+
+
+def mask_members(mask) -> dict:
+    """The texture-masked rule's parameters (``check_strength``'s result); nothing for uniform strength.  Like ``alpha``
+    they are not covered by the HMAC."""
+    return {} if mask is None else dict(mask=np.asarray(mask, dtype=np.float32))
 
 
 def gray_members(Sc, Uw, Vwt, Sw) -> dict:
@@ -156,6 +166,13 @@ def tile_of(meta) -> Optional[int]:
     return TILE if np.asarray(s).ndim == 3 else None
 
 
+def mask_of(meta):
+    """None, or the (lo, hi, cut) a tile-mode meta was written with (texture-masked strength)."""
+    if "mask" not in meta:
+        return None
+    return check_mask(np.asarray(meta["mask"], dtype=np.float32).reshape(-1).tolist())
+
+
 def chroma_of(meta) -> str:
     """Chroma format of the container a colour video meta was written for: its ``chroma`` member, else 4:4:4."""
     return str(meta["chroma"]) if "chroma" in meta else "444"
@@ -222,6 +239,40 @@ def require_password(password, what: str) -> None:
 def check_tile(tile) -> None:
     if tile is not None and int(tile) != TILE:
         raise ValueError("tile must be 8 or None")
+
+
+STRENGTHS = ("uniform", "masked")
+MASK_DEFAULT = (8.0, 64.0, 0.25)       # a texture RMS of 1 and of 8 gray levels per pixel; at most 4x noise gain on carried tiles
+
+
+def check_mask(mask) -> tuple:
+    """(lo, hi, cut) as floats holding the float32 values the meta stores, checked by the binding's own rule
+    (hostapi.check_mask: 0 <= lo < hi, both finite, 0 < cut <= 1)."""
+    try:
+        mask = [float(np.float32(x)) for x in mask]
+    except (TypeError, ValueError):
+        raise ValueError("mask must be (lo, hi, cut)") from None
+    return hostapi.check_mask(mask)
+
+
+def check_strength(strength, mask, tile):
+    """The rule an embed call asks for: None for ``strength="uniform"``, the checked (lo, hi, cut) for "masked".  Masking
+    is a per-tile gain: full-frame mode (tile=None) has no tiles to mask."""
+    if strength not in STRENGTHS:
+        raise ValueError(f"strength must be one of {STRENGTHS}, got {strength!r}")
+    if strength == "uniform":
+        return None
+    if not tile:
+        raise ValueError('strength="masked" needs tile=8: full-frame mode has no tiles')
+    return check_mask(mask)
+
+
+def mask_gain(Sc, lo: float, hi: float) -> np.ndarray:
+    """The rule's per-tile gain g from cover singular values Sc [..., 8], float32 [...]: a caller's look at the map
+    without a device.  r = sqrt(s_2^2 + .. + s_8^2), g = clamp((r - lo) / (hi - lo), 0, 1), all in float32."""
+    Sc = np.asarray(Sc, dtype=np.float32)
+    r = np.sqrt(np.sum(Sc[..., 1:] * Sc[..., 1:], axis=-1, dtype=np.float32))
+    return np.clip((r - np.float32(lo)) / (np.float32(hi) - np.float32(lo)), 0, 1).astype(np.float32)
 
 
 check_enhance = hg.check_enhance

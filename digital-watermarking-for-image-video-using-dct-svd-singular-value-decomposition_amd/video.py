@@ -110,13 +110,14 @@ def prepare_watermark(ctx: hostapi.Context, wm_bgr: np.ndarray, H: int, W: int, 
 
 
 def _embed_frames_into(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int, batch: int,
-                       tile: Optional[int], stego: np.ndarray) -> np.ndarray:
+                       tile: Optional[int], stego: np.ndarray, mask=None) -> np.ndarray:
     """embed_frames with the stego frames written into ``stego`` ([N, H, W], may be strided); returns Sc."""
+    M.check_strength("uniform" if mask is None else "masked", mask, tile)
     n, H, W = frames_y.shape
     sc = np.empty((n, H // TILE, W // TILE, 8) if tile else (n, min(H, W)), np.float32)
     for b0 in range(0, n, batch):
         if tile:
-            s, c, _ = ctx.embed_tiles(frames_y[b0:b0 + batch], Sw, alpha, K)
+            s, c, _ = ctx.embed_tiles(frames_y[b0:b0 + batch], Sw, alpha, K, mask=mask)
         else:
             s, c, _ = ctx.ref_embed_planes(frames_y[b0:b0 + batch], Sw, alpha, K)
         stego[b0:b0 + batch] = s; sc[b0:b0 + batch] = c
@@ -124,21 +125,25 @@ def _embed_frames_into(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarra
 
 
 def embed_frames(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8,
-                 batch: int = 32, tile: Optional[int] = TILE):
+                 batch: int = 32, tile: Optional[int] = TILE, mask=None):
     """frames_y uint8 [N, H, W] -> (stego [N, H, W], Sc); one set of launches per batch.
-    tile=8: Sc [N, nby, nbx, 8] (K1); tile=None: Sc [N, min(H, W)] (batched full-plane SVDs)."""
+    tile=8: Sc [N, nby, nbx, 8] (K1); tile=None: Sc [N, min(H, W)] (batched full-plane SVDs).
+    ``mask=(lo, hi, cut)``: texture-masked strength (tile mode), every frame with the gain of its own tiles."""
     stego = np.empty_like(frames_y)
-    return stego, _embed_frames_into(ctx, frames_y, Sw, alpha, K, batch, tile, stego)
+    return stego, _embed_frames_into(ctx, frames_y, Sw, alpha, K, batch, tile, stego, mask)
 
 
 def extract_frames_mean(ctx: hostapi.Context, frames_y: np.ndarray, Sc: np.ndarray, Uw, Vwt, alpha: float,
-                        K: int = 8, batch: int = 32, tile: Optional[int] = TILE) -> np.ndarray:
-    """Mean over frames of the scrambled-watermark estimates (float32 [H, W])."""
+                        K: int = 8, batch: int = 32, tile: Optional[int] = TILE, mask=None) -> np.ndarray:
+    """Mean over frames of the scrambled-watermark estimates (float32 [H, W]).  With ``mask`` every frame's estimate
+    follows the masked rule with that frame's own gains; the multi-frame estimate stays the PLAIN mean of the per-frame
+    estimates (a tile that some frames do not carry contributes zeros there: no weighting by carried counts)."""
+    M.check_strength("uniform" if mask is None else "masked", mask, tile)
     n, H, W = frames_y.shape
     acc = np.zeros((H, W), np.float64)
     for b0 in range(0, n, batch):
         if tile:      # the batch's estimates are added on the device: one plane per batch crosses PCIe
-            acc += ctx.extract_tiles(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Uw, Vwt, alpha, K, sum_planes=True)
+            acc += ctx.extract_tiles(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Uw, Vwt, alpha, K, sum_planes=True, mask=mask)
         else:
             w = ctx.ref_extract_planes(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Uw, Vwt, alpha, K)
             acc += w.sum(axis=0, dtype=np.float64)
@@ -146,20 +151,24 @@ def extract_frames_mean(ctx: hostapi.Context, frames_y: np.ndarray, Sc: np.ndarr
 
 
 def detect_frames(ctx: hostapi.Context, frames_y: np.ndarray, Sc: np.ndarray, Sw: np.ndarray, alpha: float,
-                  batch: int = 32, tile: Optional[int] = TILE) -> np.ndarray:
+                  batch: int = 32, tile: Optional[int] = TILE, mask=None) -> np.ndarray:
+    """Per-frame NC scores; ``mask``: over the values the masked rule takes (tile mode)."""
+    M.check_strength("uniform" if mask is None else "masked", mask, tile)
     scores = np.empty(frames_y.shape[0], np.float64)
     for b0 in range(0, frames_y.shape[0], batch):
-        f = ctx.detect_tiles if tile else ctx.ref_detect_planes
-        scores[b0:b0 + batch] = f(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Sw, alpha)
+        if tile:
+            scores[b0:b0 + batch] = ctx.detect_tiles(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Sw, alpha, mask=mask)
+        else:
+            scores[b0:b0 + batch] = ctx.ref_detect_planes(frames_y[b0:b0 + batch], Sc[b0:b0 + batch], Sw, alpha)
     return scores
 
 
 def embed_frames_sharded(ctx: hostapi.Context, frames_y: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8,
-                         rank: int = 0, world_size: int = 1, batch: int = 32, tile: Optional[int] = TILE):
+                         rank: int = 0, world_size: int = 1, batch: int = 32, tile: Optional[int] = TILE, mask=None):
     """This rank's share [r*N//W, (r+1)*N//W) of a batch of frames (no collective:
     the watermark sigma was broadcast beforehand, sharding.broadcast_watermark)."""
     lo, hi = sharding.frame_range(rank, world_size, frames_y.shape[0])
-    stego, sc = embed_frames(ctx, frames_y[lo:hi], Sw, alpha, K, batch, tile)
+    stego, sc = embed_frames(ctx, frames_y[lo:hi], Sw, alpha, K, batch, tile, mask)
     return (lo, hi), stego, sc
 
 
@@ -206,12 +215,12 @@ def prepare_watermark_color(ctx: hostapi.Context, wm_bgr: np.ndarray, H: int, W:
 
 
 def embed_frames_color(ctx: hostapi.Context, planes: np.ndarray, Sw: np.ndarray, alpha: float, K: int = 8, batch: int = 8,
-                       tile: Optional[int] = TILE):
+                       tile: Optional[int] = TILE, mask=None):
     """planes uint8 [n, 3, H, W] (B, G, R of n frames), Sw [3, ...] -> (stego [n, 3, H, W], [Sb, Sg, Sr]): channel c of every
     frame gets the watermark's channel c (single:139-152); one set of launches per channel and batch.  (Any number of
-    channels: the luma loop passes [n, 1, H, W].)"""
+    channels: the luma loop passes [n, 1, H, W].)  ``mask``: as in embed_frames, one gain per channel plane."""
     st = np.empty_like(planes)
-    sc = [_embed_frames_into(ctx, np.ascontiguousarray(planes[:, ch]), Sw[ch], alpha, K, batch, tile, st[:, ch])
+    sc = [_embed_frames_into(ctx, np.ascontiguousarray(planes[:, ch]), Sw[ch], alpha, K, batch, tile, st[:, ch], mask)
           for ch in range(planes.shape[1])]
     return st, sc
 
@@ -279,8 +288,10 @@ def _is_marked(i: int, frame_interval: int) -> bool:
 
 
 def _embed_video(codec, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
-                 password, nonce, kfrac, k_floor, batch, device, tile, subsampling="refuse"):
+                 password, nonce, kfrac, k_floor, batch, device, tile, subsampling="refuse", strength="uniform",
+                 mask=M.MASK_DEFAULT):
     M.check_tile(tile)
+    mask = M.check_strength(strength, mask, tile)                          # None: uniform
     M.require_password(password, "embed")
     _check_subsampling(subsampling)
     ctx = hostapi.Context(device)
@@ -305,7 +316,7 @@ def _embed_video(codec, host_video_path, watermark_path, output_video_path, meta
                 marked = [p for p in pend if p[3]]
                 if marked:
                     planes = codec.planes(ctx, [p[1:3] for p in marked], H, W)                   # [n, C, H, W]
-                    st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile)
+                    st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile, mask)
                     for ch, c in enumerate(sc):
                         sc_all[ch].append(c)
                     psnrs.extend(hg.psnr(planes[i], st[i]) for i in range(len(marked)))
@@ -328,7 +339,8 @@ def _embed_video(codec, host_video_path, watermark_path, output_video_path, meta
         empty = np.zeros((0, H // TILE, W // TILE, 8) if tile else (0, min(H, W)), np.float32)
         S = [np.concatenate(c) if c else empty for c in sc_all]
         members = {"mode": codec.mode, **M.common_members(H, W, alpha, kfrac, nonce),
-                   **M.video_members(frame_interval, n_frames, tile, k_floor), **codec.members(S, Uw, Vwt, Sw)}
+                   **M.video_members(frame_interval, n_frames, tile, k_floor), **M.mask_members(mask),
+                   **codec.members(S, Uw, Vwt, Sw)}
         digest = hg.hmac_digest(key, M.hmac_parts(members))                # the coverage of single:152-156,182
         # uncompressed .npz: the per-frame singular values are float noise to zlib (ratio ~1.1) and compressing them was
         # 80 % of this function's time (1.7 s for 64 frames of 1080p); np.load reads either form
@@ -387,7 +399,8 @@ def _extract_video(codec, stego_video_path, metadata_path, output_image_path, pa
         idx = hg.permutation_index(H, W, key)
         chans = []
         for ch, (Sc, Uw, Vwt) in enumerate(factors):
-            w_s = extract_frames_mean(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Uw, Vwt, float(data["alpha"]), K, batch, tile)
+            w_s = extract_frames_mean(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Uw, Vwt, float(data["alpha"]), K, batch, tile,
+                                      M.mask_of(data))
             chans.append(ctx.unpermute_normalize_u8(w_s, idx, normalize))                    # single:74-80, 221-222, 265-271 on the device
         img = hg.apply_enhance(ctx, chans[0] if len(chans) == 1 else np.stack(chans, axis=-1), enhance)   # single:223-227, 275-277
     finally:
@@ -405,7 +418,7 @@ def _detect_video(codec, stego_video_path, metadata_path, thresh, batch, device)
         sigmas = M.per_plane(data, "Sc", "Sw")
         planes = _marked_planes(codec, ctx, stego_video_path, data, sigmas[0][0].shape[0], len(sigmas), batch)
         tile = M.tile_of(data)
-        per_ch = [detect_frames(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Sw, float(data["alpha"]), batch, tile)
+        per_ch = [detect_frames(ctx, np.ascontiguousarray(planes[:, ch]), Sc, Sw, float(data["alpha"]), batch, tile, M.mask_of(data))
                   for ch, (Sc, Sw) in enumerate(sigmas)]
     finally:
         ctx.close()
@@ -417,25 +430,30 @@ def _detect_video(codec, stego_video_path, metadata_path, thresh, batch, device)
 def embed_watermark_video(host_video_path: str, watermark_path: str, output_video_path: str,
                           metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
                           password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
-                          k_floor: int = 8, batch: int = 32, device: int = 0, tile: Optional[int] = TILE):
+                          k_floor: int = 8, batch: int = 32, device: int = 0, tile: Optional[int] = TILE,
+                          strength: str = "uniform", mask=M.MASK_DEFAULT):
     """Embed the watermark into the luma of every ``frame_interval``-th frame of a
     .y4m video.  Returns (output_video_path, metadata_path, mean PSNR of marked frames).
     tile=8: 8x8-block formulation (fast path); tile=None: one SVD per frame like the reference's
-    image embed (batched over the frames of a chunk; use a smaller ``batch``, e.g. 8)."""
+    image embed (batched over the frames of a chunk; use a smaller ``batch``, e.g. 8).
+    ``strength="masked"`` with ``mask=(lo, hi, cut)``: texture-masked strength as in dct_svd_core_secure.embed (tile mode);
+    the meta carries the rule and extract / detect read it back."""
     return _embed_video(_Luma, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
-                        password, nonce, kfrac, k_floor, batch, device, tile)
+                        password, nonce, kfrac, k_floor, batch, device, tile, strength=strength, mask=mask)
 
 
 def extract_watermark_video(stego_video_path: str, metadata_path: str, output_image_path: str,
                             password: str, normalize: bool = True, *, batch: int = 32, device: int = 0,
                             enhance=False) -> str:
-    """Averaged multi-frame extraction -> watermark image (PNG).  ``enhance`` as in dct_svd_core_secure.extract."""
+    """Averaged multi-frame extraction -> watermark image (PNG).  ``enhance`` as in dct_svd_core_secure.extract.  A meta
+    written with ``strength="masked"`` is extracted by its rule, frame by frame; the frames' estimates are then averaged
+    plainly (extract_frames_mean)."""
     return _extract_video(_Luma, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance)
 
 
 def detect_watermark_video(stego_video_path: str, metadata_path: str, thresh: float = 0.6, *,
                            batch: int = 32, device: int = 0):
-    """(bool, mean score, per-frame scores) over the marked frames."""
+    """(bool, mean score, per-frame scores) over the marked frames; a masked meta is scored by its rule."""
     return _detect_video(_Luma, stego_video_path, metadata_path, thresh, batch, device)
 
 
@@ -443,26 +461,28 @@ def embed_watermark_video_color(host_video_path: str, watermark_path: str, outpu
                                 metadata_path: str, alpha: float = 0.1, frame_interval: int = 1, *,
                                 password: str = "", nonce: Optional[bytes] = None, kfrac: float = hg.K_FRAC_DEFAULT,
                                 k_floor: int = 8, batch: int = 8, device: int = 0, tile: Optional[int] = TILE,
-                                subsampling: str = "refuse"):
+                                subsampling: str = "refuse", strength: str = "uniform", mask=M.MASK_DEFAULT):
     """Embed a colour watermark into the B, G, R planes of every ``frame_interval``-th frame of a .y4m video.
     Returns (output_video_path, metadata_path, mean PSNR of the marked frames' BGR planes).
     ``subsampling``: what to do with a container whose chroma is subsampled.  "refuse" (default): only 4:4:4 (C444) is
     taken.  "box": 4:2:0 (C420, C420jpeg, C420mpeg2, C420paldv) and 4:2:2 (C422) are taken too - chroma is replicated to
     full resolution on the way in and box-averaged (half up) on the way out; the siting a C420* tag names is carried
     through in the header and otherwise ignored, one filter serves all of them.  The meta then names the chroma format
-    and extract / detect read the same kind of container with nothing but the meta and the password."""
+    and extract / detect read the same kind of container with nothing but the meta and the password.
+    ``strength`` / ``mask``: as in embed_watermark_video, one gain per channel plane."""
     return _embed_video(_Bgr444, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
-                        password, nonce, kfrac, k_floor, batch, device, tile, subsampling)
+                        password, nonce, kfrac, k_floor, batch, device, tile, subsampling, strength, mask)
 
 
 def extract_watermark_video_color(stego_video_path: str, metadata_path: str, output_image_path: str, password: str,
                                   normalize: bool = True, *, batch: int = 8, device: int = 0, enhance=False) -> str:
     """Averaged multi-frame extraction per channel -> colour watermark image (PNG).  ``enhance`` as in
-    dct_svd_core_secure.extract."""
+    dct_svd_core_secure.extract; a masked meta as in extract_watermark_video."""
     return _extract_video(_Bgr444, stego_video_path, metadata_path, output_image_path, password, normalize, batch, device, enhance)
 
 
 def detect_watermark_video_color(stego_video_path: str, metadata_path: str, thresh: float = 0.6, *,
                                  batch: int = 8, device: int = 0):
-    """(bool, mean score, per-frame scores): a frame's score is the mean of its three channels' NC (single:317)."""
+    """(bool, mean score, per-frame scores): a frame's score is the mean of its three channels' NC (single:317); a masked
+    meta is scored by its rule."""
     return _detect_video(_Bgr444, stego_video_path, metadata_path, thresh, batch, device)

@@ -178,6 +178,66 @@ int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c,
                        int n_planes, int H, int W, int row_stride, size_t plane_stride,
                        size_t sigma_w_plane_stride, float alpha);
 
+/* ---- Tile mode with texture-masked strength ------------------------------
+ * The rule ("Texture-masked strength"; part of the meta format).  For a tile with cover singular values
+ * s_1 >= .. >= s_8 (float32, as written to sigma_c) and parameters lo, hi, cut:
+ *   r = sqrt(s_2^2 + .. + s_8^2);  g = clamp((r - lo) / (hi - lo), 0, 1) in float32;  G = (1, g, g, g, g, g, g, g)
+ *   embed    s'_i = s_i + alpha * G_i * sw_i for i < K
+ *   carried  a tile is carried iff g >= cut
+ *   extract  sw_hat_1 = (s~_1 - s_1) / max(alpha, 1e-8) for every tile; sw_hat_i = (s~_i - s_i) / (max(alpha, 1e-8) * g) for
+ *            i >= 2 on carried tiles, 0 on the others; then sw_hat_i = 0 for i >= K
+ *   detect   _nc (single:284-289) over the i = 1 values of all tiles and the i >= 2 values of carried tiles only
+ * Parameters: 0 <= lo < hi, both finite, 0 < cut <= 1; anything else is WM_ERR_BADARG (checked by the _dev entry points,
+ * which the host-pointer forms go through).  Rows and columns outside the tile
+ * grid pass through as in the unmasked entry points, whose arguments the masked ones share. */
+
+/* The rule's g and G o sigma_w per tile: K2 on the cover planes, then
+ *   sigma_w_eff  [n_planes][n_tiles][8]  G o sigma_w (dense, also where sigma_w is shared: sigma_w_plane_stride 0)
+ *   gain         [n_planes][n_tiles] g, or NULL to skip.
+ * sigma_w and sigma_w_eff may both be NULL when only gain is wanted. */
+int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                                 int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float lo, float hi);
+int wm_mask_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                             int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                             size_t sigma_w_plane_stride, float lo, float hi);
+
+/* The rule's embed: wm_mask_sigma_w_tiles_u8_dev into a buffer the context owns, then wm_embed_tiles_u8_dev with
+ * G o sigma_w.  sigma_c is the cover's, as in the unmasked embed; stego may alias host. */
+int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
+                                 float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi);
+int wm_embed_tiles_masked_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
+                             float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                             size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi);
+
+/* The rule's extract: wm_extract_tiles_u8_dev / _px_u8_dev / wm_extract_tiles_u8 / _sum_u8 with g taken from sigma_c inside
+ * the kernel (the whole chain to uint8: wm_extract_unscrambled_masked_u8_dev, below). */
+int wm_extract_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                   const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
+                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K,
+                                   float lo, float hi, float cut);
+int wm_extract_tiles_px_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Ux,
+                                      const float* Vxt, float* out, int n_planes, int H, int W, int row_stride,
+                                      size_t plane_stride, size_t uv_plane_stride, float alpha, int K,
+                                      float lo, float hi, float cut);
+int wm_extract_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                               const float* Vwt, float* out, int n_planes, int H, int W, int row_stride,
+                               size_t plane_stride, size_t uv_plane_stride, float alpha, int K,
+                               float lo, float hi, float cut);
+int wm_extract_tiles_sum_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                   const float* Vwt, float* out_sum, int n_planes, int H, int W, int row_stride,
+                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K,
+                                   float lo, float hi, float cut);
+
+/* The rule's detect: wm_detect_tiles_u8[_dev] over the values the rule takes; their number is counted on the device. */
+int wm_detect_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                                  double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                  size_t sigma_w_plane_stride, float alpha, float lo, float hi, float cut);
+int wm_detect_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
+                              double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                              size_t sigma_w_plane_stride, float alpha, float lo, float hi, float cut);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
@@ -346,6 +406,11 @@ int wm_unpermute_normalize_u8_dev(wm_ctx* ctx, const float* src, const wm_route*
 int wm_extract_unscrambled_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw, const float* Vwt,
                                   const wm_route* route, uint8_t* out, int n_planes, int H, int W, int row_stride,
                                   size_t plane_stride, size_t uv_plane_stride, float alpha, int K, int px, int do_norm);
+/* The same with texture-masked strength (the rule above wm_mask_sigma_w_tiles_u8_dev): sw_hat by the rule's extract. */
+int wm_extract_unscrambled_masked_u8_dev(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
+                                         const float* Vwt, const wm_route* route, uint8_t* out, int n_planes, int H, int W,
+                                         int row_stride, size_t plane_stride, size_t uv_plane_stride, float alpha, int K,
+                                         int px, int do_norm, float lo, float hi, float cut);
 /* the scramble direction through the same route (single:66-72, 124-126): dst[p][i] = (float) src[p][idx[i]], uint8 planes
  * in, float32 out; values identical to wm_permute_u8_f32_dev */
 int wm_permute_u8_f32_routed_dev(wm_ctx* ctx, const uint8_t* src, const wm_route* route, float* dst, size_t n, int n_planes);
