@@ -16,7 +16,12 @@ extract_watermark = _impl.extract_watermark
 embed_arrays = _impl.embed_arrays
 extract_arrays = _impl.extract_arrays
 detect_arrays = _impl.detect_arrays
+embed_payload = _impl.embed_payload
+extract_payload = _impl.extract_payload
+embed_payload_arrays = _impl.embed_payload_arrays
+extract_payload_arrays = _impl.extract_payload_arrays
 K_FRAC_DEFAULT = _impl.K_FRAC_DEFAULT
 
 __all__ = ["embed", "extract", "detect", "embed_watermark", "extract_watermark",
-           "embed_arrays", "extract_arrays", "detect_arrays", "K_FRAC_DEFAULT"]
+           "embed_arrays", "extract_arrays", "detect_arrays", "embed_payload", "extract_payload",
+           "embed_payload_arrays", "extract_payload_arrays", "K_FRAC_DEFAULT"]

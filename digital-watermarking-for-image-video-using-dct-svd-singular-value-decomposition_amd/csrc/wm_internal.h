@@ -52,6 +52,8 @@ struct wm_ctx {
   size_t extract_f32_bytes = 0;
   void* mask_sw = nullptr;        // grow-only G o sigma_w of the masked tile embed (k_mask_sigma_w -> the embed launches)
   size_t mask_sw_bytes = 0;
+  void* payload_ws = nullptr;     // grow-only: the payload embed's sigma_w rows, or the payload decode's per-tile metric
+  size_t payload_ws_bytes = 0;
   static constexpr int MAX_PAIR_TABS = 6;   // round-robin tournaments of the block Jacobi, by block count
   void* pair_tab[MAX_PAIR_TABS] = {};
   int pair_tab_nbk[MAX_PAIR_TABS] = {};

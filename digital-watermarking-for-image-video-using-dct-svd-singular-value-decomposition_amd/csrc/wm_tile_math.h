@@ -1326,4 +1326,48 @@ WM_HD bool mask_keep(const float (&sc)[8], const float lo, const float hi, const
   return carried;
 }
 
+// ---- blind payload: sigma_1 quantisation ("Blind payload"; include/wmhip.h) ----------
+// A tile carries one bit in the parity of its leading singular value on the lattice {k delta}: bit 0 on the even points,
+// bit 1 on the odd ones.  The decoder needs delta and nothing of the cover.
+// PAYLOAD_BIAS: the embed kernel clips and TRUNCATES to uint8, which takes half a gray level off each of the 64 pixels on
+// average, and sigma_1 of a natural tile is close to 8 x its mean: 64 * 0.5 / 8 = 4.  The embed aims that much above the
+// lattice point so that the stored tile lands on it.
+constexpr float PAYLOAD_BIAS = 4.0f;
+constexpr float PAYLOAD_SIGMA_MAX = 2040.0f;   // 8 * 255: sigma_1 of a white tile
+constexpr float PAYLOAD_DELTA_MIN = 8.0f, PAYLOAD_DELTA_MAX = 512.0f;
+
+WM_HD bool payload_delta_ok(const float delta) { return delta >= PAYLOAD_DELTA_MIN && delta <= PAYLOAD_DELTA_MAX; }   // (NaN fails)
+
+// What sigma_1 of the stego tile is aimed at, q + PAYLOAD_BIAS: q the point of {2 k delta + bit * delta} nearest to s_1
+// (ties to even, as rintf), one step down where the aim would lie above a white tile, then up until it leaves s_2 at least
+// delta behind - sigma_1 stays the leading value (q >= s_1 - 3 delta and s_2 <= s_1: at most 2 steps; the loop allows 3).
+// All in float32; the product 2 delta * k + bit * delta is ONE fused multiply-add, so host and device agree for every delta
+// (for a delta with few mantissa bits - 8, 16, 24 .. - the product is exact and a separate multiply and add give the same).
+WM_HD float payload_target(const float (&s)[8], const int bit, const float delta) {
+  const float two_d = 2.0f * delta, b = bit ? delta : 0.0f;
+  float q = ffma(two_d, rintf((s[0] - b) / two_d), b);
+  if (q + PAYLOAD_BIAS > PAYLOAD_SIGMA_MAX) q -= two_d;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    if (q < s[1] + delta) q += two_d;
+  return q + PAYLOAD_BIAS;
+}
+
+// The sigma_w row the unchanged embed is fed with alpha = 1, K = 1: (target - s_1, 0, .., 0)
+WM_HD void payload_sigma_w(const float (&s)[8], const int bit, const float delta, float (&sw)[8]) {
+  sw[0] = payload_target(s, bit, delta) - s[0];
+#pragma unroll
+  for (int i = 1; i < 8; ++i) sw[i] = 0.0f;
+}
+
+// The decoder's soft value of a stego tile: +1 on a bit-0 lattice point, -1 on a bit-1 point, linear in between (0 half
+// way).  The multiply by the float32 reciprocal of 2 delta is the one place a compiler could not change the result of: x -
+// floor(x) is exact, and the doublings are exact, so 2 f - 1 and 2 |.| - 1 round the same fused or not.  Host, device and a
+// NumPy restatement agree bit for bit.
+WM_HD float payload_metric(const float s1, const float inv_2delta) {
+  const float x = s1 * inv_2delta;
+  const float f = x - floorf(x);
+  return 2.0f * fabsf(2.0f * f - 1.0f) - 1.0f;
+}
+
 }  // namespace wm

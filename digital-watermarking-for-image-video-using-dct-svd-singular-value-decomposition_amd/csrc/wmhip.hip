@@ -864,6 +864,93 @@ __global__ __launch_bounds__(256) void k_detect_finalize(const double* __restric
 }
 
 // ---------------------------------------------------------------------------
+// Blind payload (wm_tile_math.h, payload_target / payload_metric): one bit per tile in the parity of sigma_1
+// ---------------------------------------------------------------------------
+// K2 on the cover tile, then the rule's sigma_w row (target - s_1, 0, .., 0) to a dense [plane][tile][8] array that the
+// unchanged embed launches are fed with a per-plane stride, alpha = 1 and K = 1.  tile_bit[n_tiles] is shared by the planes.
+// `black` (optional, [plane][tile]): 1 for a tile whose 64 pixels are 0 - see k_payload_black.
+template <bool ALIGNED>
+__global__ __launch_bounds__(WAVE, 3) void k_payload_sigma_w(const uint8_t* __restrict__ planes,
+                                                         const uint8_t* __restrict__ tile_bit, float* __restrict__ sw_eff,
+                                                         uint8_t* __restrict__ black, const Geom g, const float delta,
+                                                         int* __restrict__ status) {
+  int t, ty, tx;
+  if (!tile_coords(g, t, ty, tx)) return;
+  const size_t plane = blockIdx.y;
+  wm::RawTile raw;
+  float s[8], sw[8];
+  load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
+  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
+  wm::payload_sigma_w(s, tile_bit[t] & 1, delta, sw);
+  store_row8_f32<true>(sw_eff + (plane * g.n_tiles + t) * 8, sw);
+  if (black) black[plane * g.n_tiles + t] = (wm::raw_is_constant(raw) && raw.lo[0] == 0u) ? 1 : 0;
+}
+
+// A black cover tile is the zero matrix: it has no leading singular vector of its own, and the embed's closed form for
+// constant tiles gives it those of a fixed noise pattern, half of whose pixels clip at 0 - sigma_1 would land far from its
+// lattice point.  The payload embed takes the flat vector instead (what np.linalg.svd returns for a zero matrix: U = V = I,
+// the DC term): the tile becomes the constant (q + c) / 8.  Runs after the unchanged embed launches and rewrites only the
+// tiles flagged by k_payload_sigma_w (sw_eff[0] = q + c there, s_1 being 0); stego and yw are addressed as the embed does.
+template <bool ALIGNED>
+__global__ __launch_bounds__(WAVE) void k_payload_black(uint8_t* __restrict__ stego, float* __restrict__ yw,
+                                                    const float* __restrict__ sw_eff, const uint8_t* __restrict__ black,
+                                                    const Geom g) {
+  int t, ty, tx;
+  if (!tile_coords(g, t, ty, tx)) return;
+  const size_t plane = blockIdx.y;
+  const size_t i = plane * g.n_tiles + t;
+  if (!black[i]) return;
+  const float v = sw_eff[i * 8] * 0.125f;
+  const uint32_t w = wm::quant_u8(v) * 0x01010101u;
+  uint8_t* p = STRIDED_TILE(stego, g, plane, ty, tx);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) store_px8<ALIGNED>(p + r * g.row_stride, w, w);
+  if (yw) {
+    float* o = DENSE_TILE(yw, g, plane, ty, tx);
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+      for (int c = 0; c < 8; ++c) o[(size_t)r * g.W + c] = v;
+  }
+}
+
+// K2 on the stego tile, then the decoder's soft value of its sigma_1 to metric[plane][tile]: 4 bytes a tile where K2 stores 32
+template <bool ALIGNED>
+__global__ __launch_bounds__(WAVE, 3) void k_payload_metric(const uint8_t* __restrict__ stego, float* __restrict__ metric,
+                                                        const Geom g, const float inv_2delta, int* __restrict__ status) {
+  int t, ty, tx;
+  if (!tile_coords(g, t, ty, tx)) return;
+  const size_t plane = blockIdx.y;
+  wm::RawTile raw;
+  float s[8];
+  load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
+  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
+  metric[plane * g.n_tiles + t] = wm::payload_metric(s[0], inv_2delta);
+}
+
+// soft[j] = sum of metric[p][order[i]], i in [offs[j], offs[j + 1]), over all planes: one wave per bit, no atomics.  order /
+// offs are the CSR inverse of the tile-to-bit map (a bit's tiles in ascending tile index).  A lane adds its strided share in
+// float64 - planes ascending, then i ascending - and the 64 shares are added by the fixed tree of wave_sum: the same inputs
+// give the same bits.  (The terms are float32 values of magnitude <= 1, so the float64 sums carry no visible rounding.)
+__global__ __launch_bounds__(WAVE) void k_payload_reduce(const float* __restrict__ metric, const int* __restrict__ order,
+                                                     const int* __restrict__ offs, double* __restrict__ soft,
+                                                     const int n_tiles, const int n_planes) {
+  const int j = blockIdx.x;
+  const int lo = max(offs[j], 0), hi = min(offs[j + 1], n_tiles);     // (order has n_tiles entries: device offsets are not trusted)
+  double acc = 0.0;
+  for (int p = 0; p < n_planes; ++p) {
+    const float* __restrict__ m = metric + (size_t)p * n_tiles;
+#pragma unroll 4
+    for (int i = lo + (int)threadIdx.x; i < hi; i += WAVE) {
+      const int t = order[i];
+      if ((unsigned)t < (unsigned)n_tiles) acc += (double)m[t];   // (an entry outside the grid is never followed)
+    }
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) soft[j] = acc;
+}
+
+// ---------------------------------------------------------------------------
 // host-side argument checking / launch helpers
 // ---------------------------------------------------------------------------
 int check_plane_args(const wm_ctx* ctx, const void* p, int n_planes, int H, int W, int row_stride,
@@ -904,6 +991,12 @@ inline dim3 tile_grid(const Geom& g, int n_planes) {
 int check_mask(const float lo, const float hi, const float cut) {
   if (!(isfinite(lo) && isfinite(hi) && lo >= 0.0f && lo < hi)) return set_err(WM_ERR_BADARG, "mask needs finite 0 <= lo < hi");
   if (!(cut > 0.0f && cut <= 1.0f)) return set_err(WM_ERR_BADARG, "mask needs 0 < cut <= 1");
+  return WM_OK;
+}
+
+// the payload rule's step (include/wmhip.h): 8 <= delta <= 512, finite
+int check_delta(const float delta) {
+  if (!(isfinite(delta) && wm::payload_delta_ok(delta))) return set_err(WM_ERR_BADARG, "payload needs a finite delta in 8..512");
   return WM_OK;
 }
 
@@ -974,6 +1067,7 @@ int wm_destroy(wm_ctx* ctx) {
   if (ctx->route_tmp) (void)hipFree(ctx->route_tmp);
   if (ctx->extract_f32) (void)hipFree(ctx->extract_f32);
   if (ctx->mask_sw) (void)hipFree(ctx->mask_sw);
+  if (ctx->payload_ws) (void)hipFree(ctx->payload_ws);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) if (ctx->pair_tab[i]) (void)hipFree(ctx->pair_tab[i]);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) {
     if (ctx->hier_dev[i]) (void)hipFree(ctx->hier_dev[i]);
@@ -1178,6 +1272,97 @@ int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* 
                                         sigma_w_plane_stride, lo, hi));
   }
   return wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, alpha, K);
+}
+
+// ---- blind payload: K2 + target, K1 fed with it; K2 + metric, per-bit sums -------
+static int payload_sigma_w_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff, uint8_t* black,
+                               int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const Geom g = make_geom(H, W, row_stride, plane_stride);
+  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
+  if (!tile_bit) return set_err(WM_ERR_BADARG, "tile_bit is NULL");
+  if (!sigma_w_eff || ((uintptr_t)sigma_w_eff & 15u)) return set_err(WM_ERR_BADARG, "sigma_w_eff is NULL or not 16-byte aligned");
+  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+  with_bools([&](auto A) {
+    hipLaunchKernelGGL((k_payload_sigma_w<A.value>), grid, block, 0, ctx->stream, planes, tile_bit, sigma_w_eff, black, g,
+                       delta, ctx->d_status);
+  }, u8_aligned(planes, planes, row_stride, plane_stride));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+int wm_payload_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+                                    int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return payload_sigma_w_dev(ctx, planes, tile_bit, sigma_w_eff, nullptr, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+// The structure of wm_embed_tiles_masked_u8_dev: the sigma pass reads the host planes before anything writes (one stream),
+// so stego may alias host; the rule's sigma_w rows live in a grow-only buffer of the context.
+int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
+  const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
+  float* eff = nullptr;
+  uint8_t* black = nullptr;
+  if (n_planes > 0 && nt8 > 0) {
+    if (!tile_bit || !sigma_c) return set_err(WM_ERR_BADARG, "tile_bit / sigma_c is NULL");
+    WM_TRY(staged(ctx, &ctx->payload_ws, &ctx->payload_ws_bytes, "payload sigma_w", [&](Carve& cv) {
+      eff = cv.take<float>((size_t)n_planes * nt8);
+      black = cv.take<uint8_t>((size_t)n_planes * (nt8 / 8));
+    }));
+    WM_TRY(payload_sigma_w_dev(ctx, host, tile_bit, eff, black, n_planes, H, W, row_stride, plane_stride, delta));
+  }
+  WM_TRY(wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, 1.0f, 1));
+  if (eff) {
+    const Geom g = make_geom(H, W, row_stride, plane_stride);
+    const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+    with_bools([&](auto A) {
+      hipLaunchKernelGGL((k_payload_black<A.value>), grid, block, 0, ctx->stream, stego, yw, (const float*)eff,
+                         (const uint8_t*)black, g);
+    }, u8_aligned(host, stego, row_stride, plane_stride));
+    WM_HIP(hipGetLastError());
+  }
+  return WM_OK;
+}
+
+int wm_payload_metric_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+                                   int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const Geom g = make_geom(H, W, row_stride, plane_stride);
+  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
+  if (!metric || ((uintptr_t)metric & 3u)) return set_err(WM_ERR_BADARG, "metric is NULL or not 4-byte aligned");
+  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+  const float inv_2delta = 1.0f / (2.0f * delta);
+  with_bools([&](auto A) {
+    hipLaunchKernelGGL((k_payload_metric<A.value>), grid, block, 0, ctx->stream, stego, metric, g, inv_2delta, ctx->d_status);
+  }, u8_aligned(stego, stego, row_stride, plane_stride));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// the metric into a grow-only buffer of the context, then one wave per bit over it
+int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                                 double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const size_t nt = (size_t)(H / 8) * (size_t)(W / 8);
+  if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
+  if (n_bits < 1 || (size_t)n_bits > nt) return set_err(WM_ERR_BADARG, "n_bits must be in 1..n_tiles");
+  if (!order || !offs || !soft || (((uintptr_t)order | (uintptr_t)offs) & 3u) || ((uintptr_t)soft & 7u))
+    return set_err(WM_ERR_BADARG, "order / offs / soft is NULL or misaligned");
+  float* metric = nullptr;
+  WM_TRY(staged(ctx, &ctx->payload_ws, &ctx->payload_ws_bytes, "payload metric", [&](Carve& cv) {
+    metric = cv.take<float>((size_t)n_planes * nt);
+  }));
+  WM_TRY(wm_payload_metric_tiles_u8_dev(ctx, stego, metric, n_planes, H, W, row_stride, plane_stride, delta));
+  hipLaunchKernelGGL(k_payload_reduce, dim3((unsigned)n_bits), dim3(WAVE), 0, ctx->stream, (const float*)metric,
+                     (const int*)order, (const int*)offs, soft, (int)nt, n_planes);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
 }
 
 // ---- K3 --------------------------------------------------------------------
@@ -1653,6 +1838,111 @@ int wm_detect_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* si
   const MaskParams mk{lo, hi, cut};
   return detect_tiles_host(ctx, stego, sigma_c, sigma_w, scores, n_planes, H, W, row_stride, plane_stride,
                            sigma_w_plane_stride, alpha, &mk);
+}
+
+// ---- blind payload, host pointers ---------------------------------------------
+int wm_payload_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+                                int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  if (n_planes == 0 || nt == 0) return WM_OK;
+  if (!tile_bit || !sigma_w_eff) return set_err(WM_ERR_BADARG, "tile_bit / sigma_w_eff is NULL");
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  const size_t n_eff = (size_t)n_planes * nt * 8;
+  uint8_t *d_p, *d_bit; float* d_eff;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_bit = cv.take<uint8_t>(nt);
+    d_eff = cv.take<float>(n_eff);
+  }));
+  WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
+  WM_HIP(hipMemcpyAsync(d_bit, tile_bit, nt, hipMemcpyHostToDevice, ctx->stream));
+  WM_TRY(wm_payload_sigma_w_tiles_u8_dev(ctx, d_p, d_bit, d_eff, n_planes, H, W, row_stride, plane_stride, delta));
+  WM_HIP(hipMemcpyAsync(sigma_w_eff, d_eff, n_eff * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return wm_check_status(ctx);
+}
+
+int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                              float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");
+  if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  if (nt > 0 && (!tile_bit || !sigma_c)) return set_err(WM_ERR_BADARG, "tile_bit / sigma_c is NULL");
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  const size_t n_sc = (size_t)n_planes * nt * 8;
+  const size_t n_yw = yw ? (size_t)n_planes * H * W : 0;
+  uint8_t *d_host, *d_stego, *d_bit; float *d_sc, *d_yw;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_host = cv.take<uint8_t>(span);
+    d_stego = cv.take<uint8_t>(span);
+    d_bit = cv.take<uint8_t>(nt);
+    d_sc = cv.take<float>(n_sc);
+    d_yw = yw ? cv.take<float>(n_yw) : nullptr;
+  }));
+  WM_HIP(hipMemcpyAsync(d_host, host, span, hipMemcpyHostToDevice, ctx->stream));
+  // bytes between rows / planes that belong to the caller must survive the round trip
+  if (stego != host) WM_HIP(hipMemcpyAsync(d_stego, stego, span, hipMemcpyHostToDevice, ctx->stream));
+  else d_stego = d_host;
+  if (nt) WM_HIP(hipMemcpyAsync(d_bit, tile_bit, nt, hipMemcpyHostToDevice, ctx->stream));
+  WM_TRY(wm_embed_tiles_payload_u8_dev(ctx, d_host, d_bit, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride, delta));
+  WM_HIP(hipMemcpyAsync(stego, d_stego, span, hipMemcpyDeviceToHost, ctx->stream));
+  if (nt) WM_HIP(hipMemcpyAsync(sigma_c, d_sc, n_sc * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (yw) WM_HIP(hipMemcpyAsync(yw, d_yw, n_yw * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return wm_check_status(ctx);
+}
+
+int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+                               int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  if (n_planes == 0 || nt == 0) return WM_OK;
+  if (!metric) return set_err(WM_ERR_BADARG, "metric is NULL");
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  const size_t n_m = (size_t)n_planes * nt;
+  uint8_t* d_p; float* d_m;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_m = cv.take<float>(n_m);
+  }));
+  WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
+  WM_TRY(wm_payload_metric_tiles_u8_dev(ctx, d_p, d_m, n_planes, H, W, row_stride, plane_stride, delta));
+  WM_HIP(hipMemcpyAsync(metric, d_m, n_m * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return wm_check_status(ctx);
+}
+
+// The host form sees order / offs and checks them: offs runs from 0 to n_tiles without decreasing, every order entry names
+// a tile of the grid (the device form takes both as they are and only refuses to follow an entry outside the grid).
+int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                             double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  if (n_bits < 1 || (size_t)n_bits > nt) return set_err(WM_ERR_BADARG, "n_bits must be in 1..n_tiles");
+  if (!order || !offs || !soft) return set_err(WM_ERR_BADARG, "order / offs / soft is NULL");
+  if (offs[0] != 0 || (size_t)offs[n_bits] != nt) return set_err(WM_ERR_BADARG, "offs must run from 0 to n_tiles");
+  for (int j = 0; j < n_bits; ++j)
+    if (offs[j + 1] < offs[j]) return set_err(WM_ERR_BADARG, "offs decreases");
+  for (size_t i = 0; i < nt; ++i)
+    if (order[i] < 0 || (size_t)order[i] >= nt) return set_err(WM_ERR_BADARG, "order names a tile outside the grid");
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  uint8_t* d_p; int32_t *d_order, *d_offs; double* d_soft;
+  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span);
+    d_order = cv.take<int32_t>(nt);
+    d_offs = cv.take<int32_t>((size_t)n_bits + 1);
+    d_soft = cv.take<double>((size_t)n_bits);
+  }));
+  WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
+  WM_HIP(hipMemcpyAsync(d_order, order, nt * 4, hipMemcpyHostToDevice, ctx->stream));
+  WM_HIP(hipMemcpyAsync(d_offs, offs, ((size_t)n_bits + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  WM_TRY(wm_payload_soft_tiles_u8_dev(ctx, d_p, d_order, d_offs, n_bits, d_soft, n_planes, H, W, row_stride, plane_stride, delta));
+  WM_HIP(hipMemcpyAsync(soft, d_soft, (size_t)n_bits * 8, hipMemcpyDeviceToHost, ctx->stream));
+  return wm_check_status(ctx);
 }
 
 }  // extern "C"

@@ -44,6 +44,7 @@ import numpy as np
 from . import hostapi
 from . import hostglue as hg
 from . import meta as M
+from . import payload as P
 
 K_FRAC_DEFAULT = hg.K_FRAC_DEFAULT
 TILE = 8
@@ -235,6 +236,7 @@ def extract_arrays(stego: np.ndarray, meta, password: str, normalize: bool = Tru
     M.check_enhance(enhance)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")                                # single:193-194
+    M.refuse_payload(meta, "extract")
     mode = _mode_of(meta); alpha = float(meta["alpha"])                    # single:196
     H, W = map(int, meta["shape"])
     nonce = M.nonce_of(meta); digest = M.digest_of(meta)
@@ -289,6 +291,7 @@ def _extract_checked(stego, meta, mode, alpha, kfrac, k_floor, H, W, key, normal
 
 
 def detect_arrays(stego: np.ndarray, meta, thresh: float = 0.6, device: int = 0):
+    M.refuse_payload(meta, "detect")
     mode = _mode_of(meta); alpha = float(meta["alpha"])                    # single:293
     tile = M.tile_of(meta)
     if tile is not None:
@@ -356,8 +359,106 @@ def extract(stego_path: str, meta_path: str, out_path: str, password: str,
 def detect(stego_path: str, meta_path: str, thresh: float = 0.6, *, device: int = 0):
     """single:291-318.  Returns (bool, score)."""
     data = np.load(meta_path, allow_pickle=False)                          # single:292
+    M.refuse_payload(data, "detect")
     st = hg.read_image_bgr(stego_path)                                     # single:294
     return detect_arrays(st, data, thresh, device)
+
+
+# ---------------------------------------------------------------------------
+# blind text / JSON / bytes payload (tile mode): one bit per 8x8 tile in the parity of its leading singular value
+# (include/wmhip.h, DESIGN.md section 14).  The payload goes into Y of BGR2YCrCb and comes back through _from_Y - the gray
+# pipeline the reference's text branch uses (core:116-123) - and is read back with the password and a meta of a few
+# hundred bytes: nothing of the cover.
+# ---------------------------------------------------------------------------
+def _payload_map_of(H: int, W: int, key: bytes, n_bits: int):
+    return P.payload_map(H // TILE, W // TILE, key, n_bits)
+
+
+def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: bytes, *, payload_type: str = "text",
+                         delta: float = P.DELTA_DEFAULT, device: int = 0) -> dict:
+    """cover BGR uint8, data bytes (or a str: the text / JSON itself).  Returns dict(stego BGR uint8, meta dict, psnr, ssim)."""
+    M.check_password_type(password, "embed")
+    M.require_password(password, "embed")
+    delta = hostapi.check_delta(delta)
+    data = P.payload_bytes(data, payload_type, allow_file=False)
+    if cover_bgr.dtype != np.uint8 or cover_bgr.ndim != 3 or cover_bgr.shape[2] != 3:
+        raise ValueError("cover must be uint8 [H, W, 3]")
+    H, W = cover_bgr.shape[:2]
+    bits = P.payload_frame(data)
+    P.check_capacity(bits.size, P.capacity_bits(H, W))                     # before any device call
+    key = hg.derive_key(password, nonce)
+    tbi, _, _ = _payload_map_of(H, W, key, bits.size)
+    ctx = _ctx(device)
+    Y = _Gray.planes_in(ctx, cover_bgr)                                    # core:117 (_to_Y)
+    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(bits, tbi), delta, want_yw=True)
+    members = M.payload_members(payload_type, H, W, delta, bits.size, nonce)
+    digest = hg.hmac_digest(key, M.hmac_parts(members))
+    stego = _Gray.planes_out(ctx, cover_bgr, stego_y)                      # core:123 (_from_Y)
+    ps = ctx.psnr(cover_bgr, stego)
+    ss = ctx.ssim(ctx.color("bgr2gray", cover_bgr), Yw)
+    return dict(stego=stego, meta=M.sealed(members, TILE, digest), psnr=ps, ssim=ss)
+
+
+def _payload_meta_checked(meta, password: str):
+    """(H, W, delta, n_bits, payload_type, key) of an authentic payload meta"""
+    M.check_password_type(password, "extract")
+    M.require_password(password, "extract")
+    meta = M.unpack_payload(meta)
+    M.require_payload(meta)
+    key = hg.derive_key(password, M.nonce_of(meta))
+    if not M.authentic(meta, key):
+        raise ValueError(M.WRONG_PASSWORD)
+    H, W = map(int, meta["shape"])
+    n_bits = int(meta["payload_bits"])
+    if n_bits < 8 * P.OVERHEAD_BYTES or n_bits % 8 or n_bits > P.capacity_bits(H, W) or M.tile_of(meta) != TILE:
+        raise ValueError("payload meta does not describe a frame of this image size")
+    ptype = str(meta["payload_type"])
+    P.check_type(ptype)
+    return meta, H, W, hostapi.check_delta(float(meta["delta"])), n_bits, ptype, key
+
+
+def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0):
+    """-> (data bytes, valid, confidence).  valid: the decoded frame's length header and CRC hold.  confidence: the mean
+    over the bits of |soft| / (tiles voting), 1 for an untouched stego and near 0 for an image that carries nothing."""
+    meta, H, W, delta, n_bits, _, key = _payload_meta_checked(meta, password)
+    _check_stego_shape(stego_bgr, meta)
+    _, order, offs = _payload_map_of(H, W, key, n_bits)
+    ctx = _ctx(device)
+    soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, n_bits, delta)
+    data, valid = P.payload_unframe(soft < 0)
+    return data, bool(valid), P.confidence(soft, offs, 1)
+
+
+def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, password: Optional[str] = None,
+                  payload_type: str = "text", delta: float = P.DELTA_DEFAULT, nonce: Optional[bytes] = None, device: int = 0):
+    """``payload``: a str or bytes, or the path of a .txt / .json file (read when it exists, like the reference's
+    text_data / wm_source, core:102-106).  Returns (out_path, meta_path, psnr, ssim); the stego is written as PNG."""
+    M.check_password_type(password, "embed")
+    M.require_password(password, "embed")
+    hostapi.check_delta(delta)
+    data = P.payload_bytes(payload, payload_type)                          # refused before anything else is read
+    cover = hg.read_image_bgr(cover_path)
+    if nonce is None:
+        nonce = os.urandom(8)
+    # (a json payload is canonical by now; canonicalising it again inside leaves it as it is)
+    r = embed_payload_arrays(cover, data, password, nonce, payload_type=payload_type, delta=delta, device=device)
+    out_path = M.out_name(out_path, "_stego.png")
+    if not hg.write_png(out_path, r["stego"], 0):
+        raise IOError("Ghi stego thất bại.")
+    M.save_payload_meta(meta_path, r["meta"])                              # one packed member: 0.7 KB, the same size whatever the values
+    return out_path, meta_path, r["psnr"], r["ssim"]
+
+
+def extract_payload(stego_path: str, meta_path: str, out_path: Optional[str] = None, *, password: Optional[str] = None,
+                    device: int = 0):
+    """-> (data, valid, confidence, path written or None).  With ``out_path`` the payload is written as ``_text.txt`` /
+    ``_data.json`` by the reference's renaming (core:229-242)."""
+    M.check_password_type(password, "extract")
+    M.require_password(password, "extract")
+    meta = M.load_payload_meta(meta_path)
+    data, valid, conf = extract_payload_arrays(hg.read_image_bgr(stego_path), meta, password, device)
+    written = P.write_payload(out_path, data, str(meta["payload_type"])) if out_path else None
+    return data, valid, conf, written
 
 
 embed_watermark = embed

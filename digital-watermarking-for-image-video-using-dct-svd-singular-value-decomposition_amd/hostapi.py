@@ -85,6 +85,15 @@ SIGNATURES = {
     "wm_extract_unscrambled_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _i, _i, _i, _f, _f, _f],
     "wm_detect_tiles_masked_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f, _f, _f],
     "wm_detect_tiles_masked_u8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f, _f, _f, _f],
+    # blind payload (one bit per tile in the parity of sigma_1): the plane arguments, then delta
+    "wm_payload_sigma_w_tiles_u8_dev": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_sigma_w_tiles_u8": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_embed_tiles_payload_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_embed_tiles_payload_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_metric_tiles_u8_dev": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_metric_tiles_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_soft_tiles_u8_dev": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_soft_tiles_u8": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _f],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -240,6 +249,47 @@ def _mask_args(mask) -> tuple:
     return () if mask is None else check_mask(mask)
 
 
+PAYLOAD_DELTA_MIN, PAYLOAD_DELTA_MAX = 8.0, 512.0
+
+
+def check_delta(delta) -> float:
+    """The payload rule's step as a float holding a float32 value, checked on the host as the library checks it
+    (include/wmhip.h): finite, 8 <= delta <= 512."""
+    try:
+        d = float(np.float32(delta))
+    except (TypeError, ValueError):
+        raise ValueError("delta must be a number") from None
+    if not (np.isfinite(d) and PAYLOAD_DELTA_MIN <= d <= PAYLOAD_DELTA_MAX):
+        raise ValueError(f"payload needs a finite delta in 8..512, got {delta}")
+    return d
+
+
+def _tile_bits(tile_bit, n_tiles: int) -> np.ndarray:
+    """tile_bit as the ABI takes it: uint8 [n_tiles] of 0 / 1"""
+    tb = np.ascontiguousarray(tile_bit).reshape(-1)
+    if tb.size != n_tiles:
+        raise ValueError(f"tile_bit has {tb.size} entries for {n_tiles} tiles")
+    if tb.size and (tb.min() < 0 or tb.max() > 1):
+        raise ValueError("tile_bit entries must be 0 or 1")
+    return tb.astype(np.uint8)
+
+
+def check_payload_csr(order, offs, n_bits: int, n_tiles: int):
+    """(order int32 [n_tiles], offs int32 [n_bits + 1]) of a tile-to-bit map, checked as the host-pointer entry point checks
+    them: 1 <= n_bits <= n_tiles, offs from 0 to n_tiles without decreasing, every order entry a tile of the grid."""
+    n_bits = int(n_bits)
+    if n_bits < 1 or n_bits > n_tiles:
+        raise ValueError(f"n_bits must be in 1..n_tiles ({n_tiles}), got {n_bits}")
+    order = np.ascontiguousarray(order).reshape(-1); offs = np.ascontiguousarray(offs).reshape(-1)
+    if order.size != n_tiles or offs.size != n_bits + 1:
+        raise ValueError(f"order / offs have {order.size} / {offs.size} entries for {n_tiles} tiles and {n_bits} bits")
+    if int(offs[0]) != 0 or int(offs[-1]) != n_tiles or np.any(np.diff(offs) < 0):
+        raise ValueError("offs must run from 0 to n_tiles without decreasing")
+    if int(order.min()) < 0 or int(order.max()) >= n_tiles:
+        raise ValueError("order names a tile outside the grid")
+    return order.astype(np.int32), offs.astype(np.int32)
+
+
 def _planes_of(a: np.ndarray, dtype, what: str):
     """_plane_layout of a [H, W] / [N, H, W] input of the given dtype, which may be strided"""
     if a.dtype != dtype:
@@ -262,7 +312,7 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None):
-            for ent in self.__dict__.pop("_idx_cache", []):
+            for ent in self.__dict__.pop("_idx_cache", []) + self.__dict__.pop("_payload_cache", []):
                 self._drop_index(ent)
             for d in self.__dict__.pop("_enh_bufs", (0, 0, 0))[1:]:
                 self.lib.wm_free(self._h, _vp(d))
@@ -425,6 +475,83 @@ class Context:
         g = np.empty((n, nby, nbx), np.float32)
         self._call("wm_mask_sigma_w_tiles_u8", _p(planes), None, None, _p(g), n, H, W, rs, ps, 0, lo, hi)
         return g[0] if planes.ndim == 2 else g
+
+    # ---- blind payload: raw-bit level (include/wmhip.h; the framing and the keyed map are payload.py's) ----------------
+    def payload_sigma_w(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float) -> np.ndarray:
+        """The rule's sigma_w rows (target - s_1, 0, .., 0) of uint8 planes [H,W] / [N,H,W] whose tile t carries
+        tile_bit[t] -> float32 [N?, nby, nbx, 8]."""
+        delta = check_delta(delta)
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        nby, nbx = H // TILE, W // TILE
+        tb = _tile_bits(tile_bit, nby * nbx)
+        eff = np.empty((n, nby, nbx, 8), np.float32)
+        self._call("wm_payload_sigma_w_tiles_u8", _p(planes), _p(tb), _p(eff), n, H, W, rs, ps, delta)
+        return eff[0] if planes.ndim == 2 else eff
+
+    def embed_tiles_payload(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float, want_yw: bool = False):
+        """One bit per tile into the parity of sigma_1 on the lattice of step delta; every plane carries the same bits.
+        Returns (stego uint8, the cover's sigma_c float32 [N?, nby, nbx, 8], yw or None) like embed_tiles."""
+        delta = check_delta(delta)
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        nby, nbx = H // TILE, W // TILE
+        tb = _tile_bits(tile_bit, nby * nbx)
+        stego = np.empty((n, H, W), np.uint8)
+        sc = np.empty((n, nby, nbx, 8), np.float32)
+        yw = np.empty((n, H, W), np.float32) if want_yw else None
+        hostc = np.ascontiguousarray(planes.reshape(n, H, W))
+        self._call("wm_embed_tiles_payload_u8", _p(hostc), _p(tb), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W, delta)
+        if planes.ndim == 2:
+            return stego[0], sc[0], (yw[0] if want_yw else None)
+        return stego, sc, yw
+
+    def payload_metric(self, planes: np.ndarray, delta: float) -> np.ndarray:
+        """The decoder's soft value m of every tile -> float32 [N?, nby, nbx]."""
+        delta = check_delta(delta)
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        m = np.empty((n, H // TILE, W // TILE), np.float32)
+        self._call("wm_payload_metric_tiles_u8", _p(planes), _p(m), n, H, W, rs, ps, delta)
+        return m[0] if planes.ndim == 2 else m
+
+    def _payload_csr_dev(self, order: np.ndarray, offs: np.ndarray):
+        """Device copies of a checked (order, offs), kept like the permutation index (a list of its own): two entries,
+        keyed by content."""
+        cache = self.__dict__.setdefault("_payload_cache", [])
+        tag = ("payload", order.size, offs.size, hashlib.blake2b(order.view(np.uint8), digest_size=16).digest(),
+               hashlib.blake2b(offs.view(np.uint8), digest_size=16).digest())
+        for ent in cache:
+            if ent["tag"] == tag:
+                return ent["d"], ent["d_offs"]
+        d = self.malloc(order.nbytes + 256 + offs.nbytes)
+        d_offs = d + (order.nbytes + 255) // 256 * 256
+        self.h2d(d, order); self.h2d(d_offs, offs)
+        cache.append({"tag": tag, "d": d, "d_offs": d_offs, "n": int(order.size), "route": None})
+        while len(cache) > 2:
+            old = cache.pop(0)
+            self.sync()
+            self._drop_index(old)
+        return d, d_offs
+
+    def payload_soft(self, planes: np.ndarray, order: np.ndarray, offs: np.ndarray, n_bits: int, delta: float) -> np.ndarray:
+        """soft[j] = sum over the planes and over the tiles order[offs[j] : offs[j + 1]] of the decoder's m -> float64
+        [n_bits]; bit j decodes to soft[j] < 0.  The planes stay on the device; only n_bits doubles come back."""
+        delta = check_delta(delta)
+        n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        order, offs = check_payload_csr(order, offs, n_bits, (H // TILE) * (W // TILE))
+        soft = np.zeros(int(n_bits), np.float64)
+        if n == 0:
+            return soft
+        d_order, d_offs = self._payload_csr_dev(order, offs)
+        p = np.ascontiguousarray(planes.reshape(n, H, W))
+        d_p = self.malloc(p.nbytes); d_soft = self.malloc(soft.nbytes)
+        try:
+            self.h2d(d_p, p)
+            self._call("wm_payload_soft_tiles_u8_dev", _vp(d_p), _vp(d_order), _vp(d_offs), int(n_bits), _vp(d_soft),
+                       n, H, W, W, H * W, delta)
+            self.d2h(soft, d_soft)
+            self.check_status()
+        finally:
+            self.free(d_p); self.free(d_soft)
+        return soft
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

@@ -54,6 +54,12 @@ _ORDER = {
     "video_gray": ("mode", "payload_type") + _GRAY + _VIDEO_COMMON[1:] + ("digest",),
     "video_color": ("mode",) + _VIDEO_COLOR_COMMON + ("digest",) + _BY_CHANNEL,
 }
+# A blind payload (payload.py, include/wmhip.h): the rule's step, the bit count and the key's nonce - no Sc, Uw or Vwt, so the
+# file's size depends neither on the image size nor on the frame count.  A video writes frame_interval and n_frames too
+# (and chroma, should a colour container ever be named); payload_type is "text", "json" or "bytes".
+PAYLOAD_MODE = "payload"
+_PAYLOAD = ("payload_type", "shape", "delta", "payload_bits", "nonce", "tile", "frame_interval", "n_frames", "chroma")
+_ORDER[PAYLOAD_MODE] = ("mode",) + _PAYLOAD + ("digest",)
 _ORDER_FULL_FRAME = dict(_ORDER, color=("mode",) + _IMAGE_COMMON + _BY_CHANNEL_THEN_S + ("digest",))
 
 
@@ -64,9 +70,111 @@ def is_color(meta) -> bool:
 def hmac_parts(meta) -> list:
     """The arrays the HMAC covers, in its order: Sc, Uw, Vwt (single:182) or Sb Sg Sr, UWb UWg UWr, VWbt VWgt VWrt
     (single:152-156)."""
+    if is_payload(meta):
+        return payload_hmac_parts(meta)
     if is_color(meta):
         return [meta[f(n)] for f in (s_key, uw_key, vwt_key) for n in CHANNELS]
     return [meta["Sc"], meta["Uw"], meta["Vwt"]]
+
+
+def is_payload(meta) -> bool:
+    return str(meta["mode"]) == PAYLOAD_MODE
+
+
+# what a payload meta's members are stored as - and hashed as, whatever a reader's np.load made of them
+_PAYLOAD_DTYPES = dict(shape=np.int64, delta=np.float32, payload_bits=np.int32, nonce=np.uint8, tile=np.int32,
+                       frame_interval=np.int32, n_frames=np.int32)
+
+
+def payload_hmac_parts(meta) -> list:
+    """A payload meta has no factors to protect; its HMAC covers every member but the digest, in file order: the strings as
+    UTF-8 bytes, the numbers in their stored dtypes.  A changed delta, bit count or nonce is a wrong password."""
+    parts = []
+    for k in _ORDER[PAYLOAD_MODE]:
+        if k == "digest" or k not in meta:
+            continue
+        if k in _PAYLOAD_DTYPES:
+            parts.append(np.asarray(meta[k]).astype(_PAYLOAD_DTYPES[k]).reshape(-1))
+        else:
+            parts.append(np.frombuffer((k + "=" + str(meta[k])).encode("utf-8"), dtype=np.uint8))
+    return parts
+
+
+def payload_members(payload_type: str, H: int, W: int, delta: float, n_bits: int, nonce: bytes, frame_interval=None,
+                    n_frames=None) -> dict:
+    out = dict(mode=PAYLOAD_MODE, payload_type=str(payload_type), shape=np.array((H, W), dtype=np.int64),
+               delta=np.float32(delta), payload_bits=np.int32(n_bits), nonce=np.frombuffer(nonce, dtype=np.uint8),
+               tile=np.int32(TILE))
+    if n_frames is not None:
+        out.update(frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames))
+    return out
+
+
+# The file.  Every member of a .npz costs a zip local header, a central-directory entry and a .npy header: about 200 bytes
+# for a 4-byte integer, 2 KB for the members above.  A payload meta is therefore written as ONE member, ``payload``: a 0-d
+# structured array whose fields are the members, in their order and dtypes (strings at fixed widths) - a plain .npz that
+# np.load reads without pickle, about 0.5 KB, the same size to the byte whatever the values (the member is stored, not
+# deflated).  pack_payload / unpack_payload go between the two forms; everything else sees the members.
+PAYLOAD_MEMBER = "payload"
+_PAYLOAD_STR = dict(mode="<U7", payload_type="<U5", chroma="<U8")
+
+
+def is_packed_payload(meta) -> bool:
+    return PAYLOAD_MEMBER in meta and "mode" not in meta
+
+
+def pack_payload(meta: dict) -> dict:
+    """The sealed members of a payload meta -> {"payload": 0-d structured array}, what goes to the file."""
+    fields, values = [], []
+    for k in _ORDER[PAYLOAD_MODE]:
+        if k not in meta:
+            continue
+        if k in _PAYLOAD_STR:
+            if len(str(meta[k])) > int(_PAYLOAD_STR[k][2:]):
+                raise ValueError(f"{k} {str(meta[k])!r} is too long for a payload meta")
+            fields.append((k, _PAYLOAD_STR[k])); values.append(str(meta[k]))
+        else:
+            a = np.asarray(meta[k]).astype(_PAYLOAD_DTYPES.get(k, np.uint8))
+            fields.append((k, a.dtype.str) if a.ndim == 0 else (k, a.dtype.str, a.shape)); values.append(a)
+    rec = np.zeros((), dtype=np.dtype(fields))
+    for (k, *_), v in zip(fields, values):
+        rec[k] = v
+    return {PAYLOAD_MEMBER: rec}
+
+
+def unpack_payload(meta) -> dict:
+    """The members of a payload meta, in their order, from its file form (a dict or an np.load handle); a meta that is
+    already in member form comes back as it is."""
+    if not is_packed_payload(meta):
+        return meta
+    rec = np.asarray(meta[PAYLOAD_MEMBER])
+    if rec.dtype.names is None or rec.ndim != 0 or "mode" not in rec.dtype.names:
+        raise ValueError("not a payload meta")
+    out = {k: (str(rec[k]) if k in _PAYLOAD_STR else np.array(rec[k])) for k in rec.dtype.names}
+    for k in out:
+        if k not in _PAYLOAD_STR and out[k].ndim == 0:
+            out[k] = out[k][()]                                            # numpy scalars, as payload_members writes them
+    return out
+
+
+def save_payload_meta(path: str, meta: dict) -> str:
+    return hg.save_npz(path, pack_payload(meta), compressed=False)
+
+
+def load_payload_meta(path: str) -> dict:
+    return unpack_payload(hg.load_npz(path))
+
+
+def refuse_payload(meta, what: str) -> None:
+    """extract / detect read a watermark image's factors; a payload meta has none."""
+    if is_packed_payload(meta) or ("mode" in meta and is_payload(meta)):
+        raise ValueError(f"{what}: this meta carries a blind payload (mode='payload'), not a watermark image - "
+                         "use extract_payload / extract_payload_video")
+
+
+def require_payload(meta) -> None:
+    if "mode" not in meta or not is_payload(meta):
+        raise ValueError("this meta was not written by embed_payload / embed_payload_video")
 
 
 # ---- writers ------------------------------------------------------------------

@@ -1,0 +1,147 @@
+"""Blind text / JSON / bytes payload: the host side of the sigma_1 quantisation rule (include/wmhip.h, DESIGN.md
+section 14).  Framing of the bytes into bits, the keyed tile-to-bit map and its CSR inverse, what a caller's payload
+argument means.  NumPy, json and zlib only: nothing here touches the device.
+
+Frame: ``len(data)`` as 4 little-endian bytes, ``data``, ``zlib.crc32(data)`` as 4 little-endian bytes, most significant
+bit of every byte first - the header and bit order of the reference's bit image (core:56-60), with a checksum the
+reference does not have.  n_bits = 8 * (len(data) + 8).
+"""
+from __future__ import annotations
+
+import json
+import os
+import zlib
+
+import numpy as np
+
+from . import hostglue as hg
+
+TYPES = ("text", "json", "bytes")
+DELTA_DEFAULT = 16.0
+OVERHEAD_BYTES = 8                                  # length header + CRC
+
+
+def payload_frame(data: bytes) -> np.ndarray:
+    """bytes -> the bits that are embedded, uint8 [8 * (len(data) + 8)]"""
+    data = bytes(data)
+    framed = len(data).to_bytes(4, "little") + data + (zlib.crc32(data) & 0xFFFFFFFF).to_bytes(4, "little")
+    return np.unpackbits(np.frombuffer(framed, dtype=np.uint8))
+
+
+def payload_unframe(bits) -> tuple:
+    """decoded bits -> (data, crc_ok).  crc_ok: the length header is the one a frame of this many bits has AND the checksum
+    matches; a header that does not fit (a stego without this payload, too many bit errors) gives the bytes that are
+    there and False, never an exception."""
+    bits = (np.asarray(bits).reshape(-1) != 0).astype(np.uint8)
+    n_bytes = bits.size // 8
+    if n_bytes < OVERHEAD_BYTES:
+        return b"", False
+    raw = np.packbits(bits[:n_bytes * 8]).tobytes()
+    L = int.from_bytes(raw[:4], "little")
+    room = n_bytes - OVERHEAD_BYTES
+    if L != room or bits.size != n_bytes * 8:
+        return raw[4:4 + min(L, room)], False
+    data = raw[4:4 + L]
+    return data, int.from_bytes(raw[4 + L:8 + L], "little") == (zlib.crc32(data) & 0xFFFFFFFF)
+
+
+def capacity_bits(H: int, W: int) -> int:
+    return (H // 8) * (W // 8)
+
+
+def check_capacity(n_bits: int, n_tiles: int) -> None:
+    if n_bits > n_tiles:
+        # the reference's wording (core:63), with the tile count where it has the pixel count
+        raise ValueError(f"Payload quá dài ({n_bits} bits) > dung lượng ({n_tiles} tiles, 1 bit mỗi tile 8x8). "
+                         "Dùng ảnh host lớn hơn hoặc rút gọn dữ liệu.")
+
+
+def payload_map(nby: int, nbx: int, key: bytes, n_bits: int) -> tuple:
+    """The keyed tile-to-bit map of an nby x nbx tile grid and its CSR inverse:
+      tile_bit_index  int32 [n_tiles]: tile t carries bit perm[t] % n_bits, perm = hostglue.permutation_index(nby, nbx, key)
+      order           int32 [n_tiles]: the tiles grouped by bit, ascending tile index within a bit (a stable argsort)
+      offs            int32 [n_bits + 1]: bit j owns order[offs[j] : offs[j + 1]]
+    perm is a permutation of the tiles, so the bits' tile counts differ by at most 1."""
+    n_tiles = int(nby) * int(nbx)
+    n_bits = int(n_bits)
+    if n_bits < 1:
+        raise ValueError("n_bits must be at least 1")
+    check_capacity(n_bits, n_tiles)
+    tbi = (np.asarray(hg.permutation_index(nby, nbx, key)) % n_bits).astype(np.int32)
+    order = np.argsort(tbi, kind="stable").astype(np.int32)
+    offs = np.concatenate([[0], np.cumsum(np.bincount(tbi, minlength=n_bits))]).astype(np.int32)
+    return tbi, order, offs
+
+
+def tile_bits(bits: np.ndarray, tile_bit_index: np.ndarray) -> np.ndarray:
+    """the bit every tile carries, uint8 [n_tiles]"""
+    return np.asarray(bits, np.uint8)[tile_bit_index]
+
+
+def confidence(soft: np.ndarray, offs: np.ndarray, n_planes: int) -> float:
+    """mean over the bits of |soft[j]| / count[j], count[j] = the number of tiles summed into bit j: 1 when every tile sits
+    on its lattice point, 0 when the votes cancel"""
+    count = np.diff(np.asarray(offs, np.int64)) * max(int(n_planes), 1)
+    return float(np.mean(np.abs(soft) / np.maximum(count, 1))) if len(soft) else 0.0
+
+
+def check_type(payload_type: str) -> None:
+    if payload_type not in TYPES:
+        raise ValueError(f"payload_type must be one of {TYPES}, got {payload_type!r}")
+
+
+def payload_bytes(payload, payload_type: str, allow_file: bool = True) -> bytes:
+    """What a caller's ``payload`` stands for: bytes as they are; a str that names an existing file is read (text and
+    json: as UTF-8 text with undecodable bytes dropped, core:105; bytes: raw), any other str is the text itself.  json is
+    canonicalised through json.loads / json.dumps(ensure_ascii=False, separators=(',', ':')) (core:109-110).
+    ``allow_file=False`` (the array level): a str is always the text itself."""
+    check_type(payload_type)
+    if isinstance(payload, (bytes, bytearray, memoryview)):
+        raw = bytes(payload)
+        if payload_type == "bytes":
+            return raw
+        text = raw.decode("utf-8", errors="ignore")
+    elif isinstance(payload, (str, os.PathLike)):
+        if allow_file and os.path.isfile(payload):
+            if payload_type == "bytes":
+                with open(payload, "rb") as f:
+                    return f.read()
+            with open(payload, "r", encoding="utf-8", errors="ignore") as f:
+                text = f.read()
+        elif isinstance(payload, str):
+            text = payload
+        else:
+            raise ValueError(f"payload file not found: {os.fspath(payload)}")
+    else:
+        raise TypeError(f"payload must be str, bytes or a path, got {type(payload).__name__}")
+    if payload_type == "json":
+        try:
+            text = json.dumps(json.loads(text), ensure_ascii=False, separators=(",", ":"))
+        except Exception as e:
+            raise ValueError(f"JSON không hợp lệ: {e}") from None
+    return text.encode("utf-8")
+
+
+def out_name(path: str, payload_type: str) -> str:
+    """core:235-240: ``_data.json`` / ``_text.txt`` unless the path already ends in .json / .txt (bytes: ``_data.bin``)"""
+    ext, suffix = {"json": (".json", "_data.json"), "text": (".txt", "_text.txt"), "bytes": (".bin", "_data.bin")}[payload_type]
+    return path if path.lower().endswith(ext) else os.path.splitext(path)[0] + suffix
+
+
+def write_payload(path: str, data: bytes, payload_type: str) -> str:
+    """The decoded payload to a file named by out_name: text as UTF-8 with undecodable bytes dropped; json re-indented when
+    it parses, else as text (core:229-242); bytes raw."""
+    path = out_name(path, payload_type)
+    if payload_type == "bytes":
+        with open(path, "wb") as f:
+            f.write(data)
+        return path
+    text = data.decode("utf-8", errors="ignore")
+    if payload_type == "json":
+        try:
+            text = json.dumps(json.loads(text), ensure_ascii=False, indent=2)
+        except Exception:
+            pass
+    with open(path, "w", encoding="utf-8", errors="ignore") as f:
+        f.write(text)
+    return path

@@ -29,6 +29,7 @@ import numpy as np
 from . import hostapi
 from . import hostglue as hg
 from . import meta as M
+from . import payload as P
 from . import sharding
 
 TILE = M.TILE
@@ -352,6 +353,7 @@ def _embed_video(codec, host_video_path, watermark_path, output_video_path, meta
 
 def _load_video_meta(codec, metadata_path: str):
     data = np.load(metadata_path, allow_pickle=False)
+    M.refuse_payload(data, codec.writer.replace("embed", "extract / detect"))
     if str(data["mode"]) != codec.mode:
         raise ValueError("metadata was not written by " + codec.writer)
     return data
@@ -486,3 +488,113 @@ def detect_watermark_video_color(stego_video_path: str, metadata_path: str, thre
     """(bool, mean score, per-frame scores): a frame's score is the mean of its three channels' NC (single:317); a masked
     meta is scored by its rule."""
     return _detect_video(_Bgr444, stego_video_path, metadata_path, thresh, batch, device)
+
+
+# ---------------------------------------------------------------------------
+# blind payload in the luma of a .y4m (payload.py, include/wmhip.h): every marked frame carries the same bits under the
+# same tile-to-bit map, and the decoder adds the frames' soft votes.  The meta holds the rule, not the frames.
+# ---------------------------------------------------------------------------
+def payload_soft_frames(ctx: hostapi.Context, frames_y: np.ndarray, order, offs, n_bits: int, delta: float,
+                        batch: int = 32) -> np.ndarray:
+    """soft [n_bits] float64 over all frames of uint8 [N, H, W]: one device call per batch, the batches' vectors added on
+    the host in batch order."""
+    soft = np.zeros(int(n_bits), np.float64)
+    for b0 in range(0, frames_y.shape[0], max(1, int(batch))):
+        soft += ctx.payload_soft(frames_y[b0:b0 + batch], order, offs, n_bits, delta)
+    return soft
+
+
+def embed_payload_video(host_video_path: str, payload, output_video_path: str, metadata_path: str, *, password: str = "",
+                        payload_type: str = "text", frame_interval: int = 1, delta: float = P.DELTA_DEFAULT,
+                        nonce: Optional[bytes] = None, batch: int = 32, device: int = 0):
+    """Embed a text / JSON / bytes payload (``payload`` as in dct_svd_core_secure.embed_payload) into the luma of every
+    ``frame_interval``-th frame of an 8-bit .y4m; chroma and unmarked frames are copied byte for byte.
+    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' luma)."""
+    M.require_password(password, "embed")
+    delta = hostapi.check_delta(delta)
+    bits = P.payload_frame(P.payload_bytes(payload, payload_type))
+    batch = max(1, int(batch))
+    vid = Y4M(host_video_path)
+    ctx = None
+    try:
+        H, W = vid.H, vid.W
+        P.check_capacity(bits.size, P.capacity_bits(H, W))                 # before any device call
+        if nonce is None:
+            nonce = os.urandom(8)
+        key = hg.derive_key(password, nonce)
+        tile_bit = P.tile_bits(bits, P.payload_map(H // TILE, W // TILE, key, bits.size)[0])
+        ctx = hostapi.Context(device)
+        psnrs, n_frames = [], 0
+        with open(output_video_path, "wb") as out:
+            out.write(vid.header_line)
+            pend = []          # (frame_line, y, chroma, marked)
+
+            def flush():
+                marked = [p for p in pend if p[3]]
+                if marked:
+                    ys = np.stack([p[1] for p in marked])
+                    st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta)
+                    psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
+                j = 0
+                for line, y, chroma, is_marked in pend:
+                    out.write(line)
+                    if is_marked:
+                        out.write(st[j].tobytes()); j += 1
+                    else:
+                        out.write(y.tobytes())
+                    out.write(chroma.tobytes())
+                pend.clear()
+
+            for line, y, chroma in vid:
+                pend.append((line, y.copy(), chroma.copy(), _is_marked(n_frames, frame_interval)))
+                n_frames += 1
+                if len(pend) >= batch * max(1, frame_interval):
+                    flush()
+            flush()
+        members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, frame_interval, n_frames)
+        M.save_payload_meta(metadata_path, M.sealed(members, TILE, hg.hmac_digest(key, M.hmac_parts(members))))
+        return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0
+    finally:
+        vid.close()
+        if ctx is not None:
+            ctx.close()
+
+
+def extract_payload_video(stego_video_path: str, metadata_path: str, *, password: str = "", batch: int = 32,
+                          device: int = 0, return_soft: bool = False):
+    """-> (data, valid, confidence) from the marked frames' luma; with ``return_soft`` the summed soft vector follows."""
+    M.require_password(password, "extract")
+    data = M.load_payload_meta(metadata_path)
+    M.require_payload(data)
+    if "n_frames" not in data:
+        raise ValueError("metadata was not written by embed_payload_video")
+    key = hg.derive_key(password, M.nonce_of(data))
+    if not M.authentic(data, key):
+        raise ValueError(M.WRONG_PASSWORD)
+    H, W = map(int, data["shape"])
+    n_bits, delta = int(data["payload_bits"]), hostapi.check_delta(float(data["delta"]))
+    fi = int(data["frame_interval"])
+    batch = max(1, int(batch))
+    _, order, offs = P.payload_map(H // TILE, W // TILE, key, n_bits)
+    vid = Y4M(stego_video_path)
+    ctx = None
+    try:
+        if (vid.H, vid.W) != (H, W):
+            raise ValueError(f"video is {vid.W}x{vid.H} but the meta was written for {W}x{H}")
+        ctx = hostapi.Context(device)
+        soft = np.zeros(n_bits, np.float64)
+        pend, n_marked = [], 0
+        for i, (_, y, _) in enumerate(vid):
+            if _is_marked(i, fi):
+                pend.append(y.copy()); n_marked += 1
+                if len(pend) >= batch:
+                    soft += ctx.payload_soft(np.stack(pend), order, offs, n_bits, delta); pend = []
+        if pend:
+            soft += ctx.payload_soft(np.stack(pend), order, offs, n_bits, delta)
+    finally:
+        vid.close()
+        if ctx is not None:
+            ctx.close()
+    payload, valid = P.payload_unframe(soft < 0)
+    out = (payload, bool(valid), P.confidence(soft, offs, n_marked))
+    return out + (soft,) if return_soft else out

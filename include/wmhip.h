@@ -238,6 +238,59 @@ int wm_detect_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* si
                               double* scores, int n_planes, int H, int W, int row_stride, size_t plane_stride,
                               size_t sigma_w_plane_stride, float alpha, float lo, float hi, float cut);
 
+/* ---- Tile mode, blind payload: one bit per tile in the parity of sigma_1 --
+ * The rule ("Blind payload"; part of the meta format).  Parameter: delta, float32, finite, 8 <= delta <= 512.
+ * The bias c = 4 is a constant (the embed truncates to uint8, which lowers sigma_1 of a tile by 64 * 0.5 / 8 on average).
+ * embed   a tile carries bit b; its cover singular values are s_1 >= s_2 >= .. (float32, as K2 writes them):
+ *           q = fma(2 delta, rint((s_1 - b delta) / (2 delta)), b delta)    nearest point of {2 k delta + b delta}, float32,
+ *                                                                          ties to even as rintf, one fused multiply-add
+ *           if q + c > 2040: q -= 2 delta                                  2040 = 8 * 255: never aim above a white tile
+ *           up to 3 times: if q < s_2 + delta: q += 2 delta                sigma_1 stays the leading value
+ *           sigma_w_eff = (q + c - s_1, 0, 0, 0, 0, 0, 0, 0), then the unchanged embed with alpha = 1, K = 1
+ *         A black cover tile (64 zeros) has no leading singular vector; the payload embed gives it the flat one, as
+ *         np.linalg.svd does for a zero matrix: the tile becomes the constant (q + c) / 8.
+ * decode  with s~_1 the leading singular value of the stego tile:
+ *           x = s~_1 * (1 / (2 delta))    one float32 multiply by the float32 reciprocal
+ *           f = x - floor(x);  m = 2 |2 f - 1| - 1          +1 on a bit-0 lattice point, -1 on a bit-1 point
+ *         soft[j] = sum of m over all planes and all tiles mapped to bit j, in float64 and in a fixed order (no
+ *         atomics: two calls give the same bits); the decoded bit is soft[j] < 0.
+ * The tile-to-bit map is the caller's (the Python side: tile t carries bit perm[t] % n_bits of a keyed permutation of the
+ * tiles); all planes of a call share it.  Tiles pinned by clipping (a 0/255 checkerboard ..) do not take their bit:
+ * repetition over tiles and frames is what covers them.  Rows and columns outside the tile grid pass through.
+ * WM_ERR_BADARG: delta outside the range or not finite, n_bits < 1 or > n_tiles, NULL pointers, and in the host-pointer
+ * form offs[0] != 0, offs[n_bits] != n_tiles, a decreasing offs or an order entry outside the grid.  Empty inputs
+ * (no planes, no tiles) return WM_OK without a launch. */
+
+/* K2 on the cover planes, then the rule's sigma_w rows:
+ *   tile_bit     [n_tiles] uint8, the bit (0 / 1) each tile carries, shared by the planes
+ *   sigma_w_eff  [n_planes][n_tiles][8] float32 (out) */
+int wm_payload_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+                                    int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+int wm_payload_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+                                int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+
+/* The rule's embed: the pass above into a buffer the context owns, then wm_embed_tiles_u8_dev with a per-plane
+ * sigma_w stride, alpha = 1 and K = 1.  sigma_c (the cover's, out) and yw as in wm_embed_tiles_u8_dev; stego may alias host. */
+int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                              float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+
+/* K2 on the stego planes, then m of every tile:  metric [n_planes][n_tiles] float32 (out) */
+int wm_payload_metric_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+                                   int row_stride, size_t plane_stride, float delta);
+int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+                               int row_stride, size_t plane_stride, float delta);
+
+/* The rule's decode: the metric into a buffer the context owns, then one wave per bit.
+ *   order  [n_tiles] int32, the tiles grouped by the bit they carry, ascending tile index within a bit
+ *   offs   [n_bits + 1] int32, bit j owns order[offs[j] .. offs[j + 1])   (the CSR inverse of the tile-to-bit map)
+ *   soft   [n_bits] float64 (out) */
+int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                                 double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                             double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
