@@ -85,6 +85,18 @@ def confidence(soft: np.ndarray, offs: np.ndarray, n_planes: int) -> float:
     return float(np.mean(np.abs(soft) / np.maximum(count, 1))) if len(soft) else 0.0
 
 
+def check_decodes(soft: np.ndarray, bits: np.ndarray, data: bytes) -> None:
+    """The embed's own check: ``soft`` is what the decoder reads from the finished stego (every marked frame added).  Tiles
+    pinned by clipping - text on a white page, saturated regions - vote for the WRONG bit at full weight, and with few tiles
+    per bit they win; such a payload must not be reported as embedded."""
+    got, valid = payload_unframe(np.asarray(soft) < 0)
+    if valid and got == bytes(data):
+        return
+    wrong = int(np.count_nonzero((np.asarray(soft) < 0) != (np.asarray(bits) != 0)))
+    raise ValueError(f"payload does not decode from its own stego: {wrong} of {len(bits)} bits wrong (tiles pinned by clipping "
+                     "vote against their bit). Use a shorter payload (more tiles per bit), a larger delta or a larger cover.")
+
+
 def check_type(payload_type: str) -> None:
     if payload_type not in TYPES:
         raise ValueError(f"payload_type must be one of {TYPES}, got {payload_type!r}")

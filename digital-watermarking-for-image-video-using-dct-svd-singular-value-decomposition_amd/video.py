@@ -506,13 +506,16 @@ def payload_soft_frames(ctx: hostapi.Context, frames_y: np.ndarray, order, offs,
 
 def embed_payload_video(host_video_path: str, payload, output_video_path: str, metadata_path: str, *, password: str = "",
                         payload_type: str = "text", frame_interval: int = 1, delta: float = P.DELTA_DEFAULT,
-                        nonce: Optional[bytes] = None, batch: int = 32, device: int = 0):
+                        nonce: Optional[bytes] = None, batch: int = 32, device: int = 0, verify: bool = True):
     """Embed a text / JSON / bytes payload (``payload`` as in dct_svd_core_secure.embed_payload) into the luma of every
     ``frame_interval``-th frame of an 8-bit .y4m; chroma and unmarked frames are copied byte for byte.
-    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' luma)."""
+    Returns (output_video_path, metadata_path, mean PSNR of the marked frames' luma).
+    ``verify``: the soft votes of the marked stego frames are added up as they are written, and a payload that does not
+    decode from them raises ValueError after the last frame; neither the output file nor the meta remains."""
     M.require_password(password, "embed")
     delta = hostapi.check_delta(delta)
-    bits = P.payload_frame(P.payload_bytes(payload, payload_type))
+    data = P.payload_bytes(payload, payload_type)
+    bits = P.payload_frame(data)
     batch = max(1, int(batch))
     vid = Y4M(host_video_path)
     ctx = None
@@ -522,9 +525,11 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
         if nonce is None:
             nonce = os.urandom(8)
         key = hg.derive_key(password, nonce)
-        tile_bit = P.tile_bits(bits, P.payload_map(H // TILE, W // TILE, key, bits.size)[0])
+        tbi, order, offs = P.payload_map(H // TILE, W // TILE, key, bits.size)
+        tile_bit = P.tile_bits(bits, tbi)
         ctx = hostapi.Context(device)
         psnrs, n_frames = [], 0
+        soft = np.zeros(bits.size, np.float64)
         with open(output_video_path, "wb") as out:
             out.write(vid.header_line)
             pend = []          # (frame_line, y, chroma, marked)
@@ -535,6 +540,8 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
                     ys = np.stack([p[1] for p in marked])
                     st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta)
                     psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
+                    if verify:
+                        np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch), out=soft)
                 j = 0
                 for line, y, chroma, is_marked in pend:
                     out.write(line)
@@ -551,6 +558,12 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
                 if len(pend) >= batch * max(1, frame_interval):
                     flush()
             flush()
+        if verify and psnrs:
+            try:
+                P.check_decodes(soft, bits, data)
+            except ValueError:
+                os.remove(output_video_path)
+                raise
         members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, frame_interval, n_frames)
         M.save_payload_meta(metadata_path, M.sealed(members, TILE, hg.hmac_digest(key, M.hmac_parts(members))))
         return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0

@@ -25,7 +25,7 @@ from oracle import wm_oracle as o
 
 pytestmark = pytest.mark.gpu
 
-SIGMA_RTOL = 1e-4                                                           # the project's sigma bar (BASELINE.json)
+SIGMA_RTOL = pr.SIGMA_RTOL                                                  # the project's sigma bar (BASELINE.json)
 DELTA = pr.DELTA
 M = importlib.import_module(PKG_NAME + ".meta")
 P = importlib.import_module(PKG_NAME + ".payload")
@@ -42,12 +42,8 @@ def _hosts():
     return pr.all_hosts()
 
 
-def _tie_tiles(Sc, bits, delta=DELTA):
-    return pr.tie_distance(Sc, bits, delta) < SIGMA_RTOL * Sc[..., 0] / (2 * delta)
-
-
-def _degenerate_tiles(Sc):
-    return (Sc[..., 0] - Sc[..., 1]) <= SIGMA_RTOL * Sc[..., 0]
+_tie_tiles = pr.tie_tiles                                                   # (shared with tests/test_gpu_payload_edges.py)
+_degenerate_tiles = pr.degenerate_tiles
 
 
 # ---- 1. the sigma_w pass --------------------------------------------------------------------------------------------

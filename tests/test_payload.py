@@ -1,6 +1,7 @@
 """Blind payload without a device: the tile-math helpers the kernels call (a stand-alone g++ program, plain and under
 AddressSanitizer + UBSan) against the NumPy restatement (tests/payload_refs.py), the framing, the keyed map, the meta layout
-and its refusals, host-side argument validation, and the value claim on the restatement alone."""
+and its refusals, host-side argument validation, the value claim on the restatement alone, and - also on the restatement
+alone - what tests/test_gpu_payload_edges.py may assume of its hosts (pinned tiles, letterboxed planes, a document page)."""
 import importlib
 import json
 import os
@@ -365,3 +366,96 @@ def test_payload_survives_noise_and_keeps_the_cover_on_the_restatement():
     print(f"PSNR {psnr:.2f} dB; clean worst |soft| / count {np.min(np.abs(clean) / count):.3f}, noisy {np.min(np.abs(soft) / count):.3f}")
     assert np.array_equal(soft < 0, bits != 0)
     assert psnr >= 45.0
+
+
+# ---- the edge hosts and what the GPU tests may assume of them, on the restatement alone ------------------------------
+def test_edge_hosts_are_what_they_say():
+    Y = pr.pinned_host()
+    assert Y.shape == pr.PINNED and Y.dtype == np.uint8 and len(pr.pinned_names()) == 32
+    tiles = o.to_tiles(Y).reshape(32, 64)
+    assert len({t.tobytes() for t in tiles}) == 32                            # one class per tile
+    D = pr.document_host(*pr.DOCUMENT, pr.DOCUMENT_SEED)
+    assert D.shape == pr.DOCUMENT and set(np.unique(D)) == {0, 255} and 0.02 < (D == 0).mean() < 0.2
+    L = pr.letterbox_planes()
+    base = pr.mr.planes_of(72, 100, 3)
+    assert L.shape == (3, 72, 100) and np.array_equal(L[0], base[0])
+    black = [pr.black_tiles(p) for p in L]
+    assert not black[0].any() and not any(pr.black_tiles(p).any() for p in base)
+    want1 = np.zeros((9, 12), bool); want1[:2] = True; want1[7:] = True
+    want2 = np.zeros((9, 12), bool); want2[:, :3] = True
+    assert np.array_equal(black[1], want1) and np.array_equal(black[2], want2)
+    assert np.array_equal(L[1][16:56], base[1][16:56]) and np.array_equal(L[2][:, 24:], base[2][:, 24:])
+    assert np.array_equal(L[2][:, 96:], base[2][:, 96:])                       # the ragged edge keeps its content
+
+
+_EDGE_NAMES = [n for n, _ in pr.edge_hosts()] + ["letterbox0", "letterbox1", "letterbox2"]
+
+
+@pytest.mark.parametrize("delta", pr.EDGE_DELTAS)
+def test_margins_ties_and_comparable_tiles(delta):
+    """For every (host, delta, bit seed) the GPU edge tests use: the share of tiles without a unique restatement or a clear
+    vote (a rounding tie, s_1 = s_2, |m| within the slope bar 2 (1e-4 2040) / delta of 0) is at most 10 % of a seeded or
+    letterbox host and at most half of the edge or pinned host.  Measured: seeded hosts 0..7 of 108 and 0..4 of 64 (all but 1
+    of them at delta = 8, where the bar is 0.051 and the worst margin 0.005), letterbox 0..4 of 108 (a black tile counts as
+    comparable: margins_of), edge 1..6 of 16, pinned 4..9 of 32; ties at most 1 of 108 / 64 and at most 6 of 16 on the edge
+    host; 2 tiles of the edge host with s_1 = s_2 (the black one among them)."""
+    assert np.isclose(pr.slope_bar(delta), 2 * (1e-4 * 2040) / delta)
+    for seed in pr.EDGE_BIT_SEEDS:
+        for name in _EDGE_NAMES:
+            r = pr.margins(name, delta, seed)
+            n = r["signed"].size
+            out = n - int(r["comparable"].sum())
+            print(f"delta {delta:g} bits {seed} {name}: left out {out} of {n} (tie {int(r['tie'].sum())}, degenerate {int(r['deg'].sum())}), "
+                  f"wrong-voting comparable tiles {int((r['signed'][r['comparable']] < 0).sum())}, worst margin {float(r['signed'].min()):+.3f}, "
+                  f"Yw in [{float(r['Yw'].min()):.0f}, {float(r['Yw'].max()):.0f}]")
+            assert out <= pr.left_out_cap(name) * n, (name, delta, seed, out, n)
+            if name == "pinned":        # the unclipped plane leaves 0..255: above at every delta, below too from delta = 16 on
+                Yw = o.to_tiles(r["Yw"])[~r["tie"] & ~r["deg"]]
+                assert Yw.max() > 255.5 and (delta < 16 or Yw.min() < -0.5), (delta, seed, float(Yw.min()), float(Yw.max()))
+            elif name == "edge":
+                assert r["tie"].sum() <= 6 and pr.degenerate_tiles(r["Sc"]).sum() == 2
+            elif name != "pinned":
+                assert r["tie"].sum() <= 2 and not r["deg"].any()
+                assert not (r["signed"][r["comparable"]] < 0).any()          # natural and black tiles take their bit
+
+
+def test_pinned_tiles_vote_against_their_bit():
+    """DESIGN 14's limit, per class at delta = 16 with every tile carrying 0, then 1: a half-255 / half-0 tile (s_1 = 1442.5,
+    aimed at 1460) carrying 1 has margin -0.69; a 0 / 255 checkerboard and the 4 + 4 block diagonal (s_1 = s_2 = 1020)
+    carrying 0 have -1.0; the 230 / 255 checkerboard carrying 0 has 0.0.  And the embed leaves 0..255 before the clip."""
+    Y = pr.pinned_host()
+    r = [pr.margins_of(Y, np.full(32, b, np.uint8), 16.0) for b in (0, 1)]
+    m = {nm: (float(r[0]["signed"].ravel()[i]), float(r[1]["signed"].ravel()[i])) for i, nm in enumerate(pr.pinned_names())}
+    for nm, (m0, m1) in m.items():
+        print(f"{nm:24s} bit 0 {m0:+.3f}  bit 1 {m1:+.3f}")
+    for nm in ("half_left_255", "half_right_255", "half_top_255", "half_bottom_255", "rows_255_0", "cols_255_0"):
+        assert abs(m[nm][1] + 0.6875) < 0.01 and m[nm][0] > 0.6, nm
+    for nm in ("checker_0_255", "checker_255_0", "blockdiag_4_4"):
+        assert abs(m[nm][0] + 1.0) < 0.01, nm
+    assert abs(m["checker_230_255"][0]) < 0.01
+    assert min(m["white"]) > 0.999                                            # (a white tile takes either bit)
+    assert sum(min(v) < 0 for v in m.values()) >= 10
+    assert min(x["Yw"].min() for x in r) < -1 and max(x["Yw"].max() for x in r) > 256
+
+
+def test_document_host_repetition_does_not_cover_pinned_tiles():
+    """White page with strokes, 128 x 256 (512 tiles), delta = 16, the keyed map of password "pw" and DOCUMENT_NONCE: with 80
+    bits (6.4 tiles a bit) every bit decodes, with 136 bits one does not, with n_bits = n_tiles 42 do not - each wrong-voting
+    tile is one wrong bit.  Measured: 43 / 39 / 42 of 512 tiles vote wrong; worst |soft| / count at 80 bits 0.35.  'sure': the
+    restatement's verdict cannot be turned by the tiles a device may legitimately see otherwise."""
+    Y = pr.document_host(*pr.DOCUMENT, pr.DOCUMENT_SEED)
+    key = hg.derive_key("pw", pr.DOCUMENT_NONCE)
+    got = {}
+    for data in pr.DOCUMENT_PAYLOADS:
+        bits = P.payload_frame(data)
+        tbi, order, offs = P.payload_map(Y.shape[0] // 8, Y.shape[1] // 8, key, bits.size)
+        v = pr.document_votes(Y, bits, tbi, order, offs)
+        got[bits.size] = v
+        print(f"n_bits {bits.size}: {int((v['signed'] < 0).sum())} of 512 tiles vote wrong ({int((v['signed'][v['comparable']] < 0).sum())} comparable, "
+              f"{int((~v['comparable']).sum())} left out), {int(v['wrong'].sum())} bits wrong ({int((v['wrong'] & v['sure']).sum())} surely), "
+              f"worst |soft| / count {float(np.min(np.abs(v['soft']) / v['count'])):.3f}")
+    assert sorted(got) == [80, 136, 512]
+    assert not got[80]["wrong"].any() and got[80]["sure"].all()
+    assert (got[136]["wrong"] & got[136]["sure"]).sum() >= 1
+    assert got[512]["wrong"].sum() >= 1 and (got[512]["wrong"] & got[512]["sure"]).sum() >= 1
+    assert (~got[512]["comparable"]).sum() <= 0.10 * 512
