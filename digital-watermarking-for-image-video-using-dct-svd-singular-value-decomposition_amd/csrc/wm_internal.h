@@ -50,10 +50,8 @@ struct wm_ctx {
   size_t route_tmp_bytes = 0;
   void* extract_f32 = nullptr;    // grow-only float estimate + min-max partials of wm_extract_unscrambled_u8_dev
   size_t extract_f32_bytes = 0;
-  void* mask_sw = nullptr;        // grow-only G o sigma_w of the masked tile embed (k_mask_sigma_w -> the embed launches)
-  size_t mask_sw_bytes = 0;
-  void* payload_ws = nullptr;     // grow-only: the payload embed's sigma_w rows, or the payload decode's per-tile metric
-  size_t payload_ws_bytes = 0;
+  void* sigma_ws = nullptr;       // grow-only output of a sigma pass inside one call: the masked / payload embed's sigma_w
+  size_t sigma_ws_bytes = 0;      // rows (k_sigma_pass -> the embed launches), or the payload decode's per-tile metric
   static constexpr int MAX_PAIR_TABS = 6;   // round-robin tournaments of the block Jacobi, by block count
   void* pair_tab[MAX_PAIR_TABS] = {};
   int pair_tab_nbk[MAX_PAIR_TABS] = {};
@@ -111,6 +109,21 @@ struct Carve {
     off += n * sizeof(T);
     return p;
   }
+  // The copies of a host-pointer entry point, stated with its layout (staged_call): `up` is enqueued on the spot, `down`
+  // is kept until the _dev call is enqueued.  Neither does anything on the sizing pass or for 0 elements, so the host
+  // pointer of an array without an element may be NULL.  in / out: a take that is uploaded from / downloaded to `host`.
+  hipStream_t stream = nullptr;     // set on the pass that copies
+  hipError_t err = hipSuccess;      // first failed upload
+  struct Down { void* host; const void* dev; size_t bytes; } downs[4] = {};      // (an entry point has at most 3)
+  int n_down = 0;
+  template <typename T> void up(T* dev, const T* host, size_t n) {
+    if (stream && n && err == hipSuccess) err = hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, stream);
+  }
+  template <typename T> void down(T* host, const T* dev, size_t n) {
+    if (stream && n) downs[n_down++] = Down{host, dev, n * sizeof(T)};
+  }
+  template <typename T> T* in(size_t n, const T* host) { T* p = take<T>(n); up(p, host, n); return p; }
+  template <typename T> T* out(size_t n, T* host) { T* p = take<T>(n); down(host, (const T*)p, n); return p; }
 };
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 // A layout stated once: `lay(Carve&)` sets the caller's pointers.  It runs on a null base for the size, the grow-only buffer
@@ -122,6 +135,25 @@ int staged(wm_ctx* ctx, void** buf, size_t* have, const char* what, Lay&& lay) {
   WM_TRY(grow(ctx, buf, have, pad256(cv.off), what));
   cv = Carve{(char*)*buf, 0};
   lay(cv);
+  return WM_OK;
+}
+// A host-pointer entry point stated once, behind its argument checks: `lay` is the layout of its arrays in the context's
+// scratch buffer together with their copies (Carve::in / out / up / down), `dev` the _dev call between the uploads and
+// the downloads.  Ends in wm_check_status, or with sync_only in a plain synchronise of the stream.
+template <typename Lay, typename Dev>
+int staged_call(wm_ctx* ctx, Lay&& lay, Dev&& dev, bool sync_only = false) {
+  Carve cv{nullptr, 0};
+  lay(cv);
+  WM_TRY(grow(ctx, &ctx->scratch, &ctx->scratch_bytes, pad256(cv.off), "scratch"));
+  cv = Carve{(char*)ctx->scratch, 0};
+  cv.stream = ctx->stream;
+  lay(cv);
+  WM_HIP(cv.err);
+  WM_TRY(dev());
+  for (int i = 0; i < cv.n_down; ++i)
+    WM_HIP(hipMemcpyAsync(cv.downs[i].host, cv.downs[i].dev, cv.downs[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (!sync_only) return wm_check_status(ctx);
+  WM_HIP(hipStreamSynchronize(ctx->stream));
   return WM_OK;
 }
 // runtime bools as template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})

@@ -576,12 +576,12 @@ __global__ void k_copy_border(const uint8_t* host, uint8_t* stego,
 }
 
 // ---------------------------------------------------------------------------
-// K2  sigma only
+// K2  sigma pass: a tile's singular values, and an epilogue that needs nothing else of the tile
 // ---------------------------------------------------------------------------
-template <bool ALIGNED>
-__global__ __launch_bounds__(WAVE, 3) void k_sigma_tiles(const uint8_t* __restrict__ planes,
-                                                     float* __restrict__ sigma, const Geom g,
-                                                     int* __restrict__ status) {
+// epi(raw, s, plane, t, ti), ti = plane * n_tiles + t: a small trivially copyable struct, passed by value
+template <bool ALIGNED, typename Epi>
+__global__ __launch_bounds__(WAVE, 3) void k_sigma_pass(const uint8_t* __restrict__ planes, const Geom g,
+                                                    int* __restrict__ status, const Epi epi) {
   int t, ty, tx;
   if (!tile_coords(g, t, ty, tx)) return;
   const size_t plane = blockIdx.y;
@@ -589,32 +589,38 @@ __global__ __launch_bounds__(WAVE, 3) void k_sigma_tiles(const uint8_t* __restri
   float s[8];
   load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
   if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
-  store_row8_f32<true>(sigma + (plane * g.n_tiles + t) * 8, s);
+  epi(raw, s, plane, t, plane * g.n_tiles + t);
 }
 
-// K2 + the masked embed's gain (wm_tile_math.h, mask_gain): the tile's cover singular values -> g, and G o sigma_w of the
+// sigma only
+struct EpiSigma {
+  float* __restrict__ sigma;
+  __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], size_t, int, const size_t ti) const {
+    store_row8_f32<true>(sigma + ti * 8, s);
+  }
+};
+
+// The masked embed's gain (wm_tile_math.h, mask_gain): the tile's cover singular values -> g, and G o sigma_w of the
 // tile to a dense [plane][tile][8] array that the unchanged embed launches are then fed with a per-plane stride; with
 // `gain`, g itself to [plane][tile].  sigma_w may be shared by the planes (sw_plane_stride 0); without sw_eff only g is left.
-template <bool ALIGNED>
-__global__ __launch_bounds__(WAVE, 3) void k_mask_sigma_w(const uint8_t* __restrict__ planes, const float* __restrict__ sigma_w,
-                                                      float* __restrict__ sw_eff, float* __restrict__ gain, const Geom g,
-                                                      const size_t sw_plane_stride, const float lo, const float hi,
-                                                      int* __restrict__ status) {
-  int t, ty, tx;
-  if (!tile_coords(g, t, ty, tx)) return;
-  const size_t plane = blockIdx.y;
-  wm::RawTile raw;
-  float s[8], sw[8];
-  load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
-  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
-  const float gn = wm::mask_gain(s, lo, hi);
-  if (sw_eff) {
-    load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
-    wm::mask_sigma_w(gn, sw);
-    store_row8_f32<true>(sw_eff + (plane * g.n_tiles + t) * 8, sw);
+struct EpiMask {
+  const float* __restrict__ sigma_w;
+  float* __restrict__ sw_eff;
+  float* __restrict__ gain;
+  size_t sw_plane_stride;
+  float lo, hi;
+  __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], const size_t plane, const int t,
+                                             const size_t ti) const {
+    float sw[8];
+    const float gn = wm::mask_gain(s, lo, hi);
+    if (sw_eff) {
+      load_row8_f32<true>(sigma_w + plane * sw_plane_stride + (size_t)t * 8, sw);
+      wm::mask_sigma_w(gn, sw);
+      store_row8_f32<true>(sw_eff + ti * 8, sw);
+    }
+    if (gain) gain[ti] = gn;
   }
-  if (gain) gain[plane * g.n_tiles + t] = gn;
-}
+};
 
 // ---------------------------------------------------------------------------
 // K3  full SVD of float tiles (watermark side)
@@ -866,31 +872,28 @@ __global__ __launch_bounds__(256) void k_detect_finalize(const double* __restric
 // ---------------------------------------------------------------------------
 // Blind payload (wm_tile_math.h, payload_target / payload_metric): one bit per tile in the parity of sigma_1
 // ---------------------------------------------------------------------------
-// K2 on the cover tile, then the rule's sigma_w row (target - s_1, 0, .., 0) to a dense [plane][tile][8] array that the
+// Sigma pass on the cover tile: the rule's sigma_w row (target - s_1, 0, .., 0) to a dense [plane][tile][8] array that the
 // unchanged embed launches are fed with a per-plane stride, alpha = 1 and K = 1.  tile_bit[n_tiles] is shared by the planes.
 // `black` (optional, [plane][tile]): 1 for a tile whose 64 pixels are 0 - see k_payload_black.
-template <bool ALIGNED>
-__global__ __launch_bounds__(WAVE, 3) void k_payload_sigma_w(const uint8_t* __restrict__ planes,
-                                                         const uint8_t* __restrict__ tile_bit, float* __restrict__ sw_eff,
-                                                         uint8_t* __restrict__ black, const Geom g, const float delta,
-                                                         int* __restrict__ status) {
-  int t, ty, tx;
-  if (!tile_coords(g, t, ty, tx)) return;
-  const size_t plane = blockIdx.y;
-  wm::RawTile raw;
-  float s[8], sw[8];
-  load_raw<ALIGNED>(STRIDED_TILE(planes, g, plane, ty, tx), g.row_stride, raw);
-  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
-  wm::payload_sigma_w(s, tile_bit[t] & 1, delta, sw);
-  store_row8_f32<true>(sw_eff + (plane * g.n_tiles + t) * 8, sw);
-  if (black) black[plane * g.n_tiles + t] = (wm::raw_is_constant(raw) && raw.lo[0] == 0u) ? 1 : 0;
-}
+struct EpiPayloadSigmaW {
+  const uint8_t* __restrict__ tile_bit;
+  float* __restrict__ sw_eff;
+  uint8_t* __restrict__ black;
+  float delta;
+  __device__ __forceinline__ void operator()(const wm::RawTile& raw, const float (&s)[8], size_t, const int t,
+                                             const size_t ti) const {
+    float sw[8];
+    wm::payload_sigma_w(s, tile_bit[t] & 1, delta, sw);
+    store_row8_f32<true>(sw_eff + ti * 8, sw);
+    if (black) black[ti] = (wm::raw_is_constant(raw) && raw.lo[0] == 0u) ? 1 : 0;
+  }
+};
 
 // A black cover tile is the zero matrix: it has no leading singular vector of its own, and the embed's closed form for
 // constant tiles gives it those of a fixed noise pattern, half of whose pixels clip at 0 - sigma_1 would land far from its
 // lattice point.  The payload embed takes the flat vector instead (what np.linalg.svd returns for a zero matrix: U = V = I,
 // the DC term): the tile becomes the constant (q + c) / 8.  Runs after the unchanged embed launches and rewrites only the
-// tiles flagged by k_payload_sigma_w (sw_eff[0] = q + c there, s_1 being 0); stego and yw are addressed as the embed does.
+// tiles flagged by EpiPayloadSigmaW (sw_eff[0] = q + c there, s_1 being 0); stego and yw are addressed as the embed does.
 template <bool ALIGNED>
 __global__ __launch_bounds__(WAVE) void k_payload_black(uint8_t* __restrict__ stego, float* __restrict__ yw,
                                                     const float* __restrict__ sw_eff, const uint8_t* __restrict__ black,
@@ -914,19 +917,15 @@ __global__ __launch_bounds__(WAVE) void k_payload_black(uint8_t* __restrict__ st
   }
 }
 
-// K2 on the stego tile, then the decoder's soft value of its sigma_1 to metric[plane][tile]: 4 bytes a tile where K2 stores 32
-template <bool ALIGNED>
-__global__ __launch_bounds__(WAVE, 3) void k_payload_metric(const uint8_t* __restrict__ stego, float* __restrict__ metric,
-                                                        const Geom g, const float inv_2delta, int* __restrict__ status) {
-  int t, ty, tx;
-  if (!tile_coords(g, t, ty, tx)) return;
-  const size_t plane = blockIdx.y;
-  wm::RawTile raw;
-  float s[8];
-  load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
-  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
-  metric[plane * g.n_tiles + t] = wm::payload_metric(s[0], inv_2delta);
-}
+// Sigma pass on the stego tile: the decoder's soft value of its sigma_1 to metric[plane][tile], 4 bytes a tile where
+// EpiSigma stores 32
+struct EpiPayloadMetric {
+  float* __restrict__ metric;
+  float inv_2delta;
+  __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], size_t, int, const size_t ti) const {
+    metric[ti] = wm::payload_metric(s[0], inv_2delta);
+  }
+};
 
 // soft[j] = sum of metric[p][order[i]], i in [offs[j], offs[j + 1]), over all planes: one wave per bit, no atomics.  order /
 // offs are the CSR inverse of the tile-to-bit map (a bit's tiles in ascending tile index).  A lane adds its strided share in
@@ -1000,6 +999,85 @@ int check_delta(const float delta) {
   return WM_OK;
 }
 
+// The launch of every sigma pass, behind the caller's check_plane_args and rule check: nothing to do without a tile; `bad`
+// is the caller's verdict on the pointers of its epilogue (the message, or nullptr), which only counts where there is a tile.
+template <typename Epi>
+int sigma_pass(wm_ctx* ctx, const uint8_t* planes, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+               const char* bad, const Epi& epi) {
+  const Geom g = make_geom(H, W, row_stride, plane_stride);
+  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
+  if (bad) return set_err(WM_ERR_BADARG, "%s", bad);
+  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+  with_bools([&](auto A) {
+    hipLaunchKernelGGL((k_sigma_pass<A.value, Epi>), grid, block, 0, ctx->stream, planes, g, ctx->d_status, epi);
+  }, u8_aligned(planes, planes, row_stride, plane_stride));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// The masked and the payload embed, behind the caller's plane and rule checks: `pass(eff, black)` enqueues the sigma pass
+// that leaves a [plane][tile][8] sigma_w in the context's grow-only workspace (with `payload`, also the [plane][tile]
+// black flags), then the unchanged embed launches are fed it with a per-plane stride.  The sigma pass reads the host planes
+// before anything writes (one stream), so stego may alias host.  `missing`: the message if an input that the tiles need
+// is NULL, else nullptr.
+template <typename Pass>
+int embed_derived_dev(wm_ctx* ctx, const uint8_t* host, uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W,
+                      int row_stride, size_t plane_stride, float alpha, int K, bool payload, const char* missing,
+                      const Pass& pass) {
+  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
+  if (K < 0 || K > 8) return set_err(WM_ERR_BADARG, "K must be in 0..8");
+  const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
+  float* eff = nullptr;
+  uint8_t* black = nullptr;
+  if (n_planes > 0 && nt8 > 0) {
+    if (missing) return set_err(WM_ERR_BADARG, "%s", missing);
+    WM_TRY(staged(ctx, &ctx->sigma_ws, &ctx->sigma_ws_bytes, "derived sigma_w", [&](Carve& cv) {
+      eff = cv.take<float>((size_t)n_planes * nt8);
+      black = payload ? cv.take<uint8_t>((size_t)n_planes * (nt8 / 8)) : nullptr;
+    }));
+    WM_TRY(pass(eff, black));
+  }
+  WM_TRY(wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, alpha, K));
+  if (black) {
+    const Geom g = make_geom(H, W, row_stride, plane_stride);
+    const dim3 grid = tile_grid(g, n_planes), block(WAVE);
+    with_bools([&](auto A) {
+      hipLaunchKernelGGL((k_payload_black<A.value>), grid, block, 0, ctx->stream, stego, yw, (const float*)eff,
+                         (const uint8_t*)black, g);
+    }, u8_aligned(host, stego, row_stride, plane_stride));
+    WM_HIP(hipGetLastError());
+  }
+  return WM_OK;
+}
+
+// ---- host-pointer wrappers: what the embeds share -------------------------------
+// Counts are 0 where there is no tile: the host pointer of such an array may be NULL, and nothing is copied.
+size_t n_sigma_w(size_t nt, int n_planes, size_t sigma_w_plane_stride) {
+  return !nt ? 0 : sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
+}
+
+// The round trip of the plain, the masked and the payload embed.  `rule` is the per-tile input of the form (sigma_w, or
+// the payload's tile bits: n_rule elements), dev(d_host, d_rule, d_stego, d_sc, d_yw) its _dev call.
+template <typename T, typename Dev>
+int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_rule, uint8_t* stego, float* sigma_c, float* yw,
+                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev) {
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  uint8_t *d_host, *d_stego; T* d_rule; float *d_sc, *d_yw;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_host = cv.in(span, host);
+    // bytes between rows / planes that belong to the caller must survive the round trip, so stego goes up first; in place,
+    // host and stego are ONE device array (k_copy_border and in-place embedding rely on the equal pointers)
+    d_stego = cv.take<uint8_t>(span);
+    if (stego != host) cv.up(d_stego, stego, span);
+    else d_stego = d_host;
+    cv.down(stego, d_stego, span);
+    d_rule = cv.in(n_rule, rule);
+    d_sc = cv.out((size_t)n_planes * nt * 8, sigma_c);
+    d_yw = yw ? cv.out((size_t)n_planes * H * W, yw) : nullptr;
+  }, [&] { return dev(d_host, d_rule, d_stego, d_sc, d_yw); });
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1066,8 +1144,7 @@ int wm_destroy(wm_ctx* ctx) {
   if (ctx->ref_ws2) (void)hipFree(ctx->ref_ws2);
   if (ctx->route_tmp) (void)hipFree(ctx->route_tmp);
   if (ctx->extract_f32) (void)hipFree(ctx->extract_f32);
-  if (ctx->mask_sw) (void)hipFree(ctx->mask_sw);
-  if (ctx->payload_ws) (void)hipFree(ctx->payload_ws);
+  if (ctx->sigma_ws) (void)hipFree(ctx->sigma_ws);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) if (ctx->pair_tab[i]) (void)hipFree(ctx->pair_tab[i]);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) {
     if (ctx->hier_dev[i]) (void)hipFree(ctx->hier_dev[i]);
@@ -1219,15 +1296,8 @@ int wm_embed_tiles_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w
 int wm_sigma_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, float* sigma, int n_planes, int H,
                           int W, int row_stride, size_t plane_stride) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
-  const Geom g = make_geom(H, W, row_stride, plane_stride);
-  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
-  if (!sigma || ((uintptr_t)sigma & 15u)) return set_err(WM_ERR_BADARG, "sigma is NULL or not 16-byte aligned");
-  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  with_bools([&](auto A) {
-    hipLaunchKernelGGL((k_sigma_tiles<A.value>), grid, block, 0, ctx->stream, planes, sigma, g, ctx->d_status);
-  }, u8_aligned(planes, planes, row_stride, plane_stride));
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  const char* bad = (!sigma || ((uintptr_t)sigma & 15u)) ? "sigma is NULL or not 16-byte aligned" : nullptr;
+  return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad, EpiSigma{sigma});
 }
 
 // ---- K2 + gain, masked K1 ----------------------------------------------------
@@ -1236,60 +1306,23 @@ int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float
                                  size_t sigma_w_plane_stride, float lo, float hi) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_mask(lo, hi, 1.0f));
-  const Geom g = make_geom(H, W, row_stride, plane_stride);
-  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
-  if (!sigma_w != !sigma_w_eff) return set_err(WM_ERR_BADARG, "sigma_w and sigma_w_eff go together");
-  if (!sigma_w_eff && !gain) return set_err(WM_ERR_BADARG, "neither sigma_w_eff nor gain is asked for");
-  if ((((uintptr_t)sigma_w | (uintptr_t)sigma_w_eff) & 15u) || (sigma_w_plane_stride & 3u))
-    return set_err(WM_ERR_BADARG, "sigma_w / sigma_w_eff is not 16-byte aligned");
-  if (((uintptr_t)gain & 3u)) return set_err(WM_ERR_BADARG, "gain is not 4-byte aligned");
-  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  with_bools([&](auto A) {
-    hipLaunchKernelGGL((k_mask_sigma_w<A.value>), grid, block, 0, ctx->stream, planes, sigma_w, sigma_w_eff, gain, g,
-                       sigma_w_plane_stride, lo, hi, ctx->d_status);
-  }, u8_aligned(planes, planes, row_stride, plane_stride));
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  const char* bad = (!sigma_w != !sigma_w_eff) ? "sigma_w and sigma_w_eff go together"
+                    : (!sigma_w_eff && !gain) ? "neither sigma_w_eff nor gain is asked for"
+                    : ((((uintptr_t)sigma_w | (uintptr_t)sigma_w_eff) & 15u) || (sigma_w_plane_stride & 3u))
+                        ? "sigma_w / sigma_w_eff is not 16-byte aligned"
+                    : ((uintptr_t)gain & 3u) ? "gain is not 4-byte aligned" : nullptr;
+  return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad,
+                    EpiMask{sigma_w, sigma_w_eff, gain, sigma_w_plane_stride, lo, hi});
 }
 
-// k_mask_sigma_w, then the unchanged embed launches fed G o sigma_w with a per-plane stride.  The sigma pass reads the host
-// planes before anything writes (one stream), so stego may alias host.  G o sigma_w lives in a grow-only buffer of the context.
-int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
-                                 float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
-                                 size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi) {
-  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
-  WM_TRY(check_mask(lo, hi, 1.0f));
-  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
-  if (K < 0 || K > 8) return set_err(WM_ERR_BADARG, "K must be in 0..8");
-  const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
-  float* eff = nullptr;
-  if (n_planes > 0 && nt8 > 0) {
-    if (!sigma_w || !sigma_c) return set_err(WM_ERR_BADARG, "sigma_w / sigma_c is NULL");
-    WM_TRY(staged(ctx, &ctx->mask_sw, &ctx->mask_sw_bytes, "masked sigma_w", [&](Carve& cv) {
-      eff = cv.take<float>((size_t)n_planes * nt8);
-    }));
-    WM_TRY(wm_mask_sigma_w_tiles_u8_dev(ctx, host, sigma_w, eff, nullptr, n_planes, H, W, row_stride, plane_stride,
-                                        sigma_w_plane_stride, lo, hi));
-  }
-  return wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, alpha, K);
-}
-
-// ---- blind payload: K2 + target, K1 fed with it; K2 + metric, per-bit sums -------
+// ---- blind payload: sigma pass + target, sigma pass + metric -----------------------
 static int payload_sigma_w_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff, uint8_t* black,
                                int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
-  const Geom g = make_geom(H, W, row_stride, plane_stride);
-  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
-  if (!tile_bit) return set_err(WM_ERR_BADARG, "tile_bit is NULL");
-  if (!sigma_w_eff || ((uintptr_t)sigma_w_eff & 15u)) return set_err(WM_ERR_BADARG, "sigma_w_eff is NULL or not 16-byte aligned");
-  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  with_bools([&](auto A) {
-    hipLaunchKernelGGL((k_payload_sigma_w<A.value>), grid, block, 0, ctx->stream, planes, tile_bit, sigma_w_eff, black, g,
-                       delta, ctx->d_status);
-  }, u8_aligned(planes, planes, row_stride, plane_stride));
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  const char* bad = !tile_bit ? "tile_bit is NULL"
+                    : (!sigma_w_eff || ((uintptr_t)sigma_w_eff & 15u)) ? "sigma_w_eff is NULL or not 16-byte aligned" : nullptr;
+  return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad, EpiPayloadSigmaW{tile_bit, sigma_w_eff, black, delta});
 }
 
 int wm_payload_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
@@ -1297,54 +1330,38 @@ int wm_payload_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const ui
   return payload_sigma_w_dev(ctx, planes, tile_bit, sigma_w_eff, nullptr, n_planes, H, W, row_stride, plane_stride, delta);
 }
 
-// The structure of wm_embed_tiles_masked_u8_dev: the sigma pass reads the host planes before anything writes (one stream),
-// so stego may alias host; the rule's sigma_w rows live in a grow-only buffer of the context.
-int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
-                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
-  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
-  WM_TRY(check_delta(delta));
-  if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
-  const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
-  float* eff = nullptr;
-  uint8_t* black = nullptr;
-  if (n_planes > 0 && nt8 > 0) {
-    if (!tile_bit || !sigma_c) return set_err(WM_ERR_BADARG, "tile_bit / sigma_c is NULL");
-    WM_TRY(staged(ctx, &ctx->payload_ws, &ctx->payload_ws_bytes, "payload sigma_w", [&](Carve& cv) {
-      eff = cv.take<float>((size_t)n_planes * nt8);
-      black = cv.take<uint8_t>((size_t)n_planes * (nt8 / 8));
-    }));
-    WM_TRY(payload_sigma_w_dev(ctx, host, tile_bit, eff, black, n_planes, H, W, row_stride, plane_stride, delta));
-  }
-  WM_TRY(wm_embed_tiles_u8_dev(ctx, host, eff, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, nt8, 1.0f, 1));
-  if (eff) {
-    const Geom g = make_geom(H, W, row_stride, plane_stride);
-    const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-    with_bools([&](auto A) {
-      hipLaunchKernelGGL((k_payload_black<A.value>), grid, block, 0, ctx->stream, stego, yw, (const float*)eff,
-                         (const uint8_t*)black, g);
-    }, u8_aligned(host, stego, row_stride, plane_stride));
-    WM_HIP(hipGetLastError());
-  }
-  return WM_OK;
-}
-
 int wm_payload_metric_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
                                    int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
-  const Geom g = make_geom(H, W, row_stride, plane_stride);
-  if (n_planes == 0 || g.n_tiles == 0) return WM_OK;
-  if (!metric || ((uintptr_t)metric & 3u)) return set_err(WM_ERR_BADARG, "metric is NULL or not 4-byte aligned");
-  const dim3 grid = tile_grid(g, n_planes), block(WAVE);
-  const float inv_2delta = 1.0f / (2.0f * delta);
-  with_bools([&](auto A) {
-    hipLaunchKernelGGL((k_payload_metric<A.value>), grid, block, 0, ctx->stream, stego, metric, g, inv_2delta, ctx->d_status);
-  }, u8_aligned(stego, stego, row_stride, plane_stride));
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  const char* bad = (!metric || ((uintptr_t)metric & 3u)) ? "metric is NULL or not 4-byte aligned" : nullptr;
+  return sigma_pass(ctx, stego, n_planes, H, W, row_stride, plane_stride, bad, EpiPayloadMetric{metric, 1.0f / (2.0f * delta)});
 }
 
-// the metric into a grow-only buffer of the context, then one wave per bit over it
+// ---- K1 fed with a sigma_w derived from the cover (embed_derived_dev): the masked and the payload embed ----------
+int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
+                                 float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi) {
+  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_mask(lo, hi, 1.0f));
+  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, alpha, K, false,
+                           (!sigma_w || !sigma_c) ? "sigma_w / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t*) {
+    return wm_mask_sigma_w_tiles_u8_dev(ctx, host, sigma_w, eff, nullptr, n_planes, H, W, row_stride, plane_stride,
+                                        sigma_w_plane_stride, lo, hi);
+  });
+}
+
+int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, 1.0f, 1, true,
+                           (!tile_bit || !sigma_c) ? "tile_bit / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t* black) {
+    return payload_sigma_w_dev(ctx, host, tile_bit, eff, black, n_planes, H, W, row_stride, plane_stride, delta);
+  });
+}
+
+// the metric into the context's grow-only workspace, then one wave per bit over it
 int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
                                  double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
@@ -1355,7 +1372,7 @@ int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_
   if (!order || !offs || !soft || (((uintptr_t)order | (uintptr_t)offs) & 3u) || ((uintptr_t)soft & 7u))
     return set_err(WM_ERR_BADARG, "order / offs / soft is NULL or misaligned");
   float* metric = nullptr;
-  WM_TRY(staged(ctx, &ctx->payload_ws, &ctx->payload_ws_bytes, "payload metric", [&](Carve& cv) {
+  WM_TRY(staged(ctx, &ctx->sigma_ws, &ctx->sigma_ws_bytes, "payload metric", [&](Carve& cv) {
     metric = cv.take<float>((size_t)n_planes * nt);
   }));
   WM_TRY(wm_payload_metric_tiles_u8_dev(ctx, stego, metric, n_planes, H, W, row_stride, plane_stride, delta));
@@ -1583,31 +1600,13 @@ static int embed_tiles_host(wm_ctx* ctx, const uint8_t* host, const float* sigma
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!sigma_w || !sigma_c)) return set_err(WM_ERR_BADARG, "sigma_w / sigma_c is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
-  const size_t n_sc = (size_t)n_planes * nt * 8;
-  const size_t n_yw = yw ? (size_t)n_planes * H * W : 0;
-  uint8_t *d_host, *d_stego; float *d_sw, *d_sc, *d_yw;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_host = cv.take<uint8_t>(span);
-    d_stego = cv.take<uint8_t>(span);
-    d_sw = cv.take<float>(n_sw);
-    d_sc = cv.take<float>(n_sc);
-    d_yw = yw ? cv.take<float>(n_yw) : nullptr;
-  }));
-  WM_HIP(hipMemcpyAsync(d_host, host, span, hipMemcpyHostToDevice, ctx->stream));
-  // bytes between rows / planes that belong to the caller must survive the round trip
-  if (stego != host) WM_HIP(hipMemcpyAsync(d_stego, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  else d_stego = d_host;
-  if (nt) WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (mask) WM_TRY(wm_embed_tiles_masked_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride,
-                                                plane_stride, sigma_w_plane_stride, alpha, K, mask->lo, mask->hi));
-  else WM_TRY(wm_embed_tiles_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride,
-                                    plane_stride, sigma_w_plane_stride, alpha, K));
-  WM_HIP(hipMemcpyAsync(stego, d_stego, span, hipMemcpyDeviceToHost, ctx->stream));
-  if (nt) WM_HIP(hipMemcpyAsync(sigma_c, d_sc, n_sc * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (yw) WM_HIP(hipMemcpyAsync(yw, d_yw, n_yw * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return embed_round_trip(ctx, host, sigma_w, n_sigma_w(nt, n_planes, sigma_w_plane_stride), stego, sigma_c, yw, n_planes, H, W,
+                          row_stride, plane_stride, [&](uint8_t* d_host, float* d_sw, uint8_t* d_stego, float* d_sc, float* d_yw) {
+    return mask ? wm_embed_tiles_masked_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride,
+                                               sigma_w_plane_stride, alpha, K, mask->lo, mask->hi)
+                : wm_embed_tiles_u8_dev(ctx, d_host, d_sw, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride,
+                                        sigma_w_plane_stride, alpha, K);
+  });
 }
 
 int wm_embed_tiles_u8(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego,
@@ -1632,23 +1631,16 @@ int wm_mask_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const float* si
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!sigma_w != !sigma_w_eff) return set_err(WM_ERR_BADARG, "sigma_w and sigma_w_eff go together");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
-  const size_t n_eff = (size_t)n_planes * nt * 8, n_g = (size_t)n_planes * nt;
   uint8_t* d_p; float *d_sw, *d_eff, *d_g;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_sw = sigma_w ? cv.take<float>(n_sw) : nullptr;
-    d_eff = sigma_w ? cv.take<float>(n_eff) : nullptr;
-    d_g = gain ? cv.take<float>(n_g) : nullptr;
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
-  if (sigma_w) WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_mask_sigma_w_tiles_u8_dev(ctx, d_p, d_sw, d_eff, d_g, n_planes, H, W, row_stride, plane_stride,
-                                      sigma_w_plane_stride, lo, hi));
-  if (sigma_w) WM_HIP(hipMemcpyAsync(sigma_w_eff, d_eff, n_eff * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (gain) WM_HIP(hipMemcpyAsync(gain, d_g, n_g * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), planes);
+    d_sw = sigma_w ? cv.in(n_sigma_w(nt, n_planes, sigma_w_plane_stride), sigma_w) : nullptr;
+    d_eff = sigma_w ? cv.out((size_t)n_planes * nt * 8, sigma_w_eff) : nullptr;
+    d_g = gain ? cv.out((size_t)n_planes * nt, gain) : nullptr;
+  }, [&] {
+    return wm_mask_sigma_w_tiles_u8_dev(ctx, d_p, d_sw, d_eff, d_g, n_planes, H, W, row_stride, plane_stride,
+                                        sigma_w_plane_stride, lo, hi);
+  });
 }
 
 int wm_sigma_tiles_u8(wm_ctx* ctx, const uint8_t* planes, float* sigma, int n_planes, int H, int W,
@@ -1657,17 +1649,11 @@ int wm_sigma_tiles_u8(wm_ctx* ctx, const uint8_t* planes, float* sigma, int n_pl
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!sigma) return set_err(WM_ERR_BADARG, "sigma is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_s = (size_t)n_planes * nt * 8;
   uint8_t* d_p; float* d_s;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_s = cv.take<float>(n_s);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_sigma_tiles_u8_dev(ctx, d_p, d_s, n_planes, H, W, row_stride, plane_stride));
-  WM_HIP(hipMemcpyAsync(sigma, d_s, n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), planes);
+    d_s = cv.out((size_t)n_planes * nt * 8, sigma);
+  }, [&] { return wm_sigma_tiles_u8_dev(ctx, d_p, d_s, n_planes, H, W, row_stride, plane_stride); });
 }
 
 int wm_svd_tiles_f32(wm_ctx* ctx, const float* planes, float* U, float* S, float* Vt, int n_planes,
@@ -1676,21 +1662,14 @@ int wm_svd_tiles_f32(wm_ctx* ctx, const float* planes, float* U, float* S, float
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!U || !S || !Vt) return set_err(WM_ERR_BADARG, "U/S/Vt is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_m = (size_t)n_planes * nt * 64, n_s = (size_t)n_planes * nt * 8;
+  const size_t n_m = (size_t)n_planes * nt * 64;
   float *d_p, *d_U, *d_V, *d_S;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<float>(span);
-    d_U = cv.take<float>(n_m);
-    d_V = cv.take<float>(n_m);
-    d_S = cv.take<float>(n_s);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, planes, span * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_svd_tiles_f32_dev(ctx, d_p, d_U, d_S, d_V, n_planes, H, W, row_stride, plane_stride));
-  WM_HIP(hipMemcpyAsync(U, d_U, n_m * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WM_HIP(hipMemcpyAsync(Vt, d_V, n_m * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WM_HIP(hipMemcpyAsync(S, d_S, n_s * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), planes);
+    d_U = cv.out(n_m, U);
+    d_V = cv.out(n_m, Vt);
+    d_S = cv.out((size_t)n_planes * nt * 8, S);
+  }, [&] { return wm_svd_tiles_f32_dev(ctx, d_p, d_U, d_S, d_V, n_planes, H, W, row_stride, plane_stride); });
 }
 
 static int extract_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
@@ -1702,38 +1681,30 @@ static int extract_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* si
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!sigma_c || !Uw || !Vwt)) return set_err(WM_ERR_BADARG, "sigma_c/Uw/Vwt is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_sc = (size_t)n_planes * nt * 8;
   const size_t n_uv = (uv_plane_stride ? (size_t)n_planes : (size_t)1) * nt * 64;
   const size_t hw = (size_t)H * W, n_out = (size_t)n_planes * hw;
   uint8_t* d_p; float *d_sc, *d_U, *d_V, *d_o, *d_sum;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_sc = cv.take<float>(n_sc);
-    d_U = cv.take<float>(n_uv);
-    d_V = cv.take<float>(n_uv);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), stego);
+    d_sc = cv.in((size_t)n_planes * nt * 8, sigma_c);
+    d_U = cv.in(n_uv, Uw);
+    d_V = cv.in(n_uv, Vwt);
     d_o = cv.take<float>(n_out);
     d_sum = cv.take<float>(hw);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  if (nt) {
-    WM_HIP(hipMemcpyAsync(d_sc, sigma_c, n_sc * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(d_U, Uw, n_uv * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(d_V, Vwt, n_uv * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (mask) WM_TRY(wm_extract_tiles_masked_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
-                                                  uv_plane_stride, alpha, K, mask->lo, mask->hi, mask->cut));
-  else WM_TRY(wm_extract_tiles_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
-                                      uv_plane_stride, alpha, K));
-  if (sum_planes) {
-    const size_t g = (hw + 255) / 256;
-    hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, ctx->stream, d_o, hw, n_planes, d_sum);
-    WM_HIP(hipGetLastError());
-    WM_HIP(hipMemcpyAsync(out, d_sum, hw * 4, hipMemcpyDeviceToHost, ctx->stream));
-  } else {
-    WM_HIP(hipMemcpyAsync(out, d_o, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  return wm_check_status(ctx);
+    if (sum_planes) cv.down(out, d_sum, hw);
+    else cv.down(out, d_o, n_out);
+  }, [&]() -> int {
+    if (mask) WM_TRY(wm_extract_tiles_masked_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
+                                                    uv_plane_stride, alpha, K, mask->lo, mask->hi, mask->cut));
+    else WM_TRY(wm_extract_tiles_u8_dev(ctx, d_p, d_sc, d_U, d_V, d_o, n_planes, H, W, row_stride, plane_stride,
+                                        uv_plane_stride, alpha, K));
+    if (sum_planes) {
+      const size_t g = (hw + 255) / 256;
+      hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, ctx->stream, d_o, hw, n_planes, d_sum);
+      WM_HIP(hipGetLastError());
+    }
+    return WM_OK;
+  });
 }
 
 int wm_extract_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* Uw,
@@ -1774,24 +1745,14 @@ int wm_reconstruct_tiles(wm_ctx* ctx, const float* Uw, const float* sw_hat, cons
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!Uw || !sw_hat || !Vwt)) return set_err(WM_ERR_BADARG, "Uw/sw_hat/Vwt is NULL");
-  const size_t n_m = (size_t)n_planes * nt * 64, n_s = (size_t)n_planes * nt * 8;
-  const size_t n_out = (size_t)n_planes * H * W;
+  const size_t n_m = (size_t)n_planes * nt * 64;
   float *d_U, *d_V, *d_s, *d_o;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_U = cv.take<float>(n_m);
-    d_V = cv.take<float>(n_m);
-    d_s = cv.take<float>(n_s);
-    d_o = cv.take<float>(n_out);
-  }));
-  if (nt) {
-    WM_HIP(hipMemcpyAsync(d_U, Uw, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(d_V, Vwt, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(d_s, sw_hat, n_s * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  WM_TRY(wm_reconstruct_tiles_dev(ctx, d_U, d_s, d_V, d_o, n_planes, H, W));
-  WM_HIP(hipMemcpyAsync(out, d_o, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WM_HIP(hipStreamSynchronize(ctx->stream));
-  return WM_OK;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_U = cv.in(n_m, Uw);
+    d_V = cv.in(n_m, Vwt);
+    d_s = cv.in((size_t)n_planes * nt * 8, sw_hat);
+    d_o = cv.out((size_t)n_planes * H * W, out);
+  }, [&] { return wm_reconstruct_tiles_dev(ctx, d_U, d_s, d_V, d_o, n_planes, H, W); }, /* sync_only: no SVD, no status */ true);
 }
 
 static int detect_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
@@ -1803,26 +1764,19 @@ static int detect_tiles_host(wm_ctx* ctx, const uint8_t* stego, const float* sig
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!sigma_c || !sigma_w)) return set_err(WM_ERR_BADARG, "sigma_c/sigma_w is NULL");
   const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_sc = (size_t)n_planes * nt * 8;
-  const size_t n_sw = sigma_w_plane_stride ? (size_t)(n_planes - 1) * sigma_w_plane_stride + nt * 8 : nt * 8;
   uint8_t* d_p; float *d_sc, *d_sw; double* d_scores;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span ? span : 1);
-    d_sc = cv.take<float>(n_sc);
-    d_sw = cv.take<float>(n_sw);
-    d_scores = cv.take<double>((size_t)n_planes);
-  }));
-  if (span) WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  if (nt) {
-    WM_HIP(hipMemcpyAsync(d_sc, sigma_c, n_sc * 4, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(hipMemcpyAsync(d_sw, sigma_w, n_sw * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (mask) WM_TRY(wm_detect_tiles_masked_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
-                                                 sigma_w_plane_stride, alpha, mask->lo, mask->hi, mask->cut));
-  else WM_TRY(wm_detect_tiles_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
-                                     sigma_w_plane_stride, alpha));
-  WM_HIP(hipMemcpyAsync(scores, d_scores, (size_t)n_planes * 8, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.take<uint8_t>(span ? span : 1);      // (planes without a sample still get a pointer the _dev form accepts)
+    cv.up(d_p, stego, span);
+    d_sc = cv.in((size_t)n_planes * nt * 8, sigma_c);
+    d_sw = cv.in(n_sigma_w(nt, n_planes, sigma_w_plane_stride), sigma_w);
+    d_scores = cv.out((size_t)n_planes, scores);
+  }, [&] {
+    return mask ? wm_detect_tiles_masked_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
+                                                sigma_w_plane_stride, alpha, mask->lo, mask->hi, mask->cut)
+                : wm_detect_tiles_u8_dev(ctx, d_p, d_sc, d_sw, d_scores, n_planes, H, W, row_stride, plane_stride,
+                                         sigma_w_plane_stride, alpha);
+  });
 }
 
 int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c, const float* sigma_w,
@@ -1848,19 +1802,12 @@ int wm_payload_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!tile_bit || !sigma_w_eff) return set_err(WM_ERR_BADARG, "tile_bit / sigma_w_eff is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_eff = (size_t)n_planes * nt * 8;
   uint8_t *d_p, *d_bit; float* d_eff;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_bit = cv.take<uint8_t>(nt);
-    d_eff = cv.take<float>(n_eff);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, planes, span, hipMemcpyHostToDevice, ctx->stream));
-  WM_HIP(hipMemcpyAsync(d_bit, tile_bit, nt, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_payload_sigma_w_tiles_u8_dev(ctx, d_p, d_bit, d_eff, n_planes, H, W, row_stride, plane_stride, delta));
-  WM_HIP(hipMemcpyAsync(sigma_w_eff, d_eff, n_eff * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), planes);
+    d_bit = cv.in(nt, tile_bit);
+    d_eff = cv.out((size_t)n_planes * nt * 8, sigma_w_eff);
+  }, [&] { return wm_payload_sigma_w_tiles_u8_dev(ctx, d_p, d_bit, d_eff, n_planes, H, W, row_stride, plane_stride, delta); });
 }
 
 int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
@@ -1871,27 +1818,10 @@ int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* t
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!tile_bit || !sigma_c)) return set_err(WM_ERR_BADARG, "tile_bit / sigma_c is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_sc = (size_t)n_planes * nt * 8;
-  const size_t n_yw = yw ? (size_t)n_planes * H * W : 0;
-  uint8_t *d_host, *d_stego, *d_bit; float *d_sc, *d_yw;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_host = cv.take<uint8_t>(span);
-    d_stego = cv.take<uint8_t>(span);
-    d_bit = cv.take<uint8_t>(nt);
-    d_sc = cv.take<float>(n_sc);
-    d_yw = yw ? cv.take<float>(n_yw) : nullptr;
-  }));
-  WM_HIP(hipMemcpyAsync(d_host, host, span, hipMemcpyHostToDevice, ctx->stream));
-  // bytes between rows / planes that belong to the caller must survive the round trip
-  if (stego != host) WM_HIP(hipMemcpyAsync(d_stego, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  else d_stego = d_host;
-  if (nt) WM_HIP(hipMemcpyAsync(d_bit, tile_bit, nt, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_embed_tiles_payload_u8_dev(ctx, d_host, d_bit, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride, delta));
-  WM_HIP(hipMemcpyAsync(stego, d_stego, span, hipMemcpyDeviceToHost, ctx->stream));
-  if (nt) WM_HIP(hipMemcpyAsync(sigma_c, d_sc, n_sc * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (yw) WM_HIP(hipMemcpyAsync(yw, d_yw, n_yw * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return embed_round_trip(ctx, host, tile_bit, nt, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride,
+                          [&](uint8_t* d_host, uint8_t* d_bit, uint8_t* d_stego, float* d_sc, float* d_yw) {
+    return wm_embed_tiles_payload_u8_dev(ctx, d_host, d_bit, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride, delta);
+  });
 }
 
 int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
@@ -1901,17 +1831,11 @@ int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric,
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!metric) return set_err(WM_ERR_BADARG, "metric is NULL");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
-  const size_t n_m = (size_t)n_planes * nt;
   uint8_t* d_p; float* d_m;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_m = cv.take<float>(n_m);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_payload_metric_tiles_u8_dev(ctx, d_p, d_m, n_planes, H, W, row_stride, plane_stride, delta));
-  WM_HIP(hipMemcpyAsync(metric, d_m, n_m * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), stego);
+    d_m = cv.out((size_t)n_planes * nt, metric);
+  }, [&] { return wm_payload_metric_tiles_u8_dev(ctx, d_p, d_m, n_planes, H, W, row_stride, plane_stride, delta); });
 }
 
 // The host form sees order / offs and checks them: offs runs from 0 to n_tiles without decreasing, every order entry names
@@ -1929,20 +1853,15 @@ int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* o
     if (offs[j + 1] < offs[j]) return set_err(WM_ERR_BADARG, "offs decreases");
   for (size_t i = 0; i < nt; ++i)
     if (order[i] < 0 || (size_t)order[i] >= nt) return set_err(WM_ERR_BADARG, "order names a tile outside the grid");
-  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
   uint8_t* d_p; int32_t *d_order, *d_offs; double* d_soft;
-  WM_TRY(staged(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", [&](Carve& cv) {
-    d_p = cv.take<uint8_t>(span);
-    d_order = cv.take<int32_t>(nt);
-    d_offs = cv.take<int32_t>((size_t)n_bits + 1);
-    d_soft = cv.take<double>((size_t)n_bits);
-  }));
-  WM_HIP(hipMemcpyAsync(d_p, stego, span, hipMemcpyHostToDevice, ctx->stream));
-  WM_HIP(hipMemcpyAsync(d_order, order, nt * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_HIP(hipMemcpyAsync(d_offs, offs, ((size_t)n_bits + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  WM_TRY(wm_payload_soft_tiles_u8_dev(ctx, d_p, d_order, d_offs, n_bits, d_soft, n_planes, H, W, row_stride, plane_stride, delta));
-  WM_HIP(hipMemcpyAsync(soft, d_soft, (size_t)n_bits * 8, hipMemcpyDeviceToHost, ctx->stream));
-  return wm_check_status(ctx);
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), stego);
+    d_order = cv.in(nt, order);
+    d_offs = cv.in((size_t)n_bits + 1, offs);
+    d_soft = cv.out((size_t)n_bits, soft);
+  }, [&] {
+    return wm_payload_soft_tiles_u8_dev(ctx, d_p, d_order, d_offs, n_bits, d_soft, n_planes, H, W, row_stride, plane_stride, delta);
+  });
 }
 
 }  // extern "C"

@@ -288,6 +288,46 @@ def _is_marked(i: int, frame_interval: int) -> bool:
     return i % max(1, int(frame_interval)) == 0
 
 
+def _embed_frame_loop(vid: Y4M, out, frame_interval: int, batch: int, embed_marked) -> int:
+    """The one embed loop: every frame of ``vid`` goes to the open file ``out`` behind its FRAME line, the unmarked ones
+    byte for byte.  Frames are held until ``batch`` marked ones are pending; ``embed_marked([(y, chroma), ...])`` then
+    returns, per marked frame and in order, the byte strings that follow its FRAME line.  Returns the frame count."""
+    pend, n_frames = [], 0          # (frame_line, y, chroma, marked)
+
+    def flush():
+        marked = [p[1:3] for p in pend if p[3]]
+        stored = iter(embed_marked(marked) if marked else ())
+        for line, y, chroma, is_marked in pend:
+            out.write(line)
+            if is_marked:
+                out.writelines(next(stored))
+            else:
+                out.write(y.tobytes()); out.write(chroma.tobytes())
+        pend.clear()
+
+    for line, y, chroma in vid:
+        pend.append((line, y.copy(), chroma.copy(), _is_marked(n_frames, frame_interval)))
+        n_frames += 1
+        if len(pend) >= batch * max(1, frame_interval):
+            flush()
+    flush()
+    return n_frames
+
+
+def _marked_batches(vid: Y4M, frame_interval: int, batch: int, limit: Optional[int] = None):
+    """The marked frames of ``vid`` in order, ``batch`` at a time: lists of (y, chroma); with ``limit`` the first that
+    many marked frames only."""
+    pend, seen = [], 0
+    for i, (_, y, chroma) in enumerate(vid):
+        if _is_marked(i, frame_interval) and (limit is None or seen < limit):
+            pend.append((y, chroma)); seen += 1
+            if len(pend) >= batch:
+                yield pend
+                pend = []
+    if pend:
+        yield pend
+
+
 def _embed_video(codec, host_video_path, watermark_path, output_video_path, metadata_path, alpha, frame_interval,
                  password, nonce, kfrac, k_floor, batch, device, tile, subsampling="refuse", strength="uniform",
                  mask=M.MASK_DEFAULT):
@@ -308,35 +348,19 @@ def _embed_video(codec, host_video_path, watermark_path, output_video_path, meta
         Uw, Sw, Vwt = codec.prepare(ctx, hg.read_image_bgr(watermark_path), H, W, key, tile)
         K = M.k_of(tile or min(H, W), kfrac, k_floor)                     # single:137, L = 8 per tile or min(H, W) per plane
         sc_all = [[] for _ in Sw]
-        psnrs, n_frames = [], 0
+        psnrs = []
+
+        def embed_marked(marked):
+            planes = codec.planes(ctx, marked, H, W)                                         # [n, C, H, W]
+            st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile, mask)
+            for ch, c in enumerate(sc):
+                sc_all[ch].append(c)
+            psnrs.extend(hg.psnr(planes[i], st[i]) for i in range(len(marked)))
+            return codec.frame_bytes(ctx, st, [chroma for _, chroma in marked])
+
         with open(output_video_path, "wb") as out:
             out.write(vid.header_line)
-            pend = []          # (frame_line, y, chroma, marked)
-
-            def flush():
-                marked = [p for p in pend if p[3]]
-                if marked:
-                    planes = codec.planes(ctx, [p[1:3] for p in marked], H, W)                   # [n, C, H, W]
-                    st, sc = embed_frames_color(ctx, planes, Sw, alpha, K, batch, tile, mask)
-                    for ch, c in enumerate(sc):
-                        sc_all[ch].append(c)
-                    psnrs.extend(hg.psnr(planes[i], st[i]) for i in range(len(marked)))
-                    stored = codec.frame_bytes(ctx, st, [p[2] for p in marked])
-                j = 0
-                for line, y, chroma, is_marked in pend:
-                    out.write(line)
-                    if is_marked:
-                        out.writelines(stored[j]); j += 1
-                    else:
-                        out.write(y.tobytes()); out.write(chroma.tobytes())
-                pend.clear()
-
-            for line, y, chroma in vid:
-                pend.append((line, y.copy(), chroma.copy(), _is_marked(n_frames, frame_interval)))
-                n_frames += 1
-                if len(pend) >= batch * max(1, frame_interval):
-                    flush()
-            flush()
+            n_frames = _embed_frame_loop(vid, out, frame_interval, batch, embed_marked)
         empty = np.zeros((0, H // TILE, W // TILE, 8) if tile else (0, min(H, W)), np.float32)
         S = [np.concatenate(c) if c else empty for c in sc_all]
         members = {"mode": codec.mode, **M.common_members(H, W, alpha, kfrac, nonce),
@@ -367,19 +391,10 @@ def _marked_planes(codec, ctx: hostapi.Context, stego_video_path: str, data, n: 
         want = M.chroma_of(data)
         codec = _container_codec(codec, vid, (want,), "a colour-watermarked video is 4:4:4" if want == "444" else
                                  f"the metadata was written for a C{want} video, this one is C{vid.chroma}")
-        fi = int(data["frame_interval"])
-        H, W = vid.H, vid.W
-        out, pend, seen = [], [], 0
-        for i, (_, y, chroma) in enumerate(vid):
-            if _is_marked(i, fi) and seen < n:
-                pend.append((y, chroma)); seen += 1
-                if len(pend) >= batch:
-                    out.append(codec.planes(ctx, pend, H, W)); pend = []
-        if pend:
-            out.append(codec.planes(ctx, pend, H, W))
+        out = [codec.planes(ctx, frames, vid.H, vid.W) for frames in _marked_batches(vid, int(data["frame_interval"]), batch, n)]
     finally:
         vid.close()
-    if seen < n:
+    if sum(len(p) for p in out) < n:
         raise ValueError("video has fewer marked frames than the metadata")
     return np.concatenate(out) if out else np.zeros((0, C) + tuple(map(int, data["shape"])), np.uint8)
 
@@ -528,36 +543,20 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
         tbi, order, offs = P.payload_map(H // TILE, W // TILE, key, bits.size)
         tile_bit = P.tile_bits(bits, tbi)
         ctx = hostapi.Context(device)
-        psnrs, n_frames = [], 0
+        psnrs = []
         soft = np.zeros(bits.size, np.float64)
+
+        def embed_marked(marked):
+            ys = np.stack([y for y, _ in marked])
+            st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta)
+            psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
+            if verify:
+                np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch), out=soft)
+            return [(s.tobytes(), chroma.tobytes()) for s, (_, chroma) in zip(st, marked)]
+
         with open(output_video_path, "wb") as out:
             out.write(vid.header_line)
-            pend = []          # (frame_line, y, chroma, marked)
-
-            def flush():
-                marked = [p for p in pend if p[3]]
-                if marked:
-                    ys = np.stack([p[1] for p in marked])
-                    st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta)
-                    psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
-                    if verify:
-                        np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch), out=soft)
-                j = 0
-                for line, y, chroma, is_marked in pend:
-                    out.write(line)
-                    if is_marked:
-                        out.write(st[j].tobytes()); j += 1
-                    else:
-                        out.write(y.tobytes())
-                    out.write(chroma.tobytes())
-                pend.clear()
-
-            for line, y, chroma in vid:
-                pend.append((line, y.copy(), chroma.copy(), _is_marked(n_frames, frame_interval)))
-                n_frames += 1
-                if len(pend) >= batch * max(1, frame_interval):
-                    flush()
-            flush()
+            n_frames = _embed_frame_loop(vid, out, frame_interval, batch, embed_marked)
         if verify and psnrs:
             try:
                 P.check_decodes(soft, bits, data)
@@ -596,14 +595,10 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
             raise ValueError(f"video is {vid.W}x{vid.H} but the meta was written for {W}x{H}")
         ctx = hostapi.Context(device)
         soft = np.zeros(n_bits, np.float64)
-        pend, n_marked = [], 0
-        for i, (_, y, _) in enumerate(vid):
-            if _is_marked(i, fi):
-                pend.append(y.copy()); n_marked += 1
-                if len(pend) >= batch:
-                    soft += ctx.payload_soft(np.stack(pend), order, offs, n_bits, delta); pend = []
-        if pend:
-            soft += ctx.payload_soft(np.stack(pend), order, offs, n_bits, delta)
+        n_marked = 0
+        for frames in _marked_batches(vid, fi, batch):
+            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, n_bits, delta)
+            n_marked += len(frames)
     finally:
         vid.close()
         if ctx is not None:

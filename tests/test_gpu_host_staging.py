@@ -9,14 +9,21 @@ import math
 import numpy as np
 import pytest
 
+import payload_refs as pr
+
 pytestmark = pytest.mark.gpu
 
 ALPHA, K = 0.15, 6
-CUT = dict(n=3, H=19, W=27, base=(3, 21, 32), at=(1, 3))      # 2 x 3 tiles, rows of 32 from element 35 on
-ONE_TILE = dict(n=1, H=8, W=8, base=None, at=None)
-NO_TILE = dict(n=1, H=7, W=13, base=None, at=None)
-LARGE = dict(n=2, H=64, W=96, base=None, at=None)
-CASES = {"cut_shared": (CUT, True), "cut_per_plane": (CUT, False), "one_tile": (ONE_TILE, False), "no_tile": (NO_TILE, True)}
+LO, HI, MCUT = 8.0, 64.0, 0.25        # the texture-masked rule's defaults (meta.MASK_DEFAULT)
+DELTA = pr.DELTA                      # the payload rule's default step
+# bits: the payload bits the case's tiles are dealt to
+CUT = dict(n=3, H=19, W=27, base=(3, 21, 32), at=(1, 3), bits=3)      # 2 x 3 tiles, rows of 32 from element 35 on
+ONE_TILE = dict(n=1, H=8, W=8, base=None, at=None, bits=1)
+NO_TILE = dict(n=1, H=7, W=13, base=None, at=None, bits=1)
+DENSE = dict(n=2, H=40, W=104, base=None, at=None, bits=5)            # 65 tiles: the second wave has one live lane
+LARGE = dict(n=2, H=64, W=96, base=None, at=None, bits=5)
+CASES = {"cut_shared": (CUT, True), "cut_per_plane": (CUT, False), "one_tile": (ONE_TILE, False), "no_tile": (NO_TILE, True),
+         "dense": (DENSE, False)}
 
 
 def _vp(x):
@@ -61,10 +68,11 @@ def make_inputs(case, shared, seed):
         host.view[0, :8, :8] = 77
         host.view[1, 8:16, 16:24] = np.outer(np.arange(1, 9), np.arange(3, 11)).astype(np.uint8)
         host.view[2, :8, 8:16] = host.view[2, :2, 8:16].repeat(4, axis=0)
+        host.view[0, 8:16, 8:16] = 0     # and a black tile, which the payload embed rewrites on its own (k_payload_black)
     lead = () if shared else (n,)
     sw = np.sort(np.abs(rng.normal(0, 300, lead + (nby, nbx, 8))).astype(np.float32), axis=-1)[..., ::-1].copy()
     idx = rng.permutation(H * W).astype(np.int32)
-    return dict(
+    I = dict(
         n=n, H=H, W=W, nt=nt, shared=shared, case=case, host=host,
         stego_fill=Planes(case, np.uint8, rng, fill=0xA5),
         fplanes=Planes(case, np.float32, rng),
@@ -84,6 +92,14 @@ def make_inputs(case, shared, seed):
         imgf=rng.normal(120, 50, (H, W)).astype(np.float32), imgfb=rng.normal(120, 50, (H, W)).astype(np.float32),
         xf=rng.normal(10, 200, n * H * W).astype(np.float32),
     )
+    # payload: a bit per tile, and the tile-to-bit map in CSR form (a bit's tiles in ascending order)
+    n_bits = case["bits"]
+    I["tile_bit"] = rng.integers(0, 2, nt).astype(np.uint8)
+    bit_of = rng.permutation(nt) % n_bits
+    I["order"] = np.argsort(bit_of, kind="stable").astype(np.int32)
+    I["offs"] = np.concatenate(([0], np.cumsum(np.bincount(bit_of, minlength=n_bits)))).astype(np.int32)
+    I["n_bits"] = n_bits
+    return I
 
 
 COLOR_OPS = ("wm_bgr_to_ycrcb_u8_dev", "wm_ycrcb_to_bgr_u8_dev", "wm_bgr_to_gray_u8_dev", "wm_bgr_to_y_u8_dev", "wm_replace_y_u8_dev")
@@ -156,6 +172,54 @@ def run_host(ctx, I):
         call("wm_enhance_extract_u8", ptr(img), ptr(o), H, W, ch)
         R[f"enhance{ch}"] = o
     R.update(_unscrambled(ctx, I, fused=True))
+    # texture-masked strength
+    eff = np.zeros((n, nby, nbx, 8), np.float32); g = np.zeros((n, nby, nbx), np.float32)
+    call("wm_mask_sigma_w_tiles_u8", ptr(hp.view), ptr(I["sw"]), ptr(eff), ptr(g), n, H, W, hp.rs, hp.ps, I["sw_ps"], LO, HI)
+    R["mask_sw"] = (eff, g)
+    g = np.zeros((n, nby, nbx), np.float32)
+    call("wm_mask_sigma_w_tiles_u8", ptr(hp.view), None, None, ptr(g), n, H, W, hp.rs, hp.ps, 0, LO, HI)
+    R["mask_gain"] = g
+    st = hp.like(I["stego_fill"].base.copy())
+    sc = np.zeros((n, nby, nbx, 8), np.float32); yw = np.zeros((n, H, W), np.float32)
+    call("wm_embed_tiles_masked_u8", ptr(hp.view), ptr(I["sw"]), ptr(st.view), ptr(sc), ptr(yw), n, H, W, hp.rs, hp.ps, I["sw_ps"],
+         ALPHA, K, LO, HI)
+    R["masked_embed_yw"] = (st.base, sc, yw)
+    ip = hp.like(hp.base.copy())
+    sc = np.zeros((n, nby, nbx, 8), np.float32)
+    call("wm_embed_tiles_masked_u8", ptr(ip.view), ptr(I["sw"]), ptr(ip.view), ptr(sc), None, n, H, W, hp.rs, hp.ps, I["sw_ps"],
+         ALPHA, K, LO, HI)
+    R["masked_embed_inplace"] = (ip.base, sc)
+    out = np.zeros((n, H, W), np.float32)
+    call("wm_extract_tiles_masked_u8", ptr(hp.view), ptr(I["sc"]), ptr(I["U"]), ptr(I["Vt"]), ptr(out), n, H, W, hp.rs, hp.ps,
+         I["uv_ps"], ALPHA, K, LO, HI, MCUT)
+    R["masked_extract"] = out
+    tot = np.zeros((H, W), np.float32)
+    call("wm_extract_tiles_sum_masked_u8", ptr(hp.view), ptr(I["sc"]), ptr(I["U"]), ptr(I["Vt"]), ptr(tot), n, H, W, hp.rs, hp.ps,
+         I["uv_ps"], ALPHA, K, LO, HI, MCUT)
+    R["masked_extract_sum"] = tot
+    scores = np.zeros(n, np.float64)
+    call("wm_detect_tiles_masked_u8", ptr(hp.view), ptr(I["sc"]), ptr(I["sw"]), ptr(scores), n, H, W, hp.rs, hp.ps, I["sw_ps"],
+         ALPHA, LO, HI, MCUT)
+    R["masked_detect"] = scores
+    # blind payload
+    eff = np.zeros((n, nby, nbx, 8), np.float32)
+    call("wm_payload_sigma_w_tiles_u8", ptr(hp.view), ptr(I["tile_bit"]), ptr(eff), n, H, W, hp.rs, hp.ps, DELTA)
+    R["payload_sw"] = eff
+    st = hp.like(I["stego_fill"].base.copy())
+    sc = np.zeros((n, nby, nbx, 8), np.float32); yw = np.zeros((n, H, W), np.float32)
+    call("wm_embed_tiles_payload_u8", ptr(hp.view), ptr(I["tile_bit"]), ptr(st.view), ptr(sc), ptr(yw), n, H, W, hp.rs, hp.ps, DELTA)
+    R["payload_embed_yw"] = (st.base, sc, yw)
+    ip = hp.like(hp.base.copy())
+    sc = np.zeros((n, nby, nbx, 8), np.float32)
+    call("wm_embed_tiles_payload_u8", ptr(ip.view), ptr(I["tile_bit"]), ptr(ip.view), ptr(sc), None, n, H, W, hp.rs, hp.ps, DELTA)
+    R["payload_embed_inplace"] = (ip.base, sc)
+    m = np.zeros((n, nby, nbx), np.float32)
+    call("wm_payload_metric_tiles_u8", ptr(hp.view), ptr(m), n, H, W, hp.rs, hp.ps, DELTA)
+    R["payload_metric"] = m
+    soft = np.zeros(I["n_bits"], np.float64)
+    rc = ctx.lib.wm_payload_soft_tiles_u8(ctx._h, ptr(hp.view), ptr(I["order"]), ptr(I["offs"]), I["n_bits"], ptr(soft),
+                                          n, H, W, hp.rs, hp.ps, DELTA)
+    R["payload_soft"] = (np.int32(rc), soft)         # (no tile: both forms refuse, and with the same code)
     return R
 
 
@@ -296,6 +360,63 @@ def run_dev(ctx, I):
             d_i, d_e = d.put(img), d.new(img.nbytes)
             call("wm_enhance_extract_u8_dev", _vp(d_i), _vp(d_e), H, W, ch)
             R[f"enhance{ch}"] = d.get(d_e, img.shape, np.uint8)
+        # texture-masked strength
+        d_eff, d_g = d.new(n * nt * 32), d.new(n * nt * 4)
+        ctx.memset(d_eff, 0, n * nt * 32); ctx.memset(d_g, 0, n * nt * 4)
+        ctx.mask_sigma_w_tiles_u8_dev(d_host, d_sw, d_eff, d_g, n, H, W, hp.rs, hp.ps, I["sw_ps"], LO, HI)
+        ctx.check_status()
+        R["mask_sw"] = (d.get(d_eff, (n, nby, nbx, 8), np.float32), d.get(d_g, (n, nby, nbx), np.float32))
+        ctx.memset(d_g, 0, n * nt * 4)
+        ctx.mask_sigma_w_tiles_u8_dev(d_host, 0, 0, d_g, n, H, W, hp.rs, hp.ps, 0, LO, HI)
+        ctx.check_status()
+        R["mask_gain"] = d.get(d_g, (n, nby, nbx), np.float32)
+
+        def embed_pair(key, embed):
+            """embed(host, stego, sigma_c, yw): with yw into the caller's stego array, then in place without"""
+            d_st = d.put_planes(hp, I["stego_fill"].base)
+            ctx.memset(d_sc, 0, n * nt * 32); ctx.memset(d_yw, 0, n * H * W * 4)
+            embed(d_host, d_st, d_sc, d_yw)
+            ctx.check_status()
+            R[key + "_yw"] = (d.get_planes(d_st, hp, I["stego_fill"].base), d.get(d_sc, (n, nby, nbx, 8), np.float32),
+                              d.get(d_yw, (n, H, W), np.float32))
+            d_ip = d.put_planes(hp)
+            ctx.memset(d_sc, 0, n * nt * 32)
+            embed(d_ip, d_ip, d_sc, 0)
+            ctx.check_status()
+            R[key + "_inplace"] = (d.get_planes(d_ip, hp, hp.base), d.get(d_sc, (n, nby, nbx, 8), np.float32))
+
+        embed_pair("masked_embed", lambda h, s, c, y: ctx.embed_tiles_masked_u8_dev(
+            h, d_sw, s, c, y, n, H, W, hp.rs, hp.ps, I["sw_ps"], ALPHA, K, LO, HI))
+        call("wm_extract_tiles_masked_u8_dev", _vp(d_host), _vp(d_scin), _vp(d_u), _vp(d_v), _vp(d_out), n, H, W, hp.rs, hp.ps,
+             I["uv_ps"], ALPHA, K, LO, HI, MCUT)
+        ctx.check_status()
+        R["masked_extract"] = d.get(d_out, (n, H, W), np.float32)
+        tot = np.zeros((H, W), np.float32)
+        for z in range(n):
+            tot = tot + R["masked_extract"][z]
+        R["masked_extract_sum"] = tot
+        call("wm_detect_tiles_masked_u8_dev", _vp(d_host), _vp(d_scin), _vp(d_sw), _vp(d_scores), n, H, W, hp.rs, hp.ps,
+             I["sw_ps"], ALPHA, LO, HI, MCUT)
+        ctx.check_status()
+        R["masked_detect"] = d.get(d_scores, n, np.float64)
+        # blind payload
+        d_bit = d.put(I["tile_bit"])
+        ctx.memset(d_eff, 0, n * nt * 32)
+        call("wm_payload_sigma_w_tiles_u8_dev", _vp(d_host), _vp(d_bit), _vp(d_eff), n, H, W, hp.rs, hp.ps, DELTA)
+        ctx.check_status()
+        R["payload_sw"] = d.get(d_eff, (n, nby, nbx, 8), np.float32)
+        embed_pair("payload_embed", lambda h, s, c, y: call(
+            "wm_embed_tiles_payload_u8_dev", _vp(h), _vp(d_bit), _vp(s), _vp(c), _vp(y), n, H, W, hp.rs, hp.ps, DELTA))
+        ctx.memset(d_g, 0, n * nt * 4)
+        call("wm_payload_metric_tiles_u8_dev", _vp(d_host), _vp(d_g), n, H, W, hp.rs, hp.ps, DELTA)
+        ctx.check_status()
+        R["payload_metric"] = d.get(d_g, (n, nby, nbx), np.float32)
+        d_order, d_offs, d_soft = d.put(I["order"]), d.put(I["offs"]), d.new(I["n_bits"] * 8)
+        ctx.memset(d_soft, 0, I["n_bits"] * 8)
+        rc = ctx.lib.wm_payload_soft_tiles_u8_dev(ctx._h, _vp(d_host), _vp(d_order), _vp(d_offs), I["n_bits"], _vp(d_soft),
+                                                  n, H, W, hp.rs, hp.ps, DELTA)
+        ctx.check_status()
+        R["payload_soft"] = (np.int32(rc), d.get(d_soft, I["n_bits"], np.float64))
     finally:
         d.close()
     R.update(_unscrambled(ctx, I, fused=False))
@@ -328,13 +449,19 @@ def test_host_form_equals_dev_form(gpu_ctx, host_results, name):
     assert _differences(host_results[name], run_dev(gpu_ctx, I)) == []
     # what the caller owns around the planes comes back as it went in, the planes themselves are written
     hp, fill = I["host"], I["stego_fill"]
-    st = host_results[name]["embed_yw"][0]
-    assert np.array_equal(st[~hp.inside], fill.base[~hp.inside])
-    assert not np.array_equal(st[hp.inside], fill.base[hp.inside])
-    ip = host_results[name]["embed_inplace"][0]
-    assert np.array_equal(ip[~hp.inside], hp.base[~hp.inside])
-    if I["nt"] == 0:         # no tile: the border copy alone
-        assert np.array_equal(st[hp.inside], hp.base[hp.inside]) and np.array_equal(ip, hp.base)
+    for embed in ("embed", "masked_embed", "payload_embed"):
+        st = host_results[name][embed + "_yw"][0]
+        assert np.array_equal(st[~hp.inside], fill.base[~hp.inside]), embed
+        assert not np.array_equal(st[hp.inside], fill.base[hp.inside]), embed
+        ip = host_results[name][embed + "_inplace"][0]
+        assert np.array_equal(ip[~hp.inside], hp.base[~hp.inside]), embed
+        if I["nt"] == 0:         # no tile: the border copy alone
+            assert np.array_equal(st[hp.inside], hp.base[hp.inside]) and np.array_equal(ip, hp.base), embed
+    # payload_soft: answered where the case has a tile, refused (by both forms, with the compared code) where it has none
+    assert (int(host_results[name]["payload_soft"][0]) != 0) == (I["nt"] == 0)
+    if case is CUT:          # the black tile takes the payload embed's flat form: a constant tile, no longer black
+        t = host_results[name]["payload_embed_yw"][0][hp.inside].reshape(hp.view.shape)[0, 8:16, 8:16]
+        assert t.min() == t.max() and t.max() > 0
 
 
 def test_layouts_do_not_depend_on_the_buffers_history(hostapi, host_results):

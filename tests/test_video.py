@@ -263,3 +263,65 @@ def test_video_color_444(tmp_path, gpu_ctx, tile):
         v.embed_watermark_video_color(p420, wp, str(tmp_path / "o2.y4m"), str(tmp_path / "m2.npz"), password="pw")
     with pytest.raises(ValueError):
         v.detect_watermark_video(outp, meta)
+
+
+# ---- the one frame loop and the one marked-frame reader, driven by stubs (no device) ----
+# (frames, frame_interval, batch): every frame marked; every other one, with a batch that does not divide the three marked
+# frames; one batch for all; an interval larger than the clip; a clip without a frame
+FRAME_LOOP_CASES = [(5, 1, 2), (5, 2, 2), (5, 1, 8), (5, 7, 2), (0, 1, 2)]
+
+
+def _small_clip(tmp_path, n):
+    rng = np.random.default_rng(17)
+    ys = rng.integers(0, 256, (n, 16, 24), dtype=np.uint8)
+    chroma = rng.integers(0, 256, (n, 2 * 8 * 12), dtype=np.uint8)
+    v = importlib.import_module(PKG_NAME + ".video")
+    p = str(tmp_path / "clip.y4m")
+    v.write_y4m(p, ys, chroma)
+    return v, p, ys, chroma
+
+
+@pytest.mark.parametrize("n,interval,batch", FRAME_LOOP_CASES)
+def test_embed_frame_loop(tmp_path, n, interval, batch):
+    v, p, ys, chroma = _small_clip(tmp_path, n)
+    marked = list(range(0, n, interval))
+    calls = []
+
+    def stub(frames):                       # a marked frame's luma inverted, its chroma as it is
+        calls.append([y.copy() for y, _ in frames])
+        return [((255 - y).tobytes(), c.tobytes()) for y, c in frames]
+
+    outp = str(tmp_path / "out.y4m")
+    vid = v.Y4M(p)
+    with open(outp, "wb") as out:
+        out.write(vid.header_line)
+        assert v._embed_frame_loop(vid, out, interval, batch, stub) == n
+    vid.close()
+    # batches arrive in order, none empty, none larger than batch, and together they are the marked frames
+    assert all(1 <= len(c) <= batch for c in calls)
+    seen = [y for c in calls for y in c]
+    assert len(seen) == len(marked) and all(np.array_equal(y, ys[i]) for y, i in zip(seen, marked))
+    res = v.Y4M(outp); got = [(line, y.copy(), c.copy()) for line, y, c in res]; res.close()
+    assert res.header_line == vid.header_line and len(got) == n
+    for i, (line, y, c) in enumerate(got):
+        assert line == b"FRAME\n" and np.array_equal(c, chroma[i])
+        assert np.array_equal(y, 255 - ys[i] if i in marked else ys[i])
+    if interval == 1 and n:                 # no unmarked frame: the whole file is header + stub output
+        assert os.path.getsize(outp) == os.path.getsize(p)
+
+
+@pytest.mark.parametrize("n,interval,batch", FRAME_LOOP_CASES)
+def test_marked_batches(tmp_path, n, interval, batch):
+    v, p, ys, chroma = _small_clip(tmp_path, n)
+    marked = list(range(0, n, interval))
+    for limit in (None, 2, 0):
+        want = marked if limit is None else marked[:limit]
+        vid = v.Y4M(p)
+        batches = [[(y.copy(), c.copy()) for y, c in b] for b in v._marked_batches(vid, interval, batch, limit)]
+        vid.close()
+        assert all(1 <= len(b) <= batch for b in batches)
+        assert all(len(b) == batch for b in batches[:-1])
+        flat = [f for b in batches for f in b]
+        assert len(flat) == len(want)
+        for (y, c), i in zip(flat, want):
+            assert np.array_equal(y, ys[i]) and np.array_equal(c, chroma[i])

@@ -14,6 +14,12 @@ difference is that call's own.  The mode is deterministic, so any differing byte
 
     python tools/ab_libs.py --ref --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so
 
+Sigma passes of the tile mode (--sigma-pass): the BYTES of both builds' sigma_tiles, mask_sigma_w, payload_sigma_w,
+payload_metric, masked embed, payload embed and payload_soft on seeded planes (noise with a constant, a black and a rank-1
+tile) at an aligned and a misaligned base.  These kernels are deterministic too: any differing byte is a change of behaviour.
+
+    python tools/ab_libs.py --sigma-pass --a /path/to/parent/libwmhip.so --b <package>/csrc/libwmhip.so
+
 Development aid; bench.py is the contract benchmark."""
 import argparse
 import ctypes as C
@@ -146,9 +152,78 @@ def ref_bits(path_a, path_b, alpha=0.15):
     return 1 if n_diff else 0
 
 
+def sigma_pass_bits(path_a, path_b, alpha=0.15, mask=(8.0, 64.0), delta=16.0):
+    """Tile mode, everything that runs a sigma pass: the BYTES of both builds' sigma_tiles, mask_sigma_w (eff + gain),
+    payload_sigma_w, payload_metric, masked embed, payload embed (stego with the caller's bytes around it, Sc, yw) and
+    payload_soft, on 3 planes of 72 x 136 (153 tiles: the third wave is partial) of noise with a constant, a black and a
+    rank-1 tile, cut out of a larger array at an aligned and at a misaligned base."""
+    ctx = {"a": LibContext(api.load_library(path_a)), "b": LibContext(api.load_library(path_b))}
+    n, H, W = 3, 72, 136
+    nt = (H // 8) * (W // 8)
+    rng = np.random.default_rng(31)
+    sw = np.sort(np.abs(rng.normal(0, 300, (nt, 8))).astype(np.float32), axis=-1)[:, ::-1].copy()
+    tile_bit = rng.integers(0, 2, nt).astype(np.uint8)
+    bit_of = rng.permutation(nt) % 16
+    order = np.argsort(bit_of, kind="stable").astype(np.int32)
+    offs = np.concatenate(([0], np.cumsum(np.bincount(bit_of, minlength=16)))).astype(np.int32)
+    n_diff = n_cmp = 0
+    for name, rs, (y0, x0) in (("aligned", 144, (0, 0)), ("misaligned", 139, (1, 3))):
+        base = rng.integers(0, 256, (n, H + 2, rs), dtype=np.uint8)
+        view = base[:, y0:y0 + H, x0:x0 + W]
+        view[0, 8:16, 16:24] = 77
+        view[1, 16:24, 8:16] = 0
+        view[2, 24:32, 40:48] = np.outer(np.arange(1, 9), np.arange(3, 11)).astype(np.uint8)
+        off, ps = y0 * rs + x0, (H + 2) * rs
+        plane = (n, H, W, rs, ps)
+        got = {}
+        for k, c in ctx.items():
+            d = {q: c.malloc(b) for q, b in dict(p=base.nbytes, st=base.nbytes, s=n * nt * 32, eff=n * nt * 32, g=n * nt * 4, sc=n * nt * 32,
+                                                 yw=n * H * W * 4, sw=sw.nbytes, bit=nt, order=order.nbytes, offs=offs.nbytes, soft=128).items()}
+            for q, arr in (("p", base), ("sw", sw), ("bit", tile_bit), ("order", order), ("offs", offs)):
+                c.h2d(d[q], arr)
+            R = got[k] = {}
+
+            def get(q, shape, dtype):
+                out = np.empty(shape, dtype); c.sync(); c.d2h(out, d[q]); c.sync()
+                return out
+
+            c.sigma_tiles_u8_dev(d["p"] + off, d["s"], *plane)
+            R["sigma_tiles"] = get("s", (n, nt, 8), np.float32)
+            c.mask_sigma_w_tiles_u8_dev(d["p"] + off, d["sw"], d["eff"], d["g"], *plane, 0, *mask)
+            R["mask_sigma_w"] = get("eff", (n, nt, 8), np.float32); R["mask_gain"] = get("g", (n, nt), np.float32)
+            c._call("wm_payload_sigma_w_tiles_u8_dev", d["p"] + off, d["bit"], d["eff"], *plane, delta)
+            R["payload_sigma_w"] = get("eff", (n, nt, 8), np.float32)
+            c._call("wm_payload_metric_tiles_u8_dev", d["p"] + off, d["g"], *plane, delta)
+            R["payload_metric"] = get("g", (n, nt), np.float32)
+            for what, embed in (("masked_embed", lambda: c.embed_tiles_masked_u8_dev(d["p"] + off, d["sw"], d["st"] + off, d["sc"], d["yw"], *plane,
+                                                                                      0, alpha, 6, *mask)),
+                                ("payload_embed", lambda: c._call("wm_embed_tiles_payload_u8_dev", d["p"] + off, d["bit"], d["st"] + off, d["sc"],
+                                                                  d["yw"], *plane, delta))):
+                c.memset(d["st"], 0xA5, base.nbytes); c.memset(d["sc"], 0, n * nt * 32); c.memset(d["yw"], 0, n * H * W * 4)
+                embed()
+                R[what + "_stego"], R[what + "_Sc"] = get("st", base.shape, np.uint8), get("sc", (n, nt, 8), np.float32)
+                R[what + "_yw"] = get("yw", (n, H, W), np.float32)
+            c._call("wm_payload_soft_tiles_u8_dev", d["st"] + off, d["order"], d["offs"], 16, d["soft"], *plane, delta)   # (of the payload stego)
+            R["payload_soft"] = get("soft", 16, np.float64)
+            c.check_status()
+            for q in d.values():
+                c.free(q)
+        diff = [q for q in got["a"] if got["a"][q].tobytes() != got["b"][q].tobytes()]
+        n_cmp += len(got["a"]); n_diff += len(diff)
+        st = got["a"]["payload_embed_stego"][:, y0:y0 + H, x0:x0 + W]
+        print(f"{name:10s} base offset {off}, row stride {rs}: " + ("all %d results equal bytes" % len(got["a"]) if not diff else
+              "DIFFERENT: " + ", ".join(diff)) + f"  (payload stego: black tile -> {int(st[1, 16, 8])}, soft[:4] "
+              f"{np.round(got['a']['payload_soft'][:4], 3).tolist()})", flush=True)
+    print(f"{n_cmp} results compared, {n_diff} differ")
+    for c in ctx.values():
+        c.close()
+    return 1 if n_diff else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", action="store_true", help="full-frame mode: compare the bytes of both builds' results")
+    ap.add_argument("--sigma-pass", action="store_true", help="tile mode: compare the bytes of everything that runs a sigma pass")
     ap.add_argument("--a", required=True, help="libwmhip.so of the baseline")
     ap.add_argument("--b", required=True, help="libwmhip.so of the variant")
     ap.add_argument("--frames", type=int, default=32)
@@ -162,6 +237,8 @@ def main():
     a = ap.parse_args()
     if a.ref:
         sys.exit(ref_bits(a.a, a.b, a.alpha))
+    if a.sigma_pass:
+        sys.exit(sigma_pass_bits(a.a, a.b, a.alpha))
     rng = np.random.default_rng(1234)
     host = np.ascontiguousarray(make_frames(a.content, a.frames, a.H, a.W, rng))
     wys = rng.integers(0, 256, (a.H, a.W)).astype(np.float32)

@@ -9,7 +9,9 @@ context's stream, after warm-up rounds that are left out:
 
 The expectation to confirm or correct: embed_masked = embed_uniform + mask_sigma_w.  With --parent-lib the unmasked
 variants of ANOTHER build of libwmhip.so (the parent commit's) run in the same rounds, so a difference beyond the
-round-to-round spread on embed_uniform / extract_plain / detect_plain would mean the change is not free for them.
+round-to-round spread on embed_uniform / extract_plain / detect_plain would mean the change is not free for them.  A
+parent that has the gain pass also runs its sigma_tiles and mask_sigma_w there, and --sigma-pass-out records this build's
+against the parent's own round-to-round spread (sigma_pass_record).
 
 Also records the parity figures of the masked embed against the oracle on the test hosts (tests/mask_refs.py: what
 tests/test_gpu_mask.py holds to its bars), uniform and masked.
@@ -57,6 +59,24 @@ class LibContext(api.Context):
         self.device = 0
 
 
+def sigma_pass_record(path, entries):
+    """entries: name -> (this build's round values, the parent's, both in us, same interleaved rounds).  Adds to the JSON at
+    ``path``, per name, both medians and whether this build's lies within the parent's OWN round-to-round spread
+    (max - min) above the parent's median - the bar a refactor of the sigma passes is held to - and prints it."""
+    rec = json.load(open(path)) if os.path.exists(path) else {}
+    for name, (new, par) in entries.items():
+        spread, diff = float(np.ptp(par)), float(np.median(new) - np.median(par))
+        rec[name] = dict(unit="us per launch", rounds=len(new), new_median=float(np.median(new)), new_min=float(np.min(new)),
+                         new_max=float(np.max(new)), parent_median=float(np.median(par)), parent_min=float(np.min(par)),
+                         parent_max=float(np.max(par)), parent_spread=spread, new_minus_parent=diff,
+                         within_parent_spread=bool(diff <= spread))
+        print(f"sigma pass {name:38s} new {np.median(new):9.1f} us  parent {np.median(par):9.1f} us  ({diff:+.1f} us; parent's "
+              f"round-to-round spread {spread:.1f} us: {'within' if diff <= spread else 'SLOWER THAN THE SPREAD ALLOWS'})", flush=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def make_frames(content, F, H, W, rng):
     if content == "noise":
         return rng.integers(0, 256, (F, H, W), dtype=np.uint8)
@@ -83,12 +103,16 @@ class Side:
         self.d_sc = ctx.malloc(F * nt * 32)
         self.d_out = ctx.malloc(F * H * W * 4)
         self.d_scores = ctx.malloc(F * 8)
-        self.d_eff = ctx.malloc(F * nt * 32) if masked else 0
+        gain_pass = masked or hasattr(ctx.lib, "wm_mask_sigma_w_tiles_u8_dev")       # (a parent build that has the pass)
+        self.d_eff = ctx.malloc(F * nt * 32) if gain_pass else 0
         ctx.svd_tiles_f32_dev(d_wys, self.d_U, self.d_S, self.d_V, 1, H, W, W, H * W)
         ctx.tile_factors_to_pixel_dev(self.d_U, self.d_V, self.d_U, self.d_V, nt)
         self.plane = (F, H, W, W, H * W)
         self.variants = {"embed_uniform": self.embed_uniform, "extract_plain": self.extract_plain, "detect_plain": self.detect_plain}
+        if gain_pass and not masked:
+            self.variants.update(sigma_tiles=self.sigma_tiles, mask_sigma_w=self.mask_sigma_w)
         if masked:
+            self.variants.update(sigma_tiles=self.sigma_tiles)
             self.variants.update(embed_masked=self.embed_masked, mask_sigma_w=self.mask_sigma_w,
                                  extract_masked=self.extract_masked, detect_masked=self.detect_masked,
                                  extract_plain_on_masked_stego=self.extract_plain_m, detect_plain_on_masked_stego=self.detect_plain_m)
@@ -105,6 +129,9 @@ class Side:
     def embed_masked(self):
         self.ctx.embed_tiles_masked_u8_dev(self.d_host, self.d_S, self.d_stego_m, self.d_sc_m, None, *self.plane, 0, self.alpha, 8,
                                            *MASK[:2])
+
+    def sigma_tiles(self):          # (into d_eff: [plane][tile][8] as well)
+        self.ctx.sigma_tiles_u8_dev(self.d_host, self.d_eff, *self.plane)
 
     def mask_sigma_w(self):
         self.ctx.mask_sigma_w_tiles_u8_dev(self.d_host, self.d_S, self.d_eff, None, *self.plane, 0, *MASK[:2])
@@ -175,6 +202,9 @@ def bench_size(name, a, ctxs):
                           masked_detect_over_plain_same_stego=m["detect_masked"] / m["detect_plain_on_masked_stego"])
     if "parent" in ctxs:
         out["derived"].update({f"{v}_new_over_parent": m[v] / m[f"parent.{v}"] for v in ("embed_uniform", "extract_plain", "detect_plain")})
+        if a.sigma_pass_out:
+            sigma_pass_record(a.sigma_pass_out, {f"mask_bench.{v}_{name}": (t["new", v], t["parent", v]) for v in ("sigma_tiles", "mask_sigma_w")
+                                                 if ("parent", v) in t})
     print(name, json.dumps(out["derived"]), flush=True)
     return out
 
@@ -195,6 +225,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", help="libwmhip.so of the parent commit: its unmasked variants run in the same rounds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mask_bench.json"))
+    ap.add_argument("--sigma-pass-out", help="with --parent-lib: add sigma_tiles / mask_sigma_w of both builds to this JSON (sigma_pass_record)")
     ap.add_argument("--sizes", default="1080p,4k")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=7)

@@ -6,7 +6,9 @@ after warm-up rounds that are left out:
     sigma_tiles (K2, the yardstick)   payload_metric (K2 + m, 4 bytes a tile)   payload_soft (metric + per-bit sums)
     embed_masked (the yardstick)      payload_sigma_w (K2 + target)            embed_payload
 
-With --parent-lib the two yardsticks run from ANOTHER build of libwmhip.so (the parent commit's) in the same rounds.
+With --parent-lib the two yardsticks run from ANOTHER build of libwmhip.so (the parent commit's) in the same rounds, and
+so do its payload_sigma_w and payload_metric; --sigma-pass-out then records each sigma pass of this build against the
+parent's own round-to-round spread.
 The expectations to confirm or correct: payload_metric <= sigma_tiles, payload_soft - payload_metric = a few us,
 embed_payload = embed_masked.  payload_soft is timed at n_bits = 16 (each wave sums n_planes * n_tiles / 16 values: the
 reduce at its least parallel), at 1024 and at n_tiles.
@@ -28,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from mask_bench import LibContext, api, load_build, make_frames   # noqa: E402
+from mask_bench import LibContext, api, load_build, make_frames, sigma_pass_record   # noqa: E402
 
 SIZES = {"1080p": (1080, 1920), "4k": (2160, 3840)}
 MASK = (8.0, 64.0)
@@ -43,11 +45,25 @@ def csr(n_tiles, n_bits, rng):
 
 
 def time_variants(ctxs, variants, warmup, rounds):
-    """variants: name -> (ctx key, callable).  Returns name -> list of ms, one per round, interleaved."""
+    """variants: name -> (ctx key, callable).  Returns name -> list of ms, one per round, interleaved.
+    Two builds are two contexts with a stream each, and launches on two streams overlap on the device: with a parent build
+    every variant starts on an idle device (both contexts synchronised first), so that no variant is timed against whatever
+    the other build happens to run beside it, and a variant and its `_parent` twin, which stand next to each other, swap
+    places every other round, so that neither always follows the same neighbour."""
     out = {k: [] for k in variants}
+    two_streams = ctxs["parent"] is not ctxs["this"]
+    names = list(variants)
     for r in range(warmup + rounds):
-        for slot, (name, (ck, fn)) in enumerate(variants.items()):
+        order = list(range(len(names)))
+        if r % 2:
+            for i in range(len(names) - 1):
+                if names[i] + "_parent" == names[i + 1] or names[i] == names[i + 1] + "_parent":
+                    order[i], order[i + 1] = order[i + 1], order[i]
+        for slot in order:
+            ck, fn = variants[names[slot]]
             c = ctxs[ck]
+            if two_streams:
+                ctxs["this"].sync(); ctxs["parent"].sync()
             c.event_record(2 * slot); fn(); c.event_record(2 * slot + 1)
         for slot, (name, (ck, fn)) in enumerate(variants.items()):
             ms = ctxs[ck].event_elapsed_ms(2 * slot, 2 * slot + 1)
@@ -61,7 +77,7 @@ def summary(ms):
     return dict(median_ms=float(np.median(a)), min_ms=float(a[0]), max_ms=float(a[-1]), rounds=len(a))
 
 
-def bench_size(ctx, parent, label, F, warmup, rounds, content):
+def bench_size(ctx, parent, label, F, warmup, rounds, content, sigma_pass_out=None):
     H, W = SIZES[label]
     rng = np.random.default_rng(17)
     nt = (H // 8) * (W // 8)
@@ -78,8 +94,12 @@ def bench_size(ctx, parent, label, F, warmup, rounds, content):
         c.h2d(b["sw"], rng.uniform(0, 2000, (nt, 8)).astype(np.float32))
         bufs[k] = b
     t = bufs["this"]
-    t["metric"] = ctx.malloc(F * nt * 4); t["eff"] = ctx.malloc(F * nt * 32); t["bit"] = ctx.malloc(nt)
-    ctx.h2d(t["bit"], rng.integers(0, 2, nt).astype(np.uint8))
+    tile_bit = rng.integers(0, 2, nt).astype(np.uint8)
+    for k, c in ctxs.items():
+        if k == "this" or parent is not None:
+            b = bufs[k]
+            b["metric"] = c.malloc(F * nt * 4); b["eff"] = c.malloc(F * nt * 32); b["bit"] = c.malloc(nt)
+            c.h2d(b["bit"], tile_bit)
     maps = {}
     for nb in (16, 1024, nt):
         _, order, offs = csr(nt, nb, rng)
@@ -100,9 +120,11 @@ def bench_size(ctx, parent, label, F, warmup, rounds, content):
         "sigma_tiles_parent": ("parent", lambda: pc.sigma_tiles_u8_dev(p["pstego"], p["sigma"], *plane)),
         "sigma_tiles": ("this", lambda: ctx.sigma_tiles_u8_dev(t["stego"], t["sigma"], *plane)),
         "payload_metric": ("this", lambda: ctx._call("wm_payload_metric_tiles_u8_dev", t["stego"], t["metric"], *plane, DELTA)),
+        "payload_metric_parent": ("parent", lambda: pc._call("wm_payload_metric_tiles_u8_dev", p["pstego"], p["metric"], *plane, DELTA)),
         "embed_masked_parent": ("parent", lambda: pc.embed_tiles_masked_u8_dev(p["host"], p["sw"], p["stego"], p["sc"], None, *plane, 0, 0.12, 8, *MASK)),
         "embed_masked": ("this", lambda: ctx.embed_tiles_masked_u8_dev(t["host"], t["sw"], t["stego"], t["sc"], None, *plane, 0, 0.12, 8, *MASK)),
         "payload_sigma_w": ("this", lambda: ctx._call("wm_payload_sigma_w_tiles_u8_dev", t["host"], t["bit"], t["eff"], *plane, DELTA)),
+        "payload_sigma_w_parent": ("parent", lambda: pc._call("wm_payload_sigma_w_tiles_u8_dev", p["host"], p["bit"], p["eff"], *plane, DELTA)),
         "embed_payload": ("this", lambda: ctx._call("wm_embed_tiles_payload_u8_dev", t["host"], t["bit"], t["stego"], t["sc"], None, *plane, DELTA)),
     }
     for nb, (d_o, d_f, d_s) in maps.items():
@@ -112,6 +134,9 @@ def bench_size(ctx, parent, label, F, warmup, rounds, content):
     ms = time_variants(ctxs, variants, warmup, rounds)
     ctx.sync(); ctx.check_status(); pc.sync(); pc.check_status()
     res = {k: summary(v) for k, v in ms.items()}
+    if parent is not None and sigma_pass_out:
+        sigma_pass_record(sigma_pass_out, {f"payload_bench.{v}_{label}": (1e3 * np.asarray(ms[v]), 1e3 * np.asarray(ms[v + "_parent"]))
+                                           for v in ("sigma_tiles", "payload_sigma_w", "payload_metric")})
     for k, c in ctxs.items():
         if k == "parent" and parent is None:
             continue
@@ -151,6 +176,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "payload_bench.json"))
+    ap.add_argument("--sigma-pass-out", help="with --parent-lib: add sigma_tiles / payload_sigma_w / payload_metric of both builds "
+                    "to this JSON (mask_bench.sigma_pass_record)")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=12)
@@ -161,7 +188,7 @@ def main():
     parent = LibContext(load_build(a.parent_lib)) if a.parent_lib else None
     res = dict(parent_lib=bool(a.parent_lib), delta=DELTA, sizes={}, figures=device_figures(ctx))
     for label in a.sizes.split(","):
-        res["sizes"][label] = bench_size(ctx, parent, label, a.frames, a.warmup, a.rounds, a.content)
+        res["sizes"][label] = bench_size(ctx, parent, label, a.frames, a.warmup, a.rounds, a.content, a.sigma_pass_out)
         v = res["sizes"][label]["variants"]
         print(label, {k: round(x["median_ms"], 3) for k, x in v.items()}, flush=True)
     with open(a.out, "w") as f:
