@@ -393,6 +393,64 @@ WM_HD void jacobi_rot_pk(v2f (&a)[4][8], float (&n2)[8], const int p, const int 
   }
 }
 
+// jacobi_rot_pk<0> on SCALED columns a_c = sqrt(w2[c]) at_c, for the untested sweeps: `a` holds at_c, w2 the squared
+// scales (rotation_scaled() of tools/gen_jacobi_asm.py, same operations).  wave_swaps: some tile of the wave wants the
+// de Rijk swap at this pair (tau > 0).  Where none does, the update is two FMAs per element and no product:
+//   at_p += t_p at_q ; at_q -= t_q at_p'     t_p = (gt / h) w_q / c^2,  t_q = (gt / h) w_p,  w_p *= c^2,  w_q /= c^2
+// (a_p' = c (a_p + t a_q), a_q' = a_q / c - t a_p'; gt = at_p . at_q, g^2 = gt^2 w_p w_q); c^2 and 1 / c^2 come out of
+// the angle's two rsq.  Where one does, the wave takes jacobi_rot_pk's four-product update with the scale ratios folded
+// into its coefficients; the scales stay.  n2 are the TRUE squared norms throughout.
+// c^2 is in [0.5, 1] and a column meets 7 rotations in each of at most 3 such sweeps: 2^-21 <= w2 <= 2^21, no rescaling.
+WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], const int p, const int q, const bool wave_swaps) {
+  v2f gv = a[0][p] * a[0][q];
+#pragma unroll
+  for (int rp = 1; rp < 4; ++rp) gv = fma2(a[rp][p], a[rp][q], gv);
+  const float gt = gv[0] + gv[1];
+  const float al = n2[p], be = n2[q];
+  const float gg = (gt * (w2[p] * w2[q])) * gt;  // g^2
+  const float tau = be - al;
+  const float ta = fabsf(tau) + 1e-18f;
+  const float ih = frsq(ffma(gg, 4.0f, ta * ta));  // 1/h
+  const float x = ffma(0.5f * ta, ih, 0.5f);       // cos^2 in [0.5, 1]
+  const float rx = frsq(x);
+  const float u = gt * ih;
+  const float gh = gg * ih;
+  float w;                                         // |t g|
+  if (!wave_swaps) {
+    const float rx2 = rx * rx;                     // 1 / cos^2
+    const float tq = u * w2[p];
+    const float v = u * rx2;
+    w = gh * rx2;
+    w2[p] *= x;
+    const float tp = v * w2[q];
+    w2[q] *= rx2;
+    const v2f Tp = splat2(tp), Tq = splat2(-tq);
+#pragma unroll
+    for (int rp = 0; rp < 4; ++rp) {
+      a[rp][p] = fma2(Tp, a[rp][q], a[rp][p]);
+      a[rp][q] = fma2(Tq, a[rp][p], a[rp][q]);
+    }
+  } else {
+    const float pq = w2[p] * w2[q];
+    const float c0 = x * rx;
+    const float r = frsq(pq);                      // 1 / (d_p d_q)
+    w = (gh * rx) * rx;
+    const float s0 = (u * rx) * (pq * r);          // sin * sign(g)
+    const float rq = w2[q] * r, rp_ = w2[p] * r;   // d_q / d_p, d_p / d_q
+    const bool sw = tau > 0.0f;                    // de Rijk: larger column ends in p
+    const float Sn = sw ? c0 : s0, C = sw ? s0 : c0;
+    const v2f Cv = splat2(C), Sp = splat2(Sn * rq), Sq = splat2(Sn * rp_);
+#pragma unroll
+    for (int rp = 0; rp < 4; ++rp) {
+      const v2f X = a[rp][p], Y = a[rp][q];
+      a[rp][p] = fma2(Cv, X, Sp * Y);
+      a[rp][q] = fma2(Cv, Y, -(Sq * X));
+    }
+  }
+  n2[p] = fmaxf(al, be) + w;
+  n2[q] = fminf(al, be) - w;
+}
+
 WM_HD void col_norms2_pk(const v2f (&a)[4][8], float (&n2)[8]) {
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
@@ -411,6 +469,27 @@ WM_HD void jacobi_sweep_pk(v2f (&a)[4][8], float (&n2)[8], bool& notconv) {
   for (int p = 0; p < 7; ++p)
 #pragma unroll
     for (int q = p + 1; q < 8; ++q) jacobi_rot_pk<CHECK, SKIP>(a, n2, p, q, notconv);
+}
+// an untested sweep of jacobi_cols_pk: scaled columns, the swap decided per pair for the whole wave
+WM_HD void jacobi_sweep_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8]) {
+#pragma unroll
+  for (int p = 0; p < 7; ++p)
+#pragma unroll
+    for (int q = p + 1; q < 8; ++q) jacobi_rot_scaled_pk(a, n2, w2, p, q, wave_any(n2[q] - n2[p] > 0.0f));
+}
+// n2 of the scaled columns made true, and the scales folded back into B
+WM_HD void col_norms2_scaled_pk(const v2f (&a)[4][8], const float (&w2)[8], float (&n2)[8]) {
+  col_norms2_pk(a, n2);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) n2[c] *= w2[c];
+}
+WM_HD void fold_scales_pk(v2f (&a)[4][8], const float (&w2)[8]) {
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const v2f d = splat2(w2[c] * frsq(w2[c]));
+#pragma unroll
+    for (int rp = 0; rp < 4; ++rp) a[rp][c] = d * a[rp][c];
+  }
 }
 
 // ---- LQ prelude: B0 = X Q ahead of the sweeps ----------------------------------------------------------------------
@@ -479,20 +558,24 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
   // The sweeps run on B0 = X Q (LQ prelude above).  Sweeps 1 and 2 carry no convergence test (a sweep can only be the
   // last one if it tested every pair, so these two are never last).  Column norms are recomputed before odd sweeps and
   // tracked through the even ones.
+  // The untested sweeps work on scaled columns (jacobi_rot_scaled_pk): a holds a_c / sqrt(w2[c]) until the scales are
+  // folded back behind the last of them; n2 are the true squared norms throughout.
   lq_prelude_pk(a);
   bool notconv = false;
+  float w2[8] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
   col_norms2_pk(a, n2);
-  jacobi_sweep_pk<0>(a, n2, notconv);
-  jacobi_sweep_pk<0>(a, n2, notconv);
+  jacobi_sweep_scaled_pk(a, n2, w2);
+  jacobi_sweep_scaled_pk(a, n2, w2);
   int sweep = 2;
   // The embed's third sweep carries no test either: behind the prelude no image or noise tile is done after three
   // sweeps at cos^2 <= 1e-7 (tools/skip_study.cpp), so the earliest last sweep is the 4th - and that one already tests
   // every pair before rotating it (JAC_SKIP2), as every later one does.
   if (!SIGMA_ONLY) {
-    col_norms2_pk(a, n2);
-    jacobi_sweep_pk<0>(a, n2, notconv);
+    col_norms2_scaled_pk(a, w2, n2);
+    jacobi_sweep_scaled_pk(a, n2, w2);
     sweep = 3;
   }
+  fold_scales_pk(a, w2);
   bool more = true;
   while (more && sweep < JAC_MAX_SWEEPS) {
     if ((sweep & 1) == 0) col_norms2_pk(a, n2);

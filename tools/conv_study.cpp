@@ -3,6 +3,10 @@
 // (64 consecutive tiles sweep in lock-step until none of them saw cos^2 > T).
 //   g++ -O2 -o tools/bin/conv_study tools/conv_study.cpp && tools/bin/conv_study [3 [move2 [waves [seed]]]]
 // (argument 3: the sweeps run behind the LQ prelude, lq_prelude_pk - what the kernels do since round 5;
+//  argument 4: behind the prelude, the untested sweeps (three at T = 1e-7, the embed's rule; two otherwise) rotate scaled
+//  columns (jacobi_rot_scaled_pk), the swap branch taken by a whole wave at a pair where any of its 64 tiles has tau > 0,
+//  and the scales are folded back behind them - what the kernels do since round 6; also reported: the share of a
+//  sweep's 28 pairs at which the wave wants that branch, and the range of the squared scales;
 //  move2 > 0: a sweep is the last one only if, besides cos^2 <= T, no rotation of it moved the squared norms by w with
 //  w^2 > move2 n2[0] max(n2[p], n2[q]) - the second stopping test of jacobi_rot_pk, JAC_MOVE2)
 #include <math.h>
@@ -29,6 +33,20 @@ static void rot(v2f (&a)[4][8], float (&n2)[8], int p, int q, float& maxc2, floa
   jacobi_rot_pk<0>(a, n2, p, q, dummy);
 }
 
+// the same around jacobi_rot_scaled_pk
+static void rot_scaled(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], int p, int q, float& maxc2, float& maxmv, bool wave_swaps) {
+  v2f gv = a[0][p] * a[0][q];
+  for (int rp = 1; rp < 4; ++rp) gv = fma2(a[rp][p], a[rp][q], gv);
+  const float gt = gv[0] + gv[1], gg = (gt * (w2[p] * w2[q])) * gt;
+  const float al = n2[p], be = n2[q];
+  const float c2 = gg / fmaxf(al * be, 1e-30f);
+  if (c2 > maxc2) maxc2 = c2;
+  const float ta = fabsf(be - al) + 1e-18f, ih = frsq(ffma(gg, 4.0f, ta * ta)), rx = frsq(ffma(0.5f * ta, ih, 0.5f));
+  const float w = ((gg * ih) * rx) * rx, mv = w * w / fmaxf(fmaxf(al, be) * n2[0], 1e-30f);
+  if (mv > maxmv) maxmv = mv;
+  jacobi_rot_scaled_pk(a, n2, w2, p, q, wave_swaps);
+}
+
 static void svd_f64(const double (&x)[8][8], double (&s)[8]) {
   double a[8][8];
   for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) a[r][c] = x[r][c];
@@ -49,6 +67,7 @@ static void svd_f64(const double (&x)[8][8], double (&s)[8]) {
 int main(int argc, char** argv) {
   const float MOVE2 = argc > 2 ? (float)atof(argv[2]) : 0.0f;
   const int NW = argc > 3 ? atoi(argv[3]) : 400;   // waves of 64 tiles
+  const int MODE = argc > 1 ? atoi(argv[1]) : 0;
   // quantised: a smooth tile after a JPEG-like round trip (8x8 DCT, luminance table at quality 50, rounded back to 8 bits);
   // posterised: the natural tile at 16 grey levels.  Both are rich in repeated rows, rank-deficient tiles and
   // near-degenerate pairs - what compressed or banded content feeds the kernels.
@@ -90,16 +109,18 @@ int main(int argc, char** argv) {
     for (float T : thr) {
       double sum_sweeps = 0, max_err = 0, sum_err = 0, max_cos = 0, sum_tile_sweeps = 0; long nerr = 0, above = 0;
       int hist[16] = {0};
+      long swap_pairs[12] = {0}, sweeps_run[12] = {0}; float w2min = 1.0f, w2max = 1.0f;
       for (int w = 0; w < NW; ++w) {
-        static v2f a[64][4][8]; static float n2[64][8];
+        static v2f a[64][4][8]; static float n2[64][8]; static float w2[64][8];
         int tile_done[64];
         for (int l = 0; l < 64; ++l) {
           for (int rp = 0; rp < 4; ++rp) for (int c = 0; c < 8; ++c) {
             v2f v = {(float)px[((size_t)w * 64 + l) * 64 + (2 * rp) * 8 + c], (float)px[((size_t)w * 64 + l) * 64 + (2 * rp + 1) * 8 + c]};
             a[l][rp][c] = v;
           }
-          if (argc > 1 && atoi(argv[1]) == 3) lq_prelude_pk(a[l]);   // B0 = X Q: row-pivoted Householder LQ from the right
+          if (MODE == 3 || MODE == 4) lq_prelude_pk(a[l]);   // B0 = X Q: row-pivoted Householder LQ from the right
           col_norms2_pk(a[l], n2[l]); tile_done[l] = 0;
+          for (int c = 0; c < 8; ++c) w2[l][c] = 1.0f;
           if (argc > 1 && atoi(argv[1]) == 1) {      // experiment: columns sorted by norm (descending) before the first sweep
             int ord[8]; for (int c = 0; c < 8; ++c) ord[c] = c;
             std::sort(ord, ord + 8, [&](int u, int v) { return n2[l][u] > n2[l][v]; });
@@ -119,10 +140,30 @@ int main(int argc, char** argv) {
         int sweep = 0; bool more = true;
         while (more && sweep < 12) {
           more = false;
+          float ms[64], mvs[64];
+          const bool scaled = MODE == 4 && sweep < (T <= 1e-7f ? 3 : 2);
           for (int l = 0; l < 64; ++l) {
-            if (sweep >= 2 && (sweep & 1) == 0) col_norms2_pk(a[l], n2[l]);
-            float m = 0, mv = 0;
-            for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) rot(a[l], n2[l], p, q, m, mv);
+            if (MODE == 4 && !scaled) {              // (the first time: the scales go back into B; afterwards w2 == 1)
+              for (int c = 0; c < 8; ++c) { w2min = fminf(w2min, w2[l][c]); w2max = fmaxf(w2max, w2[l][c]); }
+              fold_scales_pk(a[l], w2[l]);
+              for (int c = 0; c < 8; ++c) w2[l][c] = 1.0f;
+            }
+            if (sweep >= 2 && (sweep & 1) == 0) col_norms2_scaled_pk(a[l], w2[l], n2[l]);   // (w2 == 1 unless MODE 4)
+            ms[l] = mvs[l] = 0;
+            if (!scaled)
+              for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) rot(a[l], n2[l], p, q, ms[l], mvs[l]);
+          }
+          if (MODE == 4) {                           // pair by pair across the wave: the swap branch is the wave's
+            ++sweeps_run[sweep];
+            for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) {
+              bool any = false;
+              for (int l = 0; l < 64; ++l) any = any || (n2[l][q] - n2[l][p] > 0.0f);
+              swap_pairs[sweep] += any;
+              if (scaled) for (int l = 0; l < 64; ++l) rot_scaled(a[l], n2[l], w2[l], p, q, ms[l], mvs[l], any);
+            }
+          }
+          for (int l = 0; l < 64; ++l) {
+            const float m = ms[l], mv = mvs[l];
             bool bad = m > T || (MOVE2 > 0 && mv > MOVE2);
             if (sweep + 1 >= JAC_DEFI_FROM && !(n2[l][7] > SIGMA_RATIO_MIN2 * n2[l][0])) bad = false;   // the rank-deficient exit of jacobi_cols_pk
             if (sweep >= 2 && bad) more = true;
@@ -149,6 +190,11 @@ int main(int argc, char** argv) {
       printf("%-8s T=%.0e  wave sweeps avg %.3f [3:%d 4:%d 5:%d 6:%d 7+:%d]  per-tile avg %.3f  sigma err/s1 max %.2e mean %.2e above 2e-6: %ld  final max cos %.2e\n",
              kinds[kind], T, sum_sweeps / NW, hist[3], hist[4], hist[5], hist[6], hist[7] + hist[8] + hist[9] + hist[10] + hist[11] + hist[12],
              sum_tile_sweeps / (NW * 64.0), max_err, sum_err / nerr, above, max_cos);
+      if (MODE == 4) {
+        printf("%-8s T=%.0e  pairs of 28 in the swap branch, sweep 1..6:", kinds[kind], T);
+        for (int k = 0; k < 6; ++k) printf(" %.2f", sweeps_run[k] ? (double)swap_pairs[k] / sweeps_run[k] : 0.0);
+        printf("  squared scales in [%.2e, %.2e]\n", w2min, w2max);
+      }
     }
   }
   return 0;

@@ -15,10 +15,12 @@ import gen_jacobi_asm as G
 F = np.float32
 
 
-def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128, stats=None, stop_at=None):
+def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, stats=None, stop_at=None, scales=None):
     """Runs the stream on n lanes; returns (vector registers [n_vregs, n], more mask, sweeps).  stats (a dict) receives
-    the executed VALU instructions of the wave: "pk" (v_pk_*), "trans" (v_rsq) and "valu" (the rest).  stop_at: a label
-    at which the run ends (the registers as they are there)."""
+    the executed VALU instructions of the wave: "pk" (v_pk_*, also under their mnemonics), "trans" (v_rsq) and "valu"
+    (the rest), and per 0-based sweep k the rotations carried out ("rot", k), those of them that took the wave's swap
+    branch ("swap", k) and the number of lanes that wanted the swap at each ("swap_lanes", k: a list).  stop_at: a label at which the run ends (the registers as they are there).  scales (a list)
+    receives the V-free stream's squared column scales [n, 8] as they are behind the last sweep."""
     v = np.zeros((n_vregs, n), F)
     if v_init:
         for r_, val in v_init.items():
@@ -90,11 +92,19 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128, stats=None
         if ln.endswith(":"):
             if stop_at is not None and ln[:-1] == stop_at:
                 break
+            if stats is not None and ln.startswith(".Lwmj_swap_"):
+                stats["swap", sweeps] = stats.get(("swap", sweeps), 0) + 1
+            if scales is not None and ln == ".Lwmj_fold_%=:":
+                scales.append(np.stack([v[G.LAY.W0 + c] for c in range(8)], axis=1))
             continue
         mn, rest = ln.split(None, 1)
         if stats is not None and mn.startswith("v_"):
             kind_ = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith("v_rsq") else "valu"
             stats[kind_] = stats.get(kind_, 0) + 1
+            if kind_ == "pk":
+                stats[mn] = stats.get(mn, 0) + 1
+            if mn.startswith("v_cmp_lt"):            # the de Rijk compare: once per rotation carried out
+                stats["rot", sweeps] = stats.get(("rot", sweeps), 0) + 1
         opnds = [o.strip() for o in re.split(r"\s+(?:op_sel|neg_)", rest)[0].split(",")]
         with np.errstate(all="ignore"):
             if mn.startswith("v_cvt_f32_ubyte"):
@@ -146,6 +156,8 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128, stats=None
                 vcc = (src(opnds[1]) > src(opnds[2])) & ex     # inactive lanes read 0
             elif mn.startswith("v_cmp_lt_f32"):
                 vcc = (src(opnds[1]) < src(opnds[2])) & ex
+                if stats is not None:                          # lanes that want the de Rijk swap, per rotation of the sweep
+                    stats.setdefault(("swap_lanes", sweeps), []).append(int(vcc.sum()))
             elif mn.startswith("v_cndmask_b32"):
                 wr(int(opnds[0][1:]), np.where(vcc, src(opnds[2]), src(opnds[1])))
             elif mn == "s_mov_b32":
@@ -203,6 +215,9 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=128, stats=None
             elif mn == "s_cbranch_scc1":
                 if scc:
                     pc = labels[opnds[0]]
+            elif mn == "s_cbranch_vccnz":
+                if vcc.any():
+                    pc = labels[opnds[0]]
             elif mn == "s_cbranch_vccz":
                 if not vcc.any():
                     pc = labels[opnds[0]]
@@ -236,21 +251,23 @@ def _unpack(v, base, n):
 _STREAM = {}
 
 
-def _stream(move_test=True, lq=True):
-    if (move_test, lq) not in _STREAM:
-        _STREAM[move_test, lq] = G.build(move_test, lq)
-    return _STREAM[move_test, lq]
+def _stream(move_test=True, lq=True, scaled=True):
+    if (move_test, lq, scaled) not in _STREAM:
+        _STREAM[move_test, lq, scaled] = G.build(move_test, lq, scaled)
+    return _STREAM[move_test, lq, scaled]
 
 
 def run(raw_tiles: np.ndarray, conv2: float, skip2: float, min_sweeps: int, skip_from: int, lq: int = 1, stats=None,
-        move_test=True):
+        move_test=True, scaled=True, scales=None):
     """raw_tiles uint8 [n, 8, 8] -> (a [n, 4, 8, 2] float32, n2 [n, 8], more mask (bool [n]), sweeps).
+    scaled=False: the stream whose every pair takes the unscaled rotation (gen_jacobi_asm.build(scaled=False), the baseline
+    of the scaled rotations); scales (a list) receives the squared column scales [n, 8] as the last sweep left them.
     lq=0: the stream without the LQ prelude (gen_jacobi_asm.build(lq=False), the baseline); stats: see _interp; move_test=False: the stream that stops on cos^2
     alone (gen_jacobi_asm.build(False): the iteration before the prelude)."""
     n = raw_tiles.shape[0]
     lo, hi = _pack_words(raw_tiles)
     named = {"%[conv]": F(conv2), "%[skip]": F(skip2), "%[minsw]": int(min_sweeps), "%[skipfrom]": int(skip_from)}
-    v, more, sweeps = _interp(_stream(move_test, bool(lq)), n, named, lo, hi, stats=stats)
+    v, more, sweeps = _interp(_stream(move_test, bool(lq), scaled), n, named, lo, hi, stats=stats, scales=scales)
     n2 = np.stack([v[G.N0 + c] for c in range(8)], axis=1)
     return _unpack(v, G.A0, n), n2, more, sweeps
 

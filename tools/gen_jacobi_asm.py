@@ -7,8 +7,9 @@ Why not leave it to hipcc (profiles/r02_embed_variants.md): for the C++ form it 
 scalar angle arithmetic into v_pk ops stitched together with v_mov, spends an `s_nop` after most packed
 instructions (gfx940 forwarding hazard of VOP3P results), keeps ~140 VGPRs live (3 waves per SIMD) and
 spills as soon as the sweep is split into basic blocks.  Here the whole iteration lives in a fixed
-register file - B in v[40:103], the column norms in v[104:111], 16 temporaries in v[112:127] - so the
-kernel fits 128 VGPRs (4 waves per SIMD), and every hazard the stream has is resolved by ORDER:
+register file - B in v[40:103], the column norms in v[104:111], 16 temporaries in v[112:127], the squared column
+scales of the untested sweeps' scaled rotations in v[128:135] - so the stream needs 136 VGPRs (three waves per SIMD, where the embed
+and extract kernels round it are anyway), and every hazard the stream has is resolved by ORDER:
   * a VOP3P result is never read by the next instruction            (DstSel forwarding hazard, 1 state)
   * a v_rsq_f32 result is never read by the next instruction        (trans-use hazard, 1 state)
   * VCC written by v_cmp is read by v_cndmask two instructions later (VALU SGPR write -> VALU read, 2 states)
@@ -18,6 +19,10 @@ does not already satisfy them (it never needs to inside a rotation).
 Same arithmetic as jacobi_rot_pk (two-rsq angle, de Rijk swap, cancellation-free norm update, wave-uniform
 skip of a pair that is below the skip threshold in all 64 tiles), same pair order (row-cyclic), same sweep
 control (norms recomputed before odd sweeps, convergence test on cos^2 and on the norm move w = |t g|, sweep bound 12).
+
+The untested sweeps (the first min_sweeps - 1) keep the columns scaled, so that a rotation in which no tile of the wave
+takes the de Rijk swap costs two packed FMAs per row pair instead of four packed operations (rotation_scaled,
+jacobi_rot_scaled_pk); the scales are folded back into B behind the last of them and the tested sweeps are rotation().
 
 Ahead of the first sweep the stream runs the LQ prelude (lq_prelude: B0 = X Q, Householder LQ with greedy row
 pivoting applied from the right - about one sweep fewer).  build(lq=False) is the stream without it: never compiled into
@@ -40,8 +45,8 @@ MOVE2 = 1e-6          # JAC_MOVE2 of wm_tile_math.h
 class Lay:
     """Register file of one stream: B at v[a0 ..], optionally V at v[v0 ..], norms, 16 temporaries at v[t ..]."""
 
-    def __init__(self, a0, n0, t, v0=None, vn0=None):
-        self.A0, self.N0, self.T, self.V0, self.VN0 = a0, n0, t, v0, vn0
+    def __init__(self, a0, n0, t, v0=None, vn0=None, w0=None):
+        self.A0, self.N0, self.T, self.V0, self.VN0, self.W0 = a0, n0, t, v0, vn0, w0
         pr = lambda k: f"v[{t + k}:{t + k + 1}]"
         self.GV, self.T1, self.T2, self.CS, self.T3 = pr(0), pr(2), pr(4), pr(6), pr(14)
         self.GVl, self.GVh, self.C, self.S = f"v{t}", f"v{t + 1}", f"v{t + 6}", f"v{t + 7}"
@@ -63,9 +68,17 @@ class Lay:
     def N(self, c, base=None):
         return f"v{(self.N0 if base is None else base) + c}"
 
+    def W(self, c):
+        return f"v{self.W0 + c}"
 
-# the V-free stream (embed / sigma kernels): B in v[40:103], n2 in v[104:111], temporaries v[112:127]
-LAY = Lay(40, 104, 112)
+    def WP(self, c):
+        b = self.W0 + 2 * (c >> 1)
+        return f"v[{b}:{b + 1}]"
+
+
+# the V-free stream (embed / sigma kernels): B in v[40:103], n2 in v[104:111], temporaries v[112:127], the squared
+# column scales of the scaled rotations in v[128:135]
+LAY = Lay(40, 104, 112, w0=128)
 A0, N0, T = LAY.A0, LAY.N0, LAY.T
 # the stream with V (fallback embed, watermark-side SVD): B v[40:103], V v[104:167], |b|^2 v[168:175], |v|^2 v[176:183],
 # temporaries v[184:199]
@@ -232,6 +245,118 @@ def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False, move_test=True):
         st.hist.append(("nop", set()))       # a taken branch lands here: nothing before it may be assumed
 
 
+def rotation_scaled(st, p, q, uid, L=LAY):
+    """rotation(plain=True) on SCALED columns a_c = sqrt(w_c) at_c, for the untested sweeps of the V-free stream: B's
+    registers hold at_c, L.W(c) the squared scale w_c (jacobi_rot_scaled_pk).  Where no tile of the wave takes the de
+    Rijk swap (tau <= 0 in all 64 lanes) the update is two packed FMAs per row pair and no product,
+        at_p += t_p at_q ;  at_q -= t_q at_p'         (a_p' = c (a_p + t a_q),  a_q' = a_q / c - t a_p')
+        t_p = (gt / h) w_q / c^2,  t_q = (gt / h) w_p,   w_p *= c^2,  w_q /= c^2,      gt = at_p . at_q
+    and needs no reciprocal or root of a scale: c^2 and 1 / c^2 are what the angle's two v_rsq_f32 deliver anyway.
+    g^2 = gt^2 w_p w_q feeds the angle, the norm move is |t g| = g^2 / (h c^2); the tracked norms n2 are the TRUE ones.
+    Behind the LQ prelude the columns arrive graded: a swap is wanted at about 8 of the first sweep's 28 pairs, 3 of the
+    second's and none later (tools/conv_study.cpp 4).  Where any lane swaps, the wave takes rotation()'s four-product
+    update with the scale ratios folded into its coefficients, at_p' = C at_p + S (d_q / d_p) at_q, at_q' = C at_q -
+    S (d_p / d_q) at_p (one more v_rsq_f32, of w_p w_q); the scales stay as they are.
+    Scale range: c^2 is in [0.5, 1], a rotation leaves the product of the eight w at 1, and a column meets 7 rotations
+    in each of at most 3 untested sweeps: 2^-21 <= w <= 2^21, no rescaling.  (The study's tiles stay within [0.2, 5].)"""
+    A, N, W = L.A, L.N, L.W
+    GV, T1, T2, CS, T3, GVl, GVh, C, S = L.GV, L.T1, L.T2, L.CS, L.T3, L.GVl, L.GVh, L.C, L.S
+    g, gg, ab, tau, ta, t1, ih, x = L.g, L.gg, L.ab, L.tau, L.ta, L.t1, L.ih, L.x
+    P89 = f"v[{L.T + 8}:{L.T + 9}]"                                     # (g, gg): free once s0 and the norms are there
+    Np, Nq = N(p), N(q)
+    st.emit(f"v_pk_mul_f32 {GV}, {A(0, p)}, {A(0, q)}")
+    st.emit(f"v_max_f32_e32 {ab}, {Np}, {Nq}")
+    st.emit(f"v_pk_fma_f32 {GV}, {A(1, p)}, {A(1, q)}, {GV}")
+    st.emit(f"v_sub_f32_e32 {tau}, {Nq}, {Np}")                       # tau = be - al
+    st.emit(f"v_pk_fma_f32 {GV}, {A(2, p)}, {A(2, q)}, {GV}")
+    st.emit(f"v_add_f32_e64 {ta}, |{tau}|, {EPS}")                     # |tau| + 1e-18
+    st.emit(f"v_pk_fma_f32 {GV}, {A(3, p)}, {A(3, q)}, {GV}")
+    st.emit(f"v_mul_f32_e32 {t1}, {ta}, {ta}")
+    st.emit(f"v_add_f32_e32 {g}, {GVl}, {GVh}")                        # gt = at_p . at_q
+    st.emit(f"v_mul_f32_e32 {x}, {W(p)}, {W(q)}")
+    st.emit(f"v_mul_f32_e32 {gg}, {g}, {x}")
+    st.emit(f"v_mul_f32_e32 {gg}, {gg}, {g}")                          # g^2 = (gt w_p w_q) gt
+    st.emit(f"v_fma_f32 {t1}, {gg}, 4.0, {t1}")                        # h^2 = tau^2 + 4 g^2
+    st.emit(f"v_rsq_f32_e32 {ih}, {t1}")                               # 1/h
+    st.emit(f"v_mul_f32_e32 {x}, 0.5, {ta}")
+    st.emit(f"v_fma_f32 {x}, {x}, {ih}, 0.5")                          # cos^2 in [0.5, 1]
+    st.emit(f"v_rsq_f32_e32 {t1}, {x}")                                # rx = 1 / cos
+    st.emit(f"v_mul_f32_e32 {GVh}, {g}, {ih}")                         # u = gt / h
+    st.emit(f"v_cmp_lt_f32_e32 vcc, 0, {tau}")                         # de Rijk: does any tile of the wave want the swap?
+    st.emit(f"v_mul_f32_e32 {gg}, {gg}, {ih}")                         # g^2 / h
+    st.emit(f"v_min_f32_e32 {ta}, {Np}, {Nq}")                         # (ta is dead after cos^2)
+    st.emit(f"s_cbranch_vccnz .Lwmj_swap_{uid}_%=", kind="salu")
+    # -- no lane swaps
+    st.emit(f"v_mul_f32_e32 {t1}, {t1}, {t1}")                         # 1 / cos^2
+    st.emit(f"v_mul_f32_e32 {S}, {GVh}, {W(p)}")                       # t_q = u w_p
+    st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {t1}")
+    st.emit(f"v_mul_f32_e32 {gg}, {gg}, {t1}")                         # w = g^2 / (h cos^2) = |t g|
+    st.emit(f"v_mul_f32_e32 {W(p)}, {W(p)}, {x}")
+    st.emit(f"v_mul_f32_e32 {C}, {GVh}, {W(q)}")                       # t_p = u w_q / cos^2
+    st.emit(f"v_mul_f32_e32 {W(q)}, {W(q)}, {t1}")
+    st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")                       # larger norm grows by |t g|
+    st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
+    for rp in range(4):
+        st.emit(f"v_pk_fma_f32 {A(rp, p)}, {CS}, {A(rp, q)}, {A(rp, p)} op_sel_hi:[0,1,1]")
+    for rp in range(4):
+        st.emit(f"v_pk_fma_f32 {A(rp, q)}, {CS}, {A(rp, p)}, {A(rp, q)} op_sel:[1,0,0] neg_lo:[1,0,0] neg_hi:[1,0,0]")
+    st.emit(f"s_branch .Lwmj_rot_{uid}_%=", kind="salu")
+    # -- some lane swaps: rotation()'s update on the scaled columns
+    st.emit(f".Lwmj_swap_{uid}_%=:", kind="label")
+    st.hist.append(("nop", set()))
+    st.emit(f"v_mul_f32_e32 {ih}, {W(p)}, {W(q)}")
+    st.emit(f"v_mul_f32_e32 {GVl}, {x}, {t1}")                         # c0 = cos
+    st.emit(f"v_rsq_f32_e32 {x}, {ih}")                                # 1 / (d_p d_q)
+    st.emit(f"v_mul_f32_e32 {gg}, {gg}, {t1}")
+    st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {t1}")
+    st.emit(f"v_mul_f32_e32 {gg}, {gg}, {t1}")                         # w
+    st.emit(f"v_mul_f32_e32 {ih}, {ih}, {x}")                          # d_p d_q
+    st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")
+    st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
+    st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {ih}")                       # s0 = u d_p d_q / cos = sin * sign(g)
+    st.emit(f"v_mul_f32_e32 {ih}, {W(q)}, {x}")                        # d_q / d_p
+    st.emit(f"v_mul_f32_e32 {x}, {W(p)}, {x}")                         # d_p / d_q
+    st.emit(f"v_cndmask_b32_e32 {t1}, {GVh}, {GVl}, vcc", reads_vcc=True)    # S = sw ? c0 : s0
+    st.emit(f"v_cndmask_b32_e32 {C}, {GVl}, {GVh}, vcc", reads_vcc=True)     # C = sw ? s0 : c0, in both pairs
+    st.emit(f"v_cndmask_b32_e32 {g}, {GVl}, {GVh}, vcc", reads_vcc=True)
+    st.emit(f"v_mul_f32_e32 {S}, {t1}, {ih}")                          # CS = (C, S d_q / d_p): the new at_p
+    st.emit(f"v_mul_f32_e32 {gg}, {t1}, {x}")                          # P89 = (C, S d_p / d_q): the new at_q
+    for rp0 in (0, 2):
+        tt = ((T1, T2), (GV, T3))
+        for i in (0, 1):
+            rp = rp0 + i
+            st.emit(f"v_pk_mul_f32 {tt[i][0]}, {CS}, {A(rp, q)} op_sel:[1,0]")
+            st.emit(f"v_pk_mul_f32 {tt[i][1]}, {P89}, {A(rp, p)} op_sel:[1,0]")
+        for i in (0, 1):
+            rp = rp0 + i
+            st.emit(f"v_pk_fma_f32 {A(rp, p)}, {CS}, {A(rp, p)}, {tt[i][0]} op_sel_hi:[0,1,1]")
+            st.emit(f"v_pk_fma_f32 {A(rp, q)}, {P89}, {A(rp, q)}, {tt[i][1]} op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]")
+    st.emit(f".Lwmj_rot_{uid}_%=:", kind="label")
+    st.hist.append(("nop", set()))       # a taken branch lands here: nothing before it may be assumed
+
+
+def scale_norms(st, L=LAY):
+    """the squared norms col_norms() took from the scaled columns, made true: n2[c] *= w_c (w_c = 1 once the scales are
+    folded back)"""
+    for c in range(8):
+        st.emit(f"v_mul_f32_e32 {L.N(c)}, {L.N(c)}, {L.W(c)}")
+
+
+def fold_scales(st, L=LAY):
+    """B's registers become the true columns again, a_c = sqrt(w_c) at_c, and the scales 1: once, behind the last
+    untested sweep"""
+    for c in range(8):
+        st.emit(f"v_rsq_f32_e32 v{L.T + c}, {L.W(c)}")
+    for c in range(8):
+        st.emit(f"v_mul_f32_e32 {L.W(c)}, {L.W(c)}, v{L.T + c}")
+    for c in range(8):
+        h = c & 1
+        for rp in range(4):
+            st.emit(f"v_pk_mul_f32 {L.A(rp, c)}, {L.WP(c)}, {L.A(rp, c)} op_sel:[{h},0] op_sel_hi:[{h},1]")
+    for c in range(8):
+        st.emit(f"v_mov_b32_e32 {L.W(c)}, 1.0")
+
+
 def f32_literal(x):
     return f"0x{struct.unpack('<I', struct.pack('<f', x))[0]:08x}"
 
@@ -314,9 +439,10 @@ def eps_literal():
     return struct.unpack("<I", struct.pack("<f", 1e-18))[0]  # keeps 0/0 out; its square (1e-36) is a normal float
 
 
-def build(move_test=True, lq=True):
+def build(move_test=True, lq=True, scaled=True):
     """lq=False: no LQ prelude; move_test=False: the tested sweeps stop on cos^2 alone, as they did before the LQ prelude (what the emulator
-    measures the prelude against); the committed stream is build()."""
+    measures the prelude against); scaled=False: every pair takes rotation() on unscaled columns (what the scaled
+    rotations are measured against); the committed stream is build()."""
     st = Stream()
     e = st.emit
     Alo, Ahi = LAY.Alo, LAY.Ahi
@@ -334,6 +460,9 @@ def build(move_test=True, lq=True):
             e(f"v_cvt_f32_ubyte{c & 3}_e32 {dst}, {src}")
     if lq:
         lq_prelude(st)
+    if scaled:
+        for c in range(8):
+            e(f"v_mov_b32_e32 {LAY.W(c)}, 1.0")
     e(".Lwmj_lqdone_%=:", kind="label")
     st.hist.append(("nop", set()))
     e(".Lwmj_sweep_%=:", kind="label")
@@ -341,6 +470,8 @@ def build(move_test=True, lq=True):
     e(f"s_bitcmp1_b32 {SW}, 0", kind="salu")                 # norms are recomputed before odd-numbered sweeps
     e("s_cbranch_scc1 .Lwmj_nonorm_%=", kind="salu")
     col_norms(st)
+    if scaled:
+        scale_norms(st)
     e(".Lwmj_nonorm_%=:", kind="label")
     st.hist.append(("nop", set()))
     e(f"s_cmp_ge_i32 {SW}, {SKIPFROM}", kind="salu")         # pairs are skipped from sweep `skipfrom` on (0-based);
@@ -351,7 +482,18 @@ def build(move_test=True, lq=True):
     e("s_cbranch_scc0 .Lwmj_tested_%=", kind="salu")
     for p in range(7):
         for q in range(p + 1, 8):
-            rotation(st, p, q, -1, plain=True)
+            if scaled:
+                rotation_scaled(st, p, q, f"{p}{q}")
+            else:
+                rotation(st, p, q, -1, plain=True)
+    if scaled:
+        # behind the last untested sweep the scales are folded back into B: the tested sweeps, the final norms and the
+        # pinned output registers see the true columns, as they always did
+        e(f"s_add_i32 {TMPS}, {SW}, 2", kind="salu")
+        e(f"s_cmp_lt_i32 {TMPS}, {MINSW}", kind="salu")
+        e("s_cbranch_scc1 .Lwmj_swept_%=", kind="salu")
+        e(".Lwmj_fold_%=:", kind="label")
+        fold_scales(st)
     e("s_branch .Lwmj_swept_%=", kind="salu")
     e(".Lwmj_tested_%=:", kind="label")
     st.hist.append(("nop", set()))
@@ -430,7 +572,9 @@ def build_v():
 HEADER = """// GENERATED by tools/gen_jacobi_asm.py - do not edit.  The packed one-sided Jacobi of the tile kernels
 // (raw_to_pk + jacobi_cols_pk + final col_norms2_pk of wm_tile_math.h) as one gfx950 instruction stream with
 // pinned registers: B = X V in v[40:103] (a[rp][c] = v[40 + 2 (8 rp + c)] : rows 2 rp, 2 rp + 1),
-// |b_c|^2 in v[104:111], temporaries v[112:127], control in s[80:98].  {n_inst} instructions, {n_nop} s_nop.
+// |b_c|^2 in v[104:111], temporaries v[112:127], the squared column scales of the scaled rotations in v[128:135]
+// (through the untested sweeps the registers of B hold a_c / sqrt(w_c); the scales are folded back behind the last of them),
+// control in s[80:98].  {n_inst} instructions, {n_nop} s_nop.
 // The sweeps run on B0 = X Q, the row-pivoted Householder LQ of the tile applied from the right (its column Gram
 // matrix is one QR-algorithm step further on: about one sweep fewer); B stays X * orthogonal.
 //   conv2:     a sweep that saw no pair with cos^2 > conv2 in any tile of the wave, and no rotation that moved the two
@@ -485,7 +629,7 @@ def render():
     outs.append('[more] "=&s"(more)')
     ins = [f'[lo{r}] "v"(lo[{r}])' for r in range(8)] + [f'[hi{r}] "v"(hi[{r}])' for r in range(8)]
     ins += ['[conv] "s"(conv2)', '[skip] "s"(skip2)', '[minsw] "s"(min_sweeps)', '[skipfrom] "s"(skip_from)']
-    clob = [f'"v{i}"' for i in range(T, 128)] + [f'"s{i}"' for i in range(80, 99)] + ['"vcc"', '"scc"']
+    clob = [f'"v{i}"' for i in range(T, LAY.W0 + 8)] + [f'"s{i}"' for i in range(80, 99)] + ['"vcc"', '"scc"']
     body += "      : " + ",\n        ".join(outs) + "\n"
     body += "      : " + ",\n        ".join(ins) + "\n"
     body += "      : " + ", ".join(clob) + ");\n  return more;\n}\n"

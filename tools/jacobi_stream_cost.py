@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Executed instructions per class of the V-free Jacobi stream (tools/gen_jacobi_asm.py, interpreted by
+tools/emu_jacobi_asm.py) on the 40 noise waves tests/test_jacobi_lq_prelude.py counts on, priced with the instruction
+costs measured on the part (profiles/r02_embed_variants.md section 2, middle of each range): the stream with the scaled
+rotations against the one whose every pair takes the unscaled rotation (gen_jacobi_asm.build(scaled=False)).
+
+    python tools/jacobi_stream_cost.py
+"""
+import numpy as np
+
+import emu_jacobi_asm as emu
+
+# cycles per wave-instruction: v_mul / v_fma and their like 2.1-2.6, v_pk_mul_f32 4.3, v_pk_fma_f32 4.8-5.9, v_rsq_f32 8
+PRICE = {"valu": 2.35, "v_pk_mul_f32": 4.3, "v_pk_fma_f32": 5.3, "trans": 8.0}
+CONFIGS = {"embed": (1e-7, 1e-12, 4, 3), "sigma": (1e-2, 1e-8, 3, 2)}       # what csrc/wmhip.hip passes to the stream
+
+
+def noise_waves():
+    return np.random.default_rng(2025).integers(0, 256, (40, 64, 8, 8), dtype=np.uint8)
+
+
+def count(cfg, scaled, waves=None):
+    """-> (executed instructions per wave by class, mean sweeps per wave, {sweep: (rotations, of them in the swap branch)})"""
+    waves = noise_waves() if waves is None else waves
+    tot, sweeps = {}, []
+    for t in waves:
+        st = {}
+        _, _, more, k = emu.run(t, *cfg, stats=st, scaled=scaled)
+        assert not np.any(more)
+        sweeps.append(k)
+        for key, val in st.items():
+            if not isinstance(val, list):
+                tot[key] = tot.get(key, 0) + val
+    n = len(waves)
+    per_class = {k: tot.get(k, 0) / n for k in ("valu", "v_pk_mul_f32", "v_pk_fma_f32", "trans")}
+    per_sweep = {k[1]: (tot[k] / n, tot.get(("swap", k[1]), 0) / n) for k in sorted(x for x in tot if isinstance(x, tuple) and x[0] == "rot")}
+    return per_class, float(np.mean(sweeps)), per_sweep
+
+
+def cycles(per_class):
+    return sum(PRICE[k] * v for k, v in per_class.items())
+
+
+if __name__ == "__main__":
+    for name, cfg in CONFIGS.items():
+        cyc = {}
+        for scaled in (False, True):
+            pc, sw, ps = count(cfg, scaled)
+            cyc[scaled] = cycles(pc)
+            print(f"{name:5s} {'scaled  ' if scaled else 'unscaled'}  sweeps per wave {sw:.3f}  per wave: "
+                  + "  ".join(f"{k} {v:.0f}" for k, v in pc.items()) + f"  priced {cyc[scaled]:.0f} cycles")
+            print("      rotations per sweep (of them in the swap branch): "
+                  + "  ".join(f"{k + 1}: {r:.1f} ({s:.1f})" for k, (r, s) in ps.items()))
+        print(f"{name:5s} priced cycles {100 * (cyc[True] / cyc[False] - 1):+.2f} %")
