@@ -603,13 +603,15 @@ struct EpiSigma {
 // The masked embed's gain (wm_tile_math.h, mask_gain): the tile's cover singular values -> g, and G o sigma_w of the
 // tile to a dense [plane][tile][8] array that the unchanged embed launches are then fed with a per-plane stride; with
 // `gain`, g itself to [plane][tile].  sigma_w may be shared by the planes (sw_plane_stride 0); without sw_eff only g is left.
+// `black` (optional, [plane][tile]): 1 for a tile whose 64 pixels are 0 - see k_embed_black.
 struct EpiMask {
   const float* __restrict__ sigma_w;
   float* __restrict__ sw_eff;
   float* __restrict__ gain;
+  uint8_t* __restrict__ black;
   size_t sw_plane_stride;
   float lo, hi;
-  __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], const size_t plane, const int t,
+  __device__ __forceinline__ void operator()(const wm::RawTile& raw, const float (&s)[8], const size_t plane, const int t,
                                              const size_t ti) const {
     float sw[8];
     const float gn = wm::mask_gain(s, lo, hi);
@@ -619,6 +621,7 @@ struct EpiMask {
       store_row8_f32<true>(sw_eff + ti * 8, sw);
     }
     if (gain) gain[ti] = gn;
+    if (black) black[ti] = (wm::raw_is_constant(raw) && raw.lo[0] == 0u) ? 1 : 0;
   }
 };
 
@@ -874,7 +877,7 @@ __global__ __launch_bounds__(256) void k_detect_finalize(const double* __restric
 // ---------------------------------------------------------------------------
 // Sigma pass on the cover tile: the rule's sigma_w row (target - s_1, 0, .., 0) to a dense [plane][tile][8] array that the
 // unchanged embed launches are fed with a per-plane stride, alpha = 1 and K = 1.  tile_bit[n_tiles] is shared by the planes.
-// `black` (optional, [plane][tile]): 1 for a tile whose 64 pixels are 0 - see k_payload_black.
+// `black` (optional, [plane][tile]): 1 for a tile whose 64 pixels are 0 - see k_embed_black.
 struct EpiPayloadSigmaW {
   const uint8_t* __restrict__ tile_bit;
   float* __restrict__ sw_eff;
@@ -890,20 +893,22 @@ struct EpiPayloadSigmaW {
 };
 
 // A black cover tile is the zero matrix: it has no leading singular vector of its own, and the embed's closed form for
-// constant tiles gives it those of a fixed noise pattern, half of whose pixels clip at 0 - sigma_1 would land far from its
-// lattice point.  The payload embed takes the flat vector instead (what np.linalg.svd returns for a zero matrix: U = V = I,
-// the DC term): the tile becomes the constant (q + c) / 8.  Runs after the unchanged embed launches and rewrites only the
-// tiles flagged by EpiPayloadSigmaW (sw_eff[0] = q + c there, s_1 being 0); stego and yw are addressed as the embed does.
+// constant tiles gives it those of a fixed noise pattern, half of whose pixels clip at 0 - sigma_1 of the stored tile lands
+// far from what was aimed at (the payload's lattice point; the masked rule's alpha sw_1, which then reads back a third
+// short).  The embeds with a derived sigma_w take the flat vector instead (what np.linalg.svd returns for a zero matrix:
+// U = V = I, the DC term): the tile becomes the constant a0 sw_eff[0] / 8, a0 = alpha_k[0] (the payload: 1, and sw_eff[0]
+// = q + c there, s_1 being 0; the masked embed: alpha, or 0 for K = 0).  Runs after the unchanged embed launches and
+// rewrites only the tiles flagged by the sigma pass; stego and yw are addressed as the embed does.
 template <bool ALIGNED>
-__global__ __launch_bounds__(WAVE) void k_payload_black(uint8_t* __restrict__ stego, float* __restrict__ yw,
-                                                    const float* __restrict__ sw_eff, const uint8_t* __restrict__ black,
-                                                    const Geom g) {
+__global__ __launch_bounds__(WAVE) void k_embed_black(uint8_t* __restrict__ stego, float* __restrict__ yw,
+                                                  const float* __restrict__ sw_eff, const uint8_t* __restrict__ black,
+                                                  const Geom g, const float a0) {
   int t, ty, tx;
   if (!tile_coords(g, t, ty, tx)) return;
   const size_t plane = blockIdx.y;
   const size_t i = plane * g.n_tiles + t;
   if (!black[i]) return;
-  const float v = sw_eff[i * 8] * 0.125f;
+  const float v = (a0 * sw_eff[i * 8]) * 0.125f;
   const uint32_t w = wm::quant_u8(v) * 0x01010101u;
   uint8_t* p = STRIDED_TILE(stego, g, plane, ty, tx);
 #pragma unroll
@@ -1016,14 +1021,13 @@ int sigma_pass(wm_ctx* ctx, const uint8_t* planes, int n_planes, int H, int W, i
 }
 
 // The masked and the payload embed, behind the caller's plane and rule checks: `pass(eff, black)` enqueues the sigma pass
-// that leaves a [plane][tile][8] sigma_w in the context's grow-only workspace (with `payload`, also the [plane][tile]
-// black flags), then the unchanged embed launches are fed it with a per-plane stride.  The sigma pass reads the host planes
-// before anything writes (one stream), so stego may alias host.  `missing`: the message if an input that the tiles need
-// is NULL, else nullptr.
+// that leaves a [plane][tile][8] sigma_w and the [plane][tile] black flags in the context's grow-only workspace, then the
+// unchanged embed launches are fed the sigma_w with a per-plane stride and k_embed_black redoes the flagged tiles.  The
+// sigma pass reads the host planes before anything writes (one stream), so stego may alias host.  `missing`: the message if
+// an input that the tiles need is NULL, else nullptr.
 template <typename Pass>
 int embed_derived_dev(wm_ctx* ctx, const uint8_t* host, uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W,
-                      int row_stride, size_t plane_stride, float alpha, int K, bool payload, const char* missing,
-                      const Pass& pass) {
+                      int row_stride, size_t plane_stride, float alpha, int K, const char* missing, const Pass& pass) {
   if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");           // (before the sigma pass is enqueued)
   if (K < 0 || K > 8) return set_err(WM_ERR_BADARG, "K must be in 0..8");
   const size_t nt8 = (size_t)(H / 8) * (size_t)(W / 8) * 8;
@@ -1033,7 +1037,7 @@ int embed_derived_dev(wm_ctx* ctx, const uint8_t* host, uint8_t* stego, float* s
     if (missing) return set_err(WM_ERR_BADARG, "%s", missing);
     WM_TRY(staged(ctx, &ctx->sigma_ws, &ctx->sigma_ws_bytes, "derived sigma_w", [&](Carve& cv) {
       eff = cv.take<float>((size_t)n_planes * nt8);
-      black = payload ? cv.take<uint8_t>((size_t)n_planes * (nt8 / 8)) : nullptr;
+      black = cv.take<uint8_t>((size_t)n_planes * (nt8 / 8));
     }));
     WM_TRY(pass(eff, black));
   }
@@ -1042,8 +1046,8 @@ int embed_derived_dev(wm_ctx* ctx, const uint8_t* host, uint8_t* stego, float* s
     const Geom g = make_geom(H, W, row_stride, plane_stride);
     const dim3 grid = tile_grid(g, n_planes), block(WAVE);
     with_bools([&](auto A) {
-      hipLaunchKernelGGL((k_payload_black<A.value>), grid, block, 0, ctx->stream, stego, yw, (const float*)eff,
-                         (const uint8_t*)black, g);
+      hipLaunchKernelGGL((k_embed_black<A.value>), grid, block, 0, ctx->stream, stego, yw, (const float*)eff,
+                         (const uint8_t*)black, g, K > 0 ? alpha : 0.0f);
     }, u8_aligned(host, stego, row_stride, plane_stride));
     WM_HIP(hipGetLastError());
   }
@@ -1301,9 +1305,9 @@ int wm_sigma_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, float* sigma, int 
 }
 
 // ---- K2 + gain, masked K1 ----------------------------------------------------
-int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
-                                 int n_planes, int H, int W, int row_stride, size_t plane_stride,
-                                 size_t sigma_w_plane_stride, float lo, float hi) {
+static int mask_sigma_w_dev(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                           uint8_t* black, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                           size_t sigma_w_plane_stride, float lo, float hi) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_mask(lo, hi, 1.0f));
   const char* bad = (!sigma_w != !sigma_w_eff) ? "sigma_w and sigma_w_eff go together"
@@ -1312,7 +1316,14 @@ int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float
                         ? "sigma_w / sigma_w_eff is not 16-byte aligned"
                     : ((uintptr_t)gain & 3u) ? "gain is not 4-byte aligned" : nullptr;
   return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad,
-                    EpiMask{sigma_w, sigma_w_eff, gain, sigma_w_plane_stride, lo, hi});
+                    EpiMask{sigma_w, sigma_w_eff, gain, black, sigma_w_plane_stride, lo, hi});
+}
+
+int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float* sigma_w, float* sigma_w_eff, float* gain,
+                                 int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                 size_t sigma_w_plane_stride, float lo, float hi) {
+  return mask_sigma_w_dev(ctx, planes, sigma_w, sigma_w_eff, gain, nullptr, n_planes, H, W, row_stride, plane_stride,
+                          sigma_w_plane_stride, lo, hi);
 }
 
 // ---- blind payload: sigma pass + target, sigma pass + metric -----------------------
@@ -1344,10 +1355,10 @@ int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* 
                                  size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi) {
   WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_mask(lo, hi, 1.0f));
-  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, alpha, K, false,
-                           (!sigma_w || !sigma_c) ? "sigma_w / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t*) {
-    return wm_mask_sigma_w_tiles_u8_dev(ctx, host, sigma_w, eff, nullptr, n_planes, H, W, row_stride, plane_stride,
-                                        sigma_w_plane_stride, lo, hi);
+  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, alpha, K,
+                           (!sigma_w || !sigma_c) ? "sigma_w / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t* black) {
+    return mask_sigma_w_dev(ctx, host, sigma_w, eff, nullptr, black, n_planes, H, W, row_stride, plane_stride,
+                            sigma_w_plane_stride, lo, hi);
   });
 }
 
@@ -1355,7 +1366,7 @@ int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_
                                   float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
-  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, 1.0f, 1, true,
+  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, 1.0f, 1,
                            (!tile_bit || !sigma_c) ? "tile_bit / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t* black) {
     return payload_sigma_w_dev(ctx, host, tile_bit, eff, black, n_planes, H, W, row_stride, plane_stride, delta);
   });

@@ -447,7 +447,8 @@ class Context:
         """host uint8 [H,W] or [N,H,W]; sigma_w float32 [nby,nbx,8] (shared) or
         [N,nby,nbx,8].  Returns (stego uint8, sigma_c float32 [N?,nby,nbx,8], yw or None).
         ``mask=(lo, hi, cut)``: texture-masked strength (include/wmhip.h) - every tile adds alpha * G * sigma_w with
-        G = (1, g, .., g) and g from its own cover singular values; ``cut`` plays no part in the embed."""
+        G = (1, g, .., g) and g from its own cover singular values (a black tile, which has no singular vectors of its
+        own, along the flat one: it becomes the constant alpha * sw_1 / 8); ``cut`` plays no part in the embed."""
         m = _mask_args(mask)
         n, H, W, rs, ps = _planes_of(host, np.uint8, "host planes must be uint8")
         nby, nbx = H // TILE, W // TILE

@@ -182,7 +182,10 @@ int wm_detect_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const float* sigma_c,
  * The rule ("Texture-masked strength"; part of the meta format).  For a tile with cover singular values
  * s_1 >= .. >= s_8 (float32, as written to sigma_c) and parameters lo, hi, cut:
  *   r = sqrt(s_2^2 + .. + s_8^2);  g = clamp((r - lo) / (hi - lo), 0, 1) in float32;  G = (1, g, g, g, g, g, g, g)
- *   embed    s'_i = s_i + alpha * G_i * sw_i for i < K
+ *   embed    s'_i = s_i + alpha * G_i * sw_i for i < K, along the tile's own singular vectors.  A black tile (64 zeros)
+ *            has none: it moves along the flat vector (U = V = I in the DCT domain, what np.linalg.svd returns for a zero
+ *            matrix) and becomes the constant alpha * sw_1 / 8 (clipped, truncated; untouched for K = 0).  Its sigma_c is
+ *            what the unmasked embed writes.
  *   carried  a tile is carried iff g >= cut
  *   extract  sw_hat_1 = (s~_1 - s_1) / max(alpha, 1e-8) for every tile; sw_hat_i = (s~_i - s_i) / (max(alpha, 1e-8) * g) for
  *            i >= 2 on carried tiles, 0 on the others; then sw_hat_i = 0 for i >= K
@@ -203,7 +206,9 @@ int wm_mask_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const float* si
                              size_t sigma_w_plane_stride, float lo, float hi);
 
 /* The rule's embed: wm_mask_sigma_w_tiles_u8_dev into a buffer the context owns, then wm_embed_tiles_u8_dev with
- * G o sigma_w.  sigma_c is the cover's, as in the unmasked embed; stego may alias host. */
+ * G o sigma_w, then the black tiles redone along the flat vector (wm_embed_tiles_u8_dev itself gives a black tile the
+ * vectors of a fixed pattern, as the reference's arbitrary ones; that entry point is unchanged).  sigma_c is the cover's,
+ * as in the unmasked embed; stego may alias host. */
 int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* sigma_w, uint8_t* stego, float* sigma_c,
                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
                                  size_t sigma_w_plane_stride, float alpha, int K, float lo, float hi);

@@ -68,7 +68,7 @@ def make_inputs(case, shared, seed):
         host.view[0, :8, :8] = 77
         host.view[1, 8:16, 16:24] = np.outer(np.arange(1, 9), np.arange(3, 11)).astype(np.uint8)
         host.view[2, :8, 8:16] = host.view[2, :2, 8:16].repeat(4, axis=0)
-        host.view[0, 8:16, 8:16] = 0     # and a black tile, which the payload embed rewrites on its own (k_payload_black)
+        host.view[0, 8:16, 8:16] = 0     # and a black tile, which the payload embed rewrites on its own (k_embed_black)
     lead = () if shared else (n,)
     sw = np.sort(np.abs(rng.normal(0, 300, lead + (nby, nbx, 8))).astype(np.float32), axis=-1)[..., ::-1].copy()
     idx = rng.permutation(H * W).astype(np.int32)

@@ -62,15 +62,98 @@ def test_tile_math_against_numpy_on_the_test_hosts(harness, tmp_path, K):
 
 
 def test_tile_math_edge_rows_against_numpy(harness, tmp_path):
-    rows = np.zeros((7, 8), np.float32)
-    rows[1, :2] = (500, 8); rows[2, :2] = (500, 64); rows[3] = (900, 300, 100, 100, 100, 100, 100, 100)
-    rows[4, :2] = (500, 36); rows[5, :2] = (500, 1e-3); rows[6] = (1000, 20, 15, 10, 8, 5, 3, 1)
+    rows = mr.edge_rows()
     for lo, hi, cut, K in ((8.0, 64.0, 0.25, 8), (0.0, 1e-6, 1.0, 8), (8.0, 3.0e38, 0.25, 8), (0.0, 64.0, 0.5, 5), (8.0, 64.0, 1.0, 0)):
         g, carried, keep, _ = _run_harness(harness, tmp_path, rows, lo, hi, cut, K)
         g_np, _ = mr.gain(rows, lo, hi)
         carried_np, keep_np = mr.keep(rows, lo, hi, cut, K)
         assert np.abs(g - g_np).max() < 1e-6 and np.array_equal(carried, carried_np)
         assert np.allclose(keep, keep_np, rtol=1e-5, atol=0) and np.array_equal(keep == 0, keep_np == 0)
+
+
+# ---- the exact restatement and the hosts of tests/test_gpu_mask_edges.py --------------------------------------------
+_EDGE_RULES = [r for r in mr.RULES if r[2] < 1 and r[1] < 1e30]             # the rules whose cut a row with s_1 = 500 can sit on
+_RULE_IDS = ["-".join(f"{x:g}" for x in r) for r in mr.RULES]
+
+
+@pytest.mark.parametrize("rule", mr.RULES, ids=_RULE_IDS)
+def test_gain_exact_is_the_harness_bit_for_bit(harness, tmp_path, rule):
+    """mask_refs.gain_exact / carried_exact - the rule with every operation rounded once to float32, the squares added in
+    rational arithmetic - against mask_gain / mask_keep of the g++ program, on the three test hosts' Sc, the edge rows and
+    the rows on the edge of both cuts: the same bits, under every rule of the table."""
+    lo, hi, cut = rule
+    Sc = np.concatenate([mr.cover_sigma(H, W, seed).reshape(-1, 8) for H, W, seed in mr.HOSTS] + [mr.edge_rows()]
+                        + [mr.near_cut_rows(*r) for r in _EDGE_RULES])
+    g, carried, keep, _ = _run_harness(harness, tmp_path, Sc, lo, hi, cut, 8)
+    ge = mr.gain_exact(Sc, lo, hi)
+    assert np.array_equal(g.view(np.uint32), ge.view(np.uint32))
+    assert np.array_equal(carried, mr.carried_exact(Sc, lo, hi, cut))
+    with np.errstate(divide="ignore", over="ignore"):
+        inv = np.where(carried, np.float32(1.0) / ge, np.float32(0.0)).astype(np.float32)
+    assert np.array_equal(keep[:, 1].view(np.uint32), inv.view(np.uint32)) and np.all(keep[:, 0] == 1)
+
+
+@pytest.mark.parametrize("rule", _EDGE_RULES, ids=["-".join(f"{x:g}" for x in r) for r in _EDGE_RULES])
+def test_near_cut_rows_split_the_two_sums(rule):
+    """near_cut_rows asserts its own composition (the three single-component rows at, below and above the cut; everything
+    within 3e-7 of it); here: the exact fused sum and NumPy's pairwise sum disagree on at least 64 rows, both carried
+    classes hold at least 16, and the detect restatement tells the two carried sets apart by more than 1e-3."""
+    lo, hi, cut = rule
+    rows = mr.near_cut_rows(lo, hi, cut)
+    assert rows.shape == (128, 8) and np.all(rows[:, 0] == 500) and np.all(np.diff(rows, axis=-1) <= 0)
+    ce, cp = mr.carried_exact(rows, lo, hi, cut), mr.keep(rows, lo, hi, cut)[0]
+    print(rule, "carried exact", int(ce.sum()), "pairwise", int(cp.sum()), "disagree", int((ce != cp).sum()))
+    assert (ce != cp).sum() >= 64
+    assert min(ce.sum(), (~ce).sum()) >= 16
+    assert ce[0] and not ce[1] and ce[2]
+    _, _, _, exact, pairwise = mr.near_cut_case(lo, hi, cut)
+    print(rule, "detect restatement: carried_exact", exact, "pairwise", pairwise)
+    assert abs(exact - pairwise) > 1e-3
+
+
+def test_flagged_hosts_hold_what_the_device_tests_need():
+    """From the oracle's Sc: JPEG-quantised and posterised content is rich in rank-deficient tiles (s_8 <= 1e-5 s_1) that
+    the rule gives 0 < g < 1 (measured: 20 / 68 of quantised under the default rule / (0, 16, 0.05), 99 of posterised), the
+    hand-made plane holds every class, and no tile of any host lies within 1e-4 of the cut of a rule with cut < 1: no tile
+    is left out of any comparison."""
+    def count(name, rule):
+        Sc = mr.flagged_sigma(name)
+        g, _ = mr.gain(Sc, rule[0], rule[1])
+        return int((~(Sc[..., 7] > 1e-5 * Sc[..., 0]) & (g > 0) & (g < 1)).sum())
+    assert count("quantised_72x100", mr.RULES[0]) >= 15
+    assert count("quantised_72x100", mr.RULES[1]) >= 60
+    assert count("posterised_72x100", mr.RULES[0]) >= 90
+    hosts = mr.flagged_hosts()
+    assert sorted(hosts) == sorted([f"{k}_{s}" for k in ("quantised", "posterised", "natural") for s in ("64x64", "72x100")]
+                                   + ["handmade_64x64"])
+    for name in hosts:
+        assert hosts[name].reshape(-1).max() > 0 and not (o.to_tiles(hosts[name]).max((-1, -2)) == 0).any()    # no black tile
+        Sc = mr.flagged_sigma(name)
+        for lo, hi, cut in mr.RULES:
+            if cut < 1:
+                assert np.abs(mr.gain(Sc, lo, hi)[0] - np.float32(cut)).min() > 1e-4, (name, lo, hi, cut)
+    # the hand-made plane: ranks 7, 2, 4, 0 + constant, 1, and near-deficient full-rank tiles
+    S = np.linalg.svd(o.to_tiles(hosts["handmade_64x64"]).astype(np.float64), compute_uv=False).reshape(64, 8)
+    rank = (S > 1e-9 * S[:, :1]).sum(-1)
+    assert all((rank == k).sum() >= 4 for k in (1, 2, 4, 7, 8))
+    assert ((rank == 8) & (S[:, 7] < 1e-5 * S[:, 0])).sum() >= 8
+    assert mr.constant_tiles(hosts["handmade_64x64"]).sum() == 4
+
+
+def test_constant_batch_and_letterbox_hold_black_tiles():
+    import payload_refs as pr
+    lb = pr.letterbox_planes()
+    assert [int(pr.black_tiles(p).sum()) for p in lb] == [0, 48, 27]
+    cb = mr.constant_batch()
+    assert [int(pr.black_tiles(p).sum()) for p in cb] == [64, 0, 0, 0, 63]
+    assert [int(mr.constant_tiles(p).sum()) for p in cb] == [64, 64, 64, 0, 63]
+    # the oracle composed with the rule moves a black or constant tile along the flat vector: the reference of the device test
+    wm = mr.watermark(64, 64)
+    for p in (0, 2, 4):
+        ref = mr.embed_ref(cb[p], wm)
+        t, c = o.to_tiles(ref["Yw"]), mr.constant_tiles(cb[p])
+        assert np.all((t.max((-1, -2)) - t.min((-1, -2)))[c] < 1e-3)
+        assert np.abs(t[c][:, 0, 0] - (float(cb[p, 0, 0]) + mr.ALPHA * wm[2][c][:, 0] / 8)).max() < 1e-3
 
 
 # ---- meta -----------------------------------------------------------------------------------------------------------

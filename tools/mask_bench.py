@@ -16,7 +16,12 @@ against the parent's own round-to-round spread (sigma_pass_record).
 Also records the parity figures of the masked embed against the oracle on the test hosts (tests/mask_refs.py: what
 tests/test_gpu_mask.py holds to its bars), uniform and masked.
 
+--content letterbox: the textured frames with black bars (an eighth of the height at the top and at the bottom), whose
+tiles the masked embed redoes along the flat vector (k_embed_black); a parent build that has the masked embed runs its
+masked variants in the same rounds, and derived.embed_masked_new_over_parent is what the repair costs.
+
     python tools/mask_bench.py [--parent-lib /path/to/parent/libwmhip.so] [--out profiles/mask_bench.json]
+    python tools/mask_bench.py --parent-lib ... --content letterbox --sizes 1080p --out profiles/mask_bench_letterbox.json
 
 Development aid; bench.py is the contract benchmark."""
 import argparse
@@ -80,6 +85,11 @@ def sigma_pass_record(path, entries):
 def make_frames(content, F, H, W, rng):
     if content == "noise":
         return rng.integers(0, 256, (F, H, W), dtype=np.uint8)
+    if content == "letterbox":
+        frames = make_frames("textured", F, H, W, rng)
+        bar = H // 64 * 8                                                   # whole tile rows
+        frames[:, :bar] = 0; frames[:, H - bar:] = 0
+        return frames
     # smooth field + sensor noise: every regime of the gain
     yy, xx = np.mgrid[0:H, 0:W]
     base = 128 + 70 * np.sin(xx / 37.0) * np.cos(yy / 23.0) + 40 * np.sin((xx + 2 * yy) / 91.0)
@@ -178,7 +188,8 @@ def bench_size(name, a, ctxs):
     rng = np.random.default_rng(1234)
     host = np.ascontiguousarray(make_frames(a.content, a.frames, H, W, rng))
     wys = rng.integers(0, 256, (H, W)).astype(np.float32)
-    sides = {k: Side(c, host, wys, a.alpha, masked=(k == "new")) for k, c in ctxs.items()}
+    sides = {k: Side(c, host, wys, a.alpha, masked=(k == "new" or hasattr(c.lib, "wm_embed_tiles_masked_u8_dev")))
+             for k, c in ctxs.items()}
     runs = [(k, v) for k, s in sides.items() for v in s.variants]
     t = {kv: [] for kv in runs}
     for r in range(-a.warmup_rounds, a.rounds):
@@ -201,7 +212,8 @@ def bench_size(name, a, ctxs):
                           masked_extract_over_plain_same_stego=m["extract_masked"] / m["extract_plain_on_masked_stego"],
                           masked_detect_over_plain_same_stego=m["detect_masked"] / m["detect_plain_on_masked_stego"])
     if "parent" in ctxs:
-        out["derived"].update({f"{v}_new_over_parent": m[v] / m[f"parent.{v}"] for v in ("embed_uniform", "extract_plain", "detect_plain")})
+        out["derived"].update({f"{v}_new_over_parent": m[v] / m[f"parent.{v}"]
+                               for v in ("embed_uniform", "extract_plain", "detect_plain", "embed_masked") if f"parent.{v}" in m})
         if a.sigma_pass_out:
             sigma_pass_record(a.sigma_pass_out, {f"mask_bench.{v}_{name}": (t["new", v], t["parent", v]) for v in ("sigma_tiles", "mask_sigma_w")
                                                  if ("parent", v) in t})
@@ -232,7 +244,7 @@ def main():
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--warmup-rounds", type=int, default=2)
     ap.add_argument("--alpha", type=float, default=0.12)
-    ap.add_argument("--content", default="textured", choices=["textured", "noise"])
+    ap.add_argument("--content", default="textured", choices=["textured", "noise", "letterbox"])
     a = ap.parse_args()
     if api.device_count() < 1:
         sys.exit("mask_bench needs a GPU: there is no host fallback")
