@@ -1426,14 +1426,19 @@ WM_HD bool payload_delta_ok(const float delta) { return delta >= PAYLOAD_DELTA_M
 // delta behind - sigma_1 stays the leading value (q >= s_1 - 3 delta and s_2 <= s_1: at most 2 steps; the loop allows 3).
 // All in float32; the product 2 delta * k + bit * delta is ONE fused multiply-add, so host and device agree for every delta
 // (for a delta with few mantissa bits - 8, 16, 24 .. - the product is exact and a separate multiply and add give the same).
-WM_HD float payload_target(const float (&s)[8], const int bit, const float delta) {
-  const float two_d = 2.0f * delta, b = bit ? delta : 0.0f;
-  float q = ffma(two_d, rintf((s[0] - b) / two_d), b);
+// The rule's last two steps, shared with the dithered form: the cap under a white tile, then the climb above s_2 + delta
+WM_HD float payload_lift(float q, const float (&s)[8], const float delta) {
+  const float two_d = 2.0f * delta;
   if (q + PAYLOAD_BIAS > PAYLOAD_SIGMA_MAX) q -= two_d;
 #pragma unroll
   for (int i = 0; i < 3; ++i)
     if (q < s[1] + delta) q += two_d;
   return q + PAYLOAD_BIAS;
+}
+
+WM_HD float payload_target(const float (&s)[8], const int bit, const float delta) {
+  const float two_d = 2.0f * delta, b = bit ? delta : 0.0f;
+  return payload_lift(ffma(two_d, rintf((s[0] - b) / two_d), b), s, delta);
 }
 
 // The sigma_w row the unchanged embed is fed with alpha = 1, K = 1: (target - s_1, 0, .., 0)
@@ -1443,14 +1448,50 @@ WM_HD void payload_sigma_w(const float (&s)[8], const int bit, const float delta
   for (int i = 1; i < 8; ++i) sw[i] = 0.0f;
 }
 
+// ---- keyed dither ("Keyed dither"; include/wmhip.h) ----------
+// Every tile's lattice is shifted by a secret offset d in [0, 2 delta), from the tile's 16-bit dither word u (the caller's
+// keyed table): d = float(u) * (delta * 2^-15).  The step delta * 2^-15 is exact; the product is ONE float32 multiply,
+// rounded on its own - the value passes through an empty asm statement so that no compiler contracts it into the add or the
+// subtraction that follows, and host, device and a NumPy restatement agree bit for bit.  u = 0 gives d = +0 and, through
+// the forms below, today's results to the bit (b + 0 = b, s_1 - 0 = s_1).
+WM_HD float payload_dither(const uint16_t u, const float delta) {
+  float d = (float)u * (delta * (1.0f / 32768.0f));
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(d));
+#elif defined(__GNUC__)
+  asm("" : "+m"(d));
+#endif
+  return d;
+}
+
+// payload_target on the shifted lattice {2 k delta + bit * delta + d}: b' = bit * delta + d is one float32 add, the lattice
+// point one fused multiply-add as above; the cap and the climb are unchanged.
+WM_HD float payload_target(const float (&s)[8], const int bit, const float delta, const float d) {
+  const float two_d = 2.0f * delta, b = (bit ? delta : 0.0f) + d;
+  return payload_lift(ffma(two_d, rintf((s[0] - b) / two_d), b), s, delta);
+}
+
+WM_HD void payload_sigma_w(const float (&s)[8], const int bit, const float delta, const float d, float (&sw)[8]) {
+  sw[0] = payload_target(s, bit, delta, d) - s[0];
+#pragma unroll
+  for (int i = 1; i < 8; ++i) sw[i] = 0.0f;
+}
+
 // The decoder's soft value of a stego tile: +1 on a bit-0 lattice point, -1 on a bit-1 point, linear in between (0 half
 // way).  The multiply by the float32 reciprocal of 2 delta is the one place a compiler could not change the result of: x -
-// floor(x) is exact, and the doublings are exact, so 2 f - 1 and 2 |.| - 1 round the same fused or not.  Host, device and a
-// NumPy restatement agree bit for bit.
+// floor(x) is exact, and the doublings are exact, so 2 f - 1 and 2 |.| - 1 round the same fused or not.  The host build and a
+// NumPy restatement agree bit for bit; so does the device where 1 / (2 delta) is a power of two (the default 16 among them).
+// For any other delta the device compiler contracts x - floor(x) into one fused multiply-add on the unrounded product, and m
+// lies within 4 * 2^-19 of the restatement's (tests/test_gpu_payload_dither.py) - far inside the sigma bar, in both forms.
 WM_HD float payload_metric(const float s1, const float inv_2delta) {
   const float x = s1 * inv_2delta;
   const float f = x - floorf(x);
   return 2.0f * fabsf(2.0f * f - 1.0f) - 1.0f;
+}
+
+// The same of a tile whose lattice is shifted by d: x = (s_1 - d) * (1 / (2 delta)), one subtraction and one multiply
+WM_HD float payload_metric(const float s1, const float inv_2delta, const float d) {
+  return payload_metric(s1 - d, inv_2delta);
 }
 
 }  // namespace wm

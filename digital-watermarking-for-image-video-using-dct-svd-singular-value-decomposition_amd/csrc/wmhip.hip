@@ -892,6 +892,27 @@ struct EpiPayloadSigmaW {
   }
 };
 
+// The same on the keyed lattice (wm_tile_math.h, payload_dither): tile t of a plane reads its 16-bit dither word from
+// tile_dither[plane * dither_plane_stride + t] - stride 0 for a table shared by the planes, n_tiles or more for one table
+// per plane, as sigma_w_plane_stride - 2 bytes beside the tile's 64.  A struct of its own: the dither-free kernel keeps its
+// arguments and its registers.
+struct EpiPayloadSigmaWDither {
+  const uint8_t* __restrict__ tile_bit;
+  const uint16_t* __restrict__ tile_dither;
+  float* __restrict__ sw_eff;
+  uint8_t* __restrict__ black;
+  size_t dither_plane_stride;
+  float delta;
+  __device__ __forceinline__ void operator()(const wm::RawTile& raw, const float (&s)[8], const size_t plane, const int t,
+                                             const size_t ti) const {
+    float sw[8];
+    const float d = wm::payload_dither(tile_dither[plane * dither_plane_stride + (size_t)t], delta);
+    wm::payload_sigma_w(s, tile_bit[t] & 1, delta, d, sw);
+    store_row8_f32<true>(sw_eff + ti * 8, sw);
+    if (black) black[ti] = (wm::raw_is_constant(raw) && raw.lo[0] == 0u) ? 1 : 0;
+  }
+};
+
 // A black cover tile is the zero matrix: it has no leading singular vector of its own, and the embed's closed form for
 // constant tiles gives it those of a fixed noise pattern, half of whose pixels clip at 0 - sigma_1 of the stored tile lands
 // far from what was aimed at (the payload's lattice point; the masked rule's alpha sw_1, which then reads back a third
@@ -929,6 +950,19 @@ struct EpiPayloadMetric {
   float inv_2delta;
   __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], size_t, int, const size_t ti) const {
     metric[ti] = wm::payload_metric(s[0], inv_2delta);
+  }
+};
+
+// The metric on the keyed lattice: the tile's dither word as in EpiPayloadSigmaWDither
+struct EpiPayloadMetricDither {
+  float* __restrict__ metric;
+  const uint16_t* __restrict__ tile_dither;
+  size_t dither_plane_stride;
+  float delta, inv_2delta;
+  __device__ __forceinline__ void operator()(const wm::RawTile&, const float (&s)[8], const size_t plane, const int t,
+                                             const size_t ti) const {
+    const float d = wm::payload_dither(tile_dither[plane * dither_plane_stride + (size_t)t], delta);
+    metric[ti] = wm::payload_metric(s[0], inv_2delta, d);
   }
 };
 
@@ -1061,10 +1095,11 @@ size_t n_sigma_w(size_t nt, int n_planes, size_t sigma_w_plane_stride) {
 }
 
 // The round trip of the plain, the masked and the payload embed.  `rule` is the per-tile input of the form (sigma_w, or
-// the payload's tile bits: n_rule elements), dev(d_host, d_rule, d_stego, d_sc, d_yw) its _dev call.
-template <typename T, typename Dev>
+// the payload's tile bits: n_rule elements), dev(d_host, d_rule, d_stego, d_sc, d_yw) its _dev call.  `more(cv)` stages
+// what a form takes beside them (the payload's dither table) behind the shared arrays.
+template <typename T, typename Dev, typename More>
 int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_rule, uint8_t* stego, float* sigma_c, float* yw,
-                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev) {
+                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev, const More& more) {
   const size_t nt = (size_t)(H / 8) * (W / 8);
   const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
   uint8_t *d_host, *d_stego; T* d_rule; float *d_sc, *d_yw;
@@ -1079,7 +1114,13 @@ int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_r
     d_rule = cv.in(n_rule, rule);
     d_sc = cv.out((size_t)n_planes * nt * 8, sigma_c);
     d_yw = yw ? cv.out((size_t)n_planes * H * W, yw) : nullptr;
+    more(cv);
   }, [&] { return dev(d_host, d_rule, d_stego, d_sc, d_yw); });
+}
+template <typename T, typename Dev>
+int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_rule, uint8_t* stego, float* sigma_c, float* yw,
+                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev) {
+  return embed_round_trip(ctx, host, rule, n_rule, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, dev, [](Carve&) {});
 }
 
 }  // namespace
@@ -1327,26 +1368,71 @@ int wm_mask_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const float
 }
 
 // ---- blind payload: sigma pass + target, sigma pass + metric -----------------------
-static int payload_sigma_w_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff, uint8_t* black,
-                               int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+// The keyed dither of a payload call (include/wmhip.h): `on` false for the dither-free entry points, else the table of 16-bit
+// words and its plane stride.  bad_dither: the message where the table cannot serve n_tiles tiles a plane, else nullptr -
+// it only counts where there is a tile (sigma_pass).
+struct Dither {
+  bool on;
+  const uint16_t* table;
+  size_t plane_stride;
+};
+constexpr Dither NO_DITHER{false, nullptr, 0};
+
+static const char* bad_dither(const Dither& dz, int H, int W) {
+  if (!dz.on) return nullptr;
+  if (!dz.table || ((uintptr_t)dz.table & 1u)) return "tile_dither is NULL or not 2-byte aligned";
+  if (dz.plane_stride != 0 && dz.plane_stride < (size_t)(H / 8) * (size_t)(W / 8))
+    return "dither_plane_stride must be 0 (shared) or at least n_tiles";
+  return nullptr;
+}
+
+static int payload_sigma_w_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const Dither& dz, float* sigma_w_eff,
+                               uint8_t* black, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   const char* bad = !tile_bit ? "tile_bit is NULL"
-                    : (!sigma_w_eff || ((uintptr_t)sigma_w_eff & 15u)) ? "sigma_w_eff is NULL or not 16-byte aligned" : nullptr;
+                    : (!sigma_w_eff || ((uintptr_t)sigma_w_eff & 15u)) ? "sigma_w_eff is NULL or not 16-byte aligned"
+                    : bad_dither(dz, H, W);
+  if (dz.on)
+    return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad,
+                      EpiPayloadSigmaWDither{tile_bit, dz.table, sigma_w_eff, black, dz.plane_stride, delta});
   return sigma_pass(ctx, planes, n_planes, H, W, row_stride, plane_stride, bad, EpiPayloadSigmaW{tile_bit, sigma_w_eff, black, delta});
+}
+
+static int payload_metric_dev(wm_ctx* ctx, const uint8_t* stego, const Dither& dz, float* metric, int n_planes, int H, int W,
+                              int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const char* bad = (!metric || ((uintptr_t)metric & 3u)) ? "metric is NULL or not 4-byte aligned" : bad_dither(dz, H, W);
+  const float inv_2delta = 1.0f / (2.0f * delta);
+  if (dz.on)
+    return sigma_pass(ctx, stego, n_planes, H, W, row_stride, plane_stride, bad,
+                      EpiPayloadMetricDither{metric, dz.table, dz.plane_stride, delta, inv_2delta});
+  return sigma_pass(ctx, stego, n_planes, H, W, row_stride, plane_stride, bad, EpiPayloadMetric{metric, inv_2delta});
 }
 
 int wm_payload_sigma_w_tiles_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
                                     int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
-  return payload_sigma_w_dev(ctx, planes, tile_bit, sigma_w_eff, nullptr, n_planes, H, W, row_stride, plane_stride, delta);
+  return payload_sigma_w_dev(ctx, planes, tile_bit, NO_DITHER, sigma_w_eff, nullptr, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_sigma_w_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                           float* sigma_w_eff, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                           size_t dither_plane_stride, float delta) {
+  return payload_sigma_w_dev(ctx, planes, tile_bit, Dither{true, tile_dither, dither_plane_stride}, sigma_w_eff, nullptr, n_planes,
+                             H, W, row_stride, plane_stride, delta);
 }
 
 int wm_payload_metric_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
                                    int row_stride, size_t plane_stride, float delta) {
-  WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
-  WM_TRY(check_delta(delta));
-  const char* bad = (!metric || ((uintptr_t)metric & 3u)) ? "metric is NULL or not 4-byte aligned" : nullptr;
-  return sigma_pass(ctx, stego, n_planes, H, W, row_stride, plane_stride, bad, EpiPayloadMetric{metric, 1.0f / (2.0f * delta)});
+  return payload_metric_dev(ctx, stego, NO_DITHER, metric, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_metric_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, float* metric,
+                                          int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                          size_t dither_plane_stride, float delta) {
+  return payload_metric_dev(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, metric, n_planes, H, W, row_stride,
+                            plane_stride, delta);
 }
 
 // ---- K1 fed with a sigma_w derived from the cover (embed_derived_dev): the masked and the payload embed ----------
@@ -1362,19 +1448,33 @@ int wm_embed_tiles_masked_u8_dev(wm_ctx* ctx, const uint8_t* host, const float* 
   });
 }
 
-int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
-                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+static int embed_payload_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const Dither& dz, uint8_t* stego,
+                            float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                            float delta) {
   WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
-  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, 1.0f, 1,
-                           (!tile_bit || !sigma_c) ? "tile_bit / sigma_c is NULL" : nullptr, [&](float* eff, uint8_t* black) {
-    return payload_sigma_w_dev(ctx, host, tile_bit, eff, black, n_planes, H, W, row_stride, plane_stride, delta);
+  const char* missing = (!tile_bit || !sigma_c) ? "tile_bit / sigma_c is NULL" : bad_dither(dz, H, W);
+  return embed_derived_dev(ctx, host, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, 1.0f, 1, missing,
+                           [&](float* eff, uint8_t* black) {
+    return payload_sigma_w_dev(ctx, host, tile_bit, dz, eff, black, n_planes, H, W, row_stride, plane_stride, delta);
   });
 }
 
+int wm_embed_tiles_payload_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                                  float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return embed_payload_dev(ctx, host, tile_bit, NO_DITHER, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_embed_tiles_payload_dither_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                         uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                                         size_t plane_stride, size_t dither_plane_stride, float delta) {
+  return embed_payload_dev(ctx, host, tile_bit, Dither{true, tile_dither, dither_plane_stride}, stego, sigma_c, yw, n_planes, H, W,
+                           row_stride, plane_stride, delta);
+}
+
 // the metric into the context's grow-only workspace, then one wave per bit over it
-int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
-                                 double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+static int payload_soft_dev(wm_ctx* ctx, const uint8_t* stego, const Dither& dz, const int32_t* order, const int32_t* offs,
+                            int n_bits, double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   const size_t nt = (size_t)(H / 8) * (size_t)(W / 8);
@@ -1382,15 +1482,28 @@ int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_
   if (n_bits < 1 || (size_t)n_bits > nt) return set_err(WM_ERR_BADARG, "n_bits must be in 1..n_tiles");
   if (!order || !offs || !soft || (((uintptr_t)order | (uintptr_t)offs) & 3u) || ((uintptr_t)soft & 7u))
     return set_err(WM_ERR_BADARG, "order / offs / soft is NULL or misaligned");
+  if (const char* bad = bad_dither(dz, H, W)) return set_err(WM_ERR_BADARG, "%s", bad);      // (before the workspace grows)
   float* metric = nullptr;
   WM_TRY(staged(ctx, &ctx->sigma_ws, &ctx->sigma_ws_bytes, "payload metric", [&](Carve& cv) {
     metric = cv.take<float>((size_t)n_planes * nt);
   }));
-  WM_TRY(wm_payload_metric_tiles_u8_dev(ctx, stego, metric, n_planes, H, W, row_stride, plane_stride, delta));
+  WM_TRY(payload_metric_dev(ctx, stego, dz, metric, n_planes, H, W, row_stride, plane_stride, delta));
   hipLaunchKernelGGL(k_payload_reduce, dim3((unsigned)n_bits), dim3(WAVE), 0, ctx->stream, (const float*)metric,
                      (const int*)order, (const int*)offs, soft, (int)nt, n_planes);
   WM_HIP(hipGetLastError());
   return WM_OK;
+}
+
+int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                                 double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return payload_soft_dev(ctx, stego, NO_DITHER, order, offs, n_bits, soft, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_soft_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, const int32_t* order,
+                                        const int32_t* offs, int n_bits, double* soft, int n_planes, int H, int W, int row_stride,
+                                        size_t plane_stride, size_t dither_plane_stride, float delta) {
+  return payload_soft_dev(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, order, offs, n_bits, soft, n_planes, H, W,
+                          row_stride, plane_stride, delta);
 }
 
 // ---- K3 --------------------------------------------------------------------
@@ -1806,53 +1919,108 @@ int wm_detect_tiles_masked_u8(wm_ctx* ctx, const uint8_t* stego, const float* si
 }
 
 // ---- blind payload, host pointers ---------------------------------------------
-int wm_payload_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+// Each form once, with the call's Dither (here `table` is the caller's HOST array): the dither-free entry point passes
+// NO_DITHER, the dithered one its table, which is staged like the other inputs - n_dither() words.
+static size_t n_dither(const Dither& dz, size_t nt, int n_planes) {
+  return !dz.on || !nt || !n_planes ? 0 : dz.plane_stride ? (size_t)(n_planes - 1) * dz.plane_stride + nt : nt;
+}
+
+static int payload_sigma_w_host(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const Dither& dz, float* sigma_w_eff,
                                 int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, planes, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!tile_bit || !sigma_w_eff) return set_err(WM_ERR_BADARG, "tile_bit / sigma_w_eff is NULL");
-  uint8_t *d_p, *d_bit; float* d_eff;
+  if (const char* bad = bad_dither(dz, H, W)) return set_err(WM_ERR_BADARG, "%s", bad);
+  uint8_t *d_p, *d_bit; float* d_eff; uint16_t* d_dz;
   return staged_call(ctx, [&](Carve& cv) {
     d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), planes);
     d_bit = cv.in(nt, tile_bit);
     d_eff = cv.out((size_t)n_planes * nt * 8, sigma_w_eff);
-  }, [&] { return wm_payload_sigma_w_tiles_u8_dev(ctx, d_p, d_bit, d_eff, n_planes, H, W, row_stride, plane_stride, delta); });
+    d_dz = cv.in(n_dither(dz, nt, n_planes), dz.table);
+  }, [&] {
+    return payload_sigma_w_dev(ctx, d_p, d_bit, Dither{dz.on, d_dz, dz.plane_stride}, d_eff, nullptr, n_planes, H, W, row_stride,
+                               plane_stride, delta);
+  });
 }
 
-int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
-                              float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+int wm_payload_sigma_w_tiles_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, float* sigma_w_eff,
+                                int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return payload_sigma_w_host(ctx, planes, tile_bit, NO_DITHER, sigma_w_eff, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_sigma_w_tiles_dither_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                       float* sigma_w_eff, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                       size_t dither_plane_stride, float delta) {
+  return payload_sigma_w_host(ctx, planes, tile_bit, Dither{true, tile_dither, dither_plane_stride}, sigma_w_eff, n_planes, H, W,
+                              row_stride, plane_stride, delta);
+}
+
+static int embed_payload_host(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const Dither& dz, uint8_t* stego,
+                              float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                              float delta) {
   WM_TRY(check_plane_args(ctx, host, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   if (!stego) return set_err(WM_ERR_BADARG, "stego is NULL");
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (nt > 0 && (!tile_bit || !sigma_c)) return set_err(WM_ERR_BADARG, "tile_bit / sigma_c is NULL");
+  if (nt > 0)
+    if (const char* bad = bad_dither(dz, H, W)) return set_err(WM_ERR_BADARG, "%s", bad);
+  uint16_t* d_dz = nullptr;
   return embed_round_trip(ctx, host, tile_bit, nt, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride,
                           [&](uint8_t* d_host, uint8_t* d_bit, uint8_t* d_stego, float* d_sc, float* d_yw) {
-    return wm_embed_tiles_payload_u8_dev(ctx, d_host, d_bit, d_stego, d_sc, d_yw, n_planes, H, W, row_stride, plane_stride, delta);
-  });
+    return embed_payload_dev(ctx, d_host, d_bit, Dither{dz.on, d_dz, dz.plane_stride}, d_stego, d_sc, d_yw, n_planes, H, W,
+                             row_stride, plane_stride, delta);
+  }, [&](Carve& cv) { d_dz = cv.in(n_dither(dz, nt, n_planes), dz.table); });
 }
 
-int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+int wm_embed_tiles_payload_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, uint8_t* stego, float* sigma_c,
+                              float* yw, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return embed_payload_host(ctx, host, tile_bit, NO_DITHER, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_embed_tiles_payload_dither_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                     uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                                     size_t plane_stride, size_t dither_plane_stride, float delta) {
+  return embed_payload_host(ctx, host, tile_bit, Dither{true, tile_dither, dither_plane_stride}, stego, sigma_c, yw, n_planes, H, W,
+                            row_stride, plane_stride, delta);
+}
+
+static int payload_metric_host(wm_ctx* ctx, const uint8_t* stego, const Dither& dz, float* metric, int n_planes, int H, int W,
                                int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   const size_t nt = (size_t)(H / 8) * (W / 8);
   if (n_planes == 0 || nt == 0) return WM_OK;
   if (!metric) return set_err(WM_ERR_BADARG, "metric is NULL");
-  uint8_t* d_p; float* d_m;
+  if (const char* bad = bad_dither(dz, H, W)) return set_err(WM_ERR_BADARG, "%s", bad);
+  uint8_t* d_p; float* d_m; uint16_t* d_dz;
   return staged_call(ctx, [&](Carve& cv) {
     d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), stego);
     d_m = cv.out((size_t)n_planes * nt, metric);
-  }, [&] { return wm_payload_metric_tiles_u8_dev(ctx, d_p, d_m, n_planes, H, W, row_stride, plane_stride, delta); });
+    d_dz = cv.in(n_dither(dz, nt, n_planes), dz.table);
+  }, [&] {
+    return payload_metric_dev(ctx, d_p, Dither{dz.on, d_dz, dz.plane_stride}, d_m, n_planes, H, W, row_stride, plane_stride, delta);
+  });
+}
+
+int wm_payload_metric_tiles_u8(wm_ctx* ctx, const uint8_t* stego, float* metric, int n_planes, int H, int W,
+                               int row_stride, size_t plane_stride, float delta) {
+  return payload_metric_host(ctx, stego, NO_DITHER, metric, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_metric_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, float* metric, int n_planes,
+                                      int H, int W, int row_stride, size_t plane_stride, size_t dither_plane_stride, float delta) {
+  return payload_metric_host(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, metric, n_planes, H, W, row_stride,
+                             plane_stride, delta);
 }
 
 // The host form sees order / offs and checks them: offs runs from 0 to n_tiles without decreasing, every order entry names
 // a tile of the grid (the device form takes both as they are and only refuses to follow an entry outside the grid).
-int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
-                             double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+static int payload_soft_host(wm_ctx* ctx, const uint8_t* stego, const Dither& dz, const int32_t* order, const int32_t* offs,
+                             int n_bits, double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, H, W, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
   if (n_planes == 0 || H == 0 || W == 0) return WM_OK;
@@ -1864,15 +2032,30 @@ int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* o
     if (offs[j + 1] < offs[j]) return set_err(WM_ERR_BADARG, "offs decreases");
   for (size_t i = 0; i < nt; ++i)
     if (order[i] < 0 || (size_t)order[i] >= nt) return set_err(WM_ERR_BADARG, "order names a tile outside the grid");
-  uint8_t* d_p; int32_t *d_order, *d_offs; double* d_soft;
+  if (const char* bad = bad_dither(dz, H, W)) return set_err(WM_ERR_BADARG, "%s", bad);
+  uint8_t* d_p; int32_t *d_order, *d_offs; double* d_soft; uint16_t* d_dz;
   return staged_call(ctx, [&](Carve& cv) {
     d_p = cv.in(plane_span(n_planes, H, row_stride, plane_stride, W), stego);
     d_order = cv.in(nt, order);
     d_offs = cv.in((size_t)n_bits + 1, offs);
     d_soft = cv.out((size_t)n_bits, soft);
+    d_dz = cv.in(n_dither(dz, nt, n_planes), dz.table);
   }, [&] {
-    return wm_payload_soft_tiles_u8_dev(ctx, d_p, d_order, d_offs, n_bits, d_soft, n_planes, H, W, row_stride, plane_stride, delta);
+    return payload_soft_dev(ctx, d_p, Dither{dz.on, d_dz, dz.plane_stride}, d_order, d_offs, n_bits, d_soft, n_planes, H, W,
+                            row_stride, plane_stride, delta);
   });
+}
+
+int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
+                             double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta) {
+  return payload_soft_host(ctx, stego, NO_DITHER, order, offs, n_bits, soft, n_planes, H, W, row_stride, plane_stride, delta);
+}
+
+int wm_payload_soft_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, const int32_t* order,
+                                    const int32_t* offs, int n_bits, double* soft, int n_planes, int H, int W, int row_stride,
+                                    size_t plane_stride, size_t dither_plane_stride, float delta) {
+  return payload_soft_host(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, order, offs, n_bits, soft, n_planes, H, W,
+                           row_stride, plane_stride, delta);
 }
 
 }  // extern "C"

@@ -374,9 +374,16 @@ def _payload_map_of(H: int, W: int, key: bytes, n_bits: int):
     return P.payload_map(H // TILE, W // TILE, key, n_bits)
 
 
+def _payload_dither_of(H: int, W: int, key: bytes, on) -> Optional[np.ndarray]:
+    """the image's keyed dither words (frame index 0), or None for the dither-free rule"""
+    return P.dither_table(H // TILE, W // TILE, key) if on else None
+
+
 def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: bytes, *, payload_type: str = "text",
-                         delta: float = P.DELTA_DEFAULT, device: int = 0, verify: bool = True) -> dict:
+                         delta: float = P.DELTA_DEFAULT, device: int = 0, verify: bool = True, dither: bool = False) -> dict:
     """cover BGR uint8, data bytes (or a str: the text / JSON itself).  Returns dict(stego BGR uint8, meta dict, psnr, ssim).
+    ``dither``: every tile's lattice is shifted by a keyed offset (payload.dither_table), so that the stego shows neither
+    the payload's presence nor delta to a reader without the password; the meta says so and the extract follows it.
     ``verify``: the stego is decoded by the extract's own path before it is returned, and a payload that does not come back
     valid and equal to ``data`` is a ValueError (tiles pinned by clipping vote for the wrong bit: DESIGN.md section 14)."""
     M.check_password_type(password, "embed")
@@ -392,12 +399,13 @@ def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: byte
     tbi, order, offs = _payload_map_of(H, W, key, bits.size)
     ctx = _ctx(device)
     Y = _Gray.planes_in(ctx, cover_bgr)                                    # core:117 (_to_Y)
-    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(bits, tbi), delta, want_yw=True)
-    members = M.payload_members(payload_type, H, W, delta, bits.size, nonce)
+    dz = _payload_dither_of(H, W, key, dither)
+    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(bits, tbi), delta, want_yw=True, dither=dz)
+    members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, dither=P.DITHER_TABLE if dither else 0)
     digest = hg.hmac_digest(key, M.hmac_parts(members))
     stego = _Gray.planes_out(ctx, cover_bgr, stego_y)                      # core:123 (_from_Y)
     if verify:                                                             # one metric and reduce pass on the final BGR stego
-        P.check_decodes(ctx.payload_soft(_Gray.planes_in(ctx, stego), order, offs, bits.size, delta), bits, data)
+        P.check_decodes(ctx.payload_soft(_Gray.planes_in(ctx, stego), order, offs, bits.size, delta, dither=dz), bits, data)
     ps = ctx.psnr(cover_bgr, stego)
     ss = ctx.ssim(ctx.color("bgr2gray", cover_bgr), Yw)
     return dict(stego=stego, meta=M.sealed(members, TILE, digest), psnr=ps, ssim=ss)
@@ -428,18 +436,19 @@ def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: i
     _check_stego_shape(stego_bgr, meta)
     _, order, offs = _payload_map_of(H, W, key, n_bits)
     ctx = _ctx(device)
-    soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, n_bits, delta)
+    dz = _payload_dither_of(H, W, key, M.payload_dither_of(meta))
+    soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, n_bits, delta, dither=dz)
     data, valid = P.payload_unframe(soft < 0)
     return data, bool(valid), P.confidence(soft, offs, 1)
 
 
 def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, password: Optional[str] = None,
                   payload_type: str = "text", delta: float = P.DELTA_DEFAULT, nonce: Optional[bytes] = None, device: int = 0,
-                  verify: bool = True):
+                  verify: bool = True, dither: bool = False):
     """``payload``: a str or bytes, or the path of a .txt / .json file (read when it exists, like the reference's
     text_data / wm_source, core:102-106).  Returns (out_path, meta_path, psnr, ssim); the stego is written as PNG.
     ``verify`` as in embed_payload_arrays: a payload that does not decode from its own stego raises, and neither the
-    stego nor the meta is written."""
+    stego nor the meta is written.  ``dither`` as there."""
     M.check_password_type(password, "embed")
     M.require_password(password, "embed")
     hostapi.check_delta(delta)
@@ -448,7 +457,8 @@ def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, pa
     if nonce is None:
         nonce = os.urandom(8)
     # (a json payload is canonical by now; canonicalising it again inside leaves it as it is)
-    r = embed_payload_arrays(cover, data, password, nonce, payload_type=payload_type, delta=delta, device=device, verify=verify)
+    r = embed_payload_arrays(cover, data, password, nonce, payload_type=payload_type, delta=delta, device=device, verify=verify,
+                             dither=dither)
     out_path = M.out_name(out_path, "_stego.png")
     if not hg.write_png(out_path, r["stego"], 0):
         raise IOError("Ghi stego thất bại.")

@@ -94,6 +94,15 @@ SIGNATURES = {
     "wm_payload_metric_tiles_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
     "wm_payload_soft_tiles_u8_dev": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _f],
     "wm_payload_soft_tiles_u8": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _f],
+    # the same with keyed dither: tile_dither after the tile bits / the stego, dither_plane_stride before delta
+    "wm_payload_sigma_w_tiles_dither_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_payload_sigma_w_tiles_dither_u8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_embed_tiles_payload_dither_u8_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_embed_tiles_payload_dither_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_payload_metric_tiles_dither_u8_dev": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_payload_metric_tiles_dither_u8": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_payload_soft_tiles_dither_u8_dev": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    "wm_payload_soft_tiles_dither_u8": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _sz, _f],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -274,6 +283,21 @@ def _tile_bits(tile_bit, n_tiles: int) -> np.ndarray:
     return tb.astype(np.uint8)
 
 
+def _dither_words(dither, n_planes: int, n_tiles: int):
+    """``dither=`` of a payload call as the ABI takes it: None (the dither-free rule), else (uint16 words, plane stride) of a
+    [n_tiles] table shared by the planes (stride 0) or an [N, n_tiles] one with a row per plane (stride n_tiles)."""
+    if dither is None:
+        return None
+    d = np.ascontiguousarray(dither)
+    if d.dtype != np.uint16:
+        raise ValueError("dither must be uint16")
+    if d.shape == (n_tiles,):
+        return d, 0
+    if d.shape == (n_planes, n_tiles):
+        return d, n_tiles
+    raise ValueError(f"dither has shape {d.shape} for {n_planes} planes of {n_tiles} tiles: [n_tiles] or [N, n_tiles]")
+
+
 def check_payload_csr(order, offs, n_bits: int, n_tiles: int):
     """(order int32 [n_tiles], offs int32 [n_bits + 1]) of a tile-to-bit map, checked as the host-pointer entry point checks
     them: 1 <= n_bits <= n_tiles, offs from 0 to n_tiles without decreasing, every order entry a tile of the grid."""
@@ -312,7 +336,8 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None):
-            for ent in self.__dict__.pop("_idx_cache", []) + self.__dict__.pop("_payload_cache", []):
+            for ent in (self.__dict__.pop("_idx_cache", []) + self.__dict__.pop("_payload_cache", [])
+                        + self.__dict__.pop("_dither_cache", [])):
                 self._drop_index(ent)
             for d in self.__dict__.pop("_enh_bufs", (0, 0, 0))[1:]:
                 self.lib.wm_free(self._h, _vp(d))
@@ -478,39 +503,53 @@ class Context:
         return g[0] if planes.ndim == 2 else g
 
     # ---- blind payload: raw-bit level (include/wmhip.h; the framing and the keyed map are payload.py's) ----------------
-    def payload_sigma_w(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float) -> np.ndarray:
+    def payload_sigma_w(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float, dither=None) -> np.ndarray:
         """The rule's sigma_w rows (target - s_1, 0, .., 0) of uint8 planes [H,W] / [N,H,W] whose tile t carries
-        tile_bit[t] -> float32 [N?, nby, nbx, 8]."""
+        tile_bit[t] -> float32 [N?, nby, nbx, 8].  ``dither`` (here and below): the keyed dither words, uint16 [n_tiles]
+        shared by the planes or [N, n_tiles] with a row per plane; None is the dither-free rule."""
         delta = check_delta(delta)
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
         nby, nbx = H // TILE, W // TILE
         tb = _tile_bits(tile_bit, nby * nbx)
+        dz = _dither_words(dither, n, nby * nbx)
         eff = np.empty((n, nby, nbx, 8), np.float32)
-        self._call("wm_payload_sigma_w_tiles_u8", _p(planes), _p(tb), _p(eff), n, H, W, rs, ps, delta)
+        if dz is None:
+            self._call("wm_payload_sigma_w_tiles_u8", _p(planes), _p(tb), _p(eff), n, H, W, rs, ps, delta)
+        else:
+            self._call("wm_payload_sigma_w_tiles_dither_u8", _p(planes), _p(tb), _p(dz[0]), _p(eff), n, H, W, rs, ps, dz[1], delta)
         return eff[0] if planes.ndim == 2 else eff
 
-    def embed_tiles_payload(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float, want_yw: bool = False):
+    def embed_tiles_payload(self, planes: np.ndarray, tile_bit: np.ndarray, delta: float, want_yw: bool = False, dither=None):
         """One bit per tile into the parity of sigma_1 on the lattice of step delta; every plane carries the same bits.
         Returns (stego uint8, the cover's sigma_c float32 [N?, nby, nbx, 8], yw or None) like embed_tiles."""
         delta = check_delta(delta)
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
         nby, nbx = H // TILE, W // TILE
         tb = _tile_bits(tile_bit, nby * nbx)
+        dz = _dither_words(dither, n, nby * nbx)
         stego = np.empty((n, H, W), np.uint8)
         sc = np.empty((n, nby, nbx, 8), np.float32)
         yw = np.empty((n, H, W), np.float32) if want_yw else None
         hostc = np.ascontiguousarray(planes.reshape(n, H, W))
-        self._call("wm_embed_tiles_payload_u8", _p(hostc), _p(tb), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W, delta)
+        if dz is None:
+            self._call("wm_embed_tiles_payload_u8", _p(hostc), _p(tb), _p(stego), _p(sc), _p(yw), n, H, W, W, H * W, delta)
+        else:
+            self._call("wm_embed_tiles_payload_dither_u8", _p(hostc), _p(tb), _p(dz[0]), _p(stego), _p(sc), _p(yw), n, H, W, W,
+                       H * W, dz[1], delta)
         if planes.ndim == 2:
             return stego[0], sc[0], (yw[0] if want_yw else None)
         return stego, sc, yw
 
-    def payload_metric(self, planes: np.ndarray, delta: float) -> np.ndarray:
+    def payload_metric(self, planes: np.ndarray, delta: float, dither=None) -> np.ndarray:
         """The decoder's soft value m of every tile -> float32 [N?, nby, nbx]."""
         delta = check_delta(delta)
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        dz = _dither_words(dither, n, (H // TILE) * (W // TILE))
         m = np.empty((n, H // TILE, W // TILE), np.float32)
-        self._call("wm_payload_metric_tiles_u8", _p(planes), _p(m), n, H, W, rs, ps, delta)
+        if dz is None:
+            self._call("wm_payload_metric_tiles_u8", _p(planes), _p(m), n, H, W, rs, ps, delta)
+        else:
+            self._call("wm_payload_metric_tiles_dither_u8", _p(planes), _p(dz[0]), _p(m), n, H, W, rs, ps, dz[1], delta)
         return m[0] if planes.ndim == 2 else m
 
     def _payload_csr_dev(self, order: np.ndarray, offs: np.ndarray):
@@ -532,26 +571,57 @@ class Context:
             self._drop_index(old)
         return d, d_offs
 
-    def payload_soft(self, planes: np.ndarray, order: np.ndarray, offs: np.ndarray, n_bits: int, delta: float) -> np.ndarray:
+    def _payload_dither_dev(self, words: np.ndarray) -> int:
+        """Device copy of a dither table shared by the planes, kept like the CSR above (a list of its own, two entries,
+        keyed by content): a video decodes batch after batch of one frame size under few tables."""
+        cache = self.__dict__.setdefault("_dither_cache", [])
+        tag = ("dither", words.size, hashlib.blake2b(words.view(np.uint8), digest_size=16).digest())
+        for ent in cache:
+            if ent["tag"] == tag:
+                return ent["d"]
+        d = self.malloc(max(words.nbytes, 2))
+        self.h2d(d, words)
+        cache.append({"tag": tag, "d": d, "route": None})
+        while len(cache) > 2:
+            old = cache.pop(0)
+            self.sync()
+            self._drop_index(old)
+        return d
+
+    def payload_soft(self, planes: np.ndarray, order: np.ndarray, offs: np.ndarray, n_bits: int, delta: float,
+                     dither=None) -> np.ndarray:
         """soft[j] = sum over the planes and over the tiles order[offs[j] : offs[j + 1]] of the decoder's m -> float64
         [n_bits]; bit j decodes to soft[j] < 0.  The planes stay on the device; only n_bits doubles come back."""
         delta = check_delta(delta)
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
         order, offs = check_payload_csr(order, offs, n_bits, (H // TILE) * (W // TILE))
+        dz = _dither_words(dither, n, (H // TILE) * (W // TILE))
         soft = np.zeros(int(n_bits), np.float64)
         if n == 0:
             return soft
         d_order, d_offs = self._payload_csr_dev(order, offs)
         p = np.ascontiguousarray(planes.reshape(n, H, W))
         d_p = self.malloc(p.nbytes); d_soft = self.malloc(soft.nbytes)
+        d_own = 0                                                           # a per-plane table lives for this call only
         try:
             self.h2d(d_p, p)
-            self._call("wm_payload_soft_tiles_u8_dev", _vp(d_p), _vp(d_order), _vp(d_offs), int(n_bits), _vp(d_soft),
-                       n, H, W, W, H * W, delta)
+            if dz is None:
+                self._call("wm_payload_soft_tiles_u8_dev", _vp(d_p), _vp(d_order), _vp(d_offs), int(n_bits), _vp(d_soft),
+                           n, H, W, W, H * W, delta)
+            else:
+                if dz[1] == 0:
+                    d_dz = self._payload_dither_dev(dz[0])
+                else:
+                    d_dz = d_own = self.malloc(dz[0].nbytes)
+                    self.h2d(d_dz, dz[0])
+                self._call("wm_payload_soft_tiles_dither_u8_dev", _vp(d_p), _vp(d_dz), _vp(d_order), _vp(d_offs), int(n_bits),
+                           _vp(d_soft), n, H, W, W, H * W, dz[1], delta)
             self.d2h(soft, d_soft)
             self.check_status()
         finally:
             self.free(d_p); self.free(d_soft)
+            if d_own:
+                self.free(d_own)
         return soft
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:

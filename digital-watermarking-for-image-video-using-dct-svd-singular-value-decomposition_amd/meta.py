@@ -56,9 +56,11 @@ _ORDER = {
 }
 # A blind payload (payload.py, include/wmhip.h): the rule's step, the bit count and the key's nonce - no Sc, Uw or Vwt, so the
 # file's size depends neither on the image size nor on the frame count.  A video writes frame_interval and n_frames too
-# (and chroma, should a colour container ever be named); payload_type is "text", "json" or "bytes".
+# (and chroma, should a colour container ever be named); payload_type is "text", "json" or "bytes".  ``dither`` (uint8,
+# directly after delta): 1 for a payload embedded with keyed dither under payload.dither_table; a meta written without
+# dither has no such member, so the files written before it existed load, hash and weigh as they did.
 PAYLOAD_MODE = "payload"
-_PAYLOAD = ("payload_type", "shape", "delta", "payload_bits", "nonce", "tile", "frame_interval", "n_frames", "chroma")
+_PAYLOAD = ("payload_type", "shape", "delta", "dither", "payload_bits", "nonce", "tile", "frame_interval", "n_frames", "chroma")
 _ORDER[PAYLOAD_MODE] = ("mode",) + _PAYLOAD + ("digest",)
 _ORDER_FULL_FRAME = dict(_ORDER, color=("mode",) + _IMAGE_COMMON + _BY_CHANNEL_THEN_S + ("digest",))
 
@@ -82,7 +84,7 @@ def is_payload(meta) -> bool:
 
 
 # what a payload meta's members are stored as - and hashed as, whatever a reader's np.load made of them
-_PAYLOAD_DTYPES = dict(shape=np.int64, delta=np.float32, payload_bits=np.int32, nonce=np.uint8, tile=np.int32,
+_PAYLOAD_DTYPES = dict(shape=np.int64, delta=np.float32, dither=np.uint8, payload_bits=np.int32, nonce=np.uint8, tile=np.int32,
                        frame_interval=np.int32, n_frames=np.int32)
 
 
@@ -101,10 +103,12 @@ def payload_hmac_parts(meta) -> list:
 
 
 def payload_members(payload_type: str, H: int, W: int, delta: float, n_bits: int, nonce: bytes, frame_interval=None,
-                    n_frames=None) -> dict:
+                    n_frames=None, dither: int = 0) -> dict:
     out = dict(mode=PAYLOAD_MODE, payload_type=str(payload_type), shape=np.array((H, W), dtype=np.int64),
-               delta=np.float32(delta), payload_bits=np.int32(n_bits), nonce=np.frombuffer(nonce, dtype=np.uint8),
-               tile=np.int32(TILE))
+               delta=np.float32(delta))
+    if dither:
+        out.update(dither=np.uint8(dither))
+    out.update(payload_bits=np.int32(n_bits), nonce=np.frombuffer(nonce, dtype=np.uint8), tile=np.int32(TILE))
     if n_frames is not None:
         out.update(frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames))
     return out
@@ -163,6 +167,14 @@ def save_payload_meta(path: str, meta: dict) -> str:
 
 def load_payload_meta(path: str) -> dict:
     return unpack_payload(hg.load_npz(path))
+
+
+def payload_dither_of(meta) -> int:
+    """0 for a payload meta without the ``dither`` member (the dither-free rule), else its value; only 1 is known"""
+    d = int(meta["dither"]) if "dither" in meta else 0
+    if d not in (0, 1):
+        raise ValueError(f"payload meta names dither table {d}, which this version does not know")
+    return d
 
 
 def refuse_payload(meta, what: str) -> None:

@@ -1,6 +1,6 @@
 """Blind text / JSON / bytes payload: the host side of the sigma_1 quantisation rule (include/wmhip.h, DESIGN.md
-section 14).  Framing of the bytes into bits, the keyed tile-to-bit map and its CSR inverse, what a caller's payload
-argument means.  NumPy, json and zlib only: nothing here touches the device.
+section 14).  Framing of the bytes into bits, the keyed tile-to-bit map and its CSR inverse, the keyed dither table, what a
+caller's payload argument means.  NumPy, hashlib, json and zlib only: nothing here touches the device.
 
 Frame: ``len(data)`` as 4 little-endian bytes, ``data``, ``zlib.crc32(data)`` as 4 little-endian bytes, most significant
 bit of every byte first - the header and bit order of the reference's bit image (core:56-60), with a checksum the
@@ -8,6 +8,7 @@ reference does not have.  n_bits = 8 * (len(data) + 8).
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import os
 import zlib
@@ -76,6 +77,27 @@ def payload_map(nby: int, nbx: int, key: bytes, n_bits: int) -> tuple:
 def tile_bits(bits: np.ndarray, tile_bit_index: np.ndarray) -> np.ndarray:
     """the bit every tile carries, uint8 [n_tiles]"""
     return np.asarray(bits, np.uint8)[tile_bit_index]
+
+
+DITHER_TABLE = 1                                    # the meta's ``dither`` member: the table below
+
+
+def dither_table(nby: int, nbx: int, key: bytes, frame_index: int = 0) -> np.ndarray:
+    """The keyed dither words of an nby x nbx tile grid, uint16 [n_tiles]: tile t's lattice is shifted by
+    float(u[t]) * delta * 2^-15 (include/wmhip.h).  NumPy's PCG64 seeded as hostglue.rng_from_key seeds it, from
+    sha256(key + b"payload-dither" + frame_index as 8 little-endian bytes): a video's frames get a table each.  Host work
+    like the tile-to-bit map; part of the meta format (``dither`` = 1)."""
+    frame_index = int(frame_index)
+    if frame_index < 0:
+        raise ValueError("frame_index must not be negative")
+    seed = hashlib.sha256(bytes(key) + b"payload-dither" + frame_index.to_bytes(8, "little")).digest()
+    return hg.rng_from_key(seed).integers(0, 65536, int(nby) * int(nbx), dtype=np.uint16)
+
+
+def dither_tables(nby: int, nbx: int, key: bytes, frame_indices) -> np.ndarray:
+    """uint16 [N, n_tiles]: dither_table of every frame index, one row per plane of a batch"""
+    return np.stack([dither_table(nby, nbx, key, i) for i in frame_indices]) if len(frame_indices) else \
+        np.zeros((0, int(nby) * int(nbx)), np.uint16)
 
 
 def confidence(soft: np.ndarray, offs: np.ndarray, n_planes: int) -> float:

@@ -510,23 +510,34 @@ def detect_watermark_video_color(stego_video_path: str, metadata_path: str, thre
 # same tile-to-bit map, and the decoder adds the frames' soft votes.  The meta holds the rule, not the frames.
 # ---------------------------------------------------------------------------
 def payload_soft_frames(ctx: hostapi.Context, frames_y: np.ndarray, order, offs, n_bits: int, delta: float,
-                        batch: int = 32) -> np.ndarray:
+                        batch: int = 32, dither=None) -> np.ndarray:
     """soft [n_bits] float64 over all frames of uint8 [N, H, W]: one device call per batch, the batches' vectors added on
-    the host in batch order."""
+    the host in batch order.  ``dither``: uint16 [N, n_tiles], a row of keyed dither words per frame (None: dither-free)."""
     soft = np.zeros(int(n_bits), np.float64)
     for b0 in range(0, frames_y.shape[0], max(1, int(batch))):
-        soft += ctx.payload_soft(frames_y[b0:b0 + batch], order, offs, n_bits, delta)
+        soft += ctx.payload_soft(frames_y[b0:b0 + batch], order, offs, n_bits, delta,
+                                 dither=None if dither is None else dither[b0:b0 + batch])
     return soft
+
+
+def _payload_frame_dithers(H: int, W: int, key: bytes, first_marked: int, n: int, frame_interval: int) -> np.ndarray:
+    """uint16 [n, n_tiles]: the dither tables of n consecutive marked frames, the first of them the ``first_marked``-th
+    marked frame of the file - frame index first_marked * frame_interval"""
+    fi = max(1, int(frame_interval))
+    return P.dither_tables(H // TILE, W // TILE, key, [(first_marked + i) * fi for i in range(n)])
 
 
 def embed_payload_video(host_video_path: str, payload, output_video_path: str, metadata_path: str, *, password: str = "",
                         payload_type: str = "text", frame_interval: int = 1, delta: float = P.DELTA_DEFAULT,
-                        nonce: Optional[bytes] = None, batch: int = 32, device: int = 0, verify: bool = True):
+                        nonce: Optional[bytes] = None, batch: int = 32, device: int = 0, verify: bool = True,
+                        dither: bool = False):
     """Embed a text / JSON / bytes payload (``payload`` as in dct_svd_core_secure.embed_payload) into the luma of every
     ``frame_interval``-th frame of an 8-bit .y4m; chroma and unmarked frames are copied byte for byte.
     Returns (output_video_path, metadata_path, mean PSNR of the marked frames' luma).
     ``verify``: the soft votes of the marked stego frames are added up as they are written, and a payload that does not
-    decode from them raises ValueError after the last frame; neither the output file nor the meta remains."""
+    decode from them raises ValueError after the last frame; neither the output file nor the meta remains.
+    ``dither``: keyed dither (dct_svd_core_secure.embed_payload_arrays); every marked frame gets a table of its own, keyed
+    by the frame's index in the file, and a batch is one call with a table row per frame."""
     M.require_password(password, "embed")
     delta = hostapi.check_delta(delta)
     data = P.payload_bytes(payload, payload_type)
@@ -548,10 +559,12 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
 
         def embed_marked(marked):
             ys = np.stack([y for y, _ in marked])
-            st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta)
+            # the marked frames arrive in file order: the m-th of them is frame m * frame_interval
+            dz = _payload_frame_dithers(H, W, key, len(psnrs), len(marked), frame_interval) if dither else None
+            st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta, dither=dz)
             psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
             if verify:
-                np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch), out=soft)
+                np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch, dither=dz), out=soft)
             return [(s.tobytes(), chroma.tobytes()) for s, (_, chroma) in zip(st, marked)]
 
         with open(output_video_path, "wb") as out:
@@ -563,7 +576,8 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             except ValueError:
                 os.remove(output_video_path)
                 raise
-        members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, frame_interval, n_frames)
+        members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, frame_interval, n_frames,
+                                    dither=P.DITHER_TABLE if dither else 0)
         M.save_payload_meta(metadata_path, M.sealed(members, TILE, hg.hmac_digest(key, M.hmac_parts(members))))
         return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0
     finally:
@@ -588,6 +602,7 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     fi = int(data["frame_interval"])
     batch = max(1, int(batch))
     _, order, offs = P.payload_map(H // TILE, W // TILE, key, n_bits)
+    dither = M.payload_dither_of(data)
     vid = Y4M(stego_video_path)
     ctx = None
     try:
@@ -597,7 +612,8 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
         soft = np.zeros(n_bits, np.float64)
         n_marked = 0
         for frames in _marked_batches(vid, fi, batch):
-            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, n_bits, delta)
+            dz = _payload_frame_dithers(H, W, key, n_marked, len(frames), fi) if dither else None
+            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, n_bits, delta, dither=dz)
             n_marked += len(frames)
     finally:
         vid.close()

@@ -296,6 +296,48 @@ int wm_payload_soft_tiles_u8_dev(wm_ctx* ctx, const uint8_t* stego, const int32_
 int wm_payload_soft_tiles_u8(wm_ctx* ctx, const uint8_t* stego, const int32_t* order, const int32_t* offs, int n_bits,
                              double* soft, int n_planes, int H, int W, int row_stride, size_t plane_stride, float delta);
 
+/* ---- Blind payload with keyed dither: every tile's lattice shifted by a secret offset --
+ * The rule above puts sigma_1 of every marked tile on the public lattice {k delta}; the forms below shift the lattice of
+ * each tile by an offset from a 16-bit dither word u that the caller derives from the key (the Python side:
+ * payload.dither_table).  Without the table, sigma_1 mod 2 delta of the stego looks uniform; with it nothing is lost.
+ *   offset  d = float(u) * (delta * 2^-15)     ONE float32 multiply, rounded on its own (never contracted into the add or
+ *                                              the subtraction that follows); delta * 2^-15 is exact; 0 <= d < 2 delta
+ *   embed   b' = b delta + d                   one float32 add
+ *           q = fma(2 delta, rint((s_1 - b') / (2 delta)), b')
+ *           then as above: the step down from 2040, the climb above s_2 + delta, sigma_w_eff = (q + c - s_1, 0, ..), the
+ *           unchanged embed with alpha = 1, K = 1, the flat vector for black tiles
+ *   decode  x = (s~_1 - d) * (1 / (2 delta));  f and m as above
+ * u = 0 gives the dither-free results bit for bit.
+ *   tile_dither          uint16, tile t of plane p reads tile_dither[p * dither_plane_stride + t]
+ *   dither_plane_stride  0: one [n_tiles] table shared by the planes; >= n_tiles: one table per plane, that many words apart
+ *                        (as sigma_w_plane_stride); the host-pointer forms read (n_planes - 1) * stride + n_tiles words
+ * The other arguments are those of the dither-free forms.  WM_ERR_BADARG as there, and for a NULL (or odd-addressed) table
+ * or a stride that is neither 0 nor >= n_tiles where there is a tile to work on.  Empty inputs return WM_OK without a
+ * launch. */
+int wm_payload_sigma_w_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                           float* sigma_w_eff, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                           size_t dither_plane_stride, float delta);
+int wm_payload_sigma_w_tiles_dither_u8(wm_ctx* ctx, const uint8_t* planes, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                       float* sigma_w_eff, int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                       size_t dither_plane_stride, float delta);
+int wm_embed_tiles_payload_dither_u8_dev(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                         uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                                         size_t plane_stride, size_t dither_plane_stride, float delta);
+int wm_embed_tiles_payload_dither_u8(wm_ctx* ctx, const uint8_t* host, const uint8_t* tile_bit, const uint16_t* tile_dither,
+                                     uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W, int row_stride,
+                                     size_t plane_stride, size_t dither_plane_stride, float delta);
+int wm_payload_metric_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, float* metric,
+                                          int n_planes, int H, int W, int row_stride, size_t plane_stride,
+                                          size_t dither_plane_stride, float delta);
+int wm_payload_metric_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, float* metric, int n_planes,
+                                      int H, int W, int row_stride, size_t plane_stride, size_t dither_plane_stride, float delta);
+int wm_payload_soft_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, const int32_t* order,
+                                        const int32_t* offs, int n_bits, double* soft, int n_planes, int H, int W, int row_stride,
+                                        size_t plane_stride, size_t dither_plane_stride, float delta);
+int wm_payload_soft_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uint16_t* tile_dither, const int32_t* order,
+                                    const int32_t* offs, int n_bits, double* soft, int n_planes, int H, int W, int row_stride,
+                                    size_t plane_stride, size_t dither_plane_stride, float delta);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense

@@ -13,10 +13,17 @@ The expectations to confirm or correct: payload_metric <= sigma_tiles, payload_s
 embed_payload = embed_masked.  payload_soft is timed at n_bits = 16 (each wave sums n_planes * n_tiles / 16 values: the
 reduce at its least parallel), at 1024 and at n_tiles.
 
+With --dither the keyed-dither forms are timed beside them (payload_metric_dither, payload_sigma_w_dither,
+payload_soft_dither_*, embed_payload_dither: a per-plane table, 2 more bytes a tile), the embeds write to a buffer of their
+own so that every decode variant reads the same payload stego whatever ran before it, and the order of the variants is
+drawn afresh for every round (a variant's place in the round moves its time by more than the variants differ).  Each
+dithered row is then recorded against payload_metric_parent's own min-max spread; no threshold is set.
+
 Also records the device figures at the test shapes (tests/payload_refs.py): worst |m| deficit against the restatement,
 worst |soft - ref| / count, share of stego pixels differing from the restatement.
 
     python tools/payload_bench.py [--parent-lib /path/to/parent/libwmhip.so] [--out profiles/payload_bench.json]
+    python tools/payload_bench.py --dither --parent-lib /path/to/parent/libwmhip.so --out profiles/payload_dither_bench.json
 
 Development aid; bench.py is the contract benchmark."""
 import argparse
@@ -44,18 +51,22 @@ def csr(n_tiles, n_bits, rng):
     return tbi, order, offs
 
 
-def time_variants(ctxs, variants, warmup, rounds):
+def time_variants(ctxs, variants, warmup, rounds, shuffle_seed=None):
     """variants: name -> (ctx key, callable).  Returns name -> list of ms, one per round, interleaved.
     Two builds are two contexts with a stream each, and launches on two streams overlap on the device: with a parent build
     every variant starts on an idle device (both contexts synchronised first), so that no variant is timed against whatever
     the other build happens to run beside it, and a variant and its `_parent` twin, which stand next to each other, swap
-    places every other round, so that neither always follows the same neighbour."""
+    places every other round, so that neither always follows the same neighbour.  With shuffle_seed the order of all
+    variants is a fresh seeded permutation every round instead."""
     out = {k: [] for k in variants}
     two_streams = ctxs["parent"] is not ctxs["this"]
     names = list(variants)
+    shuffle = None if shuffle_seed is None else np.random.default_rng(shuffle_seed)
     for r in range(warmup + rounds):
         order = list(range(len(names)))
-        if r % 2:
+        if shuffle is not None:
+            order = [int(i) for i in shuffle.permutation(len(names))]
+        elif r % 2:
             for i in range(len(names) - 1):
                 if names[i] + "_parent" == names[i + 1] or names[i] == names[i + 1] + "_parent":
                     order[i], order[i + 1] = order[i + 1], order[i]
@@ -77,7 +88,7 @@ def summary(ms):
     return dict(median_ms=float(np.median(a)), min_ms=float(a[0]), max_ms=float(a[-1]), rounds=len(a))
 
 
-def bench_size(ctx, parent, label, F, warmup, rounds, content, sigma_pass_out=None):
+def bench_size(ctx, parent, label, F, warmup, rounds, content, sigma_pass_out=None, dither=False):
     H, W = SIZES[label]
     rng = np.random.default_rng(17)
     nt = (H // 8) * (W // 8)
@@ -130,8 +141,27 @@ def bench_size(ctx, parent, label, F, warmup, rounds, content, sigma_pass_out=No
     for nb, (d_o, d_f, d_s) in maps.items():
         variants[f"payload_soft_{'ntiles' if nb == nt else nb}_bits"] = (
             "this", lambda d_o=d_o, d_f=d_f, d_s=d_s, nb=nb: ctx._call("wm_payload_soft_tiles_u8_dev", t["stego"], d_o, d_f, nb, d_s, *plane, DELTA))
-    # the embeds rewrite stego: keep embed_payload last so that the decode variants of the next round read a payload stego
-    ms = time_variants(ctxs, variants, warmup, rounds)
+    if dither:
+        # the embeds of every build write beside the stego the decode variants read; the dithered forms take a table row per plane
+        t["out"] = ctx.malloc(host.nbytes)
+        if parent is not None:
+            p["out"] = pc.malloc(host.nbytes)
+        words = rng.integers(0, 65536, (F, nt), dtype=np.uint16)
+        t["words"] = ctx.malloc(words.nbytes); ctx.h2d(t["words"], words)
+        po = p["out"] if parent is not None else t["out"]
+        variants.update({
+            "embed_masked_parent": ("parent", lambda: pc.embed_tiles_masked_u8_dev(p["host"], p["sw"], po, p["sc"], None, *plane, 0, 0.12, 8, *MASK)),
+            "embed_masked": ("this", lambda: ctx.embed_tiles_masked_u8_dev(t["host"], t["sw"], t["out"], t["sc"], None, *plane, 0, 0.12, 8, *MASK)),
+            "embed_payload": ("this", lambda: ctx._call("wm_embed_tiles_payload_u8_dev", t["host"], t["bit"], t["out"], t["sc"], None, *plane, DELTA)),
+            "payload_metric_dither": ("this", lambda: ctx._call("wm_payload_metric_tiles_dither_u8_dev", t["stego"], t["words"], t["metric"], *plane, nt, DELTA)),
+            "payload_sigma_w_dither": ("this", lambda: ctx._call("wm_payload_sigma_w_tiles_dither_u8_dev", t["host"], t["bit"], t["words"], t["eff"], *plane, nt, DELTA)),
+            "embed_payload_dither": ("this", lambda: ctx._call("wm_embed_tiles_payload_dither_u8_dev", t["host"], t["bit"], t["words"], t["out"], t["sc"], None, *plane, nt, DELTA)),
+        })
+        for nb, (d_o, d_f, d_s) in maps.items():
+            variants[f"payload_soft_dither_{'ntiles' if nb == nt else nb}_bits"] = (
+                "this", lambda d_o=d_o, d_f=d_f, d_s=d_s, nb=nb: ctx._call("wm_payload_soft_tiles_dither_u8_dev", t["stego"], t["words"], d_o, d_f, nb, d_s, *plane, nt, DELTA))
+    # without --dither the embeds rewrite stego: embed_payload stays last so that the decode variants of the next round read a payload stego
+    ms = time_variants(ctxs, variants, warmup, rounds, shuffle_seed=29 if dither else None)
     ctx.sync(); ctx.check_status(); pc.sync(); pc.check_status()
     res = {k: summary(v) for k, v in ms.items()}
     if parent is not None and sigma_pass_out:
@@ -145,7 +175,23 @@ def bench_size(ctx, parent, label, F, warmup, rounds, content, sigma_pass_out=No
     for d3 in maps.values():
         for d in d3:
             ctx.free(d)
-    return dict(frames=F, H=H, W=W, n_tiles=nt, content=content, variants=res)
+    out = dict(frames=F, H=H, W=W, n_tiles=nt, content=content, variants=res)
+    if dither:
+        out["order"] = "a seeded permutation of the variants per round"
+        yard = res["payload_metric_parent" if parent is not None else "payload_metric"]
+        out["against_parent_metric"] = {
+            k: dict(median_minus_parent_median_ms=v["median_ms"] - yard["median_ms"],
+                    inside_parent_spread=bool(yard["min_ms"] <= v["median_ms"] <= yard["max_ms"]),
+                    outside_by_ms=float(max(v["median_ms"] - yard["max_ms"], yard["min_ms"] - v["median_ms"], 0.0)))
+            for k, v in res.items() if k in ("payload_metric", "payload_metric_dither")}
+        for pair in (("payload_sigma_w_dither", "payload_sigma_w"), ("embed_payload_dither", "embed_payload")) + tuple(
+                (k, k.replace("_dither", "")) for k in res if k.startswith("payload_soft_dither")):
+            a, b = res[pair[0]], res[pair[1]]
+            out["against_parent_metric"][pair[0]] = dict(
+                against=pair[1], median_minus_its_median_ms=a["median_ms"] - b["median_ms"],
+                inside_its_spread=bool(b["min_ms"] <= a["median_ms"] <= b["max_ms"]),
+                outside_by_ms=float(max(a["median_ms"] - b["max_ms"], b["min_ms"] - a["median_ms"], 0.0)))
+    return out
 
 
 def device_figures(ctx):
@@ -178,6 +224,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "payload_bench.json"))
     ap.add_argument("--sigma-pass-out", help="with --parent-lib: add sigma_tiles / payload_sigma_w / payload_metric of both builds "
                     "to this JSON (mask_bench.sigma_pass_record)")
+    ap.add_argument("--dither", action="store_true", help="add the keyed-dither rows; the order of the variants is drawn per round")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=12)
@@ -186,9 +233,9 @@ def main():
     a = ap.parse_args()
     ctx = api.Context(0)
     parent = LibContext(load_build(a.parent_lib)) if a.parent_lib else None
-    res = dict(parent_lib=bool(a.parent_lib), delta=DELTA, sizes={}, figures=device_figures(ctx))
+    res = dict(parent_lib=bool(a.parent_lib), delta=DELTA, sizes={}, figures={} if a.dither else device_figures(ctx))
     for label in a.sizes.split(","):
-        res["sizes"][label] = bench_size(ctx, parent, label, a.frames, a.warmup, a.rounds, a.content, a.sigma_pass_out)
+        res["sizes"][label] = bench_size(ctx, parent, label, a.frames, a.warmup, a.rounds, a.content, a.sigma_pass_out, a.dither)
         v = res["sizes"][label]["variants"]
         print(label, {k: round(x["median_ms"], 3) for k, x in v.items()}, flush=True)
     with open(a.out, "w") as f:
