@@ -1489,6 +1489,11 @@ WM_HD float payload_metric(const float s1, const float inv_2delta) {
   return 2.0f * fabsf(2.0f * f - 1.0f) - 1.0f;
 }
 
+// Crop resynchronisation (include/wmhip.h; DESIGN.md, "Crop resynchronisation"): the metric as an integer vote, -32768 ..
+// 32768.  m * 2^15 is exact in float32 and rintf rounds ties to even, as np.rint does; everything the grid search does with the
+// votes - sums of |vote| per phase, per-bit sums per placement - is integer arithmetic, the same on the device and in NumPy.
+WM_HD int32_t payload_vote(const float m) { return (int32_t)rintf(m * 32768.0f); }
+
 // The same of a tile whose lattice is shifted by d: x = (s_1 - d) * (1 / (2 delta)), one subtraction and one multiply
 WM_HD float payload_metric(const float s1, const float inv_2delta, const float d) {
   return payload_metric(s1 - d, inv_2delta);

@@ -989,6 +989,86 @@ __global__ __launch_bounds__(WAVE) void k_payload_reduce(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// Crop resynchronisation of the blind payload (include/wmhip.h): where the embed's tile grid lies in a cropped stego
+// ---------------------------------------------------------------------------
+// Phase scan: the sigma pass over the 8x8 windows of all 64 grid phases of an h x w plane in one launch - grid (waves of the
+// largest grid, 64 phases, planes).  Phase p = 8 py + px has the windows that start at (py + 8 r, px + 8 c), r < ny_p =
+// (h - py) / 8, c < nx_p = (w - px) / 8; a wave owns 64 consecutive windows of its phase's grid, one per lane, as k_sigma_pass
+// lays a plane out.  Windows start at any byte, so the tile is loaded by the byte path.  The vote (wm_tile_math.h,
+// payload_vote) goes to votes[plane][phase][t], `pitch` = (h / 8) (w / 8) ints per phase, each phase's own grid row-major at
+// the start of its slot (votes may be NULL); sum |vote| of the wave is added to sums[plane][phase] by one integer atomic
+// (integer addition is associative: the sums do not depend on the order the waves arrive in).  The lanes behind the last
+// window of a wave redo that window and vote 0, so the wave's sum needs no masking.
+struct PhaseGeom {
+  int h, w, pitch;
+  size_t row_stride, plane_stride;
+};
+
+__device__ __forceinline__ int wave_sum(int x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, WAVE);
+  return x;
+}
+__device__ __forceinline__ long long wave_sum(long long x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, WAVE);
+  return x;
+}
+
+__global__ __launch_bounds__(WAVE, 3) void k_payload_phase_scan(const uint8_t* __restrict__ planes, const PhaseGeom g,
+                                                            int* __restrict__ status, int32_t* __restrict__ votes,
+                                                            unsigned long long* __restrict__ sums, const float inv_2delta) {
+  const int phase = blockIdx.y, py = phase >> 3, px = phase & 7;
+  const int nx = (g.w - px) / 8, n = ((g.h - py) / 8) * nx;
+  if ((int)(blockIdx.x * WAVE) >= n) return;                             // (the whole wave: phases differ in their tile counts)
+  const int t = blockIdx.x * WAVE + threadIdx.x;
+  const bool live = t < n;
+  const int tc = live ? t : n - 1;
+  const int r = tc / nx, c = tc - r * nx;
+  const size_t plane = blockIdx.z;
+  wm::RawTile raw;
+  float s[8];
+  load_raw<false>(planes + plane * g.plane_stride + (size_t)(py + 8 * r) * g.row_stride + (size_t)(px + 8 * c), g.row_stride, raw);
+  if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
+  const int v = live ? wm::payload_vote(wm::payload_metric(s[0], inv_2delta)) : 0;
+  const size_t slot = plane * 64 + phase;
+  if (votes && live) votes[slot * (size_t)g.pitch + t] = v;
+  const int a = wave_sum(v < 0 ? -v : v);
+  if (threadIdx.x == 0) atomicAdd(sums + slot, (unsigned long long)a);
+}
+
+// Offset scan: one workgroup per placement (ty, tx) = (blockIdx.y, blockIdx.x) of the ny x nx vote grid V inside the
+// nby x nbx tile-to-bit map T.  hist[n_bits] (int32, LDS) takes V[r][c] at T[ty + r][tx + c] by LDS integer atomics - an entry
+// of T outside 0 .. n_bits - 1 is skipped, as k_payload_reduce skips an order entry outside the grid - and the first wave adds
+// |hist[j]| up to the placement's int64 score.  Integers throughout: the same inputs give the same bits in any order.
+constexpr int OFFSET_SCAN_THREADS = 256;
+constexpr int OFFSET_SCAN_MAX_BITS = 16384;          // 64 KiB of LDS: two workgroups a CU
+
+__global__ __launch_bounds__(OFFSET_SCAN_THREADS) void k_payload_offset_scan(const int32_t* __restrict__ V, const int32_t* __restrict__ T,
+                                                                         long long* __restrict__ scores, const int ny, const int nx,
+                                                                         const int nbx, const int n_bits) {
+  extern __shared__ int hist[];
+  for (int j = threadIdx.x; j < n_bits; j += OFFSET_SCAN_THREADS) hist[j] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ Tw = T + (size_t)blockIdx.y * nbx + blockIdx.x;
+  const int n = ny * nx;
+  for (int i = threadIdx.x; i < n; i += OFFSET_SCAN_THREADS) {
+    const int r = i / nx, c = i - r * nx;
+    const int j = Tw[(size_t)r * nbx + c];
+    if ((unsigned)j < (unsigned)n_bits) atomicAdd(&hist[j], V[i]);
+  }
+  __syncthreads();
+  if (threadIdx.x >= WAVE) return;
+  long long acc = 0;
+  for (int j = threadIdx.x; j < n_bits; j += WAVE) {
+    const long long x = hist[j];
+    acc += x < 0 ? -x : x;
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) scores[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// ---------------------------------------------------------------------------
 // host-side argument checking / launch helpers
 // ---------------------------------------------------------------------------
 int check_plane_args(const wm_ctx* ctx, const void* p, int n_planes, int H, int W, int row_stride,
@@ -1504,6 +1584,48 @@ int wm_payload_soft_tiles_dither_u8_dev(wm_ctx* ctx, const uint8_t* stego, const
                                         size_t plane_stride, size_t dither_plane_stride, float delta) {
   return payload_soft_dev(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, order, offs, n_bits, soft, n_planes, H, W,
                           row_stride, plane_stride, delta);
+}
+
+// ---- crop resynchronisation: the phase scan and the offset scan -----------------------
+int wm_payload_phase_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, int32_t* votes, int64_t* sums, int n_planes, int h, int w,
+                                 int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
+  if (n_planes == 0 || pitch == 0) return WM_OK;
+  if (pitch > (size_t)INT32_MAX) return set_err(WM_ERR_BADARG, "more than 2^31 - 1 tiles a plane");
+  if (!sums || ((uintptr_t)sums & 7u) || ((uintptr_t)votes & 3u)) return set_err(WM_ERR_BADARG, "sums is NULL, or sums / votes is misaligned");
+  WM_HIP(hipMemsetAsync(sums, 0, (size_t)n_planes * 64 * sizeof(int64_t), ctx->stream));
+  const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
+  const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
+  hipLaunchKernelGGL(k_payload_phase_scan, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status, votes,
+                     reinterpret_cast<unsigned long long*>(sums), 1.0f / (2.0f * delta));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
+                                 int nby, int nbx, int n_bits) {
+  WM_TRY(wmi::use_ctx(ctx));
+  if (ny < 0 || nx < 0 || nby < 0 || nbx < 0) return set_err(WM_ERR_BADARG, "negative size");
+  if (n_bits < 1 || n_bits > OFFSET_SCAN_MAX_BITS) return set_err(WM_ERR_BADARG, "n_bits must be in 1..16384");
+  if (ny > nby || nx > nbx) return WM_OK;                                // no placement
+  const size_t n_ty = (size_t)(nby - ny) + 1, n_tx = (size_t)(nbx - nx) + 1;
+  if ((size_t)nby * (size_t)nbx > (size_t)INT32_MAX || n_ty > 65535) return set_err(WM_ERR_BADARG, "tile grid too large");
+  if (!scores || ((uintptr_t)scores & 7u)) return set_err(WM_ERR_BADARG, "scores is NULL or misaligned");
+  if (ny == 0 || nx == 0) {                                              // no window: every placement scores 0
+    WM_HIP(hipMemsetAsync(scores, 0, n_ty * n_tx * sizeof(int64_t), ctx->stream));
+    return WM_OK;
+  }
+  if (!votes || !tile_bit_index || (((uintptr_t)votes | (uintptr_t)tile_bit_index) & 3u))
+    return set_err(WM_ERR_BADARG, "votes / tile_bit_index is NULL or misaligned");
+  const size_t lds = (size_t)n_bits * sizeof(int);
+  if (lds > 48 * 1024)
+    WM_HIP(hipFuncSetAttribute((const void*)k_payload_offset_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_payload_offset_scan, dim3((unsigned)n_tx, (unsigned)n_ty), dim3(OFFSET_SCAN_THREADS), lds, ctx->stream, votes,
+                     tile_bit_index, reinterpret_cast<long long*>(scores), ny, nx, nbx, n_bits);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
 }
 
 // ---- K3 --------------------------------------------------------------------
@@ -2056,6 +2178,38 @@ int wm_payload_soft_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uin
                                     size_t plane_stride, size_t dither_plane_stride, float delta) {
   return payload_soft_host(ctx, stego, Dither{true, tile_dither, dither_plane_stride}, order, offs, n_bits, soft, n_planes, H, W,
                            row_stride, plane_stride, delta);
+}
+
+// ---- crop resynchronisation, host pointers ------------------------------------
+int wm_payload_phase_scan_u8(wm_ctx* ctx, const uint8_t* stego, int32_t* votes, int64_t* sums, int n_planes, int h, int w,
+                             int row_stride, size_t plane_stride, float delta) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
+  WM_TRY(check_delta(delta));
+  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
+  if (n_planes == 0 || pitch == 0) return WM_OK;
+  if (!sums) return set_err(WM_ERR_BADARG, "sums is NULL");
+  uint8_t* d_p; int32_t* d_votes; int64_t* d_sums;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, h, row_stride, plane_stride, w), stego);
+    d_votes = votes ? cv.out((size_t)n_planes * 64 * pitch, votes) : nullptr;
+    d_sums = cv.out((size_t)n_planes * 64, sums);
+  }, [&] { return wm_payload_phase_scan_u8_dev(ctx, d_p, d_votes, d_sums, n_planes, h, w, row_stride, plane_stride, delta); });
+}
+
+int wm_payload_offset_scores(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
+                             int nby, int nbx, int n_bits) {
+  WM_TRY(wmi::use_ctx(ctx));
+  if (ny < 0 || nx < 0 || nby < 0 || nbx < 0) return set_err(WM_ERR_BADARG, "negative size");
+  if (n_bits < 1 || n_bits > OFFSET_SCAN_MAX_BITS) return set_err(WM_ERR_BADARG, "n_bits must be in 1..16384");
+  if (ny > nby || nx > nbx) return WM_OK;
+  const size_t n_win = (size_t)ny * (size_t)nx, n_place = ((size_t)(nby - ny) + 1) * ((size_t)(nbx - nx) + 1);
+  if (!scores || (n_win && (!votes || !tile_bit_index))) return set_err(WM_ERR_BADARG, "votes / tile_bit_index / scores is NULL");
+  int32_t *d_v, *d_t; int64_t* d_s;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_v = cv.in(n_win, votes);
+    d_t = cv.in(n_win ? (size_t)nby * (size_t)nbx : 0, tile_bit_index);
+    d_s = cv.out(n_place, scores);
+  }, [&] { return wm_payload_offset_scores_dev(ctx, d_v, d_t, d_s, ny, nx, nby, nbx, n_bits); }, true);
 }
 
 }  // extern "C"

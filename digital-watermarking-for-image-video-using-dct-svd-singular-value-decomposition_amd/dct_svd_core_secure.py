@@ -429,10 +429,52 @@ def _payload_meta_checked(meta, password: str):
     return meta, H, W, hostapi.check_delta(float(meta["delta"])), n_bits, ptype, key
 
 
-def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0):
+SEARCHES = (None, "crop")
+
+
+def _check_search(search):
+    if search not in SEARCHES:
+        raise ValueError(f"search must be None or 'crop', got {search!r}")
+
+
+def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
+    """search="crop" (include/wmhip.h, "crop resynchronisation"): the stego is any axis-aligned crop of the marked image.
+    Every refusal comes before the first device call."""
+    if M.payload_dither_of(meta):
+        raise ValueError("resynchronising a dithered payload is not supported: keyed dither removes the grid's keyless "
+                         "signal (search='crop' needs a payload embedded with dither=False)")
+    if n_bits > P.SYNC_MAX_BITS:
+        raise ValueError(f"search='crop' takes payloads of at most {P.SYNC_MAX_BITS} bits, this one has {n_bits}")
+    if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
+        raise ValueError("stego must be uint8 [h, w, 3]")
+    h, w = stego_bgr.shape[:2]
+    if h > H or w > W:
+        raise ValueError(f"stego is {w}x{h}, larger than the {W}x{H} the meta was written for: not a crop of it")
+    if h < TILE or w < TILE:
+        raise ValueError(f"stego is {w}x{h}: a crop without a whole 8x8 tile carries nothing")
+    nby, nbx = H // TILE, W // TILE
+    tbi = _payload_map_of(H, W, key, n_bits)[0].reshape(nby, nbx)
+    ctx = _ctx(device)
+    (py, px), place, votes = ctx.payload_locate(_Gray.planes_in(ctx, stego_bgr), tbi, n_bits, delta)
+    if place is None:                                                      # (cannot happen for h <= H, w <= W; the rule names it)
+        return b"", False, 0.0, None
+    ty, tx = place
+    soft, count = P.soft_of_votes(votes, tbi[ty:ty + votes.shape[0], tx:tx + votes.shape[1]], n_bits)
+    data, valid = P.payload_unframe(soft < 0)
+    return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
+
+
+def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0, *, search=None):
     """-> (data bytes, valid, confidence).  valid: the decoded frame's length header and CRC hold.  confidence: the mean
-    over the bits of |soft| / (tiles voting), 1 for an untouched stego and near 0 for an image that carries nothing."""
+    over the bits of |soft| / (tiles voting), 1 for an untouched stego and near 0 for an image that carries nothing.
+    ``search="crop"``: the stego may be any axis-aligned crop of the marked image (h <= H, w <= W, origin anywhere); the
+    embed's tile grid and the crop's place in it are searched for on the device, and the result is (data, valid,
+    confidence, origin) with origin = (y0, x0) of the crop in the marked image - meaningful where valid is True.  Dithered
+    payloads are refused ("Crop resynchronisation")."""
+    _check_search(search)
     meta, H, W, delta, n_bits, _, key = _payload_meta_checked(meta, password)
+    if search == "crop":
+        return _extract_payload_cropped(stego_bgr, meta, H, W, delta, n_bits, key, device)
     _check_stego_shape(stego_bgr, meta)
     _, order, offs = _payload_map_of(H, W, key, n_bits)
     ctx = _ctx(device)
@@ -467,15 +509,17 @@ def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, pa
 
 
 def extract_payload(stego_path: str, meta_path: str, out_path: Optional[str] = None, *, password: Optional[str] = None,
-                    device: int = 0):
+                    device: int = 0, search=None):
     """-> (data, valid, confidence, path written or None).  With ``out_path`` the payload is written as ``_text.txt`` /
-    ``_data.json`` by the reference's renaming (core:229-242)."""
+    ``_data.json`` by the reference's renaming (core:229-242).  ``search="crop"`` as in extract_payload_arrays: the stego
+    file may be a crop of the marked image, and the result is (data, valid, confidence, path, origin)."""
+    _check_search(search)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")
     meta = M.load_payload_meta(meta_path)
-    data, valid, conf = extract_payload_arrays(hg.read_image_bgr(stego_path), meta, password, device)
+    data, valid, conf, *origin = extract_payload_arrays(hg.read_image_bgr(stego_path), meta, password, device, search=search)
     written = P.write_payload(out_path, data, str(meta["payload_type"])) if out_path else None
-    return data, valid, conf, written
+    return (data, valid, conf, written, *origin)
 
 
 embed_watermark = embed

@@ -17,6 +17,8 @@ from typing import Optional
 
 import numpy as np
 
+from . import payload as P
+
 WM_OK, WM_ERR_BADARG, WM_ERR_HIP, WM_ERR_NOCONV, WM_ERR_NOMEM = 0, 1, 2, 3, 4
 TILE = 8
 ABI_VERSION = 1
@@ -85,6 +87,9 @@ _DECLARED = {
     "wm_embed_tiles_payload_dither_u8*": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
     "wm_payload_metric_tiles_dither_u8*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _sz, _f],
     "wm_payload_soft_tiles_dither_u8*": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _sz, _f],
+    # crop resynchronisation: (stego, votes, sums, the plane arguments, delta); (votes, tile_bit_index, scores, ny, nx, nby, nbx, n_bits)
+    "wm_payload_phase_scan_u8*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
+    "wm_payload_offset_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -626,6 +631,97 @@ class Context:
             self.d2h(soft, d_soft)
             self.check_status()
         return soft
+
+    # ---- crop resynchronisation of the blind payload (include/wmhip.h; the comparisons and tie rules are payload.py's) ----
+    def payload_phase_scan(self, planes: np.ndarray, delta: float):
+        """The votes of every 8x8 window of all 64 grid phases of uint8 planes [h, w] / [N, h, w] (strided views included)
+        -> (votes, sums int64 [N?, 8, 8], counts int64 [8, 8]).  votes[py][px] is the int32 [N?, ny_p, nx_p] grid of phase
+        (py, px), ny_p = (h - py) // 8, nx_p = (w - px) // 8; sums[.., py, px] = sum of |vote| over it, counts its size."""
+        delta = check_delta(delta)
+        n, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        pitch = (h // TILE) * (w // TILE)
+        raw = np.zeros((n, 64, pitch), np.int32)
+        sums = np.zeros((n, 8, 8), np.int64)
+        self._call("wm_payload_phase_scan_u8", _p(planes), _p(raw), _p(sums), n, h, w, rs, ps, delta)
+        one = planes.ndim == 2
+        counts = P.phase_counts(h, w)
+        votes = []
+        for py in range(8):
+            ny = max(h - py, 0) // TILE
+            row = []
+            for px in range(8):
+                nx = max(w - px, 0) // TILE
+                v = raw[:, 8 * py + px, :ny * nx].reshape(n, ny, nx).copy()
+                row.append(v[0] if one else v)
+            votes.append(row)
+        return votes, (sums[0] if one else sums), counts
+
+    @staticmethod
+    def _offset_args(votes, tile_bit_index, n_bits):
+        v = np.ascontiguousarray(votes, np.int32)
+        t = np.ascontiguousarray(tile_bit_index, np.int32)
+        if v.ndim != 2 or t.ndim != 2:
+            raise ValueError("votes must be [ny, nx] and tile_bit_index [nby, nbx]")
+        n_bits = int(n_bits)
+        if n_bits < 1 or n_bits > P.SYNC_MAX_BITS:
+            raise ValueError(f"n_bits must be in 1..{P.SYNC_MAX_BITS}, got {n_bits}")
+        return v, t, n_bits
+
+    def payload_offset_scores(self, votes: np.ndarray, tile_bit_index: np.ndarray, n_bits: int) -> np.ndarray:
+        """score[ty, tx] = sum over the bits of |sum of votes[r, c] with tile_bit_index[ty + r, tx + c] == j| for every
+        placement of the [ny, nx] votes inside the [nby, nbx] map -> int64 [nby - ny + 1, nbx - nx + 1] (empty where the
+        votes do not fit).  Map entries outside 0 .. n_bits - 1 are skipped."""
+        v, t, n_bits = self._offset_args(votes, tile_bit_index, n_bits)
+        (ny, nx), (nby, nbx) = v.shape, t.shape
+        scores = np.zeros((max(nby - ny + 1, 0), max(nbx - nx + 1, 0)), np.int64)
+        if scores.size:
+            self._call("wm_payload_offset_scores", _p(v), _p(t), _p(scores), ny, nx, nby, nbx, n_bits)
+        return scores
+
+    def _payload_tbi_dev(self, t: np.ndarray) -> int:
+        """Device copy of a tile-to-bit map, cached by content (one image size under one key decodes crop after crop)."""
+        def upload():
+            d = self.malloc(max(t.nbytes, 4))
+            self.h2d(d, t)
+            return {"d": d}
+        return self._cached("payload_tbi", (t.shape, _digest(t)), upload)["d"]
+
+    def payload_locate(self, plane: np.ndarray, tile_bit_index: np.ndarray, n_bits: int, delta: float):
+        """The chain of the rule's steps 1-3 on one uint8 plane [h, w]: phase scan, pick_phase, offset scan on the winner's
+        votes, pick_offset.  The votes stay on the device; the 64 sums, the scores and the winner's votes come back.
+        -> ((py, px), (ty, tx), votes int32 [ny, nx]); (ty, tx) is None where the winner's grid does not fit the map, and
+        the whole result is None for a plane without a whole tile."""
+        delta = check_delta(delta)
+        if plane.ndim != 2:
+            raise ValueError("plane must be [h, w]")
+        n, h, w, rs, ps = _planes_of(plane, np.uint8, "plane must be uint8")
+        _, t, n_bits = self._offset_args(np.zeros((0, 0), np.int32), tile_bit_index, n_bits)
+        nby, nbx = t.shape
+        pitch = (h // TILE) * (w // TILE)
+        if pitch == 0:
+            return None
+        sums = np.zeros((8, 8), np.int64)
+        d_t = self._payload_tbi_dev(t) if t.size else 0
+        with self._staging() as dev:
+            d_votes, d_sums = dev.alloc(64 * pitch * 4), dev.alloc(sums.nbytes)
+            d_p, = dev.up(np.ascontiguousarray(plane))
+            self._call("wm_payload_phase_scan_u8_dev", _vp(d_p), _vp(d_votes), _vp(d_sums), 1, h, w, w, h * w, delta)
+            self.d2h(sums, d_sums)
+            self.check_status()
+            py, px = P.pick_phase(sums, P.phase_counts(h, w))
+            ny, nx = (h - py) // TILE, (w - px) // TILE
+            d_win = d_votes + (8 * py + px) * pitch * 4
+            votes = np.empty((ny, nx), np.int32)
+            self.d2h(votes, d_win)
+            if ny > nby or nx > nbx:
+                self.sync()
+                return (py, px), None, votes
+            scores = np.zeros((nby - ny + 1, nbx - nx + 1), np.int64)
+            d_scores = dev.alloc(scores.nbytes)
+            self._call("wm_payload_offset_scores_dev", _vp(d_win), _vp(d_t), _vp(d_scores), ny, nx, nby, nbx, n_bits)
+            self.d2h(scores, d_scores)
+            self.sync()
+        return (py, px), P.pick_offset(scores), votes
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

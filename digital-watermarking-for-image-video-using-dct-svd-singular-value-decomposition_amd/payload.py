@@ -107,6 +107,66 @@ def confidence(soft: np.ndarray, offs: np.ndarray, n_planes: int) -> float:
     return float(np.mean(np.abs(soft) / np.maximum(count, 1))) if len(soft) else 0.0
 
 
+# ---- crop resynchronisation (include/wmhip.h): the exact comparisons and the tie rules -------------
+VOTE_ONE = 32768                                    # the vote of m = 1
+SYNC_MAX_BITS = 16384                               # the offset scan's histogram: 64 KiB of LDS
+
+
+def phase_counts(h: int, w: int) -> np.ndarray:
+    """int64 [8, 8]: count[py, px] = ((h - py) // 8) * ((w - px) // 8), the windows of grid phase (py, px) in an h x w crop"""
+    ny = np.maximum(int(h) - np.arange(8), 0) // 8
+    nx = np.maximum(int(w) - np.arange(8), 0) // 8
+    return (ny[:, None] * nx[None, :]).astype(np.int64)
+
+
+def pick_phase(sums, counts):
+    """The phase (py, px) with the largest sums / counts, compared exactly (cross-multiplied Python integers); ties go to
+    the smallest p = 8 py + px; phases with count 0 do not take part.  None when every count is 0."""
+    s = np.asarray(sums).reshape(-1)
+    n = np.asarray(counts).reshape(-1)
+    if s.size != 64 or n.size != 64:
+        raise ValueError("sums and counts must hold the 64 phases")
+    best = None
+    for p in range(64):
+        sp, cp = int(s[p]), int(n[p])
+        if cp > 0 and (best is None or sp * best[2] > best[1] * cp):
+            best = (p, sp, cp)
+    return None if best is None else (best[0] // 8, best[0] % 8)
+
+
+def pick_offset(scores):
+    """The placement (ty, tx) with the largest score, ties to the smallest (ty, tx) (row-major); None without a placement."""
+    sc = np.asarray(scores)
+    if sc.ndim != 2:
+        raise ValueError("scores must be [placements down, placements across]")
+    if sc.size == 0:
+        return None
+    ty, tx = np.unravel_index(int(np.argmax(sc)), sc.shape)        # (argmax: the first of equals in row-major order)
+    return int(ty), int(tx)
+
+
+def soft_of_votes(votes, tile_bit_window, n_bits: int) -> tuple:
+    """(soft float64 [n_bits], count int64 [n_bits]) of the winner's votes [ny, nx] under the window tile_bit_index[ty : ty +
+    ny, tx : tx + nx] of the original grid's map: soft[j] = (the integer sum of the votes of bit j's tiles) / 32768, count[j]
+    the number of those tiles.  Entries outside 0 .. n_bits - 1 are skipped, as on the device."""
+    v = np.asarray(votes).reshape(-1).astype(np.int64)
+    t = np.asarray(tile_bit_window).reshape(-1).astype(np.int64)
+    n_bits = int(n_bits)
+    if v.size != t.size:
+        raise ValueError(f"{v.size} votes for a window of {t.size} tiles")
+    ok = (t >= 0) & (t < n_bits)
+    count = np.bincount(t[ok], minlength=n_bits).astype(np.int64)
+    # (float64 weights hold these integers exactly: |vote| <= 2^15 and far fewer than 2^38 tiles)
+    hist = np.bincount(t[ok], weights=v[ok].astype(np.float64), minlength=n_bits)
+    return hist / float(VOTE_ONE), count
+
+
+def sync_confidence(soft: np.ndarray, count: np.ndarray) -> float:
+    """``confidence`` over the bits that still have a tile in the crop: the mean of |soft[j]| / count[j]"""
+    have = np.asarray(count) > 0
+    return float(np.mean(np.abs(np.asarray(soft)[have]) / np.asarray(count)[have])) if have.any() else 0.0
+
+
 def check_decodes(soft: np.ndarray, bits: np.ndarray, data: bytes) -> None:
     """The embed's own check: ``soft`` is what the decoder reads from the finished stego (every marked frame added).  Tiles
     pinned by clipping - text on a white page, saturated regions - vote for the WRONG bit at full weight, and with few tiles

@@ -338,6 +338,46 @@ int wm_payload_soft_tiles_dither_u8(wm_ctx* ctx, const uint8_t* stego, const uin
                                     const int32_t* offs, int n_bits, double* soft, int n_planes, int H, int W, int row_stride,
                                     size_t plane_stride, size_t dither_plane_stride, float delta);
 
+/* ---- Blind payload, crop resynchronisation: where the embed's tile grid lies in a cropped stego --
+ * A crop alters no pixel that survives it: every whole tile left in an h x w crop (h <= H, w <= W, origin anywhere) still
+ * sits on its lattice point.  What is lost is where the grid is.  The rule ("Crop resynchronisation"; dither-free
+ * payloads only).  All arithmetic past the metric is integer: the device and a NumPy restatement agree to the bit.
+ *   1 vote    vote = (int32) rintf(m * 32768.0f), m the metric of the window's sigma_1 as above: -32768 .. 32768
+ *   2 phase   for p = 8 py + px, py, px in 0..7: the windows start at (py + 8 r, px + 8 c), r < ny_p = (h - py) / 8,
+ *             c < nx_p = (w - px) / 8;  sum_p = sum of |vote| (int64), count_p = ny_p nx_p.  The winner is the phase with the
+ *             largest sum_p / count_p, compared exactly (cross-multiplied integers, on the host); ties go to the smallest p;
+ *             phases with count 0 do not take part.  Needs no key.
+ *   3 offset  on the winner's votes V[ny][nx] and the tile-to-bit map T[nby][nbx] of the ORIGINAL grid (tile t carries bit
+ *             T[t]): every placement 0 <= ty <= nby - ny, 0 <= tx <= nbx - nx has hist[j] = sum of V[r][c] over the windows with
+ *             T[ty + r][tx + c] == j (int32) and score = sum over j of |hist[j]| (int64).  The winner is the largest score,
+ *             ties to the smallest (ty, tx).  ny > nby or nx > nbx: there is no placement.
+ *   4 decode  soft[j] = hist[j] / 32768 at the winner (float64, on the host), the bits as above; the crop's origin in the
+ *             marked image is (8 ty - py, 8 tx - px).
+ * Only the top phase and the top placement are tried; whether they are right is what the frame's length header and CRC say. */
+
+/* Step 1 and the sums of step 2, all 64 phases of every plane in one launch (rows / columns: h, w of the crop):
+ *   votes  [n_planes][64][(h / 8) (w / 8)] int32 (out): phase p's own ny_p x nx_p grid, row-major, at the start of its slot,
+ *          the rest of the slot untouched; NULL to skip
+ *   sums   [n_planes][64] int64 (out): sum_p; zeroed and accumulated by integer atomics, one per wave
+ * WM_ERR_BADARG: delta as above, sums NULL.  No plane or no whole tile (h < 8 or w < 8): WM_OK without a launch, nothing
+ * written. */
+int wm_payload_phase_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, int32_t* votes, int64_t* sums, int n_planes, int h, int w,
+                                 int row_stride, size_t plane_stride, float delta);
+int wm_payload_phase_scan_u8(wm_ctx* ctx, const uint8_t* stego, int32_t* votes, int64_t* sums, int n_planes, int h, int w,
+                             int row_stride, size_t plane_stride, float delta);
+
+/* Step 3, one workgroup per placement:
+ *   votes           [ny][nx] int32, one phase's grid as the phase scan wrote it
+ *   tile_bit_index  [nby][nbx] int32; an entry outside 0 .. n_bits - 1 is skipped (the device does not trust the map)
+ *   scores          [nby - ny + 1][nbx - nx + 1] int64 (out)
+ * hist is int32 and wraps like any int32 sum, on the device as in NumPy (|vote| <= 2^15: no wrap below 2^16 tiles a bit).
+ * WM_ERR_BADARG: n_bits < 1 or > 16384 (hist lives in 64 KiB of LDS), negative sizes, NULL pointers.  No placement: WM_OK
+ * without a launch, nothing written; no window (ny or nx 0): every score 0, without a launch. */
+int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
+                                 int nby, int nbx, int n_bits);
+int wm_payload_offset_scores(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
+                             int nby, int nbx, int n_bits);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
