@@ -415,12 +415,11 @@ WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], 
   const float rx = frsq(x);
   const float u = gt * ih;
   const float gh = gg * ih;
-  float w;                                         // |t g|
-  if (!wave_swaps) {
+  if (!wave_swaps) {                               // tau <= 0 in every tile: al IS the larger norm, no max / min
     const float rx2 = rx * rx;                     // 1 / cos^2
     const float tq = u * w2[p];
     const float v = u * rx2;
-    w = gh * rx2;
+    const float w = gh * rx2;                      // |t g|
     w2[p] *= x;
     const float tp = v * w2[q];
     w2[q] *= rx2;
@@ -430,11 +429,13 @@ WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], 
       a[rp][p] = fma2(Tp, a[rp][q], a[rp][p]);
       a[rp][q] = fma2(Tq, a[rp][p], a[rp][q]);
     }
+    n2[p] = al + w;
+    n2[q] = be - w;
   } else {
     const float pq = w2[p] * w2[q];
     const float c0 = x * rx;
     const float r = frsq(pq);                      // 1 / (d_p d_q)
-    w = (gh * rx) * rx;
+    const float w = (gh * rx) * rx;
     const float s0 = (u * rx) * (pq * r);          // sin * sign(g)
     const float rq = w2[q] * r, rp_ = w2[p] * r;   // d_q / d_p, d_p / d_q
     const bool sw = tau > 0.0f;                    // de Rijk: larger column ends in p
@@ -446,9 +447,9 @@ WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], 
       a[rp][p] = fma2(Cv, X, Sp * Y);
       a[rp][q] = fma2(Cv, Y, -(Sq * X));
     }
+    n2[p] = fmaxf(al, be) + w;
+    n2[q] = fminf(al, be) - w;
   }
-  n2[p] = fmaxf(al, be) + w;
-  n2[q] = fminf(al, be) - w;
 }
 
 WM_HD void col_norms2_pk(const v2f (&a)[4][8], float (&n2)[8]) {

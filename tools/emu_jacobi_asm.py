@@ -251,23 +251,24 @@ def _unpack(v, base, n):
 _STREAM = {}
 
 
-def _stream(move_test=True, lq=True, scaled=True):
-    if (move_test, lq, scaled) not in _STREAM:
-        _STREAM[move_test, lq, scaled] = G.build(move_test, lq, scaled)
-    return _STREAM[move_test, lq, scaled]
+def _stream(move_test=True, lq=True, scaled=True, swapfree=True):
+    if (move_test, lq, scaled, swapfree) not in _STREAM:
+        _STREAM[move_test, lq, scaled, swapfree] = G.build(move_test, lq, scaled, swapfree)
+    return _STREAM[move_test, lq, scaled, swapfree]
 
 
 def run(raw_tiles: np.ndarray, conv2: float, skip2: float, min_sweeps: int, skip_from: int, lq: int = 1, stats=None,
-        move_test=True, scaled=True, scales=None):
+        move_test=True, scaled=True, scales=None, swapfree=True):
     """raw_tiles uint8 [n, 8, 8] -> (a [n, 4, 8, 2] float32, n2 [n, 8], more mask (bool [n]), sweeps).
     scaled=False: the stream whose every pair takes the unscaled rotation (gen_jacobi_asm.build(scaled=False), the baseline
-    of the scaled rotations); scales (a list) receives the squared column scales [n, 8] as the last sweep left them.
+    of the scaled rotations); swapfree=False: the scaled rotations that take max / min of the two norms ahead of the branch
+    (gen_jacobi_asm.build(swapfree=False), the baseline of the in-place norm update); scales (a list) receives the squared column scales [n, 8] as the last sweep left them.
     lq=0: the stream without the LQ prelude (gen_jacobi_asm.build(lq=False), the baseline); stats: see _interp; move_test=False: the stream that stops on cos^2
     alone (gen_jacobi_asm.build(False): the iteration before the prelude)."""
     n = raw_tiles.shape[0]
     lo, hi = _pack_words(raw_tiles)
     named = {"%[conv]": F(conv2), "%[skip]": F(skip2), "%[minsw]": int(min_sweeps), "%[skipfrom]": int(skip_from)}
-    v, more, sweeps = _interp(_stream(move_test, bool(lq), scaled), n, named, lo, hi, stats=stats, scales=scales)
+    v, more, sweeps = _interp(_stream(move_test, bool(lq), scaled, swapfree), n, named, lo, hi, stats=stats, scales=scales)
     n2 = np.stack([v[G.N0 + c] for c in range(8)], axis=1)
     return _unpack(v, G.A0, n), n2, more, sweeps
 

@@ -245,7 +245,7 @@ def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False, move_test=True):
         st.hist.append(("nop", set()))       # a taken branch lands here: nothing before it may be assumed
 
 
-def rotation_scaled(st, p, q, uid, L=LAY):
+def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     """rotation(plain=True) on SCALED columns a_c = sqrt(w_c) at_c, for the untested sweeps of the V-free stream: B's
     registers hold at_c, L.W(c) the squared scale w_c (jacobi_rot_scaled_pk).  Where no tile of the wave takes the de
     Rijk swap (tau <= 0 in all 64 lanes) the update is two packed FMAs per row pair and no product,
@@ -258,22 +258,31 @@ def rotation_scaled(st, p, q, uid, L=LAY):
     update with the scale ratios folded into its coefficients, at_p' = C at_p + S (d_q / d_p) at_q, at_q' = C at_q -
     S (d_p / d_q) at_p (one more v_rsq_f32, of w_p w_q); the scales stay as they are.
     Scale range: c^2 is in [0.5, 1], a rotation leaves the product of the eight w at 1, and a column meets 7 rotations
-    in each of at most 3 untested sweeps: 2^-21 <= w <= 2^21, no rescaling.  (The study's tiles stay within [0.2, 5].)"""
+    in each of at most 3 untested sweeps: 2^-21 <= w <= 2^21, no rescaling.  (The study's tiles stay within [0.2, 5].)
+    swapfree: the swap-free path runs only where tau = n2[q] - n2[p] <= 0 in every lane, so there max(n2[p], n2[q]) IS
+    n2[p] and the min IS n2[q], bit for bit: the two norms are updated in place and the max / min are left to the swap
+    branch (two scalar instructions fewer per swap-free rotation, the same bits).  swapfree=False is the body as it was,
+    max and min ahead of the branch: never compiled, only interpreted as the baseline the new body is held against."""
     A, N, W = L.A, L.N, L.W
     GV, T1, T2, CS, T3, GVl, GVh, C, S = L.GV, L.T1, L.T2, L.CS, L.T3, L.GVl, L.GVh, L.C, L.S
     g, gg, ab, tau, ta, t1, ih, x = L.g, L.gg, L.ab, L.tau, L.ta, L.t1, L.ih, L.x
     P89 = f"v[{L.T + 8}:{L.T + 9}]"                                     # (g, gg): free once s0 and the norms are there
     Np, Nq = N(p), N(q)
+    # the dot product's packed chain, a scalar instruction between two links (a packed result is never read by the
+    # next instruction); without the max, the product of the scales is what parts the last link from its sum
+    fill = [f"v_sub_f32_e32 {tau}, {Nq}, {Np}",                        # tau = be - al
+            f"v_add_f32_e64 {ta}, |{tau}|, {EPS}",                     # |tau| + 1e-18 (the eps: tau = g = 0 -> cos^2 = 1, not 0.5)
+            f"v_mul_f32_e32 {t1}, {ta}, {ta}",
+            f"v_mul_f32_e32 {x}, {W(p)}, {W(q)}"]
+    dot = f"v_add_f32_e32 {g}, {GVl}, {GVh}"                           # gt = at_p . at_q
+    tail = [fill[3], dot] if swapfree else [dot, fill[3]]
+    fill = fill[:3] if swapfree else [f"v_max_f32_e32 {ab}, {Np}, {Nq}"] + fill[:3]
     st.emit(f"v_pk_mul_f32 {GV}, {A(0, p)}, {A(0, q)}")
-    st.emit(f"v_max_f32_e32 {ab}, {Np}, {Nq}")
-    st.emit(f"v_pk_fma_f32 {GV}, {A(1, p)}, {A(1, q)}, {GV}")
-    st.emit(f"v_sub_f32_e32 {tau}, {Nq}, {Np}")                       # tau = be - al
-    st.emit(f"v_pk_fma_f32 {GV}, {A(2, p)}, {A(2, q)}, {GV}")
-    st.emit(f"v_add_f32_e64 {ta}, |{tau}|, {EPS}")                     # |tau| + 1e-18
-    st.emit(f"v_pk_fma_f32 {GV}, {A(3, p)}, {A(3, q)}, {GV}")
-    st.emit(f"v_mul_f32_e32 {t1}, {ta}, {ta}")
-    st.emit(f"v_add_f32_e32 {g}, {GVl}, {GVh}")                        # gt = at_p . at_q
-    st.emit(f"v_mul_f32_e32 {x}, {W(p)}, {W(q)}")
+    for rp in (1, 2, 3):
+        st.emit(fill[rp - 1])
+        st.emit(f"v_pk_fma_f32 {GV}, {A(rp, p)}, {A(rp, q)}, {GV}")
+    for ln in fill[3:] + tail:
+        st.emit(ln)
     st.emit(f"v_mul_f32_e32 {gg}, {g}, {x}")
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {g}")                          # g^2 = (gt w_p w_q) gt
     st.emit(f"v_fma_f32 {t1}, {gg}, 4.0, {t1}")                        # h^2 = tau^2 + 4 g^2
@@ -284,7 +293,10 @@ def rotation_scaled(st, p, q, uid, L=LAY):
     st.emit(f"v_mul_f32_e32 {GVh}, {g}, {ih}")                         # u = gt / h
     st.emit(f"v_cmp_lt_f32_e32 vcc, 0, {tau}")                         # de Rijk: does any tile of the wave want the swap?
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {ih}")                         # g^2 / h
-    st.emit(f"v_min_f32_e32 {ta}, {Np}, {Nq}")                         # (ta is dead after cos^2)
+    maxmin = [f"v_max_f32_e32 {ab}, {Np}, {Nq}", f"v_min_f32_e32 {ta}, {Np}, {Nq}"]     # (ta is dead after cos^2)
+    big, small = (Np, Nq) if swapfree else (ab, ta)                    # no lane swaps: n2[p] is the larger norm in every lane
+    if not swapfree:
+        st.emit(maxmin[1])
     st.emit(f"s_cbranch_vccnz .Lwmj_swap_{uid}_%=", kind="salu")
     # -- no lane swaps
     st.emit(f"v_mul_f32_e32 {t1}, {t1}, {t1}")                         # 1 / cos^2
@@ -294,8 +306,8 @@ def rotation_scaled(st, p, q, uid, L=LAY):
     st.emit(f"v_mul_f32_e32 {W(p)}, {W(p)}, {x}")
     st.emit(f"v_mul_f32_e32 {C}, {GVh}, {W(q)}")                       # t_p = u w_q / cos^2
     st.emit(f"v_mul_f32_e32 {W(q)}, {W(q)}, {t1}")
-    st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")                       # larger norm grows by |t g|
-    st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
+    st.emit(f"v_add_f32_e64 {Np}, {big}, |{gg}|")                      # larger norm grows by |t g|
+    st.emit(f"v_sub_f32_e64 {Nq}, {small}, |{gg}|")
     for rp in range(4):
         st.emit(f"v_pk_fma_f32 {A(rp, p)}, {CS}, {A(rp, q)}, {A(rp, p)} op_sel_hi:[0,1,1]")
     for rp in range(4):
@@ -304,6 +316,9 @@ def rotation_scaled(st, p, q, uid, L=LAY):
     # -- some lane swaps: rotation()'s update on the scaled columns
     st.emit(f".Lwmj_swap_{uid}_%=:", kind="label")
     st.hist.append(("nop", set()))
+    if swapfree:
+        st.emit(maxmin[0])
+        st.emit(maxmin[1])
     st.emit(f"v_mul_f32_e32 {ih}, {W(p)}, {W(q)}")
     st.emit(f"v_mul_f32_e32 {GVl}, {x}, {t1}")                         # c0 = cos
     st.emit(f"v_rsq_f32_e32 {x}, {ih}")                                # 1 / (d_p d_q)
@@ -439,10 +454,11 @@ def eps_literal():
     return struct.unpack("<I", struct.pack("<f", 1e-18))[0]  # keeps 0/0 out; its square (1e-36) is a normal float
 
 
-def build(move_test=True, lq=True, scaled=True):
+def build(move_test=True, lq=True, scaled=True, swapfree=True):
     """lq=False: no LQ prelude; move_test=False: the tested sweeps stop on cos^2 alone, as they did before the LQ prelude (what the emulator
     measures the prelude against); scaled=False: every pair takes rotation() on unscaled columns (what the scaled
-    rotations are measured against); the committed stream is build()."""
+    rotations are measured against); swapfree=False: the scaled rotations with max / min of the two norms ahead of the
+    branch (what the in-place norm update of the swap-free path is measured against); the committed stream is build()."""
     st = Stream()
     e = st.emit
     Alo, Ahi = LAY.Alo, LAY.Ahi
@@ -483,7 +499,7 @@ def build(move_test=True, lq=True, scaled=True):
     for p in range(7):
         for q in range(p + 1, 8):
             if scaled:
-                rotation_scaled(st, p, q, f"{p}{q}")
+                rotation_scaled(st, p, q, f"{p}{q}", swapfree=swapfree)
             else:
                 rotation(st, p, q, -1, plain=True)
     if scaled:

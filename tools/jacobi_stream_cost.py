@@ -5,7 +5,11 @@ costs measured on the part (profiles/r02_embed_variants.md section 2, middle of 
 rotations against the one whose every pair takes the unscaled rotation (gen_jacobi_asm.build(scaled=False)).
 
     python tools/jacobi_stream_cost.py
+    python tools/jacobi_stream_cost.py --swapfree     # the in-place norm update of the swap-free scaled rotation against
+                                                      # the body that takes max / min of the two norms ahead of the branch
 """
+import sys
+
 import numpy as np
 
 import emu_jacobi_asm as emu
@@ -19,13 +23,13 @@ def noise_waves():
     return np.random.default_rng(2025).integers(0, 256, (40, 64, 8, 8), dtype=np.uint8)
 
 
-def count(cfg, scaled, waves=None):
+def count(cfg, scaled, waves=None, swapfree=True):
     """-> (executed instructions per wave by class, mean sweeps per wave, {sweep: (rotations, of them in the swap branch)})"""
     waves = noise_waves() if waves is None else waves
     tot, sweeps = {}, []
     for t in waves:
         st = {}
-        _, _, more, k = emu.run(t, *cfg, stats=st, scaled=scaled)
+        _, _, more, k = emu.run(t, *cfg, stats=st, scaled=scaled, swapfree=swapfree)
         assert not np.any(more)
         sweeps.append(k)
         for key, val in st.items():
@@ -41,7 +45,28 @@ def cycles(per_class):
     return sum(PRICE[k] * v for k, v in per_class.items())
 
 
+def swapfree_rotations(per_sweep, cfg):
+    """scaled rotations per wave that took the swap-free path: those of the untested sweeps (the first min_sweeps - 1)
+    that did not enter the swap branch"""
+    return sum(r - s for k, (r, s) in per_sweep.items() if k < cfg[2] - 1)
+
+
+def price_swapfree():
+    for name, cfg in CONFIGS.items():
+        old, _, _ = count(cfg, True, swapfree=False)
+        new, sw, ps = count(cfg, True)
+        n = swapfree_rotations(ps, cfg)
+        print(f"{name:5s} sweeps per wave {sw:.3f}, swap-free scaled rotations per wave {n:.1f} of {sum(r for k, (r, s) in ps.items() if k < cfg[2] - 1):.0f}")
+        for tag, pc in (("max/min ahead", old), ("in place     ", new)):
+            print(f"      {tag}  " + "  ".join(f"{k} {v:.1f}" for k, v in pc.items()) + f"  priced {cycles(pc):.0f} cycles")
+        print(f"{name:5s} scalar VALU {new['valu'] - old['valu']:+.1f} per wave, priced cycles {cycles(new) - cycles(old):+.0f} "
+              f"({100 * (cycles(new) / cycles(old) - 1):+.2f} %)")
+
+
 if __name__ == "__main__":
+    if "--swapfree" in sys.argv[1:]:
+        price_swapfree()
+        sys.exit(0)
     for name, cfg in CONFIGS.items():
         cyc = {}
         for scaled in (False, True):
