@@ -142,6 +142,7 @@ constexpr float JAC_TOL2 = 1e-15f;   // skip a rotation below cos = 3.2e-8
 constexpr float JAC_CONV2 = 1e-7f;   // "converged" sweep: max cos < 3.2e-4
 constexpr int JAC_MAX_SWEEPS = 12;
 constexpr int JAC_DEFI_FROM = 6;     // sweeps after which a rank-deficient tile stops counting as "not converged"
+constexpr int JAC_SIGMA_FOLD_AT = 6;  // sigma-only iteration: the 0-based sweep ahead of whose norms the scales go into B, once
 // Singular VALUES alone converge one order ahead of the vectors: after a sweep that saw
 // max cos c the columns are orthogonal to ~c^2 and |b_i| = s_i (1 + O(c^4)), so the
 // sigma-only kernels (extract, detect, K2) may stop well above the embed's threshold.  The embed keeps
@@ -401,22 +402,27 @@ WM_HD void jacobi_rot_pk(v2f (&a)[4][8], float (&n2)[8], const int p, const int 
 // the angle's two rsq.  Where one does, the wave takes jacobi_rot_pk's four-product update with the scale ratios folded
 // into its coefficients; the scales stay.  n2 are the TRUE squared norms throughout.
 // c^2 is in [0.5, 1] and a column meets 7 rotations in each of at most 3 such sweeps: 2^-21 <= w2 <= 2^21, no rescaling.
-WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], const int p, const int q, const bool wave_swaps) {
+// RCP: 1 / c^2 of the swap-free path is one v_rcp_f32 of c^2, not v_rsq_f32 and a square (the sigma-only iteration).
+// TESTED: the tested form of the sigma-only iteration, whose columns stay scaled to the end - jacobi_rot_pk<2>'s
+// convergence and norm-move tests on the true g^2 and the true norms (jacobi_cols_pk<true> keeps the scales in range).
+template <bool TESTED, bool RCP>
+WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], const int p, const int q, const bool wave_swaps,
+                                bool& notconv) {
   v2f gv = a[0][p] * a[0][q];
 #pragma unroll
   for (int rp = 1; rp < 4; ++rp) gv = fma2(a[rp][p], a[rp][q], gv);
   const float gt = gv[0] + gv[1];
   const float al = n2[p], be = n2[q];
   const float gg = (gt * (w2[p] * w2[q])) * gt;  // g^2
+  if (TESTED) notconv = notconv || (gg > JAC_CONV2_SIGMA * (al * be));
   const float tau = be - al;
   const float ta = fabsf(tau) + 1e-18f;
   const float ih = frsq(ffma(gg, 4.0f, ta * ta));  // 1/h
   const float x = ffma(0.5f * ta, ih, 0.5f);       // cos^2 in [0.5, 1]
-  const float rx = frsq(x);
   const float u = gt * ih;
   const float gh = gg * ih;
   if (!wave_swaps) {                               // tau <= 0 in every tile: al IS the larger norm, no max / min
-    const float rx2 = rx * rx;                     // 1 / cos^2
+    const float rx2 = RCP ? frcp(x) : frsq(x) * frsq(x);   // 1 / cos^2
     const float tq = u * w2[p];
     const float v = u * rx2;
     const float w = gh * rx2;                      // |t g|
@@ -429,9 +435,11 @@ WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], 
       a[rp][p] = fma2(Tp, a[rp][q], a[rp][p]);
       a[rp][q] = fma2(Tq, a[rp][p], a[rp][q]);
     }
+    if (TESTED) notconv = notconv || (w * w > (JAC_MOVE2 * al) * n2[0]);
     n2[p] = al + w;
     n2[q] = be - w;
   } else {
+    const float rx = frsq(x);
     const float pq = w2[p] * w2[q];
     const float c0 = x * rx;
     const float r = frsq(pq);                      // 1 / (d_p d_q)
@@ -447,9 +455,14 @@ WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], 
       a[rp][p] = fma2(Cv, X, Sp * Y);
       a[rp][q] = fma2(Cv, Y, -(Sq * X));
     }
+    if (TESTED) notconv = notconv || (w * w > (JAC_MOVE2 * fmaxf(al, be)) * n2[0]);
     n2[p] = fmaxf(al, be) + w;
     n2[q] = fminf(al, be) - w;
   }
+}
+WM_HD void jacobi_rot_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], const int p, const int q, const bool wave_swaps) {
+  bool unused = false;
+  jacobi_rot_scaled_pk<false, false>(a, n2, w2, p, q, wave_swaps, unused);
 }
 
 WM_HD void col_norms2_pk(const v2f (&a)[4][8], float (&n2)[8]) {
@@ -472,11 +485,20 @@ WM_HD void jacobi_sweep_pk(v2f (&a)[4][8], float (&n2)[8], bool& notconv) {
     for (int q = p + 1; q < 8; ++q) jacobi_rot_pk<CHECK, SKIP>(a, n2, p, q, notconv);
 }
 // an untested sweep of jacobi_cols_pk: scaled columns, the swap decided per pair for the whole wave
+template <bool RCP = false>
 WM_HD void jacobi_sweep_scaled_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8]) {
+  bool unused = false;
 #pragma unroll
   for (int p = 0; p < 7; ++p)
 #pragma unroll
-    for (int q = p + 1; q < 8; ++q) jacobi_rot_scaled_pk(a, n2, w2, p, q, wave_any(n2[q] - n2[p] > 0.0f));
+    for (int q = p + 1; q < 8; ++q) jacobi_rot_scaled_pk<false, RCP>(a, n2, w2, p, q, wave_any(n2[q] - n2[p] > 0.0f), unused);
+}
+// a tested sweep of the sigma-only iteration: the same on scaled columns, with jacobi_rot_pk<2>'s tests
+WM_HD void jacobi_sweep_scaled_tested_pk(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], bool& notconv) {
+#pragma unroll
+  for (int p = 0; p < 7; ++p)
+#pragma unroll
+    for (int q = p + 1; q < 8; ++q) jacobi_rot_scaled_pk<true, true>(a, n2, w2, p, q, wave_any(n2[q] - n2[p] > 0.0f), notconv);
 }
 // n2 of the scaled columns made true, and the scales folded back into B
 WM_HD void col_norms2_scaled_pk(const v2f (&a)[4][8], const float (&w2)[8], float (&n2)[8]) {
@@ -565,8 +587,8 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
   bool notconv = false;
   float w2[8] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
   col_norms2_pk(a, n2);
-  jacobi_sweep_scaled_pk(a, n2, w2);
-  jacobi_sweep_scaled_pk(a, n2, w2);
+  jacobi_sweep_scaled_pk<SIGMA_ONLY>(a, n2, w2);
+  jacobi_sweep_scaled_pk<SIGMA_ONLY>(a, n2, w2);
   int sweep = 2;
   // The embed's third sweep carries no test either: behind the prelude no image or noise tile is done after three
   // sweeps at cos^2 <= 1e-7 (tools/skip_study.cpp), so the earliest last sweep is the 4th - and that one already tests
@@ -576,20 +598,37 @@ WM_HD int jacobi_cols_pk(v2f (&a)[4][8], float (&n2)[8]) {
     jacobi_sweep_scaled_pk(a, n2, w2);
     sweep = 3;
   }
-  fold_scales_pk(a, w2);
+  // The sigma-only iteration hands out nothing but the norms: its columns stay scaled to the end (no fold here, scaled
+  // rotations in the tested sweeps, every recomputed norm multiplied by its scale).  A scale moves by at most 2^+-7 per
+  // sweep, so the scales are folded into B once, ahead of the 7th sweep's norms: 2^+-42 on either side of it up to the
+  // sweep bound (only a wave with rank-deficient tiles gets there).
+  if (!SIGMA_ONLY) fold_scales_pk(a, w2);
   bool more = true;
   while (more && sweep < JAC_MAX_SWEEPS) {
-    if ((sweep & 1) == 0) col_norms2_pk(a, n2);
+    if ((sweep & 1) == 0) {
+      if (SIGMA_ONLY && sweep == JAC_SIGMA_FOLD_AT) {
+        fold_scales_pk(a, w2);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) w2[c] = 1.0f;
+      }
+      if (SIGMA_ONLY) col_norms2_scaled_pk(a, w2, n2);
+      else col_norms2_pk(a, n2);
+    }
     notconv = false;
     if (!SIGMA_ONLY) jacobi_sweep_pk<1, true>(a, n2, notconv);
-    else jacobi_sweep_pk<2>(a, n2, notconv);
+    else jacobi_sweep_scaled_tested_pk(a, n2, w2, notconv);
     ++sweep;
     // a rank-deficient tile's null columns are rounding residue whose cosines never fall (and whose tracked norms
     // cancel to garbage): after JAC_DEFI_FROM sweeps such a lane no longer keeps its wave iterating (gen_jacobi_asm.py)
     if (sweep >= JAC_DEFI_FROM && !(n2[7] > SIGMA_RATIO_MIN2 * n2[0])) notconv = false;
     more = wave_any(notconv);
   }
-  col_norms2_pk(a, n2);
+  if (SIGMA_ONLY) {
+    col_norms2_scaled_pk(a, w2, n2);
+    fold_scales_pk(a, w2);               // a caller that looks at B gets the true columns (dead code where none does)
+  } else {
+    col_norms2_pk(a, n2);
+  }
   return more ? -sweep : sweep;
 }
 

@@ -10,6 +10,7 @@
 // wave-uniform).  The path is VALU-bound (~10^4 FMA-class instructions per
 // tile against 3 B per pixel); see DESIGN.md for the roofline.
 //
+//   python ../../tools/gen_jacobi_asm.py --write     (writes wm_jacobi_sigma_gfx950.inc, which is generated and not committed)
 //   hipcc -O3 --offload-arch=gfx950 -shared -fPIC -o libwmhip.so wmhip.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -60,12 +61,15 @@ constexpr int N_SUMS = 5;          // detect: sum a, b, ab, aa, bb
 // builds the C++ form of wm_tile_math.h instead (A/B, and what the CPU harness tests).
 #if !defined(WM_NO_ASM_JACOBI)
 #include "wm_jacobi_gfx950.inc"
+#if !__has_include("wm_jacobi_sigma_gfx950.inc")
+#error "wm_jacobi_sigma_gfx950.inc is generated: run `python tools/gen_jacobi_asm.py --write` (build() does) before compiling"
+#endif
+#include "wm_jacobi_sigma_gfx950.inc"
 #endif
 
 // singular values of a raw tile (sigma-only kernels: K2, extract, detect); < 0: sweep bound hit
 __device__ __forceinline__ int sigma_tile_dev(const wm::RawTile& raw, float (&s)[8]) {
 #if !defined(WM_NO_ASM_JACOBI)
-  wm::v2f a[4][8];
   float n2[8];
   // sigma only, behind the LQ prelude (B0 = X Q, wm_tile_math.h: about one sweep fewer): test from the 3rd sweep on, a
   // sweep being the last one if it saw no pair above cos^2 = JAC_CONV2_SIGMA and no rotation that moved a squared value
@@ -77,7 +81,9 @@ __device__ __forceinline__ int sigma_tile_dev(const wm::RawTile& raw, float (&s)
   // (profiles/r02m_sigma_skip.log), 1e-7 and 1e-8 leave every value where the full sweeps leave it.
   constexpr float SIGMA_SKIP2 = 1e-8f;
   constexpr int SIGMA_SKIP_FROM = 2;
-  const unsigned long long more = jacobi_cols_gfx950(raw.lo, raw.hi, a, n2, wm::JAC_CONV2_SIGMA, SIGMA_SKIP2, 3, SIGMA_SKIP_FROM);
+  // Only the norms leave the iteration here, so this is the stream whose columns stay scaled to the end (no fold of the
+  // scales into B, scaled rotations in the tested sweeps too): wm_jacobi_sigma_gfx950.inc.
+  const unsigned long long more = jacobi_sigma_gfx950(raw.lo, raw.hi, n2, wm::JAC_CONV2_SIGMA, SIGMA_SKIP2, 3, SIGMA_SKIP_FROM);
 #pragma unroll
   for (int i = 0; i < 8; ++i) s[i] = wm::fsqrt(n2[i]);
   return more ? -1 : 1;

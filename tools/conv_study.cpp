@@ -7,6 +7,9 @@
 //  columns (jacobi_rot_scaled_pk), the swap branch taken by a whole wave at a pair where any of its 64 tiles has tau > 0,
 //  and the scales are folded back behind them - what the kernels do since round 6; also reported: the share of a
 //  sweep's 28 pairs at which the wave wants that branch, and the range of the squared scales;
+//  argument 5: as 4, but the columns stay scaled to the end, as in the sigma-only iteration since round 8 - every sweep
+//  rotates scaled columns, nothing is folded back except once ahead of the 7th sweep's norms (JAC_SIGMA_FOLD_AT), and the
+//  final norms are those of the scaled columns times their scales;
 //  move2 > 0: a sweep is the last one only if, besides cos^2 <= T, no rotation of it moved the squared norms by w with
 //  w^2 > move2 n2[0] max(n2[p], n2[q]) - the second stopping test of jacobi_rot_pk, JAC_MOVE2)
 #include <math.h>
@@ -34,7 +37,7 @@ static void rot(v2f (&a)[4][8], float (&n2)[8], int p, int q, float& maxc2, floa
 }
 
 // the same around jacobi_rot_scaled_pk
-static void rot_scaled(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], int p, int q, float& maxc2, float& maxmv, bool wave_swaps) {
+static void rot_scaled(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], int p, int q, float& maxc2, float& maxmv, bool wave_swaps, bool rcp) {
   v2f gv = a[0][p] * a[0][q];
   for (int rp = 1; rp < 4; ++rp) gv = fma2(a[rp][p], a[rp][q], gv);
   const float gt = gv[0] + gv[1], gg = (gt * (w2[p] * w2[q])) * gt;
@@ -44,7 +47,9 @@ static void rot_scaled(v2f (&a)[4][8], float (&n2)[8], float (&w2)[8], int p, in
   const float ta = fabsf(be - al) + 1e-18f, ih = frsq(ffma(gg, 4.0f, ta * ta)), rx = frsq(ffma(0.5f * ta, ih, 0.5f));
   const float w = ((gg * ih) * rx) * rx, mv = w * w / fmaxf(fmaxf(al, be) * n2[0], 1e-30f);
   if (mv > maxmv) maxmv = mv;
-  jacobi_rot_scaled_pk(a, n2, w2, p, q, wave_swaps);
+  bool dummy = false;
+  if (rcp) jacobi_rot_scaled_pk<false, true>(a, n2, w2, p, q, wave_swaps, dummy);   // the sigma-only iteration's 1 / c^2
+  else jacobi_rot_scaled_pk(a, n2, w2, p, q, wave_swaps);
 }
 
 static void svd_f64(const double (&x)[8][8], double (&s)[8]) {
@@ -118,7 +123,7 @@ int main(int argc, char** argv) {
             v2f v = {(float)px[((size_t)w * 64 + l) * 64 + (2 * rp) * 8 + c], (float)px[((size_t)w * 64 + l) * 64 + (2 * rp + 1) * 8 + c]};
             a[l][rp][c] = v;
           }
-          if (MODE == 3 || MODE == 4) lq_prelude_pk(a[l]);   // B0 = X Q: row-pivoted Householder LQ from the right
+          if (MODE >= 3 && MODE <= 5) lq_prelude_pk(a[l]);   // B0 = X Q: row-pivoted Householder LQ from the right
           col_norms2_pk(a[l], n2[l]); tile_done[l] = 0;
           for (int c = 0; c < 8; ++c) w2[l][c] = 1.0f;
           if (argc > 1 && atoi(argv[1]) == 1) {      // experiment: columns sorted by norm (descending) before the first sweep
@@ -141,9 +146,9 @@ int main(int argc, char** argv) {
         while (more && sweep < 12) {
           more = false;
           float ms[64], mvs[64];
-          const bool scaled = MODE == 4 && sweep < (T <= 1e-7f ? 3 : 2);
+          const bool scaled = (MODE == 4 && sweep < (T <= 1e-7f ? 3 : 2)) || MODE == 5;
           for (int l = 0; l < 64; ++l) {
-            if (MODE == 4 && !scaled) {              // (the first time: the scales go back into B; afterwards w2 == 1)
+            if ((MODE == 4 && !scaled) || (MODE == 5 && sweep == JAC_SIGMA_FOLD_AT)) {   // (the first time: the scales go back into B; afterwards w2 == 1)
               for (int c = 0; c < 8; ++c) { w2min = fminf(w2min, w2[l][c]); w2max = fmaxf(w2max, w2[l][c]); }
               fold_scales_pk(a[l], w2[l]);
               for (int c = 0; c < 8; ++c) w2[l][c] = 1.0f;
@@ -153,13 +158,13 @@ int main(int argc, char** argv) {
             if (!scaled)
               for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) rot(a[l], n2[l], p, q, ms[l], mvs[l]);
           }
-          if (MODE == 4) {                           // pair by pair across the wave: the swap branch is the wave's
+          if (MODE >= 4) {                           // pair by pair across the wave: the swap branch is the wave's
             ++sweeps_run[sweep];
             for (int p = 0; p < 7; ++p) for (int q = p + 1; q < 8; ++q) {
               bool any = false;
               for (int l = 0; l < 64; ++l) any = any || (n2[l][q] - n2[l][p] > 0.0f);
               swap_pairs[sweep] += any;
-              if (scaled) for (int l = 0; l < 64; ++l) rot_scaled(a[l], n2[l], w2[l], p, q, ms[l], mvs[l], any);
+              if (scaled) for (int l = 0; l < 64; ++l) rot_scaled(a[l], n2[l], w2[l], p, q, ms[l], mvs[l], any, MODE == 5);
             }
           }
           for (int l = 0; l < 64; ++l) {
@@ -176,7 +181,8 @@ int main(int argc, char** argv) {
         sum_sweeps += sweep; hist[sweep]++;
         for (int l = 0; l < 64; ++l) {
           sum_tile_sweeps += tile_done[l] ? std::max(tile_done[l], 3) : sweep;
-          col_norms2_pk(a[l], n2[l]);
+          col_norms2_scaled_pk(a[l], w2[l], n2[l]);  // (w2 == 1 unless MODE 5)
+          fold_scales_pk(a[l], w2[l]);               // (for the final cosines below)
           double x[8][8], s[8];
           for (int r = 0; r < 8; ++r) for (int c = 0; c < 8; ++c) x[r][c] = px[((size_t)w * 64 + l) * 64 + r * 8 + c];
           svd_f64(x, s);
@@ -190,7 +196,7 @@ int main(int argc, char** argv) {
       printf("%-8s T=%.0e  wave sweeps avg %.3f [3:%d 4:%d 5:%d 6:%d 7+:%d]  per-tile avg %.3f  sigma err/s1 max %.2e mean %.2e above 2e-6: %ld  final max cos %.2e\n",
              kinds[kind], T, sum_sweeps / NW, hist[3], hist[4], hist[5], hist[6], hist[7] + hist[8] + hist[9] + hist[10] + hist[11] + hist[12],
              sum_tile_sweeps / (NW * 64.0), max_err, sum_err / nerr, above, max_cos);
-      if (MODE == 4) {
+      if (MODE >= 4) {
         printf("%-8s T=%.0e  pairs of 28 in the swap branch, sweep 1..6:", kinds[kind], T);
         for (int k = 0; k < 6; ++k) printf(" %.2f", sweeps_run[k] ? (double)swap_pairs[k] / sweeps_run[k] : 0.0);
         printf("  squared scales in [%.2e, %.2e]\n", w2min, w2max);

@@ -15,12 +15,13 @@ import gen_jacobi_asm as G
 F = np.float32
 
 
-def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, stats=None, stop_at=None, scales=None):
+def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, stats=None, stop_at=None, scales=None, end_scales=None):
     """Runs the stream on n lanes; returns (vector registers [n_vregs, n], more mask, sweeps).  stats (a dict) receives
-    the executed VALU instructions of the wave: "pk" (v_pk_*, also under their mnemonics), "trans" (v_rsq) and "valu"
+    the executed VALU instructions of the wave: "pk" (v_pk_*, also under their mnemonics), "trans" (v_rsq, v_rcp), "dot4" (v_dot4_u32_u8 and v_cvt_f32_u32, which issue at one price) and "valu"
     (the rest), and per 0-based sweep k the rotations carried out ("rot", k), those of them that took the wave's swap
-    branch ("swap", k) and the number of lanes that wanted the swap at each ("swap_lanes", k: a list).  stop_at: a label at which the run ends (the registers as they are there).  scales (a list)
-    receives the V-free stream's squared column scales [n, 8] as they are behind the last sweep."""
+    branch ("swap", k), the folds of the scales into B ("fold") and the number of lanes that wanted the swap at each ("swap_lanes", k: a list).  stop_at: a label at which the run ends (the registers as they are there).  scales (a list)
+    receives the V-free stream's squared column scales [n, 8] as they are behind the last sweep; end_scales (a list) those
+    the stream ends with (the sigma-only stream never folds them away)."""
     v = np.zeros((n_vregs, n), F)
     if v_init:
         for r_, val in v_init.items():
@@ -94,12 +95,14 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, s
                 break
             if stats is not None and ln.startswith(".Lwmj_swap_"):
                 stats["swap", sweeps] = stats.get(("swap", sweeps), 0) + 1
+            if stats is not None and ln == ".Lwmj_fold_%=:":
+                stats["fold"] = stats.get("fold", 0) + 1
             if scales is not None and ln == ".Lwmj_fold_%=:":
                 scales.append(np.stack([v[G.LAY.W0 + c] for c in range(8)], axis=1))
             continue
         mn, rest = ln.split(None, 1)
         if stats is not None and mn.startswith("v_"):
-            kind_ = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith("v_rsq") else "valu"
+            kind_ = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith(("v_rsq", "v_rcp")) else "dot4" if mn.startswith(("v_dot4", "v_cvt_f32_u32")) else "valu"
             stats[kind_] = stats.get(kind_, 0) + 1
             if kind_ == "pk":
                 stats[mn] = stats.get(mn, 0) + 1
@@ -112,6 +115,16 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, s
                 m = re.fullmatch(r"%\[(lo|hi)(\d)\]", opnds[1])
                 w = (lo if m.group(1) == "lo" else hi)[int(m.group(2))]
                 wr(int(opnds[0][1:]), ((w >> np.uint32(8 * b)) & np.uint32(255)).astype(F))
+            elif mn == "v_dot4_u32_u8":                              # four byte products on top of a 32-bit integer
+                word = lambda o: (lo if o[2:4] == "lo" else hi)[int(o[4])] if o.startswith("%[") else \
+                    np.ascontiguousarray(src(o)).view(np.uint32)
+                a, b = word(opnds[1]), word(opnds[2])
+                acc = np.zeros(n, np.uint32) if opnds[3] == "0" else word(opnds[3]).copy()
+                for k in range(4):
+                    acc = acc + ((a >> np.uint32(8 * k)) & np.uint32(255)) * ((b >> np.uint32(8 * k)) & np.uint32(255))
+                wr(int(opnds[0][1:]), acc.astype(np.uint32).view(F))
+            elif mn.startswith("v_cvt_f32_u32"):
+                wr(int(opnds[0][1:]), np.ascontiguousarray(src(opnds[1])).view(np.uint32).astype(F))
             elif mn.startswith("v_mov_b32"):
                 wr(int(opnds[0][1:]), src(opnds[1]))
             elif mn in ("v_pk_mul_f32", "v_pk_fma_f32", "v_pk_add_f32"):
@@ -148,6 +161,8 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, s
             elif mn == "v_fma_f32":
                 a, b, c = (src(o).astype(np.float64) for o in opnds[1:4])
                 wr(int(opnds[0][1:]), (a * b + c).astype(F))
+            elif mn.startswith("v_rcp_f32"):                     # 1 / x in float32 (the hardware's is 1 ulp)
+                wr(int(opnds[0][1:]), (F(1) / src(opnds[1])).astype(F))
             elif mn.startswith("v_rsq_f32"):
                 xx = src(opnds[1]).copy()
                 xx[np.abs(xx) < np.finfo(F).tiny] = 0          # v_rsq_f32 does not take denormals
@@ -194,6 +209,8 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, s
                 scc = bool((sval(opnds[0]) >> sval(opnds[1])) & 1)
             elif mn == "s_cmp_ge_i32":
                 scc = sval(opnds[0]) >= sval(opnds[1])
+            elif mn == "s_cmp_eq_i32":
+                scc = sval(opnds[0]) == sval(opnds[1])
             elif mn == "s_cmp_lt_i32":
                 scc = sval(opnds[0]) < sval(opnds[1])
             elif mn == "s_cmp_eq_u64":
@@ -225,6 +242,8 @@ def _interp(st, n, named, lo=None, hi=None, v_init=None, n_vregs=G.LAY.W0 + 8, s
                 pass
             else:
                 raise NotImplementedError(ln)
+    if end_scales is not None:
+        end_scales.append(np.stack([v[G.LAY.W0 + c] for c in range(8)], axis=1))
     return v, more, sweeps
 
 
@@ -251,24 +270,27 @@ def _unpack(v, base, n):
 _STREAM = {}
 
 
-def _stream(move_test=True, lq=True, scaled=True, swapfree=True):
-    if (move_test, lq, scaled, swapfree) not in _STREAM:
-        _STREAM[move_test, lq, scaled, swapfree] = G.build(move_test, lq, scaled, swapfree)
-    return _STREAM[move_test, lq, scaled, swapfree]
+def _stream(move_test=True, lq=True, scaled=True, swapfree=True, **kw):
+    key = (move_test, lq, scaled, swapfree) + tuple(sorted(kw.items()))
+    if key not in _STREAM:
+        _STREAM[key] = G.build(move_test, lq, scaled, swapfree, **kw)
+    return _STREAM[key]
 
 
 def run(raw_tiles: np.ndarray, conv2: float, skip2: float, min_sweeps: int, skip_from: int, lq: int = 1, stats=None,
-        move_test=True, scaled=True, scales=None, swapfree=True):
+        move_test=True, scaled=True, scales=None, swapfree=True, end_scales=None, **kw):
     """raw_tiles uint8 [n, 8, 8] -> (a [n, 4, 8, 2] float32, n2 [n, 8], more mask (bool [n]), sweeps).
     scaled=False: the stream whose every pair takes the unscaled rotation (gen_jacobi_asm.build(scaled=False), the baseline
     of the scaled rotations); swapfree=False: the scaled rotations that take max / min of the two norms ahead of the branch
     (gen_jacobi_asm.build(swapfree=False), the baseline of the in-place norm update); scales (a list) receives the squared column scales [n, 8] as the last sweep left them.
     lq=0: the stream without the LQ prelude (gen_jacobi_asm.build(lq=False), the baseline); stats: see _interp; move_test=False: the stream that stops on cos^2
-    alone (gen_jacobi_asm.build(False): the iteration before the prelude)."""
+    alone (gen_jacobi_asm.build(False): the iteration before the prelude); further keywords go to gen_jacobi_asm.build as
+    they are (byte_norms=False: the prelude's row norms from the packed float chain; sigma_only=True: the sigma-only stream)."""
     n = raw_tiles.shape[0]
     lo, hi = _pack_words(raw_tiles)
     named = {"%[conv]": F(conv2), "%[skip]": F(skip2), "%[minsw]": int(min_sweeps), "%[skipfrom]": int(skip_from)}
-    v, more, sweeps = _interp(_stream(move_test, bool(lq), scaled, swapfree), n, named, lo, hi, stats=stats, scales=scales)
+    v, more, sweeps = _interp(_stream(move_test, bool(lq), scaled, swapfree, **kw), n, named, lo, hi, stats=stats, scales=scales,
+                             end_scales=end_scales)
     n2 = np.stack([v[G.N0 + c] for c in range(8)], axis=1)
     return _unpack(v, G.A0, n), n2, more, sweeps
 
@@ -280,6 +302,17 @@ def run_prelude(raw_tiles: np.ndarray):
     named = {"%[conv]": F(0), "%[skip]": F(0), "%[minsw]": 0, "%[skipfrom]": 0}
     v, _, _ = _interp(_stream(), n, named, lo, hi, stop_at=".Lwmj_lqdone_%=")
     return _unpack(v, G.A0, n)
+
+
+def run_row_norms(raw_tiles: np.ndarray, byte_norms=True):
+    """The eight |row|^2 the LQ prelude opens with ([n, 8] float32): the stream up to the first pivot search."""
+    n = raw_tiles.shape[0]
+    lo, hi = _pack_words(raw_tiles)
+    st = G.Stream()
+    full = _stream(byte_norms=byte_norms)
+    st.lines = full.lines[:next(i for i, ln in enumerate(full.lines) if ln.startswith("v_max3_f32"))]
+    v, _, _ = _interp(st, n, {}, lo, hi)
+    return np.stack([v[G.T + 8 + r] for r in range(8)], axis=1)
 
 
 def run_v(tiles_f32: np.ndarray, conv2: float):

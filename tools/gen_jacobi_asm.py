@@ -32,7 +32,11 @@ A second stream, csrc/wm_jacobi_v_gfx950.inc (build_v), is jacobi_cols_pk_v: the
 stacked rows of B and V (v[40:103], v[104:167]), every pair tested and rotated, a converged lane leaving the
 exec mask - the literal path of rank-deficient tiles and the watermark-side SVD.
 
-    python tools/gen_jacobi_asm.py          # rewrites both .inc files next to the kernels
+A third, csrc/wm_jacobi_sigma_gfx950.inc (build(sigma_only=True)), is the V-free stream for the callers that take only
+the singular values: the columns stay scaled through the tested sweeps too and are never folded back.  It is not
+committed (write_sigma() says why): `--write` and the package's build() generate it.
+
+    python tools/gen_jacobi_asm.py --write  # rewrites the .inc files next to the kernels where they differ
 """
 import os
 import struct
@@ -89,6 +93,7 @@ TMPM, NOSKIP, TMPS = "s[88:89]", "s[90:91]", "s98"
 LQ_STEPS = 7            # reflectors of the LQ prelude (5 / 6 / 7: 4.45 / 4.30 / 4.15 embed sweeps per wave on noise tiles)
 LQ_T, LQ_FOUND, LQ_M = "s[92:93]", "s[94:95]", "s[96:97]"   # LQ prelude: compare result, rows matched so far, this row's one-hot
 DEFI_FROM = 6           # from this many sweeps on, a lane whose tile is rank deficient no longer keeps its wave iterating
+SIGMA_FOLD_AT = 6       # sigma-only stream: the 0-based sweep ahead of whose norms the scales are folded into B, once
 SAVE = "s[88:89]"       # with-V stream: the caller's exec mask (TMPM / NOSKIP are unused there)
 
 
@@ -140,7 +145,7 @@ class Stream:
             self.lines.append(f"s_nop {need - 1}")
             for _ in range(need):
                 self.hist.append(("nop", set()))
-        k = "pk" if mn.startswith("v_pk_") else "trans" if mn.startswith("v_rsq") else "vcmp" if mn.startswith("v_cmp") else "valu"
+        k = "pk" if mn.startswith(("v_pk_", "v_dot4_")) else "trans" if mn.startswith(("v_rsq", "v_rcp")) else "vcmp" if mn.startswith("v_cmp") else "valu"
         self.lines.append(text)
         self.hist.append((k, self.regs(dst) | ({"vcc"} if k == "vcmp" and dst == "vcc" else set())))
 
@@ -245,7 +250,7 @@ def rotation(st, p, q, uid, plain=False, L=LAY, with_v=False, move_test=True):
         st.hist.append(("nop", set()))       # a taken branch lands here: nothing before it may be assumed
 
 
-def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
+def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True, rcp=False, tested=False, move_test=True):
     """rotation(plain=True) on SCALED columns a_c = sqrt(w_c) at_c, for the untested sweeps of the V-free stream: B's
     registers hold at_c, L.W(c) the squared scale w_c (jacobi_rot_scaled_pk).  Where no tile of the wave takes the de
     Rijk swap (tau <= 0 in all 64 lanes) the update is two packed FMAs per row pair and no product,
@@ -262,7 +267,18 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     swapfree: the swap-free path runs only where tau = n2[q] - n2[p] <= 0 in every lane, so there max(n2[p], n2[q]) IS
     n2[p] and the min IS n2[q], bit for bit: the two norms are updated in place and the max / min are left to the swap
     branch (two scalar instructions fewer per swap-free rotation, the same bits).  swapfree=False is the body as it was,
-    max and min ahead of the branch: never compiled, only interpreted as the baseline the new body is held against."""
+    max and min ahead of the branch: never compiled, only interpreted as the baseline the new body is held against.
+    rcp: 1 / c^2 is one v_rcp_f32 of c^2 where it is v_rsq_f32 and a square (one scalar instruction fewer on the
+    swap-free path, the last bit of a scale may differ); the swap branch, which needs 1 / c itself, takes its own
+    v_rsq_f32.  The sigma-only stream has it; the stream that hands out B does not (build()).
+    tested (the sigma-only stream, whose columns stay scaled to the end): rotation()'s convergence, skip and norm-move
+    tests ahead of the same update, on the true g^2 = gt^2 w_p w_q and the true norms.
+    Scale range with tested sweeps: 2^-7 <= w'/w <= 2^7 per sweep (seven rotations, c^2 in [0.5, 1]).  Up to the sweep
+    bound of 12 that would be 2^+-84 and the product w_p w_q of a rotation could leave the float range, so the
+    sigma-only stream folds the scales into B once, where the 7th sweep recomputes its norms (build(sigma_only=True)):
+    2^-42 <= w <= 2^42 on either side of it, w_p w_q and gt w_p w_q = g sqrt(w_p w_q) <= 2^21 2^42 stay normal floats.
+    (A wave gets there only with rank-deficient tiles; the study's tiles stay within [0.2, 5] throughout.)"""
+    assert swapfree or not tested
     A, N, W = L.A, L.N, L.W
     GV, T1, T2, CS, T3, GVl, GVh, C, S = L.GV, L.T1, L.T2, L.CS, L.T3, L.GVl, L.GVh, L.C, L.S
     g, gg, ab, tau, ta, t1, ih, x = L.g, L.gg, L.ab, L.tau, L.ta, L.t1, L.ih, L.x
@@ -277,6 +293,8 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     dot = f"v_add_f32_e32 {g}, {GVl}, {GVh}"                           # gt = at_p . at_q
     tail = [fill[3], dot] if swapfree else [dot, fill[3]]
     fill = fill[:3] if swapfree else [f"v_max_f32_e32 {ab}, {Np}, {Nq}"] + fill[:3]
+    if tested:
+        tail = [f"v_mul_f32_e32 {ab}, {Np}, {Nq}"] + tail
     st.emit(f"v_pk_mul_f32 {GV}, {A(0, p)}, {A(0, q)}")
     for rp in (1, 2, 3):
         st.emit(fill[rp - 1])
@@ -285,11 +303,20 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
         st.emit(ln)
     st.emit(f"v_mul_f32_e32 {gg}, {g}, {x}")
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {g}")                          # g^2 = (gt w_p w_q) gt
+    if tested:
+        st.emit(f"v_mul_f32_e32 {x}, {CONV}, {ab}")
+        st.emit(f"v_mul_f32_e32 {ih}, {SKIPC}, {ab}")
+        st.emit(f"v_cmp_gt_f32_e32 vcc, {gg}, {x}")                    # notconv |= g^2 > conv2 al be
+        st.emit(f"s_or_b64 {M}, {M}, vcc", kind="salu")
+        st.emit(f"v_cmp_gt_f32_e32 vcc, {gg}, {ih}")                   # any tile above the skip threshold ...
+        st.emit(f"s_or_b64 {TMPM}, vcc, {NOSKIP}", kind="salu")        # ... or a sweep that rotates every pair (SCC = result != 0)
+        st.emit(f"s_cbranch_scc0 .Lwmj_rot_{uid}_%=", kind="salu")
     st.emit(f"v_fma_f32 {t1}, {gg}, 4.0, {t1}")                        # h^2 = tau^2 + 4 g^2
     st.emit(f"v_rsq_f32_e32 {ih}, {t1}")                               # 1/h
     st.emit(f"v_mul_f32_e32 {x}, 0.5, {ta}")
     st.emit(f"v_fma_f32 {x}, {x}, {ih}, 0.5")                          # cos^2 in [0.5, 1]
-    st.emit(f"v_rsq_f32_e32 {t1}, {x}")                                # rx = 1 / cos
+    st.emit(f"v_rcp_f32_e32 {t1}, {x}" if rcp else                     # 1 / cos^2
+            f"v_rsq_f32_e32 {t1}, {x}")                                # rx = 1 / cos
     st.emit(f"v_mul_f32_e32 {GVh}, {g}, {ih}")                         # u = gt / h
     st.emit(f"v_cmp_lt_f32_e32 vcc, 0, {tau}")                         # de Rijk: does any tile of the wave want the swap?
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {ih}")                         # g^2 / h
@@ -299,13 +326,20 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
         st.emit(maxmin[1])
     st.emit(f"s_cbranch_vccnz .Lwmj_swap_{uid}_%=", kind="salu")
     # -- no lane swaps
-    st.emit(f"v_mul_f32_e32 {t1}, {t1}, {t1}")                         # 1 / cos^2
+    if not rcp:
+        st.emit(f"v_mul_f32_e32 {t1}, {t1}, {t1}")                     # 1 / cos^2
     st.emit(f"v_mul_f32_e32 {S}, {GVh}, {W(p)}")                       # t_q = u w_p
     st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {t1}")
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {t1}")                         # w = g^2 / (h cos^2) = |t g|
     st.emit(f"v_mul_f32_e32 {W(p)}, {W(p)}, {x}")
     st.emit(f"v_mul_f32_e32 {C}, {GVh}, {W(q)}")                       # t_p = u w_q / cos^2
     st.emit(f"v_mul_f32_e32 {W(q)}, {W(q)}, {t1}")
+    if tested and move_test:                                           # notconv |= w^2 > move2 n2[p] n2[0] (rotation())
+        st.emit(f"v_mul_f32_e32 {ih}, {f32_literal(MOVE2)}, {Np}")
+        st.emit(f"v_mul_f32_e32 {x}, {gg}, {gg}")
+        st.emit(f"v_mul_f32_e32 {ih}, {ih}, {N(0)}")
+        st.emit(f"v_cmp_gt_f32_e32 vcc, {x}, {ih}")
+        st.emit(f"s_or_b64 {M}, {M}, vcc", kind="salu")
     st.emit(f"v_add_f32_e64 {Np}, {big}, |{gg}|")                      # larger norm grows by |t g|
     st.emit(f"v_sub_f32_e64 {Nq}, {small}, |{gg}|")
     for rp in range(4):
@@ -316,6 +350,8 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     # -- some lane swaps: rotation()'s update on the scaled columns
     st.emit(f".Lwmj_swap_{uid}_%=:", kind="label")
     st.hist.append(("nop", set()))
+    if rcp:
+        st.emit(f"v_rsq_f32_e32 {t1}, {x}")                            # rx = 1 / cos
     if swapfree:
         st.emit(maxmin[0])
         st.emit(maxmin[1])
@@ -326,8 +362,15 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {t1}")
     st.emit(f"v_mul_f32_e32 {gg}, {gg}, {t1}")                         # w
     st.emit(f"v_mul_f32_e32 {ih}, {ih}, {x}")                          # d_p d_q
-    st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")
-    st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
+    if tested and move_test:                                           # (tau is dead: VCC holds the swap; n2[0] as it was)
+        st.emit(f"v_mul_f32_e32 {tau}, {gg}, {gg}")
+        st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
+        st.emit(f"v_mul_f32_e32 {ta}, {f32_literal(MOVE2)}, {ab}")
+        st.emit(f"v_mul_f32_e32 {ta}, {ta}, {N(0)}")
+        st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")
+    else:
+        st.emit(f"v_add_f32_e64 {Np}, {ab}, |{gg}|")
+        st.emit(f"v_sub_f32_e64 {Nq}, {ta}, |{gg}|")
     st.emit(f"v_mul_f32_e32 {GVh}, {GVh}, {ih}")                       # s0 = u d_p d_q / cos = sin * sign(g)
     st.emit(f"v_mul_f32_e32 {ih}, {W(q)}, {x}")                        # d_q / d_p
     st.emit(f"v_mul_f32_e32 {x}, {W(p)}, {x}")                         # d_p / d_q
@@ -336,6 +379,9 @@ def rotation_scaled(st, p, q, uid, L=LAY, swapfree=True):
     st.emit(f"v_cndmask_b32_e32 {g}, {GVl}, {GVh}, vcc", reads_vcc=True)
     st.emit(f"v_mul_f32_e32 {S}, {t1}, {ih}")                          # CS = (C, S d_q / d_p): the new at_p
     st.emit(f"v_mul_f32_e32 {gg}, {t1}, {x}")                          # P89 = (C, S d_p / d_q): the new at_q
+    if tested and move_test:
+        st.emit(f"v_cmp_gt_f32_e32 vcc, {tau}, {ta}")                  # notconv |= w^2 > move2 max(al, be) n2[0]
+        st.emit(f"s_or_b64 {M}, {M}, vcc", kind="salu")
     for rp0 in (0, 2):
         tt = ((T1, T2), (GV, T3))
         for i in (0, 1):
@@ -376,7 +422,7 @@ def f32_literal(x):
     return f"0x{struct.unpack('<I', struct.pack('<f', x))[0]:08x}"
 
 
-def lq_prelude(st, L=LAY):
+def lq_prelude(st, L=LAY, byte_norms=True):
     """B0 = X Q: Householder LQ of the tile with greedy row pivoting, reflectors applied from the RIGHT (lq_prelude_pk of
     wm_tile_math.h).  Step k = 0 .. 6: the row not yet used with the largest |x[k:]|^2 is the pivot; the reflector
     H = I - vh vh^T (vh = (x + sign(x_k) |x| e_k) sqrt(2 / v^T v), columns k .. 7) zeroes its entries k+1 .. 7 and is
@@ -387,7 +433,11 @@ def lq_prelude(st, L=LAY):
     Registers, all free before the first sweep: vh / the selected row in v[N0 : N0+7] (column c in half c & 1 of pair
     c >> 1), W = A vh in v[T : T+7], the trailing row norms in v[T+8 : T+15] (row r in v[T+8+r]); scalars of a step in
     W's registers before W is formed.  The one-hot row masks are made exclusive on the scalar unit (first match wins)
-    and read by v_cndmask from SGPRs the SALU wrote."""
+    and read by v_cndmask from SGPRs the SALU wrote.
+    byte_norms: the eight |row|^2 come from the raw row words, which are still live here: v_dot4_u32_u8 of the low word
+    with itself, of the high word on top of it, v_cvt_f32_u32 - 24 instructions for the 32 packed ones of the float
+    chain, and the same bits, since every partial sum of that chain is an integer <= 8 * 255^2 < 2^24 and so exact.
+    byte_norms=False is the packed chain: never compiled, only interpreted as the baseline."""
     e = st.emit
     X = lambda c: f"v{L.N0 + c}"
     XP = lambda c: f"v[{L.N0 + 2 * (c >> 1)}:{L.N0 + 2 * (c >> 1) + 1}]"
@@ -397,7 +447,14 @@ def lq_prelude(st, L=LAY):
     row = lambda r, c: L.Alo(r >> 1, c) if (r & 1) == 0 else L.Ahi(r >> 1, c)
     m, neg, t2, nx2, rr, nrm, vk, sb = (f"v{L.T + i}" for i in range(8))
     tiny = f32_literal(1e-36)
-    for c in range(8):                                   # |row|^2 of all eight rows: four packed chains
+    if byte_norms:                                       # |row|^2 of all eight rows, in integers
+        for r in range(8):
+            e(f"v_dot4_u32_u8 {RN(r)}, %[lo{r}], %[lo{r}], 0")
+        for r in range(8):
+            e(f"v_dot4_u32_u8 {RN(r)}, %[hi{r}], %[hi{r}], {RN(r)}")
+        for r in range(8):
+            e(f"v_cvt_f32_u32_e32 {RN(r)}, {RN(r)}")
+    for c in range(0 if byte_norms else 8):              # the same in floats: four packed chains
         for rp in range(4):
             e(f"v_pk_mul_f32 {RNP(rp)}, {L.A(rp, c)}, {L.A(rp, c)}" if c == 0 else
               f"v_pk_fma_f32 {RNP(rp)}, {L.A(rp, c)}, {L.A(rp, c)}, {RNP(rp)}")
@@ -454,11 +511,25 @@ def eps_literal():
     return struct.unpack("<I", struct.pack("<f", 1e-18))[0]  # keeps 0/0 out; its square (1e-36) is a normal float
 
 
-def build(move_test=True, lq=True, scaled=True, swapfree=True):
+def build(move_test=True, lq=True, scaled=True, swapfree=True, byte_norms=None, rcp=None, sigma_only=False):
     """lq=False: no LQ prelude; move_test=False: the tested sweeps stop on cos^2 alone, as they did before the LQ prelude (what the emulator
     measures the prelude against); scaled=False: every pair takes rotation() on unscaled columns (what the scaled
     rotations are measured against); swapfree=False: the scaled rotations with max / min of the two norms ahead of the
-    branch (what the in-place norm update of the swap-free path is measured against); the committed stream is build()."""
+    branch (what the in-place norm update of the swap-free path is measured against); byte_norms=False: the prelude's row norms from the packed float chain (what the integer dot products of the
+    raw bytes are measured against); the committed stream is build().  Left unset, it follows `scaled`: the
+    scaled=False baseline is the stream as it was before the scaled rotations, whole.
+    rcp: 1 / c^2 of the swap-free scaled rotation from one v_rcp_f32 (rotation_scaled).  It changes the last bit of a
+    scale, so it is on only in the sigma-only stream, which is not held to the bytes of its predecessor anyway; the
+    stream that hands out B keeps v_rsq_f32 and the square (measured with it: profiles/r08_ab_tile_diet.log).
+    sigma_only=True is the second V-free stream, csrc/wm_jacobi_sigma_gfx950.inc (written at build time), for the callers that take nothing
+    but the norms (sigma_tile_dev): the columns stay scaled to the end.  No fold behind the untested sweeps; the tested
+    sweeps are rotation_scaled(tested=True); every col_norms is followed by scale_norms; the scales are folded into B
+    only where the 7th sweep recomputes its norms, to keep them in range up to the sweep bound (rotation_scaled)."""
+    # (a shim for the tests of the scaled rotations, which hold build(scaled=False) to the instruction counts of the commit
+    # before them and are not to be edited: nothing else ties the row norms to the scaling)
+    byte_norms = scaled if byte_norms is None else byte_norms
+    rcp = sigma_only if rcp is None else rcp
+    assert scaled or not sigma_only
     st = Stream()
     e = st.emit
     Alo, Ahi = LAY.Alo, LAY.Ahi
@@ -475,7 +546,7 @@ def build(move_test=True, lq=True, scaled=True, swapfree=True):
             dst = Alo(r >> 1, c) if (r & 1) == 0 else Ahi(r >> 1, c)
             e(f"v_cvt_f32_ubyte{c & 3}_e32 {dst}, {src}")
     if lq:
-        lq_prelude(st)
+        lq_prelude(st, byte_norms=byte_norms)
     if scaled:
         for c in range(8):
             e(f"v_mov_b32_e32 {LAY.W(c)}, 1.0")
@@ -485,6 +556,13 @@ def build(move_test=True, lq=True, scaled=True, swapfree=True):
     e(f"s_mov_b64 {M}, 0", kind="salu")
     e(f"s_bitcmp1_b32 {SW}, 0", kind="salu")                 # norms are recomputed before odd-numbered sweeps
     e("s_cbranch_scc1 .Lwmj_nonorm_%=", kind="salu")
+    if sigma_only:
+        e(f"s_cmp_eq_i32 {SW}, {SIGMA_FOLD_AT}", kind="salu")
+        e("s_cbranch_scc0 .Lwmj_nofold_%=", kind="salu")
+        e(".Lwmj_fold_%=:", kind="label")
+        fold_scales(st)
+        e(".Lwmj_nofold_%=:", kind="label")
+        st.hist.append(("nop", set()))
     col_norms(st)
     if scaled:
         scale_norms(st)
@@ -499,10 +577,10 @@ def build(move_test=True, lq=True, scaled=True, swapfree=True):
     for p in range(7):
         for q in range(p + 1, 8):
             if scaled:
-                rotation_scaled(st, p, q, f"{p}{q}", swapfree=swapfree)
+                rotation_scaled(st, p, q, f"{p}{q}", swapfree=swapfree, rcp=rcp)
             else:
                 rotation(st, p, q, -1, plain=True)
-    if scaled:
+    if scaled and not sigma_only:
         # behind the last untested sweep the scales are folded back into B: the tested sweeps, the final norms and the
         # pinned output registers see the true columns, as they always did
         e(f"s_add_i32 {TMPS}, {SW}, 2", kind="salu")
@@ -516,7 +594,10 @@ def build(move_test=True, lq=True, scaled=True, swapfree=True):
     k = 0
     for p in range(7):
         for q in range(p + 1, 8):
-            rotation(st, p, q, k, move_test=move_test)
+            if sigma_only:
+                rotation_scaled(st, p, q, f"t{p}{q}", rcp=rcp, tested=True, move_test=move_test)
+            else:
+                rotation(st, p, q, k, move_test=move_test)
             k += 1
     e(".Lwmj_swept_%=:", kind="label")
     st.hist.append(("nop", set()))
@@ -543,6 +624,8 @@ def build(move_test=True, lq=True, scaled=True, swapfree=True):
     e(".Lwmj_done_%=:", kind="label")
     st.hist.append(("nop", set()))
     col_norms(st)
+    if sigma_only:
+        scale_norms(st)
     e(f"s_mov_b64 %[more], {M}", kind="salu")
     return st
 
@@ -652,6 +735,53 @@ def render():
     return st, body
 
 
+HEADER_SIGMA = """// GENERATED by tools/gen_jacobi_asm.py - do not edit.  The sigma-only form of the stream in wm_jacobi_gfx950.inc
+// (build(sigma_only=True)), for the kernels that take nothing but the singular values: same prelude, same sweep control,
+// same tests, but the columns stay SCALED to the end - v[40:103] hold a_c / sqrt(w_c), v[128:135] the squared scales w_c,
+// the tested sweeps rotate the scaled columns too and every recomputed norm is multiplied by its scale.  Nothing folds
+// the scales into B except once ahead of the 7th sweep's norms (range of the scales up to the sweep bound).  B does not
+// leave the stream: only |b_c|^2 in v[104:111].  {n_inst} instructions, {n_nop} s_nop.
+// Returns the wave's not-converged mask after the last sweep (non-zero only when the bound of {max_sw} is hit).
+__device__ __forceinline__ unsigned long long jacobi_sigma_gfx950(const uint32_t (&lo)[8], const uint32_t (&hi)[8],
+                                                                  float (&n2)[8], const float conv2, const float skip2,
+                                                                  const int min_sweeps, const int skip_from) {{
+  unsigned long long more;
+  asm volatile(
+"""
+
+
+def render_sigma():
+    st = build(sigma_only=True)
+    body = HEADER_SIGMA.format(n_inst=n_instructions(st), n_nop=st.nops(), max_sw=MAX_SWEEPS)
+    for ln in st.lines:
+        body += f'      "{ln}\\n\\t"\n'
+    outs = [f'"=&{{v{N0 + c}}}"(n2[{c}])' for c in range(8)] + ['[more] "=&s"(more)']
+    ins = [f'[lo{r}] "v"(lo[{r}])' for r in range(8)] + [f'[hi{r}] "v"(hi[{r}])' for r in range(8)]
+    ins += ['[conv] "s"(conv2)', '[skip] "s"(skip2)', '[minsw] "s"(min_sweeps)', '[skipfrom] "s"(skip_from)']
+    clob = [f'"v{i}"' for i in range(A0, N0)] + [f'"v{i}"' for i in range(T, LAY.W0 + 8)]
+    clob += [f'"s{i}"' for i in range(80, 99)] + ['"vcc"', '"scc"']
+    body += "      : " + ",\n        ".join(outs) + "\n"
+    body += "      : " + ",\n        ".join(ins) + "\n"
+    body += "      : " + ", ".join(clob) + ");\n  return more;\n}\n"
+    return st, body
+
+
+def write_sigma(out=None):
+    """csrc/wm_jacobi_sigma_gfx950.inc is a build product: the package's build() calls this ahead of hipcc, `--write`
+    writes it too, git ignores it.  Why it is not committed like its two siblings: it is 5 800 generated lines that differ
+    from wm_jacobi_gfx950.inc only in what rotation_scaled(tested=True), the missing fold and scale_norms put there, and a
+    change that carries them cannot be read.  What is committed instead is what decides its text - this generator - and
+    its fingerprint: tests/test_jacobi_sigma_scaled.py holds the instruction count and the SHA-256 of the rendered file,
+    so a change to the generator that changes what the sigma-only kernels run shows as a changed fingerprint in the
+    diff, and `--check` compares a file that is present.  Written only where the content differs, so that an
+    up-to-date library is not rebuilt."""
+    out = out or csrc_path("wm_jacobi_sigma_gfx950.inc")
+    body = render_sigma()[1]
+    if not os.path.exists(out) or open(out).read() != body:
+        open(out, "w").write(body)
+    return out
+
+
 def render_v():
     L = LAY_V
     st = build_v()
@@ -689,12 +819,15 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare only (the default); exit status 1 on a difference")
     args = ap.parse_args()
     differs = False
-    for name, fn in (("wm_jacobi_gfx950.inc", render), ("wm_jacobi_v_gfx950.inc", render_v)):
+    for name, fn in (("wm_jacobi_gfx950.inc", render), ("wm_jacobi_sigma_gfx950.inc", render_sigma),
+                     ("wm_jacobi_v_gfx950.inc", render_v)):
         st, body = fn()
         out = csrc_path(name)
         old = open(out).read() if os.path.exists(out) else None
         what = f"{os.path.normpath(out)}: {n_instructions(st)} instructions, {st.nops()} s_nop"
-        if old == body:
+        if old is None and fn is render_sigma and not args.write:      # a build product: absent from a clean checkout
+            print("not built   " + what + "   (written by --write and by the package's build())", file=sys.stderr)
+        elif old == body:
             print("up to date  " + what, file=sys.stderr)
         elif args.write and not args.check:
             open(out, "w").write(body)
