@@ -1000,11 +1000,10 @@ __global__ __launch_bounds__(WAVE) void k_payload_reduce(const float* __restrict
 // Phase scan: the sigma pass over the 8x8 windows of all 64 grid phases of an h x w plane in one launch - grid (waves of the
 // largest grid, 64 phases, planes).  Phase p = 8 py + px has the windows that start at (py + 8 r, px + 8 c), r < ny_p =
 // (h - py) / 8, c < nx_p = (w - px) / 8; a wave owns 64 consecutive windows of its phase's grid, one per lane, as k_sigma_pass
-// lays a plane out.  Windows start at any byte, so the tile is loaded by the byte path.  The vote (wm_tile_math.h,
-// payload_vote) goes to votes[plane][phase][t], `pitch` = (h / 8) (w / 8) ints per phase, each phase's own grid row-major at
-// the start of its slot (votes may be NULL); sum |vote| of the wave is added to sums[plane][phase] by one integer atomic
-// (integer addition is associative: the sums do not depend on the order the waves arrive in).  The lanes behind the last
-// window of a wave redo that window and vote 0, so the wave's sum needs no masking.
+// lays a plane out.  Windows start at any byte, so the tile is loaded by the byte path.  What becomes of a window's sigma_1 is
+// the epilogue's: epi(slot, i, live, s_1), slot = plane * 64 + phase, i = slot * pitch + t the window's element of a
+// [plane][phase][t] array, `pitch` = (h / 8) (w / 8) per phase, each phase's own grid row-major at the start of its slot.  Every
+// lane of the wave calls it; the lanes behind the last window of a wave redo that window with live = false.
 struct PhaseGeom {
   int h, w, pitch;
   size_t row_stride, plane_stride;
@@ -1021,9 +1020,32 @@ __device__ __forceinline__ long long wave_sum(long long x) {
   return x;
 }
 
+// The dither-free search: the vote (wm_tile_math.h, payload_vote) to votes[i] (votes may be NULL); sum |vote| of the wave is
+// added to sums[plane][phase] by one integer atomic (integer addition is associative: the sums do not depend on the order the
+// waves arrive in).  A lane that is not live votes 0, so the wave's sum needs no masking.
+struct EpiPhaseVotes {
+  int32_t* __restrict__ votes;
+  unsigned long long* __restrict__ sums;
+  float inv_2delta;
+  __device__ __forceinline__ void operator()(const size_t slot, const size_t i, const bool live, const float s1) const {
+    const int v = live ? wm::payload_vote(wm::payload_metric(s1, inv_2delta)) : 0;
+    if (votes && live) votes[i] = v;
+    const int a = wave_sum(v < 0 ? -v : v);
+    if (threadIdx.x == 0) atomicAdd(sums + slot, (unsigned long long)a);
+  }
+};
+
+// The keyed search: sigma_1 itself to s1[i], for k_payload_keyed_scan below.  No delta and no key: the scan is keyless.
+struct EpiPhaseSigma1 {
+  float* __restrict__ s1;
+  __device__ __forceinline__ void operator()(size_t, const size_t i, const bool live, const float s) const {
+    if (live) s1[i] = s;
+  }
+};
+
+template <typename Epi>
 __global__ __launch_bounds__(WAVE, 3) void k_payload_phase_scan(const uint8_t* __restrict__ planes, const PhaseGeom g,
-                                                            int* __restrict__ status, int32_t* __restrict__ votes,
-                                                            unsigned long long* __restrict__ sums, const float inv_2delta) {
+                                                            int* __restrict__ status, const Epi epi) {
   const int phase = blockIdx.y, py = phase >> 3, px = phase & 7;
   const int nx = (g.w - px) / 8, n = ((g.h - py) / 8) * nx;
   if ((int)(blockIdx.x * WAVE) >= n) return;                             // (the whole wave: phases differ in their tile counts)
@@ -1036,11 +1058,8 @@ __global__ __launch_bounds__(WAVE, 3) void k_payload_phase_scan(const uint8_t* _
   float s[8];
   load_raw<false>(planes + plane * g.plane_stride + (size_t)(py + 8 * r) * g.row_stride + (size_t)(px + 8 * c), g.row_stride, raw);
   if (sigma_tile_dev(raw, s) < 0) atomicOr(status, 1);
-  const int v = live ? wm::payload_vote(wm::payload_metric(s[0], inv_2delta)) : 0;
   const size_t slot = plane * 64 + phase;
-  if (votes && live) votes[slot * (size_t)g.pitch + t] = v;
-  const int a = wave_sum(v < 0 ? -v : v);
-  if (threadIdx.x == 0) atomicAdd(sums + slot, (unsigned long long)a);
+  epi(slot, slot * (size_t)g.pitch + t, live, s[0]);
 }
 
 // Offset scan: one workgroup per placement (ty, tx) = (blockIdx.y, blockIdx.x) of the ny x nx vote grid V inside the
@@ -1072,6 +1091,85 @@ __global__ __launch_bounds__(OFFSET_SCAN_THREADS) void k_payload_offset_scan(con
   }
   acc = wave_sum(acc);
   if (threadIdx.x == 0) scores[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// Keyed scan (include/wmhip.h, "keyed crop resynchronisation"): every grid phase and every placement of a dithered payload's
+// crop in one launch - grid (64-placement strips across, placements down, 64 phases), sized for the phase with the fewest
+// windows (7, 7), which has the most placements.  A wave owns 64 consecutive tx of one (phase, ty) and a lane one placement;
+// the lane walks its phase's ny_p x nx_p windows and reads window (r, c) on the lattice of tile (ty + r, tx + c) of the
+// embed's grid: d from that tile's dither word U[ty + r][tx + c], the metric of s1[phase][r][c] - d, its vote, and |vote|
+// added up - per window row in int32 (nx_p <= 65535 windows of at most 2^15 stay below 2^31), the rows in int64.  s1[r][c] is
+// the same for the whole wave (a uniform load); the 64 lanes' dither words of a step are consecutive in the table and slide by
+// one word per step, and a lane's own next 8 are 16 consecutive bytes, which the compiler loads at once: the table comes
+// through the L1, every line many times over, without LDS staging.  Integers past the metric and one writer per score: the
+// same inputs give the same bits.  The lanes behind the last placement of a strip redo that placement and store nothing.
+struct KeyedGeom {
+  int h, w, nby, nbx, pitch;       // pitch = (h / 8) (w / 8): floats per phase of s1
+  size_t spitch;                   // scores per phase (wmhip.h)
+};
+
+// |vote| of one window on one tile's lattice.  |vote(m)| = vote(|m|): m * 2^15 is exact and rintf is odd (ties to even on both
+// sides), so the sign costs nothing.
+__device__ __forceinline__ int keyed_abs_vote(const float s1, const uint16_t u, const float delta, const float inv_2delta) {
+  return wm::payload_vote(fabsf(wm::payload_metric(s1, inv_2delta, wm::payload_dither(u, delta))));
+}
+
+// this wave's phase and placement row: false where the phase has no window or fewer placements than the grid was sized for
+__device__ __forceinline__ bool keyed_wave(const KeyedGeom& g, const int phase, const int ty, const int tx0, int& ny, int& nx,
+                                           int& n_tx) {
+  ny = (g.h - (phase >> 3)) / 8, nx = (g.w - (phase & 7)) / 8;
+  if (ny <= 0 || nx <= 0) return false;                                  // a phase without a window writes nothing
+  n_tx = g.nbx - nx + 1;
+  return ty <= g.nby - ny && tx0 < n_tx;                                 // (the whole wave: phases differ in their placements)
+}
+
+__global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __restrict__ s1, const uint16_t* __restrict__ U,
+                                                         long long* __restrict__ scores, const KeyedGeom g, const float delta,
+                                                         const float inv_2delta) {
+  const int phase = blockIdx.z, ty = blockIdx.y, tx0 = blockIdx.x * WAVE;
+  int ny, nx, n_tx;
+  if (!keyed_wave(g, phase, ty, tx0, ny, nx, n_tx)) return;
+  const int tx = min(tx0 + (int)threadIdx.x, n_tx - 1);
+  const float* __restrict__ sp = s1 + (size_t)phase * g.pitch;
+  const uint16_t* __restrict__ up = U + (size_t)ty * g.nbx + tx;
+  constexpr int STEP = 8;          // windows a lane loads before it computes: 8 loads in flight, not one wait per window
+  long long acc = 0;
+  for (int r = 0; r < ny; ++r, sp += nx, up += g.nbx) {
+    int row = 0, c = 0;
+    for (; c + STEP <= nx; c += STEP) {
+      float s[STEP];
+      uint16_t u[STEP];
+#pragma unroll
+      for (int k = 0; k < STEP; ++k) s[k] = sp[c + k], u[k] = up[c + k];
+#pragma unroll
+      for (int k = 0; k < STEP; ++k) row += keyed_abs_vote(s[k], u[k], delta, inv_2delta);
+    }
+    for (; c < nx; ++c) row += keyed_abs_vote(sp[c], up[c], delta, inv_2delta);
+    acc += row;
+  }
+  if (tx0 + (int)threadIdx.x < n_tx) scores[(size_t)phase * g.spitch + (size_t)ty * n_tx + tx] = acc;
+}
+
+// The same scores with the lanes over the windows, for a crop with few placements across (only rows cut away, say), where the
+// mapping above leaves most of a wave without a placement: a wave owns ONE placement (phase, ty, tx) = blockIdx (z, y, x), lane
+// l adds the windows c = l, l + 64, .. of every row, and the 64 shares are added by wave_sum.  Integer sums: the two mappings
+// give the same bits, whichever the entry point picks.
+__global__ __launch_bounds__(WAVE) void k_payload_keyed_scan_windows(const float* __restrict__ s1, const uint16_t* __restrict__ U,
+                                                                 long long* __restrict__ scores, const KeyedGeom g,
+                                                                 const float delta, const float inv_2delta) {
+  const int phase = blockIdx.z, ty = blockIdx.y, tx = blockIdx.x;
+  int ny, nx, n_tx;
+  if (!keyed_wave(g, phase, ty, tx, ny, nx, n_tx)) return;
+  const float* __restrict__ sp = s1 + (size_t)phase * g.pitch;
+  const uint16_t* __restrict__ up = U + (size_t)ty * g.nbx + tx;
+  long long acc = 0;
+  for (int r = 0; r < ny; ++r, sp += nx, up += g.nbx) {
+    int row = 0;
+    for (int c = threadIdx.x; c < nx; c += WAVE) row += keyed_abs_vote(sp[c], up[c], delta, inv_2delta);
+    acc += row;
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) scores[(size_t)phase * g.spitch + (size_t)ty * n_tx + tx] = acc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1604,8 +1702,8 @@ int wm_payload_phase_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, int32_t* vot
   WM_HIP(hipMemsetAsync(sums, 0, (size_t)n_planes * 64 * sizeof(int64_t), ctx->stream));
   const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
   const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
-  hipLaunchKernelGGL(k_payload_phase_scan, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status, votes,
-                     reinterpret_cast<unsigned long long*>(sums), 1.0f / (2.0f * delta));
+  const EpiPhaseVotes epi{votes, reinterpret_cast<unsigned long long*>(sums), 1.0f / (2.0f * delta)};
+  hipLaunchKernelGGL(k_payload_phase_scan<EpiPhaseVotes>, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status, epi);
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1630,6 +1728,55 @@ int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_
     WM_HIP(hipFuncSetAttribute((const void*)k_payload_offset_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_payload_offset_scan, dim3((unsigned)n_tx, (unsigned)n_ty), dim3(OFFSET_SCAN_THREADS), lds, ctx->stream, votes,
                      tile_bit_index, reinterpret_cast<long long*>(scores), ny, nx, nbx, n_bits);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// ---- keyed crop resynchronisation: the sigma_1 scan and the keyed scan -----------------
+int wm_payload_sigma1_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* s1, int n_planes, int h, int w, int row_stride,
+                                  size_t plane_stride) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
+  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
+  if (n_planes == 0 || pitch == 0) return WM_OK;
+  if (pitch > (size_t)INT32_MAX) return set_err(WM_ERR_BADARG, "more than 2^31 - 1 tiles a plane");
+  if (!s1 || ((uintptr_t)s1 & 3u)) return set_err(WM_ERR_BADARG, "s1 is NULL or misaligned");
+  const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
+  const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
+  hipLaunchKernelGGL(k_payload_phase_scan<EpiPhaseSigma1>, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status,
+                     EpiPhaseSigma1{s1});
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// the sizes of a keyed search, checked; spitch: the scores per phase (wmhip.h)
+static int check_keyed_sizes(int h, int w, int nby, int nbx, float delta, size_t& spitch) {
+  if (h < 8 || w < 8) return set_err(WM_ERR_BADARG, "a keyed search needs a whole tile (h, w >= 8)");
+  if (nby < 0 || nbx < 0 || h / 8 > nby || w / 8 > nbx) return set_err(WM_ERR_BADARG, "the crop has more tiles than the table");
+  WM_TRY(check_delta(delta));
+  const size_t n_ty = (size_t)(nby - (h - 7) / 8) + 1, n_tx = (size_t)(nbx - (w - 7) / 8) + 1;
+  if (nbx > 65535 || n_ty > 65535 || (size_t)nby * (size_t)nbx > (size_t)INT32_MAX || n_ty * n_tx > ((size_t)1 << 24))
+    return set_err(WM_ERR_BADARG, "tile grid too large");                // (2^24 placements a phase: the launch grid, either mapping)
+  spitch = n_ty * n_tx;
+  return WM_OK;
+}
+
+int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
+                                int nbx, float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  size_t spitch;
+  WM_TRY(check_keyed_sizes(h, w, nby, nbx, delta, spitch));
+  if (!tile_dither || ((uintptr_t)tile_dither & 1u)) return set_err(WM_ERR_BADARG, "tile_dither is NULL or at an odd address");
+  if (!s1 || !scores || ((uintptr_t)s1 & 3u) || ((uintptr_t)scores & 7u)) return set_err(WM_ERR_BADARG, "s1 / scores is NULL or misaligned");
+  WM_HIP(hipMemsetAsync(scores, 0, 64 * spitch * sizeof(int64_t), ctx->stream));
+  const KeyedGeom g{h, w, nby, nbx, (h / 8) * (w / 8), spitch};
+  // The grid is sized for phase (7, 7), which has the most placements.  A lane per placement fills n_tx of every 64 lanes, a lane
+  // per window of a row nx of every 64: the second mapping where it fills at least twice as many (the first reads s1 once a
+  // wave and the table in 16-byte pieces, so it is the cheaper one per window).
+  const long long n_tx = nbx - w / 8 + 1, nx = w / 8, n_tx_max = nbx - (w - 7) / 8 + 1;
+  const bool windows = nx * ((n_tx + WAVE - 1) / WAVE) >= 2 * n_tx * ((nx + WAVE - 1) / WAVE);
+  const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(nby - (h - 7) / 8 + 1), 64);
+  hipLaunchKernelGGL(windows ? k_payload_keyed_scan_windows : k_payload_keyed_scan, grid, dim3(WAVE), 0, ctx->stream, s1, tile_dither,
+                     reinterpret_cast<long long*>(scores), g, delta, 1.0f / (2.0f * delta));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -2216,6 +2363,35 @@ int wm_payload_offset_scores(wm_ctx* ctx, const int32_t* votes, const int32_t* t
     d_t = cv.in(n_win ? (size_t)nby * (size_t)nbx : 0, tile_bit_index);
     d_s = cv.out(n_place, scores);
   }, [&] { return wm_payload_offset_scores_dev(ctx, d_v, d_t, d_s, ny, nx, nby, nbx, n_bits); }, true);
+}
+
+// ---- keyed crop resynchronisation, host pointers --------------------------------
+int wm_payload_sigma1_scan_u8(wm_ctx* ctx, const uint8_t* stego, float* s1, int n_planes, int h, int w, int row_stride,
+                              size_t plane_stride) {
+  WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
+  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
+  if (n_planes == 0 || pitch == 0) return WM_OK;
+  if (!s1) return set_err(WM_ERR_BADARG, "s1 is NULL");
+  uint8_t* d_p; float* d_s1;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_p = cv.in(plane_span(n_planes, h, row_stride, plane_stride, w), stego);
+    d_s1 = cv.out((size_t)n_planes * 64 * pitch, s1);
+  }, [&] { return wm_payload_sigma1_scan_u8_dev(ctx, d_p, d_s1, n_planes, h, w, row_stride, plane_stride); });
+}
+
+int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
+                            int nbx, float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  size_t spitch;
+  WM_TRY(check_keyed_sizes(h, w, nby, nbx, delta, spitch));
+  if (!tile_dither || ((uintptr_t)tile_dither & 1u)) return set_err(WM_ERR_BADARG, "tile_dither is NULL or at an odd address");
+  if (!s1 || !scores) return set_err(WM_ERR_BADARG, "s1 / scores is NULL");
+  float* d_s1; uint16_t* d_u; int64_t* d_sc;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_s1 = cv.in((size_t)64 * (size_t)(h / 8) * (size_t)(w / 8), s1);
+    d_u = cv.in((size_t)nby * (size_t)nbx, tile_dither);
+    d_sc = cv.out(64 * spitch, scores);
+  }, [&] { return wm_payload_keyed_scores_dev(ctx, d_s1, d_u, d_sc, h, w, nby, nbx, delta); }, true);
 }
 
 }  // extern "C"

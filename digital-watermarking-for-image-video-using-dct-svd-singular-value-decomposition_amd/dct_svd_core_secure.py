@@ -429,22 +429,16 @@ def _payload_meta_checked(meta, password: str):
     return meta, H, W, hostapi.check_delta(float(meta["delta"])), n_bits, ptype, key
 
 
-SEARCHES = (None, "crop")
+SEARCHES = (None, "crop", "crop-keyed")
 
 
 def _check_search(search):
     if search not in SEARCHES:
-        raise ValueError(f"search must be None or 'crop', got {search!r}")
+        raise ValueError(f"search must be None, 'crop' or 'crop-keyed', got {search!r}")
 
 
-def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
-    """search="crop" (include/wmhip.h, "crop resynchronisation"): the stego is any axis-aligned crop of the marked image.
-    Every refusal comes before the first device call."""
-    if M.payload_dither_of(meta):
-        raise ValueError("resynchronising a dithered payload is not supported: keyed dither removes the grid's keyless "
-                         "signal (search='crop' needs a payload embedded with dither=False)")
-    if n_bits > P.SYNC_MAX_BITS:
-        raise ValueError(f"search='crop' takes payloads of at most {P.SYNC_MAX_BITS} bits, this one has {n_bits}")
+def _check_crop_shape(stego_bgr: np.ndarray, H: int, W: int) -> tuple:
+    """(h, w) of a stego that can be a crop of the H x W marked image"""
     if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
         raise ValueError("stego must be uint8 [h, w, 3]")
     h, w = stego_bgr.shape[:2]
@@ -452,6 +446,18 @@ def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, k
         raise ValueError(f"stego is {w}x{h}, larger than the {W}x{H} the meta was written for: not a crop of it")
     if h < TILE or w < TILE:
         raise ValueError(f"stego is {w}x{h}: a crop without a whole 8x8 tile carries nothing")
+    return h, w
+
+
+def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
+    """search="crop" (include/wmhip.h, "crop resynchronisation"): the stego is any axis-aligned crop of the marked image.
+    Every refusal comes before the first device call."""
+    if M.payload_dither_of(meta):
+        raise ValueError("resynchronising a dithered payload is not supported: keyed dither removes the grid's keyless "
+                         "signal (search='crop' needs a payload embedded with dither=False); use search='crop-keyed'")
+    if n_bits > P.SYNC_MAX_BITS:
+        raise ValueError(f"search='crop' takes payloads of at most {P.SYNC_MAX_BITS} bits, this one has {n_bits}")
+    _check_crop_shape(stego_bgr, H, W)
     nby, nbx = H // TILE, W // TILE
     tbi = _payload_map_of(H, W, key, n_bits)[0].reshape(nby, nbx)
     ctx = _ctx(device)
@@ -464,17 +470,39 @@ def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, k
     return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
 
 
+def _extract_payload_cropped_keyed(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
+    """search="crop-keyed" (include/wmhip.h, "keyed crop resynchronisation"): the stego is any axis-aligned crop of an image
+    marked with dither=True.  Every refusal comes before the first device call."""
+    if not M.payload_dither_of(meta):
+        raise ValueError("search='crop-keyed' reads a payload embedded with dither=True; this one has none: use search='crop'")
+    _check_crop_shape(stego_bgr, H, W)
+    nby, nbx = H // TILE, W // TILE
+    tbi = _payload_map_of(H, W, key, n_bits)[0].reshape(nby, nbx)
+    table = _payload_dither_of(H, W, key, True).reshape(nby, nbx)
+    ctx = _ctx(device)
+    (py, px), (ty, tx), s1 = ctx.payload_locate_keyed(_Gray.planes_in(ctx, stego_bgr), table, delta)
+    ny, nx = s1.shape
+    votes = P.keyed_votes(s1, table[ty:ty + ny, tx:tx + nx], delta)
+    soft, count = P.soft_of_votes(votes, tbi[ty:ty + ny, tx:tx + nx], n_bits)
+    data, valid = P.payload_unframe(soft < 0)
+    return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
+
+
 def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0, *, search=None):
     """-> (data bytes, valid, confidence).  valid: the decoded frame's length header and CRC hold.  confidence: the mean
     over the bits of |soft| / (tiles voting), 1 for an untouched stego and near 0 for an image that carries nothing.
     ``search="crop"``: the stego may be any axis-aligned crop of the marked image (h <= H, w <= W, origin anywhere); the
     embed's tile grid and the crop's place in it are searched for on the device, and the result is (data, valid,
-    confidence, origin) with origin = (y0, x0) of the crop in the marked image - meaningful where valid is True.  Dithered
-    payloads are refused ("Crop resynchronisation")."""
+    confidence, origin) with origin = (y0, x0) of the crop in the marked image - meaningful where valid is True.
+    ``search="crop"`` takes payloads embedded with dither=False, ``search="crop-keyed"`` those embedded with dither=True
+    (one keyed search over grid phase and place); each refuses the other's meta ("Crop
+    resynchronisation" and "Keyed crop resynchronisation")."""
     _check_search(search)
     meta, H, W, delta, n_bits, _, key = _payload_meta_checked(meta, password)
     if search == "crop":
         return _extract_payload_cropped(stego_bgr, meta, H, W, delta, n_bits, key, device)
+    if search == "crop-keyed":
+        return _extract_payload_cropped_keyed(stego_bgr, meta, H, W, delta, n_bits, key, device)
     _check_stego_shape(stego_bgr, meta)
     _, order, offs = _payload_map_of(H, W, key, n_bits)
     ctx = _ctx(device)
@@ -511,7 +539,7 @@ def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, pa
 def extract_payload(stego_path: str, meta_path: str, out_path: Optional[str] = None, *, password: Optional[str] = None,
                     device: int = 0, search=None):
     """-> (data, valid, confidence, path written or None).  With ``out_path`` the payload is written as ``_text.txt`` /
-    ``_data.json`` by the reference's renaming (core:229-242).  ``search="crop"`` as in extract_payload_arrays: the stego
+    ``_data.json`` by the reference's renaming (core:229-242).  ``search="crop"`` / ``"crop-keyed"`` as in extract_payload_arrays: the stego
     file may be a crop of the marked image, and the result is (data, valid, confidence, path, origin)."""
     _check_search(search)
     M.check_password_type(password, "extract")

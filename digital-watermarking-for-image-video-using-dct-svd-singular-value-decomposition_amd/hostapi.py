@@ -90,6 +90,9 @@ _DECLARED = {
     # crop resynchronisation: (stego, votes, sums, the plane arguments, delta); (votes, tile_bit_index, scores, ny, nx, nby, nbx, n_bits)
     "wm_payload_phase_scan_u8*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _sz, _f],
     "wm_payload_offset_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
+    # keyed crop resynchronisation: (stego, s1, the plane arguments); (s1, tile_dither, scores, h, w, nby, nbx, delta)
+    "wm_payload_sigma1_scan_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz],
+    "wm_payload_keyed_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -644,17 +647,7 @@ class Context:
         sums = np.zeros((n, 8, 8), np.int64)
         self._call("wm_payload_phase_scan_u8", _p(planes), _p(raw), _p(sums), n, h, w, rs, ps, delta)
         one = planes.ndim == 2
-        counts = P.phase_counts(h, w)
-        votes = []
-        for py in range(8):
-            ny = max(h - py, 0) // TILE
-            row = []
-            for px in range(8):
-                nx = max(w - px, 0) // TILE
-                v = raw[:, 8 * py + px, :ny * nx].reshape(n, ny, nx).copy()
-                row.append(v[0] if one else v)
-            votes.append(row)
-        return votes, (sums[0] if one else sums), counts
+        return self._phase_grids(raw, h, w, one), (sums[0] if one else sums), P.phase_counts(h, w)
 
     @staticmethod
     def _offset_args(votes, tile_bit_index, n_bits):
@@ -722,6 +715,94 @@ class Context:
             self.d2h(scores, d_scores)
             self.sync()
         return (py, px), P.pick_offset(scores), votes
+
+    # ---- keyed crop resynchronisation: a dithered payload's crop (include/wmhip.h; the winner's rule is payload.pick_keyed) ----
+    @staticmethod
+    def _phase_grids(raw: np.ndarray, h: int, w: int, one: bool) -> list:
+        """grids[py][px] = the [N?, ny_p, nx_p] grid of phase (py, px) out of a [N, 64, pitch] scan"""
+        grids = []
+        for py in range(8):
+            ny = max(h - py, 0) // TILE
+            row = []
+            for px in range(8):
+                nx = max(w - px, 0) // TILE
+                v = raw[:, 8 * py + px, :ny * nx].reshape(raw.shape[0], ny, nx).copy()
+                row.append(v[0] if one else v)
+            grids.append(row)
+        return grids
+
+    def payload_sigma1_scan(self, planes: np.ndarray):
+        """sigma_1 of every 8x8 window of all 64 grid phases of uint8 planes [h, w] / [N, h, w] (strided views included) ->
+        s1[py][px], the float32 [N?, ny_p, nx_p] grid of phase (py, px), shaped as payload_phase_scan's votes."""
+        n, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        raw = np.zeros((n, 64, (h // TILE) * (w // TILE)), np.float32)
+        self._call("wm_payload_sigma1_scan_u8", _p(planes), _p(raw), n, h, w, rs, ps)
+        return self._phase_grids(raw, h, w, planes.ndim == 2)
+
+    @staticmethod
+    def _keyed_args(table, h, w, delta):
+        u = np.ascontiguousarray(table, np.uint16)
+        h, w = int(h), int(w)
+        if u.ndim != 2:
+            raise ValueError("the dither table must be [nby, nbx]")
+        nby, nbx = u.shape
+        if h < TILE or w < TILE:
+            raise ValueError(f"a keyed search needs a whole tile, got {h} x {w}")
+        if h // TILE > nby or w // TILE > nbx:
+            raise ValueError(f"a {h} x {w} plane has more tiles than the {nby} x {nbx} table: not a crop of that grid")
+        return u, h, w, nby, nbx, check_delta(delta)
+
+    @staticmethod
+    def _keyed_grids(raw: np.ndarray, h: int, w: int, nby: int, nbx: int) -> list:
+        """the 64 phases' own [nby - ny_p + 1, nbx - nx_p + 1] score grids out of [64, spitch]; [0, 0] without a window"""
+        out = []
+        for p in range(64):
+            ny, nx = max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE
+            n_ty, n_tx = (nby - ny + 1, nbx - nx + 1) if ny * nx else (0, 0)
+            out.append(raw[p, :n_ty * n_tx].reshape(n_ty, n_tx).copy())
+        return out
+
+    def payload_keyed_scores(self, s1_scan, table: np.ndarray, h: int, w: int, delta: float) -> list:
+        """The keyed scores of one plane's sigma_1 scan (s1_scan[py][px] float32 [ny_p, nx_p], as payload_sigma1_scan
+        returns it for an [h, w] plane) under the embed's dither table [nby, nbx] -> the list of the 64 phases' int64
+        [nby - ny_p + 1, nbx - nx_p + 1] grids: score[ty, tx] = sum of |vote| of the phase's windows read on the lattices
+        of the tiles (ty + r, tx + c).  A phase without a window has an empty grid."""
+        u, h, w, nby, nbx, delta = self._keyed_args(table, h, w, delta)
+        pitch = (h // TILE) * (w // TILE)
+        raw = np.zeros((64, pitch), np.float32)
+        for p in range(64):
+            g = np.asarray(s1_scan[p // 8][p % 8], np.float32)
+            want = (max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE)
+            if g.shape != want:
+                raise ValueError(f"phase {divmod(p, 8)} of the scan is {g.shape}, an {h} x {w} plane has {want}")
+            raw[p, :g.size] = g.reshape(-1)
+        scores = np.zeros((64, P.keyed_score_pitch(h, w, nby, nbx)), np.int64)
+        self._call("wm_payload_keyed_scores", _p(raw), _p(u), _p(scores), h, w, nby, nbx, delta)
+        return self._keyed_grids(scores, h, w, nby, nbx)
+
+    def payload_locate_keyed(self, plane: np.ndarray, table: np.ndarray, delta: float):
+        """The rule's steps 1-3 on one uint8 plane [h, w] of a dithered payload's crop: sigma_1 scan, keyed scores under the
+        embed's dither table [nby, nbx], pick_keyed.  The scan stays on the device; the scores and the winner's sigma_1
+        come back.  -> ((py, px), (ty, tx), s1 float32 [ny, nx])."""
+        if plane.ndim != 2:
+            raise ValueError("plane must be [h, w]")
+        _planes_of(plane, np.uint8, "plane must be uint8")
+        u, h, w, nby, nbx, delta = self._keyed_args(table, plane.shape[0], plane.shape[1], delta)
+        pitch = (h // TILE) * (w // TILE)
+        scores = np.zeros((64, P.keyed_score_pitch(h, w, nby, nbx)), np.int64)
+        d_u = self._payload_dither_dev(u.reshape(-1))
+        with self._staging() as dev:
+            d_s1, d_scores = dev.alloc(64 * pitch * 4), dev.alloc(scores.nbytes)
+            d_p, = dev.up(np.ascontiguousarray(plane))
+            self._call("wm_payload_sigma1_scan_u8_dev", _vp(d_p), _vp(d_s1), 1, h, w, w, h * w)
+            self._call("wm_payload_keyed_scores_dev", _vp(d_s1), _vp(d_u), _vp(d_scores), h, w, nby, nbx, delta)
+            self.d2h(scores, d_scores)
+            self.check_status()
+            (py, px), place = P.pick_keyed(self._keyed_grids(scores, h, w, nby, nbx), P.phase_counts(h, w))
+            s1 = np.empty(((h - py) // TILE, (w - px) // TILE), np.float32)
+            self.d2h(s1, d_s1 + (8 * py + px) * pitch * 4)
+            self.sync()
+        return (py, px), place, s1
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

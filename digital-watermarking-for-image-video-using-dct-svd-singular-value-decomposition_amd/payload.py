@@ -167,6 +167,50 @@ def sync_confidence(soft: np.ndarray, count: np.ndarray) -> float:
     return float(np.mean(np.abs(np.asarray(soft)[have]) / np.asarray(count)[have])) if have.any() else 0.0
 
 
+# ---- keyed crop resynchronisation (include/wmhip.h): a dithered payload's crop ---------------------
+def keyed_score_pitch(h: int, w: int, nby: int, nbx: int) -> int:
+    """int64 scores per phase of wm_payload_keyed_scores: the placements of the phase with the fewest windows, (7, 7)"""
+    return (int(nby) - max(int(h) - 7, 0) // 8 + 1) * (int(nbx) - max(int(w) - 7, 0) // 8 + 1)
+
+
+def pick_keyed(scores, counts):
+    """The winner ((py, px), (ty, tx)) of the keyed scores: ``scores`` holds the 64 phases' int64 [n_ty_p, n_tx_p] grids,
+    ``counts`` their window counts (phase_counts).  The largest score / count wins, compared exactly: within a phase the
+    counts are equal, so the first maximum in row-major order; across phases cross-multiplied Python integers; ties go to
+    the smallest (p, ty, tx).  Phases with count 0 or without a placement do not take part.  None when none does."""
+    n = np.asarray(counts).reshape(-1)
+    if len(scores) != 64 or n.size != 64:
+        raise ValueError("scores and counts must hold the 64 phases")
+    best = None
+    for p in range(64):
+        sc, cp = np.asarray(scores[p]), int(n[p])
+        if sc.ndim != 2:
+            raise ValueError("a phase's scores must be [placements down, placements across]")
+        if cp <= 0 or sc.size == 0:
+            continue
+        i = int(np.argmax(sc))                                             # (the first of equals in row-major order)
+        sp = int(sc.reshape(-1)[i])
+        if best is None or sp * best[2] > best[1] * cp:
+            best = (p, sp, cp, divmod(i, sc.shape[1]))
+    return None if best is None else ((best[0] // 8, best[0] % 8), (int(best[3][0]), int(best[3][1])))
+
+
+def keyed_votes(s1, u, delta: float) -> np.ndarray:
+    """int32 votes of sigma_1 values under dither words u (same shape): the rule's metric and vote stated in NumPy, every
+    step rounded to float32 - d = float(u) * (delta * 2^-15), x = (s1 - d) * (1 / (2 delta)), f = x - floor(x),
+    m = 2 |2 f - 1| - 1, vote = rint(m * 32768).  Where 1 / (2 delta) is no power of two the device contracts x - floor(x)
+    into one fused multiply-add and its vote may differ from this one by a unit."""
+    F = np.float32
+    s1 = np.asarray(s1, F)
+    d = (np.asarray(u).astype(F) * (F(delta) * F(2.0 ** -15))).astype(F)
+    if d.shape != s1.shape:
+        raise ValueError(f"{d.shape} dither words for sigma_1 of shape {s1.shape}")
+    x = ((s1 - d).astype(F) * (F(1.0) / (F(2.0) * F(delta)))).astype(F)
+    f = (x - np.floor(x)).astype(F)
+    m = (F(2.0) * np.abs(F(2.0) * f - F(1.0)) - F(1.0)).astype(F)
+    return np.rint(m * F(VOTE_ONE)).astype(np.int32)
+
+
 def check_decodes(soft: np.ndarray, bits: np.ndarray, data: bytes) -> None:
     """The embed's own check: ``soft`` is what the decoder reads from the finished stego (every marked frame added).  Tiles
     pinned by clipping - text on a white page, saturated regions - vote for the WRONG bit at full weight, and with few tiles

@@ -378,6 +378,46 @@ int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_
 int wm_payload_offset_scores(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
                              int nby, int nbx, int n_bits);
 
+/* ---- Blind payload, keyed crop resynchronisation: the same for a payload embedded with keyed dither --
+ * Keyed dither leaves the keyless phase scan nothing to find: read without the tile's dither word, (sigma_1 - d) mod 2 delta
+ * is uniform at every phase.  Read with the RIGHT word a marked tile sits on its lattice point whatever bit it carries, so
+ * one keyed score finds phase and placement together.  The rule ("Keyed crop resynchronisation"); all arithmetic
+ * past the metric is integer.
+ *   1 scan    phases and windows as in step 2 above; s1[p][r][c] = sigma_1 of the window, float32.  Needs no key.
+ *   2 scores  U[nby][nbx] is the embed's dither table.  For every phase p with ny_p nx_p > 0 and every placement
+ *             0 <= ty <= nby - ny_p, 0 <= tx <= nbx - nx_p:  d = float(U[ty + r][tx + c]) * (delta * 2^-15), m the metric of
+ *             s1[p][r][c] on the lattice shifted by d (x = (s1 - d) * (1 / (2 delta))), vote as above, and
+ *             score[p][ty][tx] = sum over the windows of |vote| (int64).
+ *   3 winner  the largest score[p][ty][tx] / (ny_p nx_p), compared exactly: within a phase the first maximum in row-major
+ *             order, across phases cross-multiplied integers (on the host); ties go to the smallest (p, ty, tx).
+ *   4 decode  the votes of the winner's s1 grid under U[ty + r][tx + c] (on the host), soft[j] their sums per bit of the
+ *             tile-to-bit map's window as in step 4 above; origin = (8 ty - py, 8 tx - px).
+ * Only the top candidate is tried; the frame's length header and CRC say whether it was right.  There is no limit on the
+ * payload's bits: nothing here scales with them. */
+
+/* Step 1, all 64 phases of every plane in one launch:
+ *   s1  [n_planes][64][(h / 8) (w / 8)] float32 (out): phase p's own ny_p x nx_p grid, row-major, at the start of its slot, the
+ *       rest of the slot untouched
+ * WM_ERR_BADARG: s1 NULL.  No plane or no whole tile: WM_OK without a launch, nothing written. */
+int wm_payload_sigma1_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* s1, int n_planes, int h, int w, int row_stride,
+                                  size_t plane_stride);
+int wm_payload_sigma1_scan_u8(wm_ctx* ctx, const uint8_t* stego, float* s1, int n_planes, int h, int w, int row_stride,
+                              size_t plane_stride);
+
+/* Step 2, every phase and placement in one launch:
+ *   s1           one plane's scan, [64][(h / 8) (w / 8)] float32
+ *   tile_dither  [nby][nbx] uint16, the embed's table
+ *   scores       [64][spitch] int64 (out), spitch = (nby - max(h - 7, 0) / 8 + 1) * (nbx - max(w - 7, 0) / 8 + 1): phase p's own
+ *                (nby - ny_p + 1) x (nbx - nx_p + 1) grid, row-major, at the start of its slot.  The whole array is zeroed
+ *                first; a phase without a window writes nothing.
+ * WM_ERR_BADARG: h / 8 > nby or w / 8 > nbx (not a crop of that grid), h or w < 8, tile_dither NULL or at an odd address,
+ * delta outside 8..512, s1 or scores NULL, nbx above 65535 or spitch above 2^24.  Two lane mappings (a lane per placement; a
+ * lane per window of a row where a crop has few placements across) give the same bits: the sums are integers. */
+int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
+                                int nbx, float delta);
+int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
+                            int nbx, float delta);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
