@@ -1539,4 +1539,59 @@ WM_HD float payload_metric(const float s1, const float inv_2delta, const float d
   return payload_metric(s1 - d, inv_2delta);
 }
 
+// ---- Channel code of the blind payload (include/wmhip.h, "channel code"): rate 1/2, constraint length 7,
+// generators 171 / 133 octal, zero tail.  Integers throughout, so the device kernel (k_payload_viterbi), this header's scalar
+// decoder in a host build and the NumPy restatement (tests/payload_code_refs.py) give the same bits.  State s = the register's
+// low 6 bits; the register that enters new state s' from predecessor p_b = (s' >> 1) | (b << 5) is r_b = s' | (b << 6).
+constexpr int K7_TAIL = 6;                     // zero bits behind the frame
+constexpr int K7_STATES = 64;
+constexpr int K7_MAX_STEPS = 1 << 18;          // n_info + K7_TAIL: every metric then stays inside (-2^30 - 2^29, 2^29]
+constexpr int32_t K7_LLR_MAX = 1024;           // |L| after the clamp on load
+constexpr int32_t K7_PM_FLOOR = -(1 << 30);    // the start metric of every state but 0
+constexpr unsigned K7_G0 = 0171u, K7_G1 = 0133u;
+
+WM_HD int k7_parity(const unsigned x) { return __builtin_popcount(x) & 1; }
+WM_HD int32_t k7_clamp(const int32_t L) { return L < -K7_LLR_MAX ? -K7_LLR_MAX : L > K7_LLR_MAX ? K7_LLR_MAX : L; }
+// The sign of generator g's output on the b = 0 branch into new state s: +1 for a coded 0, -1 for a coded 1.  Both generators
+// contain bits 0 and 6, so the b = 1 branch has the opposite sign on both outputs: bm_1 = -bm_0.
+WM_HD int32_t k7_sign(const int s, const unsigned g) { return 1 - 2 * k7_parity((unsigned)s & g); }
+// The b = 0 branch metric into a state with signs (g0, g1) under the step's clamped pair (L0, L1)
+WM_HD int32_t k7_branch(const int32_t g0, const int32_t g1, const int32_t L0, const int32_t L1) {
+  return (g0 < 0 ? -L0 : L0) + (g1 < 0 ? -L1 : L1);
+}
+// Add-compare-select of one state: pm0 / pm1 the metrics of its predecessors p_0 / p_1, bm the b = 0 branch metric.  b = 1 iff
+// its candidate is strictly larger; ties go to b = 0.
+WM_HD int32_t k7_acs(const int32_t pm0, const int32_t pm1, const int32_t bm, int& b) {
+  const int32_t c0 = pm0 + bm, c1 = pm1 - bm;
+  b = c1 > c0;
+  return b ? c1 : c0;
+}
+// One traceback step from state s under decision word d: the info bit of the step is s & 1 (read before the call)
+WM_HD int k7_back(const int s, const uint64_t d) { return (s >> 1) | ((int)((d >> s) & 1u) << 5); }
+
+// The whole decoder of one codeword in scalar form: what the kernel computes, for the host harness (tests/
+// payload_code_harness.cpp).  llr: 2 (n_info + 6) values; info: n_info bytes of 0 / 1; decisions: n_info + 6 words.
+inline int32_t k7_decode_scalar(const int32_t* llr, const int n_info, uint8_t* info, uint64_t* decisions) {
+  const int n_steps = n_info + K7_TAIL;
+  int32_t pm[K7_STATES], nw[K7_STATES];
+  for (int s = 0; s < K7_STATES; ++s) pm[s] = s ? K7_PM_FLOOR : 0;
+  for (int t = 0; t < n_steps; ++t) {
+    const int32_t L0 = k7_clamp(llr[2 * t]), L1 = k7_clamp(llr[2 * t + 1]);
+    uint64_t d = 0;
+    for (int s = 0; s < K7_STATES; ++s) {
+      int b;
+      nw[s] = k7_acs(pm[s >> 1], pm[(s >> 1) | 32], k7_branch(k7_sign(s, K7_G0), k7_sign(s, K7_G1), L0, L1), b);
+      d |= (uint64_t)b << s;
+    }
+    for (int s = 0; s < K7_STATES; ++s) pm[s] = nw[s];
+    decisions[t] = d;
+  }
+  int s = 0;
+  for (int t = n_steps - 1; t >= 0; --t) {
+    if (t < n_info) info[t] = (uint8_t)(s & 1);
+    s = k7_back(s, decisions[t]);
+  }
+  return pm[0];
+}
+
 }  // namespace wm

@@ -1172,6 +1172,59 @@ __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan_windows(const float
   if (threadIdx.x == 0) scores[(size_t)phase * g.spitch + (size_t)ty * n_tx + tx] = acc;
 }
 
+// The channel code's decoder (wmhip.h, "channel code"; the per-state arithmetic is wm_tile_math.h's): one wave per codeword,
+// lane = state, the path metric in one register, no LDS, no atomics.  Steps go in chunks of 64: lane i loads and clamps the
+// pair of step t0 + i (the pairs are wave-uniform per step and handed out by a uniform-index lane read), keeps the decision
+// word of step t0 + i, and the chunk's words leave as one 512-byte store.  A step is two cross-lane reads of pm (the
+// predecessors' lanes are fixed, so their byte addresses are computed once), one add, one subtract, a compare-select and a
+// ballot.  The traceback runs in the same launch: it depends on the state only, so the chunk's 64 words are loaded at once
+// (lane i = step t0 + i) and walked with uniform-index lane reads - no dependent global load - and lane i's info bit leaves
+// as one byte of a coalesced store.  The words are written and read back by the same wave; the barrier in between orders them.
+__global__ __launch_bounds__(WAVE) void k_payload_viterbi(const int32_t* __restrict__ llr, const int n_info, const size_t llr_stride,
+                                                      uint8_t* __restrict__ info_bits, int32_t* __restrict__ final_metric,
+                                                      unsigned long long* decisions) {
+  const int lane = threadIdx.x, n_steps = n_info + wm::K7_TAIL;
+  const int32_t* __restrict__ L = llr + (size_t)blockIdx.x * llr_stride;
+  unsigned long long* D = decisions + (size_t)blockIdx.x * (size_t)n_steps;
+  const int32_t g0 = wm::k7_sign(lane, wm::K7_G0), g1 = wm::k7_sign(lane, wm::K7_G1);
+  const int from0 = (lane >> 1) << 2, from1 = ((lane >> 1) | 32) << 2;       // ds_bpermute takes the source lane's byte address
+  int32_t pm = lane ? wm::K7_PM_FLOOR : 0;
+  for (int t0 = 0; t0 < n_steps; t0 += WAVE) {
+    const int n = min(WAVE, n_steps - t0);
+    int32_t la = 0, lb = 0;
+    if (lane < n) {
+      la = wm::k7_clamp(L[2 * (size_t)(t0 + lane)]);
+      lb = wm::k7_clamp(L[2 * (size_t)(t0 + lane) + 1]);
+    }
+    unsigned long long word = 0;
+    for (int i = 0; i < n; ++i) {                                          // (i is uniform: the lane reads are v_readlane)
+      const int32_t bm = wm::k7_branch(g0, g1, __builtin_amdgcn_readlane(la, i), __builtin_amdgcn_readlane(lb, i));
+      const int32_t p0 = __builtin_amdgcn_ds_bpermute(from0, pm), p1 = __builtin_amdgcn_ds_bpermute(from1, pm);
+      int b;
+      pm = wm::k7_acs(p0, p1, bm, b);
+      const unsigned long long d = __ballot(b);
+      if (lane == i) word = d;
+    }
+    if (lane < n) D[t0 + lane] = word;
+  }
+  if (final_metric && lane == 0) final_metric[blockIdx.x] = pm;            // state 0: the tail leads every path there
+  __syncthreads();                                                         // the wave's own stores, before it loads them
+  int s = 0;
+  for (int t0 = (n_steps - 1) / WAVE * WAVE; t0 >= 0; t0 -= WAVE) {
+    const int n = min(WAVE, n_steps - t0);
+    const unsigned long long word = lane < n ? D[t0 + lane] : 0ull;
+    const int lo = (int)(unsigned)word, hi = (int)(unsigned)(word >> 32);
+    int u = 0;
+    for (int i = n - 1; i >= 0; --i) {
+      if (lane == i) u = s & 1;
+      const unsigned long long d = (unsigned long long)(unsigned)__builtin_amdgcn_readlane(lo, i) |
+                                   ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(hi, i) << 32);
+      s = wm::k7_back(s, d);
+    }
+    if (t0 + lane < n_info) info_bits[(size_t)blockIdx.x * (size_t)n_info + (size_t)(t0 + lane)] = (uint8_t)u;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host-side argument checking / launch helpers
 // ---------------------------------------------------------------------------
@@ -1777,6 +1830,34 @@ int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* ti
   const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(nby - (h - 7) / 8 + 1), 64);
   hipLaunchKernelGGL(windows ? k_payload_keyed_scan_windows : k_payload_keyed_scan, grid, dim3(WAVE), 0, ctx->stream, s1, tile_dither,
                      reinterpret_cast<long long*>(scores), g, delta, 1.0f / (2.0f * delta));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// ---- channel code: the Viterbi decode -----------------------------------------
+// the sizes of a decode, checked (both forms, before any launch or copy)
+static int check_k7_sizes(const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, const uint8_t* info_bits) {
+  if (n_info < 1) return set_err(WM_ERR_BADARG, "n_info must be at least 1");
+  if (n_info > wm::K7_MAX_STEPS - wm::K7_TAIL) return set_err(WM_ERR_BADARG, "n_info + 6 steps exceed 2^18");
+  if (n_codewords < 1) return set_err(WM_ERR_BADARG, "n_codewords must be at least 1");
+  if (llr_stride < 2 * (size_t)(n_info + wm::K7_TAIL)) return set_err(WM_ERR_BADARG, "llr_stride < 2 (n_info + 6)");
+  if (!llr || !info_bits) return set_err(WM_ERR_BADARG, "llr / info_bits is NULL");
+  return WM_OK;
+}
+
+int wm_payload_decode_k7_dev(wm_ctx* ctx, const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, uint8_t* info_bits,
+                             int32_t* final_metric, uint64_t* decisions) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_k7_sizes(llr, n_info, n_codewords, llr_stride, info_bits));
+  if (((uintptr_t)llr | (uintptr_t)final_metric) & 3u || ((uintptr_t)decisions & 7u))
+    return set_err(WM_ERR_BADARG, "llr / final_metric / decisions is misaligned");
+  if (!decisions) {                                                      // the context's own words: 8 (n_info + 6) bytes a codeword
+    WM_TRY(wmi::grow(ctx, &ctx->sigma_ws, &ctx->sigma_ws_bytes,
+                     (size_t)n_codewords * (size_t)(n_info + wm::K7_TAIL) * sizeof(uint64_t), "decision words"));
+    decisions = static_cast<uint64_t*>(ctx->sigma_ws);
+  }
+  hipLaunchKernelGGL(k_payload_viterbi, dim3((unsigned)n_codewords), dim3(WAVE), 0, ctx->stream, llr, n_info, llr_stride, info_bits,
+                     final_metric, reinterpret_cast<unsigned long long*>(decisions));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -2392,6 +2473,21 @@ int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_d
     d_u = cv.in((size_t)nby * (size_t)nbx, tile_dither);
     d_sc = cv.out(64 * spitch, scores);
   }, [&] { return wm_payload_keyed_scores_dev(ctx, d_s1, d_u, d_sc, h, w, nby, nbx, delta); }, true);
+}
+
+// ---- channel code, host pointers ------------------------------------------------
+int wm_payload_decode_k7(wm_ctx* ctx, const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, uint8_t* info_bits,
+                         int32_t* final_metric, uint64_t* decisions) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_k7_sizes(llr, n_info, n_codewords, llr_stride, info_bits));
+  const size_t n_steps = (size_t)n_info + wm::K7_TAIL, n_cw = (size_t)n_codewords;
+  int32_t *d_llr, *d_fm; uint8_t* d_info; uint64_t* d_dec;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_llr = cv.in((n_cw - 1) * llr_stride + 2 * n_steps, llr);
+    d_info = cv.out(n_cw * (size_t)n_info, info_bits);
+    d_fm = final_metric ? cv.out(n_cw, final_metric) : nullptr;
+    d_dec = decisions ? cv.out(n_cw * n_steps, decisions) : cv.take<uint64_t>(n_cw * n_steps);   // (unwanted words: scratch)
+  }, [&] { return wm_payload_decode_k7_dev(ctx, d_llr, n_info, n_codewords, llr_stride, d_info, d_fm, d_dec); }, true);
 }
 
 }  // extern "C"

@@ -379,40 +379,54 @@ def _payload_dither_of(H: int, W: int, key: bytes, on) -> Optional[np.ndarray]:
     return P.dither_table(H // TILE, W // TILE, key) if on else None
 
 
+def _payload_read(ctx, soft: np.ndarray, code: int) -> np.ndarray:
+    """The frame's bits out of the soft values of the bits the tiles carry: their signs, or with the channel code the
+    Viterbi decode of their quantised values on the device (include/wmhip.h, "channel code")"""
+    return ctx.payload_decode(P.quantise_soft(soft))[0] if code else np.asarray(soft) < 0
+
+
 def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: bytes, *, payload_type: str = "text",
-                         delta: float = P.DELTA_DEFAULT, device: int = 0, verify: bool = True, dither: bool = False) -> dict:
+                         delta: float = P.DELTA_DEFAULT, device: int = 0, verify: bool = True, dither: bool = False,
+                         code=None) -> dict:
     """cover BGR uint8, data bytes (or a str: the text / JSON itself).  Returns dict(stego BGR uint8, meta dict, psnr, ssim).
     ``dither``: every tile's lattice is shifted by a keyed offset (payload.dither_table), so that the stego shows neither
     the payload's presence nor delta to a reader without the password; the meta says so and the extract follows it.
     ``verify``: the stego is decoded by the extract's own path before it is returned, and a payload that does not come back
-    valid and equal to ``data`` is a ValueError (tiles pinned by clipping vote for the wrong bit: DESIGN.md section 14)."""
+    valid and equal to ``data`` is a ValueError (tiles pinned by clipping vote for the wrong bit: DESIGN.md section 14).
+    ``code="k7"``: the frame goes through the rate-1/2 convolutional code of payload.encode_k7 before it is spread over the
+    tiles (twice the bits plus 12, so half the tiles per bit), and every decode goes through the Viterbi decoder on the
+    device: wrong votes and the bits a crop erased are corrected.  The meta says so and the extract follows it."""
     M.check_password_type(password, "embed")
     M.require_password(password, "embed")
     delta = hostapi.check_delta(delta)
+    code = P.check_code(code)
     data = P.payload_bytes(data, payload_type, allow_file=False)
     if cover_bgr.dtype != np.uint8 or cover_bgr.ndim != 3 or cover_bgr.shape[2] != 3:
         raise ValueError("cover must be uint8 [H, W, 3]")
     H, W = cover_bgr.shape[:2]
     bits = P.payload_frame(data)
-    P.check_capacity(bits.size, P.capacity_bits(H, W))                     # before any device call
+    carried = P.encode_k7(bits) if code else bits                          # what the tiles carry
+    P.check_capacity(carried.size, P.capacity_bits(H, W))                  # before any device call
     key = hg.derive_key(password, nonce)
-    tbi, order, offs = _payload_map_of(H, W, key, bits.size)
+    tbi, order, offs = _payload_map_of(H, W, key, carried.size)
     ctx = _ctx(device)
     Y = _Gray.planes_in(ctx, cover_bgr)                                    # core:117 (_to_Y)
     dz = _payload_dither_of(H, W, key, dither)
-    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(bits, tbi), delta, want_yw=True, dither=dz)
-    members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, dither=P.DITHER_TABLE if dither else 0)
+    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(carried, tbi), delta, want_yw=True, dither=dz)
+    members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, dither=P.DITHER_TABLE if dither else 0, code=code)
     digest = hg.hmac_digest(key, M.hmac_parts(members))
     stego = _Gray.planes_out(ctx, cover_bgr, stego_y)                      # core:123 (_from_Y)
     if verify:                                                             # one metric and reduce pass on the final BGR stego
-        P.check_decodes(ctx.payload_soft(_Gray.planes_in(ctx, stego), order, offs, bits.size, delta, dither=dz), bits, data)
+        soft = ctx.payload_soft(_Gray.planes_in(ctx, stego), order, offs, carried.size, delta, dither=dz)
+        P.check_decodes(soft, bits, data, _payload_read(ctx, soft, code) if code else None)
     ps = ctx.psnr(cover_bgr, stego)
     ss = ctx.ssim(ctx.color("bgr2gray", cover_bgr), Yw)
     return dict(stego=stego, meta=M.sealed(members, TILE, digest), psnr=ps, ssim=ss)
 
 
 def _payload_meta_checked(meta, password: str):
-    """(H, W, delta, n_bits, payload_type, key) of an authentic payload meta"""
+    """(meta, H, W, delta, n_bits, payload_type, key) of an authentic payload meta; n_bits counts the frame's bits, with a
+    channel code or without"""
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")
     meta = M.unpack_payload(meta)
@@ -422,7 +436,8 @@ def _payload_meta_checked(meta, password: str):
         raise ValueError(M.WRONG_PASSWORD)
     H, W = map(int, meta["shape"])
     n_bits = int(meta["payload_bits"])
-    if n_bits < 8 * P.OVERHEAD_BYTES or n_bits % 8 or n_bits > P.capacity_bits(H, W) or M.tile_of(meta) != TILE:
+    carried = P.coded_bits(n_bits) if M.payload_code_of(meta) else n_bits
+    if n_bits < 8 * P.OVERHEAD_BYTES or n_bits % 8 or carried > P.capacity_bits(H, W) or M.tile_of(meta) != TILE:
         raise ValueError("payload meta does not describe a frame of this image size")
     ptype = str(meta["payload_type"])
     P.check_type(ptype)
@@ -449,9 +464,9 @@ def _check_crop_shape(stego_bgr: np.ndarray, H: int, W: int) -> tuple:
     return h, w
 
 
-def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
+def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, code, key, device):
     """search="crop" (include/wmhip.h, "crop resynchronisation"): the stego is any axis-aligned crop of the marked image.
-    Every refusal comes before the first device call."""
+    n_bits: the bits the tiles carry (the coded bits under a channel code).  Every refusal comes before the first device call."""
     if M.payload_dither_of(meta):
         raise ValueError("resynchronising a dithered payload is not supported: keyed dither removes the grid's keyless "
                          "signal (search='crop' needs a payload embedded with dither=False); use search='crop-keyed'")
@@ -466,13 +481,13 @@ def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, k
         return b"", False, 0.0, None
     ty, tx = place
     soft, count = P.soft_of_votes(votes, tbi[ty:ty + votes.shape[0], tx:tx + votes.shape[1]], n_bits)
-    data, valid = P.payload_unframe(soft < 0)
+    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
     return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
 
 
-def _extract_payload_cropped_keyed(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, key, device):
+def _extract_payload_cropped_keyed(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, code, key, device):
     """search="crop-keyed" (include/wmhip.h, "keyed crop resynchronisation"): the stego is any axis-aligned crop of an image
-    marked with dither=True.  Every refusal comes before the first device call."""
+    marked with dither=True.  n_bits as above.  Every refusal comes before the first device call."""
     if not M.payload_dither_of(meta):
         raise ValueError("search='crop-keyed' reads a payload embedded with dither=True; this one has none: use search='crop'")
     _check_crop_shape(stego_bgr, H, W)
@@ -484,7 +499,7 @@ def _extract_payload_cropped_keyed(stego_bgr: np.ndarray, meta, H, W, delta, n_b
     ny, nx = s1.shape
     votes = P.keyed_votes(s1, table[ty:ty + ny, tx:tx + nx], delta)
     soft, count = P.soft_of_votes(votes, tbi[ty:ty + ny, tx:tx + nx], n_bits)
-    data, valid = P.payload_unframe(soft < 0)
+    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
     return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
 
 
@@ -499,36 +514,39 @@ def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: i
     resynchronisation" and "Keyed crop resynchronisation")."""
     _check_search(search)
     meta, H, W, delta, n_bits, _, key = _payload_meta_checked(meta, password)
+    code = M.payload_code_of(meta)
+    n_bits = P.coded_bits(n_bits) if code else n_bits                      # from here on: the bits the tiles carry
     if search == "crop":
-        return _extract_payload_cropped(stego_bgr, meta, H, W, delta, n_bits, key, device)
+        return _extract_payload_cropped(stego_bgr, meta, H, W, delta, n_bits, code, key, device)
     if search == "crop-keyed":
-        return _extract_payload_cropped_keyed(stego_bgr, meta, H, W, delta, n_bits, key, device)
+        return _extract_payload_cropped_keyed(stego_bgr, meta, H, W, delta, n_bits, code, key, device)
     _check_stego_shape(stego_bgr, meta)
     _, order, offs = _payload_map_of(H, W, key, n_bits)
     ctx = _ctx(device)
     dz = _payload_dither_of(H, W, key, M.payload_dither_of(meta))
     soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, n_bits, delta, dither=dz)
-    data, valid = P.payload_unframe(soft < 0)
+    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
     return data, bool(valid), P.confidence(soft, offs, 1)
 
 
 def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, password: Optional[str] = None,
                   payload_type: str = "text", delta: float = P.DELTA_DEFAULT, nonce: Optional[bytes] = None, device: int = 0,
-                  verify: bool = True, dither: bool = False):
+                  verify: bool = True, dither: bool = False, code=None):
     """``payload``: a str or bytes, or the path of a .txt / .json file (read when it exists, like the reference's
     text_data / wm_source, core:102-106).  Returns (out_path, meta_path, psnr, ssim); the stego is written as PNG.
     ``verify`` as in embed_payload_arrays: a payload that does not decode from its own stego raises, and neither the
-    stego nor the meta is written.  ``dither`` as there."""
+    stego nor the meta is written.  ``dither`` and ``code`` as there."""
     M.check_password_type(password, "embed")
     M.require_password(password, "embed")
     hostapi.check_delta(delta)
+    P.check_code(code)
     data = P.payload_bytes(payload, payload_type)                          # refused before anything else is read
     cover = hg.read_image_bgr(cover_path)
     if nonce is None:
         nonce = os.urandom(8)
     # (a json payload is canonical by now; canonicalising it again inside leaves it as it is)
     r = embed_payload_arrays(cover, data, password, nonce, payload_type=payload_type, delta=delta, device=device, verify=verify,
-                             dither=dither)
+                             dither=dither, code=code)
     out_path = M.out_name(out_path, "_stego.png")
     if not hg.write_png(out_path, r["stego"], 0):
         raise IOError("Ghi stego thất bại.")

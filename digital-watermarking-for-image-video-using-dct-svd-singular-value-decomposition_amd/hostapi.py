@@ -93,6 +93,8 @@ _DECLARED = {
     # keyed crop resynchronisation: (stego, s1, the plane arguments); (s1, tile_dither, scores, h, w, nby, nbx, delta)
     "wm_payload_sigma1_scan_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz],
     "wm_payload_keyed_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f],
+    # channel code: (llr, n_info, n_codewords, llr_stride, info_bits, final_metric, decisions)
+    "wm_payload_decode_k7*": [_vp, _vp, _i, _i, _sz, _vp, _vp, _vp],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -634,6 +636,29 @@ class Context:
             self.d2h(soft, d_soft)
             self.check_status()
         return soft
+
+    # ---- channel code of the blind payload (include/wmhip.h; the encoder and the quantiser are payload.py's) ------------
+    def payload_decode(self, L: np.ndarray, decisions: bool = False):
+        """The Viterbi decode of quantised soft values L, int32 [n_coded] or [n, n_coded] with n_coded = 2 (n_info + 6) ->
+        (info_bits uint8 [n?, n_info], final_metric int32 [n?]), with ``decisions=True`` also the decision words uint64
+        [n?, n_info + 6].  A strided [n, n_coded] view with contiguous rows is read in place."""
+        L = np.asarray(L)
+        if L.dtype != np.int32 or L.ndim not in (1, 2):
+            raise ValueError("L must be int32 [n_coded] or [n, n_coded]")
+        rows = L[None] if L.ndim == 1 else L
+        n, n_coded = rows.shape
+        n_info = n_coded // 2 - P.K7_TAIL
+        if n < 1 or n_coded % 2 or n_info < 1 or n_coded > 2 * P.K7_MAX_STEPS:
+            raise ValueError(f"L holds {n} codewords of {n_coded} values: 2 (n_info + 6) each, n_info in 1..{P.K7_MAX_STEPS - P.K7_TAIL}")
+        if rows.strides[1] != 4 or (n > 1 and (rows.strides[0] % 4 or rows.strides[0] < 4 * n_coded)):
+            rows = np.ascontiguousarray(rows)
+        stride = rows.strides[0] // 4 if n > 1 else n_coded
+        info = np.zeros((n, n_info), np.uint8)
+        metric = np.zeros(n, np.int32)
+        words = np.zeros((n, n_info + P.K7_TAIL), np.uint64) if decisions else None
+        self._call("wm_payload_decode_k7", _p(rows), n_info, n, stride, _p(info), _p(metric), _p(words))
+        out = (info, metric) if L.ndim == 2 else (info[0], metric[0])
+        return out if not decisions else out + ((words if L.ndim == 2 else words[0]),)
 
     # ---- crop resynchronisation of the blind payload (include/wmhip.h; the comparisons and tie rules are payload.py's) ----
     def payload_phase_scan(self, planes: np.ndarray, delta: float):

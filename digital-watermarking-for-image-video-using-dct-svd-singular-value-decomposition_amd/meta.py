@@ -58,9 +58,11 @@ _ORDER = {
 # file's size depends neither on the image size nor on the frame count.  A video writes frame_interval and n_frames too
 # (and chroma, should a colour container ever be named); payload_type is "text", "json" or "bytes".  ``dither`` (uint8,
 # directly after delta): 1 for a payload embedded with keyed dither under payload.dither_table; a meta written without
-# dither has no such member, so the files written before it existed load, hash and weigh as they did.
+# dither has no such member, so the files written before it existed load, hash and weigh as they did.  ``code`` (uint8,
+# directly after dither): 1 for a payload protected by the rate-1/2 K = 7 convolutional code of payload.encode_k7; present
+# only when the code is on, by the same reasoning.  payload_bits stays the frame's bit count whatever the code.
 PAYLOAD_MODE = "payload"
-_PAYLOAD = ("payload_type", "shape", "delta", "dither", "payload_bits", "nonce", "tile", "frame_interval", "n_frames", "chroma")
+_PAYLOAD = ("payload_type", "shape", "delta", "dither", "code", "payload_bits", "nonce", "tile", "frame_interval", "n_frames", "chroma")
 _ORDER[PAYLOAD_MODE] = ("mode",) + _PAYLOAD + ("digest",)
 _ORDER_FULL_FRAME = dict(_ORDER, color=("mode",) + _IMAGE_COMMON + _BY_CHANNEL_THEN_S + ("digest",))
 
@@ -84,7 +86,7 @@ def is_payload(meta) -> bool:
 
 
 # what a payload meta's members are stored as - and hashed as, whatever a reader's np.load made of them
-_PAYLOAD_DTYPES = dict(shape=np.int64, delta=np.float32, dither=np.uint8, payload_bits=np.int32, nonce=np.uint8, tile=np.int32,
+_PAYLOAD_DTYPES = dict(shape=np.int64, delta=np.float32, dither=np.uint8, code=np.uint8, payload_bits=np.int32, nonce=np.uint8, tile=np.int32,
                        frame_interval=np.int32, n_frames=np.int32)
 
 
@@ -103,11 +105,13 @@ def payload_hmac_parts(meta) -> list:
 
 
 def payload_members(payload_type: str, H: int, W: int, delta: float, n_bits: int, nonce: bytes, frame_interval=None,
-                    n_frames=None, dither: int = 0) -> dict:
+                    n_frames=None, dither: int = 0, code: int = 0) -> dict:
     out = dict(mode=PAYLOAD_MODE, payload_type=str(payload_type), shape=np.array((H, W), dtype=np.int64),
                delta=np.float32(delta))
     if dither:
         out.update(dither=np.uint8(dither))
+    if code:
+        out.update(code=np.uint8(code))
     out.update(payload_bits=np.int32(n_bits), nonce=np.frombuffer(nonce, dtype=np.uint8), tile=np.int32(TILE))
     if n_frames is not None:
         out.update(frame_interval=np.int32(frame_interval), n_frames=np.int32(n_frames))
@@ -175,6 +179,14 @@ def payload_dither_of(meta) -> int:
     if d not in (0, 1):
         raise ValueError(f"payload meta names dither table {d}, which this version does not know")
     return d
+
+
+def payload_code_of(meta) -> int:
+    """0 for a payload meta without the ``code`` member (repetition alone), else its value; only 1 (payload.CODE_K7) is known"""
+    c = int(meta["code"]) if "code" in meta else 0
+    if c not in (0, 1):
+        raise ValueError(f"payload meta names code {c}, which this version does not know")
+    return c
 
 
 def refuse_payload(meta, what: str) -> None:

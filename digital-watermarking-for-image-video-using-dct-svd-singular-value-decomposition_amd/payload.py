@@ -211,16 +211,71 @@ def keyed_votes(s1, u, delta: float) -> np.ndarray:
     return np.rint(m * F(VOTE_ONE)).astype(np.int32)
 
 
-def check_decodes(soft: np.ndarray, bits: np.ndarray, data: bytes) -> None:
+# ---- channel code (include/wmhip.h, "channel code"): rate 1/2, K = 7, generators 171 / 133 octal --------
+CODES = (None, "k7")                                # what a caller's ``code`` argument may be
+CODE_K7 = 1                                         # the meta's ``code`` member: this code
+K7_TAIL = 6                                         # zero bits behind the frame
+K7_MAX_STEPS = 1 << 18                              # n_info + 6 of one decode
+K7_LLR_MAX = 1024                                   # |L| of a quantised soft value
+_K7_G = (0o171, 0o133)
+_K7_PARITY = np.array([bin(r).count("1") & 1 for r in range(128)], np.uint8)
+
+
+def check_code(code) -> int:
+    """the meta's ``code`` member of a caller's ``code`` argument: 0 for None, 1 for "k7" """
+    if code not in CODES:
+        raise ValueError(f"code must be None or 'k7', got {code!r}")
+    return CODE_K7 if code else 0
+
+
+def coded_bits(n_info: int) -> int:
+    """n_coded of a frame of n_info bits: two coded bits for every info bit and every tail bit"""
+    return 2 * (int(n_info) + K7_TAIL)
+
+
+def encode_k7(bits) -> np.ndarray:
+    """info bits u (the frame) -> coded bits uint8 [2 (len(u) + 6)]: the register starts at 0 and steps as r = ((r << 1) | u_t)
+    & 127 through u and 6 zero tail bits; coded[2 t] = parity(r & 0o171), coded[2 t + 1] = parity(r & 0o133).  Host work,
+    like the map and the dither table."""
+    u = np.concatenate([(np.asarray(bits).reshape(-1) != 0).astype(np.int64), np.zeros(K7_TAIL, np.int64)])
+    # r_t holds u_t .. u_{t-6}: seven shifted copies of u, without a Python loop over the steps
+    r = np.zeros(u.size, np.int64)
+    for k in range(7):
+        r[k:] |= u[:u.size - k] << k
+    out = np.empty(2 * u.size, np.uint8)
+    out[0::2] = _K7_PARITY[r & _K7_G[0]]
+    out[1::2] = _K7_PARITY[r & _K7_G[1]]
+    return out
+
+
+def quantise_soft(soft) -> np.ndarray:
+    """float64 soft values (positive: the bit reads 0; 0: no tile voted, an erasure) -> the decoder's int32 L in -1024 .. 1024:
+    L[j] = clip(rint(soft[j] * (1024 / peak)), -1024, 1024) with peak = max |soft|, 1 where that is 0 - all in float64,
+    halves to even.  Past this line the decode is integer arithmetic."""
+    s = np.asarray(soft, np.float64)
+    peak = float(np.max(np.abs(s))) if s.size else 0.0
+    if not peak > 0.0:
+        peak = 1.0
+    return np.clip(np.rint(s * (float(K7_LLR_MAX) / peak)), -K7_LLR_MAX, K7_LLR_MAX).astype(np.int32)
+
+
+def check_decodes(soft: np.ndarray, bits: np.ndarray, data: bytes, decoded=None) -> None:
     """The embed's own check: ``soft`` is what the decoder reads from the finished stego (every marked frame added).  Tiles
     pinned by clipping - text on a white page, saturated regions - vote for the WRONG bit at full weight, and with few tiles
-    per bit they win; such a payload must not be reported as embedded."""
-    got, valid = payload_unframe(np.asarray(soft) < 0)
+    per bit they win; such a payload must not be reported as embedded.  ``decoded``: with a channel code, the info bits its
+    decoder made of ``soft`` (``bits`` is the frame either way); the count is then of info bits."""
+    got_bits = np.asarray(soft) < 0 if decoded is None else np.asarray(decoded) != 0
+    got, valid = payload_unframe(got_bits)
     if valid and got == bytes(data):
         return
-    wrong = int(np.count_nonzero((np.asarray(soft) < 0) != (np.asarray(bits) != 0)))
-    raise ValueError(f"payload does not decode from its own stego: {wrong} of {len(bits)} bits wrong (tiles pinned by clipping "
-                     "vote against their bit). Use a shorter payload (more tiles per bit), a larger delta or a larger cover.")
+    wrong = int(np.count_nonzero(got_bits != (np.asarray(bits) != 0)))
+    if decoded is None:
+        raise ValueError(f"payload does not decode from its own stego: {wrong} of {len(bits)} bits wrong (tiles pinned by "
+                         "clipping vote against their bit). Use a shorter payload (more tiles per bit), a larger delta, a "
+                         "larger cover or code='k7'.")
+    raise ValueError(f"payload does not decode from its own stego: {wrong} of {len(bits)} info bits wrong after the channel "
+                     "code's decode (tiles pinned by clipping vote against their bit). Use a shorter payload (more tiles per "
+                     "coded bit), a larger delta or a larger cover.")
 
 
 def check_type(payload_type: str) -> None:

@@ -530,32 +530,36 @@ def _payload_frame_dithers(H: int, W: int, key: bytes, first_marked: int, n: int
 def embed_payload_video(host_video_path: str, payload, output_video_path: str, metadata_path: str, *, password: str = "",
                         payload_type: str = "text", frame_interval: int = 1, delta: float = P.DELTA_DEFAULT,
                         nonce: Optional[bytes] = None, batch: int = 32, device: int = 0, verify: bool = True,
-                        dither: bool = False):
+                        dither: bool = False, code=None):
     """Embed a text / JSON / bytes payload (``payload`` as in dct_svd_core_secure.embed_payload) into the luma of every
     ``frame_interval``-th frame of an 8-bit .y4m; chroma and unmarked frames are copied byte for byte.
     Returns (output_video_path, metadata_path, mean PSNR of the marked frames' luma).
     ``verify``: the soft votes of the marked stego frames are added up as they are written, and a payload that does not
     decode from them raises ValueError after the last frame; neither the output file nor the meta remains.
     ``dither``: keyed dither (dct_svd_core_secure.embed_payload_arrays); every marked frame gets a table of its own, keyed
-    by the frame's index in the file, and a batch is one call with a table row per frame."""
+    by the frame's index in the file, and a batch is one call with a table row per frame.
+    ``code="k7"``: the channel code of dct_svd_core_secure.embed_payload_arrays; the frames' summed soft values go through
+    ONE decode."""
     M.require_password(password, "embed")
     delta = hostapi.check_delta(delta)
+    code = P.check_code(code)
     data = P.payload_bytes(payload, payload_type)
     bits = P.payload_frame(data)
+    carried = P.encode_k7(bits) if code else bits                          # what the tiles carry
     batch = max(1, int(batch))
     vid = Y4M(host_video_path)
     ctx = None
     try:
         H, W = vid.H, vid.W
-        P.check_capacity(bits.size, P.capacity_bits(H, W))                 # before any device call
+        P.check_capacity(carried.size, P.capacity_bits(H, W))              # before any device call
         if nonce is None:
             nonce = os.urandom(8)
         key = hg.derive_key(password, nonce)
-        tbi, order, offs = P.payload_map(H // TILE, W // TILE, key, bits.size)
-        tile_bit = P.tile_bits(bits, tbi)
+        tbi, order, offs = P.payload_map(H // TILE, W // TILE, key, carried.size)
+        tile_bit = P.tile_bits(carried, tbi)
         ctx = hostapi.Context(device)
         psnrs = []
-        soft = np.zeros(bits.size, np.float64)
+        soft = np.zeros(carried.size, np.float64)
 
         def embed_marked(marked):
             ys = np.stack([y for y, _ in marked])
@@ -564,7 +568,7 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             st, _, _ = ctx.embed_tiles_payload(ys, tile_bit, delta, dither=dz)
             psnrs.extend(hg.psnr(ys[i], st[i]) for i in range(len(marked)))
             if verify:
-                np.add(soft, payload_soft_frames(ctx, st, order, offs, bits.size, delta, batch, dither=dz), out=soft)
+                np.add(soft, payload_soft_frames(ctx, st, order, offs, carried.size, delta, batch, dither=dz), out=soft)
             return [(s.tobytes(), chroma.tobytes()) for s, (_, chroma) in zip(st, marked)]
 
         with open(output_video_path, "wb") as out:
@@ -572,12 +576,12 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             n_frames = _embed_frame_loop(vid, out, frame_interval, batch, embed_marked)
         if verify and psnrs:
             try:
-                P.check_decodes(soft, bits, data)
+                P.check_decodes(soft, bits, data, ctx.payload_decode(P.quantise_soft(soft))[0] if code else None)
             except ValueError:
                 os.remove(output_video_path)
                 raise
         members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, frame_interval, n_frames,
-                                    dither=P.DITHER_TABLE if dither else 0)
+                                    dither=P.DITHER_TABLE if dither else 0, code=code)
         M.save_payload_meta(metadata_path, M.sealed(members, TILE, hg.hmac_digest(key, M.hmac_parts(members))))
         return output_video_path, metadata_path, float(np.mean(psnrs)) if psnrs else 99.0
     finally:
@@ -599,6 +603,8 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
         raise ValueError(M.WRONG_PASSWORD)
     H, W = map(int, data["shape"])
     n_bits, delta = int(data["payload_bits"]), hostapi.check_delta(float(data["delta"]))
+    code = M.payload_code_of(data)
+    n_bits = P.coded_bits(n_bits) if code else n_bits                      # from here on: the bits the tiles carry
     fi = int(data["frame_interval"])
     batch = max(1, int(batch))
     _, order, offs = P.payload_map(H // TILE, W // TILE, key, n_bits)
@@ -615,10 +621,11 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
             dz = _payload_frame_dithers(H, W, key, n_marked, len(frames), fi) if dither else None
             soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, n_bits, delta, dither=dz)
             n_marked += len(frames)
+        read = ctx.payload_decode(P.quantise_soft(soft))[0] if code else soft < 0   # (one decode of the summed values)
     finally:
         vid.close()
         if ctx is not None:
             ctx.close()
-    payload, valid = P.payload_unframe(soft < 0)
+    payload, valid = P.payload_unframe(read)
     out = (payload, bool(valid), P.confidence(soft, offs, n_marked))
     return out + (soft,) if return_soft else out

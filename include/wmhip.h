@@ -418,6 +418,42 @@ int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* ti
 int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
                             int nbx, float delta);
 
+/* --------------------------------------------------------------------------
+ * Channel code of the blind payload (optional; the meta's ``code`` member = 1): the industry-standard rate-1/2 convolutional
+ * code of constraint length 7, generators 171 and 133 octal, with a zero tail, decoded by a soft-decision Viterbi decoder on
+ * the device.  Part of the meta format like the rule and the dither table; DESIGN.md section 14, "Channel code".
+ *
+ * Info bits.  u[0 .. n_info) is the payload's frame (length header, bytes, CRC: the bits embedded without a code), followed
+ *   by 6 zero tail bits: n_steps = n_info + 6.
+ * Encoder (host work).  A 7-bit register r starts at 0; step t shifts u[t] in: r = ((r << 1) | u[t]) & 127, and puts out
+ *   coded[2 t] = parity(r & 0171), coded[2 t + 1] = parity(r & 0133).  n_coded = 2 n_steps.
+ * Map.  The keyed tile-to-bit map over n_coded bits: tile t carries coded[perm[t] % n_coded].  It is the interleaver.
+ *   n_coded <= n_tiles.
+ * Soft input (host work).  soft[j], the float64 sum of the votes of coded bit j (positive: a 0), is quantised to an integer
+ *   L[j] = clip(rint(soft[j] * (1024 / peak)), -1024, 1024), peak = max |soft| (1 where that is 0), in float64, rint to even.
+ *   A coded bit without a tile (a crop) has soft = 0 and L = 0: an erasure.
+ * Decoder.  Integers from here on.  The decoder clamps L to -1024 .. 1024 again on load (part of the rule: any int32 is a
+ *   valid input).  State s = r & 63; path metrics pm[0] = 0, pm[s != 0] = -2^30.  Step t, for every new state s': the
+ *   predecessors are p_b = (s' >> 1) | (b << 5), b = 0, 1, their registers r_b = s' | (b << 6),
+ *     bm_b = (1 - 2 parity(r_b & 0171)) L[2 t] + (1 - 2 parity(r_b & 0133)) L[2 t + 1]        (bm_1 = -bm_0: both generators
+ *     c_b  = pm[p_b] + bm_b                                                                     hold bits 0 and 6)
+ *   the new pm[s'] is the larger candidate, b = 1 iff c_1 > c_0 (a tie goes to b = 0), and bit s' of the 64-bit decision
+ *   word D[t] is that b.  Traceback: s = 0 at t = n_steps - 1, going down: u[t] = s & 1, b = (D[t] >> s) & 1,
+ *   s = (s >> 1) | (b << 5).  The info bits are u[0 .. n_info); the final metric is pm[0] after the last step.
+ * Limit.  n_steps <= 2^18: every metric then stays inside (-2^30 - 2^29, 2^29] and nothing is normalised.
+ *
+ *   llr           [n_codewords] rows of 2 n_steps int32, row c at llr + c * llr_stride (elements)
+ *   info_bits     [n_codewords][n_info] uint8 (out), 0 or 1
+ *   final_metric  [n_codewords] int32 (out), may be NULL
+ *   decisions     [n_codewords][n_steps] uint64 (out), may be NULL: the context then keeps the words in a buffer of its own
+ *                 (8 n_steps bytes a codeword, at most 2 MiB)
+ * One wave per codeword, one launch: the forward pass and the traceback.  WM_ERR_BADARG, before any launch: n_info < 1,
+ * n_steps > 2^18, n_codewords < 1, llr_stride < 2 n_steps, llr or info_bits NULL (device form: a misaligned pointer). */
+int wm_payload_decode_k7_dev(wm_ctx* ctx, const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, uint8_t* info_bits,
+                             int32_t* final_metric, uint64_t* decisions);
+int wm_payload_decode_k7(wm_ctx* ctx, const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, uint8_t* info_bits,
+                         int32_t* final_metric, uint64_t* decisions);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
