@@ -1123,18 +1123,12 @@ __device__ __forceinline__ bool keyed_wave(const KeyedGeom& g, const int phase, 
   return ty <= g.nby - ny && tx0 < n_tx;                                 // (the whole wave: phases differ in their placements)
 }
 
-__global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __restrict__ s1, const uint16_t* __restrict__ U,
-                                                         long long* __restrict__ scores, const KeyedGeom g, const float delta,
-                                                         const float inv_2delta) {
-  const int phase = blockIdx.z, ty = blockIdx.y, tx0 = blockIdx.x * WAVE;
-  int ny, nx, n_tx;
-  if (!keyed_wave(g, phase, ty, tx0, ny, nx, n_tx)) return;
-  const int tx = min(tx0 + (int)threadIdx.x, n_tx - 1);
-  const float* __restrict__ sp = s1 + (size_t)phase * g.pitch;
-  const uint16_t* __restrict__ up = U + (size_t)ty * g.nbx + tx;
+// one placement's windows, the lane's own: sp the phase's sigma_1 grid, up the table at the placement's first tile
+__device__ __forceinline__ long long keyed_placement_sum(const float* __restrict__ sp, const uint16_t* __restrict__ up, const int ny,
+                                                         const int nx, const int nbx, const float delta, const float inv_2delta) {
   constexpr int STEP = 8;          // windows a lane loads before it computes: 8 loads in flight, not one wait per window
   long long acc = 0;
-  for (int r = 0; r < ny; ++r, sp += nx, up += g.nbx) {
+  for (int r = 0; r < ny; ++r, sp += nx, up += nbx) {
     int row = 0, c = 0;
     for (; c + STEP <= nx; c += STEP) {
       float s[STEP];
@@ -1147,6 +1141,17 @@ __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __rest
     for (; c < nx; ++c) row += keyed_abs_vote(sp[c], up[c], delta, inv_2delta);
     acc += row;
   }
+  return acc;
+}
+
+__global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __restrict__ s1, const uint16_t* __restrict__ U,
+                                                         long long* __restrict__ scores, const KeyedGeom g, const float delta,
+                                                         const float inv_2delta) {
+  const int phase = blockIdx.z, ty = blockIdx.y, tx0 = blockIdx.x * WAVE;
+  int ny, nx, n_tx;
+  if (!keyed_wave(g, phase, ty, tx0, ny, nx, n_tx)) return;
+  const int tx = min(tx0 + (int)threadIdx.x, n_tx - 1);
+  const long long acc = keyed_placement_sum(s1 + (size_t)phase * g.pitch, U + (size_t)ty * g.nbx + tx, ny, nx, g.nbx, delta, inv_2delta);
   if (tx0 + (int)threadIdx.x < n_tx) scores[(size_t)phase * g.spitch + (size_t)ty * n_tx + tx] = acc;
 }
 
@@ -1154,22 +1159,107 @@ __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __rest
 // mapping above leaves most of a wave without a placement: a wave owns ONE placement (phase, ty, tx) = blockIdx (z, y, x), lane
 // l adds the windows c = l, l + 64, .. of every row, and the 64 shares are added by wave_sum.  Integer sums: the two mappings
 // give the same bits, whichever the entry point picks.
+// lane l's share of one placement's windows: c = l, l + 64, .. of every row
+__device__ __forceinline__ long long keyed_windows_share(const float* __restrict__ sp, const uint16_t* __restrict__ up, const int ny,
+                                                         const int nx, const int nbx, const float delta, const float inv_2delta) {
+  long long acc = 0;
+  for (int r = 0; r < ny; ++r, sp += nx, up += nbx) {
+    int row = 0;
+    for (int c = threadIdx.x; c < nx; c += WAVE) row += keyed_abs_vote(sp[c], up[c], delta, inv_2delta);
+    acc += row;
+  }
+  return acc;
+}
+
 __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan_windows(const float* __restrict__ s1, const uint16_t* __restrict__ U,
                                                                  long long* __restrict__ scores, const KeyedGeom g,
                                                                  const float delta, const float inv_2delta) {
   const int phase = blockIdx.z, ty = blockIdx.y, tx = blockIdx.x;
   int ny, nx, n_tx;
   if (!keyed_wave(g, phase, ty, tx, ny, nx, n_tx)) return;
-  const float* __restrict__ sp = s1 + (size_t)phase * g.pitch;
-  const uint16_t* __restrict__ up = U + (size_t)ty * g.nbx + tx;
-  long long acc = 0;
-  for (int r = 0; r < ny; ++r, sp += nx, up += g.nbx) {
-    int row = 0;
-    for (int c = threadIdx.x; c < nx; c += WAVE) row += keyed_abs_vote(sp[c], up[c], delta, inv_2delta);
-    acc += row;
-  }
-  acc = wave_sum(acc);
+  const long long acc = wave_sum(keyed_windows_share(s1 + (size_t)phase * g.pitch, U + (size_t)ty * g.nbx + tx, ny, nx, g.nbx, delta,
+                                                     inv_2delta));
   if (threadIdx.x == 0) scores[(size_t)phase * g.spitch + (size_t)ty * n_tx + tx] = acc;
+}
+
+// Clip search (include/wmhip.h, "clip resynchronisation"): the keyed scan over several anchors' scans and many candidates, with
+// only (the largest score, its first place) per (candidate, phase) leaving the device.  Grid z = 64 candidate + phase; lanes
+// and waves own placements as in the two kernels above (the same selection rule in the entry point).  Candidate g reads anchor
+// a under table table_of[g][a]; an entry outside 0 .. n_tables - 1 skips the anchor (the load and the test are the wave's, not
+// the lane's).  A placement's sum stays in registers across the anchors - int32 per window row, int64 across rows and anchors -
+// and nothing is written per anchor.  Reduction: key = score * 2^24 + (2^24 - 1 - index), index = ty n_tx + tx; the index is
+// unique within (candidate, phase), so the largest key is the largest score at its FIRST index whatever order the waves arrive
+// in: a wave-level max, then one 64-bit integer atomic max per wave into best[g][p][0], which the entry point preset to -1.
+// score < 2^39 (the entry point's bound on windows x anchors) and index < 2^24 (its bound on placements) keep the key below
+// 2^63.  k_payload_keyed_best_unpack then rewrites every key >= 0 in place as (score, index).
+constexpr long long KEYED_INDEX_MASK = (1ll << 24) - 1;
+
+__device__ __forceinline__ long long keyed_key(const long long score, const int index) {
+  return (score << 24) | (KEYED_INDEX_MASK - index);
+}
+
+__device__ __forceinline__ long long wave_max(long long x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = max(x, (long long)__shfl_down(x, o, WAVE));
+  return x;
+}
+
+struct KeyedBestArgs {
+  const float* __restrict__ s1;          // [n_anchor][64][pitch]
+  const uint16_t* __restrict__ tables;   // [n_tables][nby nbx]
+  const int32_t* __restrict__ table_of;  // [candidates of this launch][n_anchor]
+  long long* __restrict__ best;          // [candidates of this launch][64][2]
+  int n_anchor, n_tables;
+};
+
+__global__ __launch_bounds__(WAVE) void k_payload_keyed_best(const KeyedBestArgs a, const KeyedGeom g, const float delta,
+                                                         const float inv_2delta) {
+  const int phase = blockIdx.z & 63, cand = blockIdx.z >> 6, ty = blockIdx.y, tx0 = blockIdx.x * WAVE;
+  int ny, nx, n_tx;
+  if (!keyed_wave(g, phase, ty, tx0, ny, nx, n_tx)) return;
+  const int tx = min(tx0 + (int)threadIdx.x, n_tx - 1);
+  const int32_t* __restrict__ tof = a.table_of + (size_t)cand * a.n_anchor;
+  const size_t tsize = (size_t)g.nby * g.nbx, at = (size_t)ty * g.nbx + tx;
+  long long acc = 0;
+  bool any = false;
+  for (int i = 0; i < a.n_anchor; ++i) {
+    const int t = tof[i];
+    if ((unsigned)t >= (unsigned)a.n_tables) continue;                    // (the whole wave)
+    any = true;
+    acc += keyed_placement_sum(a.s1 + ((size_t)i * 64 + phase) * g.pitch, a.tables + t * tsize + at, ny, nx, g.nbx, delta, inv_2delta);
+  }
+  if (!any) return;                                                      // a candidate without a marked anchor keeps (-1, -1)
+  const long long key = wave_max(tx0 + (int)threadIdx.x < n_tx ? keyed_key(acc, ty * n_tx + tx) : -1ll);
+  if (threadIdx.x == 0) atomicMax(a.best + 2 * ((size_t)cand * 64 + phase), key);
+}
+
+__global__ __launch_bounds__(WAVE) void k_payload_keyed_best_windows(const KeyedBestArgs a, const KeyedGeom g, const float delta,
+                                                                 const float inv_2delta) {
+  const int phase = blockIdx.z & 63, cand = blockIdx.z >> 6, ty = blockIdx.y, tx = blockIdx.x;
+  int ny, nx, n_tx;
+  if (!keyed_wave(g, phase, ty, tx, ny, nx, n_tx)) return;
+  const int32_t* __restrict__ tof = a.table_of + (size_t)cand * a.n_anchor;
+  const size_t tsize = (size_t)g.nby * g.nbx, at = (size_t)ty * g.nbx + tx;
+  long long acc = 0;
+  bool any = false;
+  for (int i = 0; i < a.n_anchor; ++i) {
+    const int t = tof[i];
+    if ((unsigned)t >= (unsigned)a.n_tables) continue;
+    any = true;
+    acc += keyed_windows_share(a.s1 + ((size_t)i * 64 + phase) * g.pitch, a.tables + t * tsize + at, ny, nx, g.nbx, delta, inv_2delta);
+  }
+  if (!any) return;
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) atomicMax(a.best + 2 * ((size_t)cand * 64 + phase), keyed_key(acc, ty * n_tx + tx));
+}
+
+__global__ __launch_bounds__(256) void k_payload_keyed_best_unpack(long long* __restrict__ best, const size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long long key = best[2 * i];
+  if (key < 0) return;
+  best[2 * i] = key >> 24;
+  best[2 * i + 1] = KEYED_INDEX_MASK - (key & KEYED_INDEX_MASK);
 }
 
 // The channel code's decoder (wmhip.h, "channel code"; the per-state arithmetic is wm_tile_math.h's): one wave per codeword,
@@ -1834,6 +1924,44 @@ int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* ti
   return WM_OK;
 }
 
+// the sizes of a clip search, checked (both forms, before any launch or copy)
+static int check_keyed_best_sizes(int n_anchor, int n_tables, int n_cand, int h, int w, int nby, int nbx, float delta) {
+  size_t spitch;
+  WM_TRY(check_keyed_sizes(h, w, nby, nbx, delta, spitch));
+  if (n_anchor < 1 || n_cand < 1 || n_tables < 1) return set_err(WM_ERR_BADARG, "n_anchor, n_tables and n_cand must be at least 1");
+  if ((size_t)(h / 8) * (size_t)(w / 8) * (size_t)n_anchor >= ((size_t)1 << 24))
+    return set_err(WM_ERR_BADARG, "(h / 8) (w / 8) n_anchor must stay below 2^24 (a score below 2^39)");
+  return WM_OK;
+}
+
+int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const uint16_t* tables, int n_tables, const int32_t* table_of,
+                              int n_cand, int64_t* best, int h, int w, int nby, int nbx, float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_keyed_best_sizes(n_anchor, n_tables, n_cand, h, w, nby, nbx, delta));
+  if (!tables || ((uintptr_t)tables & 1u)) return set_err(WM_ERR_BADARG, "tables is NULL or at an odd address");
+  if (!s1 || !table_of || !best || (((uintptr_t)s1 | (uintptr_t)table_of) & 3u) || ((uintptr_t)best & 7u))
+    return set_err(WM_ERR_BADARG, "s1 / table_of / best is NULL or misaligned");
+  long long* const b = reinterpret_cast<long long*>(best);
+  WM_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_cand * 64 * 2 * sizeof(int64_t), ctx->stream));      // every entry (-1, -1)
+  const KeyedGeom g{h, w, nby, nbx, (h / 8) * (w / 8), 0};
+  // the lane mapping by the rule of wm_payload_keyed_scores_dev; grid z = 64 candidates + phase, at most 1023 candidates a launch
+  const long long n_tx = nbx - w / 8 + 1, nx = w / 8, n_tx_max = nbx - (w - 7) / 8 + 1;
+  const bool windows = nx * ((n_tx + WAVE - 1) / WAVE) >= 2 * n_tx * ((nx + WAVE - 1) / WAVE);
+  constexpr int CHUNK = 1023;
+  for (int c0 = 0; c0 < n_cand; c0 += CHUNK) {
+    const int nc = std::min(CHUNK, n_cand - c0);
+    const KeyedBestArgs a{s1, tables, table_of + (size_t)c0 * n_anchor, b + (size_t)c0 * 128, n_anchor, n_tables};
+    const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(nby - (h - 7) / 8 + 1), (unsigned)(64 * nc));
+    hipLaunchKernelGGL(windows ? k_payload_keyed_best_windows : k_payload_keyed_best, grid, dim3(WAVE), 0, ctx->stream, a, g, delta,
+                       1.0f / (2.0f * delta));
+    WM_HIP(hipGetLastError());
+  }
+  const size_t n = (size_t)n_cand * 64;
+  hipLaunchKernelGGL(k_payload_keyed_best_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, b, n);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
 // ---- channel code: the Viterbi decode -----------------------------------------
 // the sizes of a decode, checked (both forms, before any launch or copy)
 static int check_k7_sizes(const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, const uint8_t* info_bits) {
@@ -2473,6 +2601,24 @@ int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_d
     d_u = cv.in((size_t)nby * (size_t)nbx, tile_dither);
     d_sc = cv.out(64 * spitch, scores);
   }, [&] { return wm_payload_keyed_scores_dev(ctx, d_s1, d_u, d_sc, h, w, nby, nbx, delta); }, true);
+}
+
+int wm_payload_keyed_best(wm_ctx* ctx, const float* s1, int n_anchor, const uint16_t* tables, int n_tables, const int32_t* table_of,
+                          int n_cand, int64_t* best, int h, int w, int nby, int nbx, float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_keyed_best_sizes(n_anchor, n_tables, n_cand, h, w, nby, nbx, delta));
+  if (!tables || ((uintptr_t)tables & 1u)) return set_err(WM_ERR_BADARG, "tables is NULL or at an odd address");
+  if (!s1 || !table_of || !best) return set_err(WM_ERR_BADARG, "s1 / table_of / best is NULL");
+  const size_t n_of = (size_t)n_cand * (size_t)n_anchor;
+  for (size_t i = 0; i < n_of; ++i)
+    if (table_of[i] < -1 || table_of[i] >= n_tables) return set_err(WM_ERR_BADARG, "table_of names a table outside -1 .. n_tables - 1");
+  float* d_s1; uint16_t* d_u; int32_t* d_of; int64_t* d_best;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_s1 = cv.in((size_t)n_anchor * 64 * (size_t)(h / 8) * (size_t)(w / 8), s1);
+    d_u = cv.in((size_t)n_tables * (size_t)nby * (size_t)nbx, tables);
+    d_of = cv.in(n_of, table_of);
+    d_best = cv.out((size_t)n_cand * 128, best);
+  }, [&] { return wm_payload_keyed_best_dev(ctx, d_s1, n_anchor, d_u, n_tables, d_of, n_cand, d_best, h, w, nby, nbx, delta); }, true);
 }
 
 // ---- channel code, host pointers ------------------------------------------------

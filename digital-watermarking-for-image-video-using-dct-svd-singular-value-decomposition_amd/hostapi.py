@@ -93,6 +93,8 @@ _DECLARED = {
     # keyed crop resynchronisation: (stego, s1, the plane arguments); (s1, tile_dither, scores, h, w, nby, nbx, delta)
     "wm_payload_sigma1_scan_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz],
     "wm_payload_keyed_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f],
+    # clip resynchronisation: (s1, n_anchor, tables, n_tables, table_of, n_cand, best, h, w, nby, nbx, delta)
+    "wm_payload_keyed_best*": [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f],
     # channel code: (llr, n_info, n_codewords, llr_stride, info_bits, final_metric, decisions)
     "wm_payload_decode_k7*": [_vp, _vp, _i, _i, _sz, _vp, _vp, _vp],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
@@ -828,6 +830,90 @@ class Context:
             self.d2h(s1, d_s1 + (8 * py + px) * pitch * 4)
             self.sync()
         return (py, px), place, s1
+
+    # ---- clip resynchronisation: a dithered video's clip (include/wmhip.h; the winner's rule is payload.pick_clip) ----------
+    @staticmethod
+    def _clip_args(tables, table_of, n_anchor, h, w, delta):
+        u = np.ascontiguousarray(tables, np.uint16)
+        if u.ndim != 3 or u.shape[0] < 1:
+            raise ValueError("the dither tables must be [n_tables, nby, nbx] with at least one table")
+        _, h, w, nby, nbx, delta = Context._keyed_args(u[0], h, w, delta)
+        tof = np.ascontiguousarray(table_of, np.int32)
+        if tof.ndim != 2 or tof.shape[0] < 1 or tof.shape[1] != n_anchor or n_anchor < 1:
+            raise ValueError(f"table_of must be [n_cand >= 1, {n_anchor} anchors], got {tof.shape}")
+        if tof.min() < -1 or tof.max() >= u.shape[0]:
+            raise ValueError(f"table_of names a table outside -1 .. {u.shape[0] - 1}")
+        if (h // TILE) * (w // TILE) * n_anchor >= 1 << 24:
+            raise ValueError(f"{n_anchor} anchors of {(h // TILE) * (w // TILE)} tiles: their product must stay below 2^24")
+        return u, tof, h, w, nby, nbx, delta
+
+    def payload_keyed_best(self, s1_scans, tables: np.ndarray, table_of: np.ndarray, h: int, w: int, delta: float) -> np.ndarray:
+        """wm_payload_keyed_best on host arrays: ``s1_scans[a]`` is anchor a's sigma_1 scan (s1[py][px] float32 [ny_p, nx_p],
+        as payload_sigma1_scan returns it for an [h, w] plane), ``tables`` uint16 [n_tables, nby, nbx], ``table_of`` int32
+        [n_cand, n_anchor] with -1 for an anchor the candidate skips -> best int64 [n_cand, 64, 2]: per candidate and phase
+        (the largest summed score, the row-major index of its first maximum), (-1, -1) where there is none."""
+        n_anchor = len(s1_scans)
+        u, tof, h, w, nby, nbx, delta = self._clip_args(tables, table_of, n_anchor, h, w, delta)
+        pitch = (h // TILE) * (w // TILE)
+        raw = np.zeros((n_anchor, 64, pitch), np.float32)
+        for a, scan in enumerate(s1_scans):
+            for p in range(64):
+                g = np.asarray(scan[p // 8][p % 8], np.float32)
+                want = (max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE)
+                if g.shape != want:
+                    raise ValueError(f"phase {divmod(p, 8)} of scan {a} is {g.shape}, an {h} x {w} plane has {want}")
+                raw[a, p, :g.size] = g.reshape(-1)
+        best = np.zeros((tof.shape[0], 64, 2), np.int64)
+        self._call("wm_payload_keyed_best", _p(raw), n_anchor, _p(u), u.shape[0], _p(tof), tof.shape[0], _p(best), h, w, nby, nbx, delta)
+        return best
+
+    CLIP_TABLE_BYTES = 64 << 20                      # device memory payload_locate_clip spends on the tables of one call
+
+    def payload_locate_clip(self, planes: np.ndarray, tables: np.ndarray, table_of: np.ndarray, delta: float, *,
+                            pick: bool = False, cands_per_call: Optional[int] = None):
+        """The clip rule's steps 1 and 3 on the anchors, uint8 planes [n_anchor, h, w]: their sigma_1 scans stay on the
+        device and only ``best`` int64 [n_cand, 64, 2] comes back (payload_keyed_best).  The candidates go in runs of
+        ``cands_per_call`` (by default as many as keep a run's tables within CLIP_TABLE_BYTES), each with the tables its
+        table_of rows name and no others; the result does not depend on the split.  With ``pick`` -> (best, winner), winner
+        = (g, (py, px), (ty, tx)) by payload.pick_clip, None where nothing took part."""
+        if planes.ndim != 3:
+            raise ValueError("planes must be [n_anchor, h, w]")
+        n_anchor, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        u, tof, h, w, nby, nbx, delta = self._clip_args(tables, table_of, n_anchor, h, w, delta)
+        pitch = (h // TILE) * (w // TILE)
+        n_cand = tof.shape[0]
+        if cands_per_call is None:
+            cands_per_call = max(1, self.CLIP_TABLE_BYTES // max(u[0].nbytes, 1) - n_anchor)
+        step = max(1, int(cands_per_call))
+        best = np.full((n_cand, 64, 2), -1, np.int64)
+        with self._staging() as dev:
+            d_s1 = dev.alloc(n_anchor * 64 * pitch * 4)
+            d_p, = dev.up(np.ascontiguousarray(planes))
+            self._call("wm_payload_sigma1_scan_u8_dev", _vp(d_p), _vp(d_s1), n_anchor, h, w, w, h * w)
+            for c0 in range(0, n_cand, step):
+                rows = tof[c0:c0 + step]
+                ids = np.unique(rows[rows >= 0])
+                if ids.size == 0:                                          # (no marked anchor in the run: every entry stays -1)
+                    continue
+                local = np.where(rows >= 0, np.searchsorted(ids, np.maximum(rows, 0)), -1).astype(np.int32)
+                part = np.zeros((rows.shape[0], 64, 2), np.int64)
+                with self._staging() as run:
+                    d_best = run.alloc(part.nbytes)
+                    d_u, d_of = run.up(np.ascontiguousarray(u[ids]), local)
+                    self._call("wm_payload_keyed_best_dev", _vp(d_s1), n_anchor, _vp(d_u), int(ids.size), _vp(d_of), rows.shape[0],
+                               _vp(d_best), h, w, nby, nbx, delta)
+                    self.d2h(part, d_best)
+                    self.sync()
+                best[c0:c0 + step] = part
+            self.check_status()
+        if not pick:
+            return best
+        win = P.pick_clip(best, P.phase_counts(h, w), (tof >= 0).sum(axis=1))
+        if win is None:
+            return best, None
+        g, p, i = win
+        n_tx = nbx - (w - p % 8) // TILE + 1
+        return best, (g, (p // 8, p % 8), (i // n_tx, i % n_tx))
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

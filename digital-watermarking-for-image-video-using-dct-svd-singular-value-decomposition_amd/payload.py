@@ -211,6 +211,43 @@ def keyed_votes(s1, u, delta: float) -> np.ndarray:
     return np.rint(m * F(VOTE_ONE)).astype(np.int32)
 
 
+# ---- clip resynchronisation (include/wmhip.h): a dithered video's clip, cut in time and cropped ------
+SEARCH_CLIP = "clip"                                # extract_payload_video's ``search`` value
+CLIP_ANCHORS = 4                                    # marked anchor frames a candidate's score adds up, by default
+
+
+def clip_table_of(F: int, fi: int, n_c: int, A: int) -> np.ndarray:
+    """int32 [F - n_c + 1, A]: candidate g = t0 (the clip's first frame is file frame t0) pairs anchor a, clip frame a, with
+    the table of marked frame (t0 + a) // fi where (t0 + a) % fi == 0 and with none (-1) otherwise.  With n_c < fi some
+    candidates have no marked anchor at all."""
+    F, fi, n_c, A = int(F), max(1, int(fi)), int(n_c), int(A)
+    if n_c < 1 or n_c > F or A < 1 or A > n_c:
+        raise ValueError(f"a clip of {n_c} frames with {A} anchors is no clip of a {F}-frame video")
+    t = np.arange(F - n_c + 1, dtype=np.int64)[:, None] + np.arange(A, dtype=np.int64)[None, :]
+    return np.where(t % fi == 0, t // fi, -1).astype(np.int32)
+
+
+def pick_clip(best, counts, marked):
+    """The winner (g, p, index) of wm_payload_keyed_best's ``best`` int64 [n_cand, 64, 2] = (score, index): the largest
+    score / (counts[p] * marked[g]) - counts the phases' window counts (phase_counts), marked[g] the candidate's marked
+    anchors - compared by cross-multiplied Python integers; ties go to the smallest (g, p, index).  Entries of -1, phases
+    without a window and candidates without a marked anchor do not take part.  None when none does."""
+    b = np.asarray(best)
+    n = np.asarray(counts).reshape(-1)
+    m = np.asarray(marked).reshape(-1)
+    if b.ndim != 3 or b.shape[1:] != (64, 2) or n.size != 64 or m.size != b.shape[0]:
+        raise ValueError("best must be [n_cand, 64, 2], counts hold the 64 phases and marked the candidates")
+    win = None
+    for g in range(b.shape[0]):
+        for p in range(64):
+            s, i, d = int(b[g, p, 0]), int(b[g, p, 1]), int(n[p]) * int(m[g])
+            if s < 0 or i < 0 or d <= 0:
+                continue
+            if win is None or s * win[1] > win[0] * d:
+                win = (s, d, g, p, i)
+    return None if win is None else win[2:]
+
+
 # ---- channel code (include/wmhip.h, "channel code"; DESIGN.md section 14): rate 1/2, K = 7, generators 171 / 133 octal --------
 CODES = (None, "k7")                                # what a caller's ``code`` argument may be
 CODE_K7 = 1                                         # the meta's ``code`` member: this code

@@ -590,9 +590,102 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             ctx.close()
 
 
+VIDEO_SEARCHES = (None, P.SEARCH_CLIP)
+
+
+def _count_frames(vid: Y4M) -> int:
+    """the whole frames of an open Y4M's file, by its FRAME lines alone: no frame is read"""
+    size = os.path.getsize(vid.path)
+    step = vid.W * vid.H + 2 * vid.cw * vid.ch
+    n = 0
+    with open(vid.path, "rb") as f:
+        f.readline()
+        while f.readline().startswith(b"FRAME") and f.tell() + step <= size:
+            f.seek(step, os.SEEK_CUR)
+            n += 1
+    return n
+
+
+def _extract_payload_clip(vid: Y4M, data, key: bytes, H: int, W: int, n_bits: int, delta: float, code: int, fi: int, batch: int,
+                          device: int, anchors: int, return_soft: bool):
+    """search="clip" (include/wmhip.h, "clip resynchronisation"): the file is a run of consecutive frames of a video marked
+    with dither=True, every frame cropped to the same rectangle.  n_bits: the bits the tiles carry.  Every refusal comes
+    before the first device call; the frames are read once."""
+    if not M.payload_dither_of(data):
+        raise ValueError("search='clip' reads a payload embedded with dither=True; this one has none")
+    anchors = int(anchors)
+    if anchors < 1:
+        raise ValueError(f"anchors must be at least 1, got {anchors}")
+    h, w, F = vid.H, vid.W, int(data["n_frames"])
+    if h > H or w > W:
+        raise ValueError(f"clip is {w}x{h}, larger than the {W}x{H} the meta was written for: not a crop of it")
+    if h < TILE or w < TILE:
+        raise ValueError(f"clip is {w}x{h}: a crop without a whole 8x8 tile carries nothing")
+    n_c = _count_frames(vid)
+    if n_c > F:
+        raise ValueError(f"clip has {n_c} frames, the marked video had {F}: not a cut of it")
+    if n_c < 1:
+        raise ValueError("clip has no frame")
+    fi = max(1, fi)
+    nby, nbx = H // TILE, W // TILE
+    A = min(n_c, anchors * fi)
+    table_of = P.clip_table_of(F, fi, n_c, A)
+    n_tables = (F + fi - 1) // fi
+    tables = P.dither_tables(nby, nbx, key, [k * fi for k in range(n_tables)]).reshape(n_tables, nby, nbx)
+    tbi = P.payload_map(nby, nbx, key, n_bits)[0].reshape(nby, nbx)
+    frames = iter(vid)
+    held = [y for _, (_, y, _) in zip(range(A), frames)]                   # the anchors, kept for the decode
+    ctx = hostapi.Context(device)
+    try:
+        _, win = ctx.payload_locate_clip(np.stack(held), tables, table_of, delta, pick=True)
+        if win is None:                                                    # (n_c < fi and no candidate with a marked frame among the anchors)
+            out = (b"", False, 0.0, None, None)
+            return out + (np.zeros(n_bits, np.float64),) if return_soft else out
+        t0, (py, px), (ty, tx) = win
+        ny, nx = (h - py) // TILE, (w - px) // TILE
+        votes = np.zeros((ny, nx), np.int64)
+        n_marked = 0
+
+        def decode(pend):
+            ys = np.stack([y[py:py + TILE * ny, px:px + TILE * nx] for _, y in pend])
+            dz = np.stack([tables[(t0 + i) // fi, ty:ty + ny, tx:tx + nx].reshape(-1) for i, _ in pend])
+            m = ctx.payload_metric(ys, delta, dither=dz)
+            np.add(votes, np.rint(m * np.float32(P.VOTE_ONE)).astype(np.int64).sum(axis=0), out=votes)
+
+        pend = []
+        for i, y in enumerate(_chain_frames(held, frames)):
+            if (t0 + i) % fi == 0:
+                pend.append((i, y)); n_marked += 1
+                if len(pend) >= batch:
+                    decode(pend); pend = []
+        if pend:
+            decode(pend)
+        soft, count = P.soft_of_votes(votes, tbi[ty:ty + ny, tx:tx + nx], n_bits)
+        read = ctx.payload_decode(P.quantise_soft(soft))[0] if code else soft < 0
+    finally:
+        ctx.close()
+    payload, valid = P.payload_unframe(read)
+    out = (payload, bool(valid), P.sync_confidence(soft, count * max(n_marked, 1)), (TILE * ty - py, TILE * tx - px), int(t0))
+    return out + (soft,) if return_soft else out
+
+
+def _chain_frames(held, frames):
+    """the anchors already read, then the luma of the frames still in the file"""
+    yield from held
+    for _, y, _ in frames:
+        yield y
+
+
 def extract_payload_video(stego_video_path: str, metadata_path: str, *, password: str = "", batch: int = 32,
-                          device: int = 0, return_soft: bool = False):
-    """-> (data, valid, confidence) from the marked frames' luma; with ``return_soft`` the summed soft vector follows."""
+                          device: int = 0, return_soft: bool = False, search=None, anchors: int = P.CLIP_ANCHORS):
+    """-> (data, valid, confidence) from the marked frames' luma; with ``return_soft`` the summed soft vector follows.
+    ``search="clip"``: the file may be any run of consecutive frames of the marked video, every frame cropped to the same
+    axis-aligned rectangle (a payload embedded with dither=True).  The first frame, the tile grid and the crop's place are
+    searched for on the device over the first ``anchors`` marked frames' worth of the clip, and the result is (data, valid,
+    confidence, origin, first_frame): origin = (y0, x0) of the crop in the marked frames, first_frame the clip's first frame
+    in the marked file - meaningful where valid is True ("Clip resynchronisation")."""
+    if search not in VIDEO_SEARCHES:
+        raise ValueError(f"search must be None or 'clip', got {search!r}")
     M.require_password(password, "extract")
     data = M.load_payload_meta(metadata_path)
     M.require_payload(data)
@@ -607,6 +700,12 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     n_bits = P.coded_bits(n_bits) if code else n_bits                      # from here on: the bits the tiles carry
     fi = int(data["frame_interval"])
     batch = max(1, int(batch))
+    if search == P.SEARCH_CLIP:
+        vid = Y4M(stego_video_path)
+        try:
+            return _extract_payload_clip(vid, data, key, H, W, n_bits, delta, code, fi, batch, device, anchors, return_soft)
+        finally:
+            vid.close()
     _, order, offs = P.payload_map(H // TILE, W // TILE, key, n_bits)
     dither = M.payload_dither_of(data)
     vid = Y4M(stego_video_path)

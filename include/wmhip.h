@@ -418,6 +418,48 @@ int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* ti
 int wm_payload_keyed_scores(wm_ctx* ctx, const float* s1, const uint16_t* tile_dither, int64_t* scores, int h, int w, int nby,
                             int nbx, float delta);
 
+/* ---- Blind payload, clip resynchronisation: a dithered video's clip, cut in time and cropped in space --
+ * Every marked frame of a video has a dither table keyed by its index in the file, so a clip that lost leading frames (or
+ * columns) reads every tile on the wrong lattice.  No surviving pixel is damaged: the keyed score above finds grid phase
+ * and placement, and summed over several clip frames it finds the first frame as well - and with more windows behind every
+ * candidate it resolves crops the single-plane search cannot.  The rule ("Clip resynchronisation"); all
+ * arithmetic past the metric is integer.
+ *   inputs   the clip is n_c luma frames of h x w; the meta holds shape (H, W), n_frames F, frame_interval fi, delta and
+ *            dither = 1.  Clip frame i is file frame t0 + i.  Unknown: t0 in 0 .. F - n_c, the phase p = 8 py + px and the
+ *            placement (ty, tx).
+ *   1 scan    step 1 above on the first A = min(n_c, anchors fi) clip frames, the anchors.
+ *   2 tables  tables[k] = the dither table of file frame k fi, for the marked frames k < ceil(F / fi).  Candidate g = t0
+ *             pairs anchor a with table (t0 + a) / fi where (t0 + a) % fi == 0 and with none (-1) otherwise:
+ *             table_of[n_cand][A], int32, host work.  The device knows nothing of frame intervals.
+ *   3 scores  score[g][p][ty][tx] = sum over the anchors a with table_of[g][a] >= 0 of step 2's score of anchor a's scan
+ *             under tables[table_of[g][a]] (int64).  Only best[g][p] = (the largest score of the phase, the row-major index
+ *             ty n_tx_p + tx of its FIRST maximum) leaves the device; a phase without a window and a candidate without a
+ *             marked anchor give (-1, -1).
+ *   4 winner  the largest score / (ny_p nx_p m_g), m_g the candidate's marked anchors, compared by cross-multiplied
+ *             integers (on the host); ties go to the smallest (g, p, index); entries of -1 do not take part.
+ *   5 decode  every clip frame i with (t0 + i) % fi == 0: the metric of the view [py : py + 8 ny, px : px + 8 nx] under the
+ *             rows [ty : ty + ny, tx : tx + nx] of the table of file frame t0 + i, vote = rint(m 32768), the frames' votes
+ *             added (int64), soft[j] their sums per bit of the tile-to-bit map's window as in step 4 above;
+ *             origin = (8 ty - py, 8 tx - px), first_frame = t0.
+ * Only the top candidate is tried; the frame's length header and CRC say whether it was right.
+ *
+ * Step 3 in one call:
+ *   s1        the anchors' scans, [n_anchor][64][(h / 8) (w / 8)] float32 (wm_payload_sigma1_scan_u8 of n_anchor planes)
+ *   tables    [n_tables][nby nbx] uint16
+ *   table_of  [n_cand][n_anchor] int32, -1 = skip the anchor
+ *   best      [n_cand][64][2] int64 (out): (score, index) per candidate and phase
+ * WM_ERR_BADARG: everything wm_payload_keyed_scores_dev refuses; n_anchor, n_tables or n_cand < 1; (h / 8) (w / 8) n_anchor
+ * >= 2^24 (a score stays below 2^39: the reduction packs score 2^24 + (2^24 - 1 - index) into one int64, and the 2^24
+ * placements a phase bound the index); s1, tables, table_of or best NULL or misaligned (the _dev form); a table_of entry
+ * < -1 or >= n_tables (the host form, which reads it; the _dev form cannot, and its kernel skips an entry outside
+ * 0 .. n_tables - 1 as it skips -1).  The reduction is a wave-level integer max and one 64-bit integer atomic max per wave:
+ * the keys of a (candidate, phase) are distinct, so the result does not depend on the order of arrival.  The two lane
+ * mappings of wm_payload_keyed_scores_dev, chosen by its rule, give the same bits. */
+int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const uint16_t* tables, int n_tables, const int32_t* table_of,
+                              int n_cand, int64_t* best, int h, int w, int nby, int nbx, float delta);
+int wm_payload_keyed_best(wm_ctx* ctx, const float* s1, int n_anchor, const uint16_t* tables, int n_tables, const int32_t* table_of,
+                          int n_cand, int64_t* best, int h, int w, int nby, int nbx, float delta);
+
 /* --------------------------------------------------------------------------
  * Channel code of the blind payload (optional; the meta's ``code`` member = 1): the industry-standard rate-1/2 convolutional
  * code of constraint length 7, generators 171 and 133 octal, with a zero tail, decoded by a soft-decision Viterbi decoder on
