@@ -197,6 +197,49 @@ __device__ __forceinline__ void store_mat_f32(float* __restrict__ p, const float
   for (int r = 0; r < 8; ++r) store_row8_f32<true>(p + r * 8, m[r]);
 }
 
+// The same pair of matrices for the 64 consecutive tiles of a tile group, staged in LDS for a workgroup whose waves all
+// work on THAT group (k_extract_tiles<SH>: one wave per plane, the planes share the factors).  The group's matrices are
+// one contiguous block of 16 KB per array.  load_mat_f32 reads such a block 16 B per lane at a 256 B stride - 64 cache lines
+// per instruction, an eighth of each used - once per wave, and the wave then waits for it with nothing else to do.  Here
+// the workgroup's threads read both blocks once, consecutive threads consecutive 16 B (an instruction covers 8 whole
+// lines), and leave them in LDS at a pitch of 16 + 1 float4 per tile; every wave then picks up its lanes' own tiles with
+// ds_read_b128 (the pitch is odd: the 16 lanes of a read group start on 16 different banks of 4).  The fetch is issued
+// before the wave's Jacobi iteration, so its latency is spent there, and the factors cross the vector L1 once per
+// workgroup, not once per wave.  `last` is the last tile of the group that exists (63, less in a plane's last group): the
+// loads clamp to it, so nothing behind the arrays is read.
+constexpr int SH_WAVES = 4;                                      // waves (planes) of a workgroup that shares a staged group
+constexpr int STAGE_PITCH4 = 17;                                 // float4 per tile and matrix in LDS
+constexpr int STAGE_MAT4 = WAVE * STAGE_PITCH4;                  // one array's block
+constexpr int STAGE_LOADS = 2 * WAVE * 16 / (SH_WAVES * WAVE);   // float4 per thread: 2 blocks of 64 x 16
+typedef float stage4 __attribute__((ext_vector_type(4)));       // (a native vector: arrays of it stay in registers)
+// thread `tid` of the SH_WAVES * 64: its pieces of both blocks, global -> registers ...
+__device__ __forceinline__ void stage_fetch(const float* __restrict__ ublk, const float* __restrict__ vblk, const int last,
+                                            const int tid, stage4 (&raw)[STAGE_LOADS]) {
+#pragma unroll
+  for (int i = 0; i < STAGE_LOADS; ++i) {
+    const int q = i * (SH_WAVES * WAVE) + tid, r = q & (WAVE * 16 - 1);      // float4 q of the 2 x 1024; r within its block
+    const float* blk = (q < WAVE * 16) ? ublk : vblk;                        // (uniform per i: a block is STAGE_LOADS / 2 rounds)
+    raw[i] = *reinterpret_cast<const stage4*>(blk + (size_t)min(r >> 4, last) * 64 + (r & 15) * 4);
+  }
+}
+// ... and registers -> LDS (a __syncthreads() of the workgroup goes between this and stage_read)
+__device__ __forceinline__ void stage_put(stage4* __restrict__ lds, const int tid, const stage4 (&raw)[STAGE_LOADS]) {
+#pragma unroll
+  for (int i = 0; i < STAGE_LOADS; ++i) {
+    const int q = i * (SH_WAVES * WAVE) + tid, r = q & (WAVE * 16 - 1);
+    lds[(q < WAVE * 16 ? 0 : STAGE_MAT4) + (r >> 4) * STAGE_PITCH4 + (r & 15)] = raw[i];
+  }
+}
+// the lane's own tile's matrix out of one array's block
+__device__ __forceinline__ void stage_read(const stage4* __restrict__ blk, const int lane, float (&m)[8][8]) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const stage4 v = blk[lane * STAGE_PITCH4 + k];
+    m[k / 2][(k & 1) * 4 + 0] = v.x; m[k / 2][(k & 1) * 4 + 1] = v.y;
+    m[k / 2][(k & 1) * 4 + 2] = v.z; m[k / 2][(k & 1) * 4 + 3] = v.w;
+  }
+}
+
 struct Geom {
   int nbx;          // tiles per tile-row
   int n_tiles;      // tiles per plane
@@ -234,16 +277,6 @@ struct GroupPlane { unsigned grp; size_t plane; };
 __device__ __forceinline__ GroupPlane group_plane_planefast(const unsigned n_planes) {
   const unsigned b = blockIdx.x, x = b % N_XCD, k = b / N_XCD;
   return {x + N_XCD * (k / n_planes), k % n_planes};
-}
-__device__ __forceinline__ bool tile_coords_planefast(const Geom& g, const unsigned n_planes, int& t, int& ty,
-                                                      int& tx, size_t& plane) {
-  const GroupPlane gp = group_plane_planefast(n_planes);
-  plane = gp.plane;
-  t = (int)(gp.grp * WAVE + threadIdx.x);
-  if (t >= g.n_tiles) return false;
-  ty = t / g.nbx;
-  tx = t - ty * g.nbx;
-  return true;
 }
 inline dim3 tile_grid_planefast(const Geom& g, int n_planes) {
   const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE;
@@ -677,25 +710,39 @@ __global__ __launch_bounds__(WAVE, 2) void k_svd_tiles(const float* __restrict__
 // of a partial wave recompute the last tile (every lane takes part in the reduction) and store nothing.
 // MASK: the texture-masked rule (wm_tile_math.h, mask_keep) folded into keep[] - 1 / g and the carried test from the sc
 // that is in registers anyway.  A template flag: the unmasked forms compile to what they were.
+// SH: the planes SHARE the factors (uv_plane_stride 0, the frames of a clip).  A workgroup is then SH_WAVES waves, wave w
+// taking plane SH_WAVES * slot + w of one tile group, and the group's factors reach the waves through LDS (stage_fetch ..
+// stage_read above) instead of once per wave from global memory.  The walk is the plane-fastest one over the plane SLOTS.
+// A wave whose plane does not exist (n_planes % SH_WAVES) helps with the fetch and leaves.  Each wave still works on the
+// 64 tiles of one plane, in the same lanes: its arithmetic, the Jacobi stream's wave-wide tests included, is that of the
+// one-wave form.  Without SH (one plane, or factors per plane) the workgroup is one wave and loads its own factors.
 struct MaskParams { float lo, hi, cut; };
-template <bool ALIGNED, bool VECF, bool PX, bool MM, bool MASK>
-__global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
+template <bool ALIGNED, bool VECF, bool PX, bool MM, bool MASK, bool SH>
+__global__ __launch_bounds__(SH ? SH_WAVES * WAVE : WAVE, 3) void k_extract_tiles(
     const uint8_t* __restrict__ stego, const float* __restrict__ sigma_c,
     const float* __restrict__ Uw, const float* __restrict__ Vwt, float* __restrict__ out,
     const Geom g, const unsigned n_planes, const size_t uv_plane_stride, const float inv_alpha, const int K,
     int* __restrict__ status, unsigned* __restrict__ mm, const MaskParams mk) {
-  int t, ty, tx;
-  size_t plane;
+  __shared__ stage4 stage[SH ? 2 * STAGE_MAT4 : 1];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const GroupPlane gp = group_plane_planefast(SH ? (n_planes + SH_WAVES - 1) / SH_WAVES : n_planes);
+  const size_t plane = SH ? gp.plane * SH_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE) : gp.plane;
+  if ((size_t)gp.grp * WAVE >= (size_t)g.n_tiles) return;                 // uniform in the workgroup: a padding group
+  if (SH) {
+    stage4 fetched[STAGE_LOADS];
+    stage_fetch(Uw + (size_t)gp.grp * WAVE * 64, Vwt + (size_t)gp.grp * WAVE * 64,
+                min((int)WAVE, g.n_tiles - (int)(gp.grp * WAVE)) - 1, threadIdx.x, fetched);
+    stage_put(stage, threadIdx.x, fetched);
+    __syncthreads();                                                     // the only one: the waves part here
+    if (plane >= n_planes) return;
+  }
+  int t = (int)(gp.grp * WAVE) + lane;
   bool valid = true;
   if (MM) {
-    const GroupPlane gp = group_plane_planefast(n_planes);
-    plane = gp.plane;
-    if ((size_t)gp.grp * WAVE >= (size_t)g.n_tiles) return;               // wave-uniform: a padding group
-    t = (int)(gp.grp * WAVE + threadIdx.x);
     valid = t < g.n_tiles;
     t = valid ? t : g.n_tiles - 1;
-    ty = t / g.nbx; tx = t - ty * g.nbx;
-  } else if (!tile_coords_planefast(g, n_planes, t, ty, tx, plane)) return;
+  } else if (t >= g.n_tiles) return;
+  const int ty = t / g.nbx, tx = t - ty * g.nbx;
   wm::RawTile raw;
   float a[8][8], s[8], sc[8], keep[8];
   load_raw<ALIGNED>(STRIDED_TILE(stego, g, plane, ty, tx), g.row_stride, raw);
@@ -707,9 +754,14 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
     for (int i = 0; i < 8; ++i) keep[i] = (i < K) ? 1.0f : 0.0f;
   }
   float uw[8][8], vwt[8][8];
-  const size_t mi = (plane * uv_plane_stride + (size_t)t) * 64;
-  load_mat_f32(Uw + mi, uw);
-  load_mat_f32(Vwt + mi, vwt);
+  if (SH) {
+    stage_read(stage, lane, uw);
+    stage_read(stage + STAGE_MAT4, lane, vwt);
+  } else {
+    const size_t mi = (plane * uv_plane_stride + (size_t)t) * 64;
+    load_mat_f32(Uw + mi, uw);
+    load_mat_f32(Vwt + mi, vwt);
+  }
   if (PX) wm::extract_tile_px(s, sc, inv_alpha, keep, uw, vwt, a);
   else wm::extract_tile(s, sc, inv_alpha, keep, uw, vwt, a);
   float* o = DENSE_TILE(out, g, plane, ty, tx);
@@ -726,9 +778,8 @@ __global__ __launch_bounds__(WAVE, 3) void k_extract_tiles(
     unsigned ulo = f2ord(lo), uhi = f2ord(hi);
 #pragma unroll
     for (int o_ = 32; o_ > 0; o_ >>= 1) { ulo = min(ulo, (unsigned)__shfl_down(ulo, o_, WAVE)); uhi = max(uhi, (unsigned)__shfl_down(uhi, o_, WAVE)); }
-    if (threadIdx.x == 0) {
-      // (the group is asked for again, not kept from above: scalar arithmetic, and nothing to hold across the tile's work)
-      const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE, pair = plane * groups + group_plane_planefast(n_planes).grp;
+    if (lane == 0) {
+      const size_t groups = ((size_t)g.n_tiles + WAVE - 1) / WAVE, pair = plane * groups + gp.grp;
       mm[2 * pair] = ulo; mm[2 * pair + 1] = uhi;
     }
   }
@@ -2029,12 +2080,14 @@ static int extract_tiles_dev(wm_ctx* ctx, const uint8_t* stego, const float* sig
   const bool vf = f32_vec_ok(out, (size_t)W, g.HW);
   if ((((size_t)g.n_tiles + WAVE - 1) / WAVE + N_XCD) * (size_t)n_planes > 0x7fffffffull)
     return set_err(WM_ERR_BADARG, "more than 2^31 tile groups in one call");
-  const dim3 grid = tile_grid_planefast(g, n_planes), block(WAVE);
+  // planes that share their factors go SH_WAVES to a workgroup, which stages a tile group's factors once (k_extract_tiles<SH>)
+  const bool sh = uv_plane_stride == 0 && n_planes >= 2;
+  const dim3 grid = tile_grid_planefast(g, sh ? (n_planes + SH_WAVES - 1) / SH_WAVES : n_planes), block(sh ? SH_WAVES * WAVE : WAVE);
   const MaskParams mk = mask ? *mask : MaskParams{0.0f, 1.0f, 1.0f};
-  with_bools([&](auto P, auto A, auto V, auto M, auto T) {
-    hipLaunchKernelGGL((k_extract_tiles<A.value, V.value, P.value, M.value, T.value>), grid, block, 0, ctx->stream, stego, sigma_c,
-                       Uw, Vwt, out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm, mk);
-  }, px, al, vf, mm != nullptr, mask != nullptr);
+  with_bools([&](auto P, auto A, auto V, auto M, auto T, auto S) {
+    hipLaunchKernelGGL((k_extract_tiles<A.value, V.value, P.value, M.value, T.value, S.value>), grid, block, 0, ctx->stream, stego,
+                       sigma_c, Uw, Vwt, out, g, (unsigned)n_planes, uv_plane_stride, inv_alpha, K, ctx->d_status, mm, mk);
+  }, px, al, vf, mm != nullptr, mask != nullptr, sh);
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
