@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import chroma_refs as cr
+import test_loop_trips as lt
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +89,54 @@ def test_codec_equals_the_numpy_statement(gpu_ctx, H, W, sub):
     assert np.array_equal(_decode_dev(gpu_ctx, frames, H, W, sub, shift=1), cr.decode_frames(frames, H, W, sub))
     planes = _planes_inputs(2, H, W, sub, rng)[0]
     assert np.array_equal(_encode_dev(gpu_ctx, planes, sub, shift=3), cr.encode_frames(planes, sub))
+
+
+GUARD = 4096                       # bytes of 0xA5 the test puts behind a second-trip output, in the same allocation
+
+
+def _second_trip_both_ways(ctx, frames, H, W, sub, what):
+    """decode and encode through the *_dev entry points, bit-equal to chroma_refs, the guard behind each output untouched"""
+    n, fsz = frames.shape
+    assert fsz == cr.frame_bytes(H, W, sub)
+    want = cr.decode_frames(frames, H, W, sub)
+    planes = want if n > 1 else np.random.default_rng(W).integers(0, 256, (n, 3, H, W), dtype=np.uint8)
+    enc = cr.encode_frames(planes, sub)
+    for k in range(-2, 0) if n > 1 else ():                                # the second trip's frames: unlike every other, in and out
+        for a in (frames, want.reshape(n, -1), enc):
+            assert (a[k] != a).any(axis=1).sum() == n - 1
+    dev = _Dev(ctx, frames, want.nbytes + GUARD, fill=0xA5)
+    with dev as (d_f, d_p):
+        ctx.yuv_frames_to_bgr_planes_u8_dev(d_f, d_p, n, H, W, sub, fsz)
+        got = dev.result()
+    bad = np.flatnonzero(got[:want.size] != want.reshape(-1))
+    print(f"{what} decode: {bad.size} of {want.size} bytes differ (first {bad[:3].tolist()}, last {bad[-3:].tolist()})")
+    assert bad.size == 0 and np.all(got[want.size:] == 0xA5)
+    dev = _Dev(ctx, planes, enc.nbytes + GUARD, fill=0xA5)
+    with dev as (d_p, d_f):
+        ctx.bgr_planes_to_yuv_frames_u8_dev(d_p, d_f, n, H, W, sub, fsz)
+        got = dev.result()
+    bad = np.flatnonzero(got[:enc.size] != enc.reshape(-1))
+    print(f"{what} encode: {bad.size} of {enc.size} bytes differ (first {bad[:3].tolist()}, last {bad[-3:].tolist()})")
+    assert bad.size == 0 and np.all(got[enc.size:] == 0xA5)
+    ctx.check_status()
+
+
+@pytest.mark.parametrize("H,W,sub,vec", lt.CODEC_ITEM_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_codec_item_loop_second_trip(gpu_ctx, H, W, sub, vec):
+    """k_frame_codec's item loop on grid_for's 2048 x 256 threads: one frame of more than 524 288 items (tests/test_loop_trips.py),
+    on the byte-wise path (odd widths) at 4:4:4 and 4:2:0 and on the 16-byte path"""
+    frames = np.random.default_rng(H).integers(0, 256, (1, cr.frame_bytes(H, W, sub)), dtype=np.uint8)
+    _second_trip_both_ways(gpu_ctx, frames, H, W, sub, f"{H}x{W} {sub} {'16-byte' if vec else 'byte-wise'}")
+
+
+@pytest.mark.parametrize("n,H,W,sub", lt.CODEC_FRAME_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_codec_frame_loop_second_trip(gpu_ctx, n, H, W, sub):
+    """k_frame_codec's frame loop (fr += gridDim.y on at most 65 535 rows of workgroups): 65 537 frames of random bytes.  The
+    last two - the second trip - differ from every other frame on both sides of both directions (asserted in the helper; the
+    seeds are ones at which the 3-byte frames do), so a frame index that wrapped shows."""
+    frames = np.random.default_rng(H).integers(0, 256, (n, cr.frame_bytes(H, W, sub)), dtype=np.uint8)
+    assert n - 2 == lt.CODEC_FRAME_CAP
+    _second_trip_both_ways(gpu_ctx, frames, H, W, sub, f"{n} frames of {H}x{W} {sub}")
 
 
 @pytest.mark.parametrize("sub", cr.SUBS, ids=lambda s: "%dx%d" % s)

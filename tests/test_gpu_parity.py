@@ -5,6 +5,7 @@ Tolerances (BASELINE.json north_star): singular values within 1e-4 relative
 import numpy as np
 import pytest
 
+import test_loop_trips as lt
 from oracle import wm_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -638,6 +639,34 @@ def test_extract_sum_over_planes(gpu_ctx):
     want = (each[0] + each[1]) + each[2]                  # same order, same float32 additions
     assert tot.shape == (H, W) and np.array_equal(tot, want)
     assert np.array_equal(gpu_ctx.extract_tiles(st[:1], sc[:1], U, Vt, alpha, sum_planes=True), each[0])
+
+
+@pytest.mark.parametrize("H,W", lt.SUM_SHAPES, ids=lambda v: str(v))
+def test_extract_sum_over_planes_past_the_grid(gpu_ctx, H, W):
+    """k_sum_planes on a grid capped at 4096 x 256 threads: planes of more than 1 048 576 px (tests/test_loop_trips.py), so that
+    its stride loop goes round twice; the second shape is ragged (a zero border).  Bit for bit the planes added in ascending
+    order, as test_extract_sum_over_planes has it at 64 x 96.  No embed: a random stego, sigma_c = the device's own sigma minus
+    a random non-negative row, factors from svd_tiles of a random plane - and once more under the masked rule of
+    tests/test_gpu_extract_staging.py (0 < g < 1 on noise tiles, every tile carried)."""
+    import mask_refs as mr
+    from test_gpu_extract_staging import MASK
+    alpha, n = 0.15, lt.SUM_PLANES
+    rng = np.random.default_rng(H + W)
+    st = rng.integers(0, 256, (n, H, W), dtype=np.uint8)
+    sc = gpu_ctx.sigma_tiles(st) - np.float32(alpha) * rng.uniform(0, 255, (n, H // 8, W // 8, 8)).astype(np.float32)
+    U, _, Vt = gpu_ctx.svd_tiles(rng.uniform(0, 255, (H, W)).astype(np.float32))
+    g = mr.gain(sc, MASK[0], MASK[1])[0]
+    assert g.min() > 2 * MASK[2] and g.max() < 1
+    for mask in (None, MASK):
+        each = gpu_ctx.extract_tiles(st, sc, U, Vt, alpha, mask=mask)
+        tot = gpu_ctx.extract_tiles(st, sc, U, Vt, alpha, sum_planes=True, mask=mask)
+        want = (each[0] + each[1]) + each[2]                  # same order, same float32 additions
+        assert each.shape == (n, H, W) and H * W > lt.SUM_TRIP and np.abs(each).max() > 1
+        bad = np.flatnonzero(tot.reshape(-1) != want.reshape(-1))
+        print(f"{H}x{W} mask={mask}: {bad.size} of {H * W} sums differ (first {bad[:3].tolist()}, last {bad[-3:].tolist()})")
+        assert tot.shape == (H, W) and np.array_equal(tot, want)
+        assert not tot[H // 8 * 8:].any() and not tot[:, W // 8 * 8:].any()
+    gpu_ctx.check_status()
 
 
 def test_generated_jacobi_stream_against_the_cpp_form_on_the_gpu(hostapi):

@@ -12,6 +12,7 @@ import __graft_entry__ as ge
 import payload_clip_refs as cl
 import payload_keyed_sync_refs as kr
 import payload_sync_refs as sr
+import test_loop_trips as lt
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +24,11 @@ WIDE = (3, 5, 118, 180)                                                    # nx 
 SMALL = (40, 64, 48, 64)                                                   # nx = 8, 17 placements across: a lane per placement
 NBY, NBX = 16, 24
 TIES = [(24, 40, 5, 7), (16, 16, 3, 70), (24, 72, 5, 10)]                  # (h, w, nby, nbx)
+# the second trips of the shared loop bodies (tests/test_loop_trips.py): a lane per placement with a group of 8 windows and a tail,
+# a lane per window with nx = 65
+TRIPS = list(lt.CLIP_TRIP_SHAPES.values())
+TRIP_IDS = list(lt.CLIP_TRIP_SHAPES)
+TIES += TRIPS
 
 
 def _lanes_over_windows(w, nbx):
@@ -34,7 +40,9 @@ def _lanes_over_windows(w, nbx):
 def test_the_shapes_take_both_lane_mappings():
     assert _lanes_over_windows(WIDE[3], NBX) and not _lanes_over_windows(SMALL[3], NBX)
     assert not _lanes_over_windows(8, NBX) and not _lanes_over_windows(9, NBX)      # the no-window planes
-    assert [_lanes_over_windows(w, nbx) for _, w, _, nbx in TIES] == [False, False, True]
+    assert [_lanes_over_windows(w, nbx) for _, w, _, nbx in TIES] == [False, False, True, False, True]
+    assert [_lanes_over_windows(w, nbx) for _, w, _, nbx in TRIPS] == [False, True]
+    assert not _lanes_over_windows(lt.CLIP_CHUNK_SHAPE[1], lt.CLIP_CHUNK_SHAPE[3])
 
 
 def _tables(n):
@@ -108,7 +116,7 @@ def test_a_phase_without_a_window_gives_minus_one(gpu_ctx, shape):
 
 
 # ---- ties -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("h,w,nby,nbx", TIES, ids=["placements-3-across", "placements-two-waves", "windows-2-across"])
+@pytest.mark.parametrize("h,w,nby,nbx", TIES, ids=["placements-3-across", "placements-two-waves", "windows-2-across"] + TRIP_IDS)
 def test_equal_scores_give_index_zero(gpu_ctx, h, w, nby, nbx):
     """a constant table: every placement of a phase reads the same lattices and scores alike - the first index must win,
     whichever wave or lane arrives first"""
@@ -151,6 +159,70 @@ def test_best_at_delta_24_agrees_within_one_unit_per_window_and_anchor(gpu_ctx, 
         print(f"{crop}: worst |score_dev - score_ref| {int(worst.max())}, bound there {int(bound.reshape(-1)[worst.argmax()])}")
         assert np.all(worst <= bound)
         assert np.array_equal(got[..., 1] < 0, want[..., 1] < 0)
+
+
+# ---- second trips: the loops inside a placement, and the candidates past one launch -----------------------------------
+def _synthetic_scan(h, w, seed):
+    rng = np.random.default_rng(seed)
+    return [[rng.uniform(0.0, 2040.0, sr.phase_shape(h, w, py, px)).astype(F) for px in range(8)] for py in range(8)]
+
+
+@pytest.mark.parametrize("h,w,nby,nbx", TRIPS, ids=TRIP_IDS)
+def test_second_trips_of_the_window_loops_are_bit_equal_to_the_restatement(gpu_ctx, h, w, nby, nbx):
+    """two anchors' synthetic scans, the rows of TOF, random, all-0 and all-65535 tables at delta 16 (a power of two: bit for bit,
+    as test_best_of_the_device_scans_is_bit_equal_to_the_restatement has it)"""
+    rng = np.random.default_rng(h * w + nbx)
+    scans = [_synthetic_scan(h, w, h * 100 + w + a) for a in range(2)]
+    U = np.stack([rng.integers(0, 65536, (nby, nbx), dtype=np.uint16), rng.integers(0, 65536, (nby, nbx), dtype=np.uint16),
+                  np.zeros((nby, nbx), np.uint16), np.full((nby, nbx), 65535, np.uint16)])
+    got = gpu_ctx.payload_keyed_best(scans, U, TOF, h, w, 16.0)
+    assert np.array_equal(got, cl.best_ref(scans, list(U), TOF, 16.0))
+    gpu_ctx.check_status()
+
+
+@pytest.fixture(scope="module")
+def chunked():
+    """(scan, tables, table_of [2047, 1], best_ref of all of them): made once; a candidate's row does not depend on the others, so
+    the first n rows are the reference of a call with n candidates"""
+    h, w, nby, nbx = lt.CLIP_CHUNK_SHAPE
+    rng = np.random.default_rng(lt.CLIP_CHUNK)
+    scan = _synthetic_scan(h, w, 7)
+    U = rng.integers(0, 65536, (lt.CLIP_CHUNK_TABLES, nby, nbx), dtype=np.uint16)
+    tof = rng.integers(-1, lt.CLIP_CHUNK_TABLES, (max(lt.CLIP_CHUNK_CANDS), 1)).astype(np.int32)
+    tof[lt.CLIP_CHUNK - 1:lt.CLIP_CHUNK + 2, 0] = (0, 1, 2)                  # candidates 1022, 1023, 1024: three different tables
+    want = cl.best_ref([scan], list(U), tof, 16.0)
+    assert len({want[c].tobytes() for c in range(lt.CLIP_CHUNK - 1, lt.CLIP_CHUNK + 2)}) == 3   # a shift by one row shows
+    assert set(tof.reshape(-1).tolist()) == set(range(-1, lt.CLIP_CHUNK_TABLES))
+    want.setflags(write=False); tof.setflags(write=False)
+    return scan, U, tof, want
+
+
+@pytest.mark.parametrize("n_cand", lt.CLIP_CHUNK_CANDS)
+def test_candidates_past_one_launch(gpu_ctx, chunked, n_cand):
+    """wm_payload_keyed_best_dev hands its candidates to the kernel 1023 at a launch: one launch, two (the second of one and of
+    two candidates) and three, bit-equal to the restatement"""
+    scan, U, tof, want = chunked
+    h, w, _, _ = lt.CLIP_CHUNK_SHAPE
+    got = gpu_ctx.payload_keyed_best([scan], U, np.ascontiguousarray(tof[:n_cand]), h, w, 16.0)
+    bad = np.flatnonzero((got != want[:n_cand]).any(axis=(1, 2)))
+    print(f"{n_cand} candidates: {bad.size} rows differ (first {bad[:3].tolist()}, last {bad[-3:].tolist()})")
+    assert got.shape == (n_cand, 64, 2) and bad.size == 0
+    gpu_ctx.check_status()
+
+
+def test_locate_clip_past_one_launch_does_not_depend_on_its_split(gpu_ctx, chunked):
+    """Context.payload_locate_clip with its default split passes all 1025 candidates to one call of the library, whose own loop
+    splits them; runs of 100 never reach that loop"""
+    _, U, tof, _ = chunked
+    h, w, _, _ = lt.CLIP_CHUNK_SHAPE
+    plane = np.random.default_rng(3).integers(0, 256, (1, h, w), dtype=np.uint8)
+    rows = np.ascontiguousarray(tof[:lt.CLIP_LOCATE_CANDS])
+    one = gpu_ctx.payload_locate_clip(plane, U, rows, 16.0)
+    part = gpu_ctx.payload_locate_clip(plane, U, rows, 16.0, cands_per_call=100)
+    assert one.shape == (lt.CLIP_LOCATE_CANDS, 64, 2) and np.array_equal(one, part)
+    marked = rows[:, 0] >= 0
+    assert np.all(one[marked, 0, 0] >= 0) and np.all(one[~marked] == -1)
+    assert np.array_equal(one, gpu_ctx.payload_keyed_best([gpu_ctx.payload_sigma1_scan(plane[0])], U, rows, h, w, 16.0))
 
 
 # ---- the resident chain -----------------------------------------------------------------------------------------------

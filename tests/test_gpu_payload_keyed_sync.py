@@ -11,6 +11,7 @@ import pytest
 import __graft_entry__ as ge
 import payload_keyed_sync_refs as kr
 import payload_refs as pr
+import test_loop_trips as lt
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +125,10 @@ def test_the_shapes_take_both_lane_mappings():
     assert _lanes_over_windows(CASE_A[3], 24) and not _lanes_over_windows(NARROW[3], 24)
     took = {name: _lanes_over_windows(w, nbx) for name, (h, w, (nby, nbx)) in EDGES.items()}
     assert took == {"full-width": True, "8-rows": False, "65-across": False, "129-across": False, "uncropped": True,
-                    "threshold-windows": True, "threshold-lanes": False}
+                    "threshold-windows": True, "threshold-lanes": False,
+                    "group-and-tail-at-px0": False, "group-and-tail": False, "tail-of-4-and-3": False, "two-groups": False,
+                    "two-groups-and-tail": False,
+                    "one-full-trip": True, "lane-0-twice": True, "lane-0-twice-every-phase": True, "three-trips": True}
 
 
 @pytest.mark.parametrize("delta", [8.0, 16.0, 512.0])
@@ -173,6 +177,10 @@ EDGES = {
     "threshold-windows": (16, 64, (3, 11)),    # 8 windows and 4 placements across: the lanes just go over the windows ...
     "threshold-lanes": (16, 56, (3, 11)),      # ... 7 and 5: just not
 }
+# the second trips (tests/test_loop_trips.py holds them against STEP = 8 and the wave's 64 lanes): keyed_placement_sum's groups of
+# 8 windows with a tail behind them, keyed_windows_share's c += 64; three window rows, so that sp += nx and up += nbx count
+EDGES.update(lt.KEYED_PLACEMENT)
+EDGES.update(lt.KEYED_WINDOWS)
 
 
 @pytest.mark.parametrize("name", list(EDGES))

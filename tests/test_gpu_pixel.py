@@ -3,12 +3,16 @@ point), PSNR / SSIM to float tolerance, min-max normalise byte for byte."""
 import numpy as np
 import pytest
 
+import test_loop_trips as lt
 from oracle import wm_oracle as o
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("shape", [(1, 1), (3, 5), (37, 53), (256, 320), (1080, 1920)])
+# the last shape (tests/test_loop_trips.py): 2056 whole LDS-staged blocks on k_color's 2048 workgroups and 526 336 groups in the
+# direct loop of the single-plane outputs - both loops go round twice, and only 8 workgroups (2048 threads) do.  (The 4096 x 4096
+# image of test_gpu_enhance_edges.py::test_colour_conversions_exhaustive takes every workgroup round exactly twice.)
+@pytest.mark.parametrize("shape", [(1, 1), (3, 5), (37, 53), (256, 320), (1080, 1920), lt.COLOUR_SHAPE])
 def test_colour_conversions_bit_exact(gpu_ctx, shape):
     H, W = shape
     img = np.random.default_rng(H * 1000 + W).integers(0, 256, (H, W, 3), dtype=np.uint8)

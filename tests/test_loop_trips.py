@@ -1,0 +1,326 @@
+"""The shapes at which the capped grids and chunked host loops of the kernels go round a second time, held against the caps.
+
+Several kernels launch a capped grid and stride over the rest of the work, others are fed in chunks by a host loop.  A loop
+that lost its stride, dropped its tail or mis-addressed its second chunk is only seen at a shape that crosses the cap, so the
+GPU tests below take their shapes from this file, and this file (CPU, no marker) restates every cap, finds the statement that
+sets it in the source, and asserts for every shape that it crosses its cap and by how much.  If a cap moves, the test here
+fails and names the shapes that have to move with it; the GPU tests cannot drift from what is checked here.
+
+    loop                                                    GPU test
+    k_embed_fallback, walks of kinds 0, 1, 2                tests/test_gpu_flagged_trips.py
+    k_sum_planes                                            tests/test_gpu_parity.py::test_extract_sum_over_planes_past_the_grid
+    k_frame_codec, items and frames                         tests/test_gpu_chroma_codec.py::test_codec_*_second_trip
+    k_color, staged blocks and direct groups                tests/test_gpu_pixel.py::test_colour_conversions_bit_exact (a second trip
+                                                            of some workgroups; test_gpu_enhance_edges.py's exhaustive 4096 x 4096
+                                                            image already takes all of them round exactly twice)
+    keyed_placement_sum, keyed_windows_share                tests/test_gpu_payload_keyed_sync.py (EDGES), test_gpu_payload_clip.py
+    wm_payload_keyed_best_dev, candidates per launch        tests/test_gpu_payload_clip.py::test_candidates_past_one_launch
+
+Left out on purpose: the second trip of kind 3 (k_embed_one_small).  Its sub-lists are clamped to fb_cap3 entries each, so its
+walk has at most 64 * fb_cap3 items, and 64 * fb_cap3 > 2048 * 64 needs fb_cap > 32 768, i.e. more than 2.1 million tiles in
+one call, all of them rank-deficient and not rank 1: over 130 MB of input, which is not a test of a few seconds.
+"""
+import functools
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd", "csrc")
+HOSTAPI = os.path.join(os.path.dirname(CSRC), "hostapi.py")
+
+WAVE = 64
+
+# ---- the caps, restated; SOURCE holds the statement of each in the source, which test_the_caps_are_where_the_source_sets_them finds
+FGRID_CAP = 2048                    # wmhip.hip, wm_embed_tiles_u8_dev: const dim3 fgrid((unsigned)(n_waves < 2048 ? n_waves : 2048));
+FLAGGED_TRIP = FGRID_CAP * WAVE     # k_embed_fallback: it0 += gridDim.x * WAVE, one item per lane -> 131 072 items of a kind per trip
+FB_SUB = 64                         # wmhip.hip: constexpr unsigned FB_SUB = 64;
+FB_CAP3_DIV, FB_CAP3_MIN = 16, 64   # wmhip.hip: const size_t cap3 = std::max<size_t>(WAVE, cap / 16);
+SUM_GRID_CAP, SUM_BLOCK = 4096, 256             # wmhip.hip, extract_tiles_host: dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256)
+SUM_TRIP = SUM_GRID_CAP * SUM_BLOCK             # k_sum_planes: one pixel per thread and trip -> 1 048 576
+GRID_FOR_CAP, GRID_FOR_BLOCK = 256 * 8, 256     # wm_pixel.hip: grid_for(size_t work_items, unsigned block = 256, unsigned cap = 256 * 8)
+CODEC_ITEM_TRIP = GRID_FOR_CAP * GRID_FOR_BLOCK  # launch_frame_codec: grid_for(ch * cols) -> 524 288 items of a frame per trip
+CODEC_FRAME_CAP = 65535             # launch_frame_codec: (unsigned)min(n_frames, 65535); k_frame_codec: fr += gridDim.y
+COLOR_PX_PER_GROUP, COLOR_GROUPS_PER_BLOCK = 16, 256     # k_color: n_groups = n_px / 16, n_full = n_groups / 256
+COLOR_BLOCK_TRIP = GRID_FOR_CAP                 # color_dispatch: grid_for(n_px / 16 + 1); staged loop: blk += gridDim.x
+COLOR_GROUP_TRIP = GRID_FOR_CAP * GRID_FOR_BLOCK  # direct loop: gidx += gridDim.x * blockDim.x -> 524 288 groups = 8 388 608 px
+KEYED_STEP = 8                      # wmhip.hip, keyed_placement_sum: constexpr int STEP = 8;
+CLIP_CHUNK = 1023                   # wmhip.hip, wm_payload_keyed_best_dev: constexpr int CHUNK = 1023;
+CLIP_TABLE_BYTES = 64 << 20         # hostapi.py, Context: CLIP_TABLE_BYTES = 64 << 20
+
+SOURCE = [      # (what, file, the statement, the shapes that move with it)
+    ("flagged-tile grid", "wmhip.hip", "const dim3 fgrid((unsigned)(n_waves < 2048 ? n_waves : 2048));", "FLAGGED_PLANE"),
+    ("flagged-tile stride", "wmhip.hip", "it0 < walk.total[0]; it0 += gridDim.x * WAVE)", "FLAGGED_PLANE"),
+    ("flagged-tile stride", "wmhip.hip", "it0 < walk.total[1]; it0 += gridDim.x * WAVE)", "FLAGGED_PLANE"),
+    ("flagged-tile stride", "wmhip.hip", "it0 < walk.total[2]; it0 += gridDim.x * WAVE)", "FLAGGED_PLANE"),
+    ("sub-lists per kind", "wmhip.hip", "constexpr unsigned FB_SUB = 64;", "FLAGGED_PLANE, RANK7_PLANES"),
+    ("sub-list size", "wmhip.hip", "const size_t cap = (n_work_sz + FB_SUB - 1) / FB_SUB * WAVE;", "RANK7_PLANES"),
+    ("kind-3 sub-list size", "wmhip.hip", "const size_t cap3 = std::max<size_t>(WAVE, cap / 16);", "RANK7_PLANES"),
+    ("k_sum_planes grid", "wmhip.hip", "hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256)", "SUM_SHAPES"),
+    ("grid_for", "wm_pixel.hip", "inline unsigned grid_for(size_t work_items, unsigned block = 256, unsigned cap = 256 * 8)",
+     "CODEC_ITEM_CASES, COLOUR_SHAPE"),
+    ("frame codec grid", "wm_pixel.hip", "const dim3 grid(grid_for(ch * cols), (unsigned)min(n_frames, 65535)), block(256);",
+     "CODEC_ITEM_CASES, CODEC_FRAME_CASES"),
+    ("frame codec frame stride", "wm_pixel.hip", "for (int fr = blockIdx.y; fr < n_frames; fr += gridDim.y)", "CODEC_FRAME_CASES"),
+    ("colour grid", "wm_pixel.hip", "const dim3 grid(grid_for(n_px / 16 + 1)), block(256);", "COLOUR_SHAPE"),
+    ("colour staged blocks", "wm_pixel.hip", "const size_t n_full = OUT3 ? n_groups / 256 : 0;", "COLOUR_SHAPE"),
+    ("keyed placement step", "wmhip.hip", "constexpr int STEP = 8;", "KEYED_PLACEMENT"),
+    ("keyed window stride", "wmhip.hip", "for (int c = threadIdx.x; c < nx; c += WAVE)", "KEYED_WINDOWS"),
+    ("clip candidates per launch", "wmhip.hip", "constexpr int CHUNK = 1023;", "CLIP_CHUNK_CANDS"),
+    ("clip tables per call", "hostapi.py", "CLIP_TABLE_BYTES = 64 << 20", "CLIP_CHUNK_CANDS (payload_locate_clip)"),
+]
+
+
+# ---- the shapes (imported by the GPU tests) ---------------------------------------------------------------------------
+# flagged-tile walks: 344 x 384 tiles = 2064 full waves, no partial one; tile t of every plane holds palette[t % 64]
+FLAGGED_PLANE = (2752, 3072)
+FLAGGED_SMALL = (8, 512)            # the palette once: one wave, nothing overflows
+RANK7_PLANES = 2                    # the rank-7 case: two such planes, whose kind-3 sub-lists overflow into kind 0
+RANK7_MEDIUM = (1024, 1024)         # sub-lists that overflow without a second trip (test_one_small_singular_value_tiles_on_gpu's size)
+RANK7_KIND0 = 247552                # tiles of the rank-7 case that the kind-0 walk redoes (asserted below)
+SUM_PLANES = 3
+SUM_SHAPES = [(264, 4000), (263, 4003)]          # the second ragged: a zero border
+# (H, W, (sx, sy), takes the 16-byte path), one frame each
+CODEC_ITEM_CASES = [(8, 65541, (1, 1), False), (16, 131075, (2, 2), False), (2056, 4096, (1, 1), True)]
+# (frames, H, W, (sx, sy))
+CODEC_FRAME_CASES = [(65537, 1, 1, (1, 1)), (65537, 2, 2, (2, 2))]
+COLOUR_SHAPE = (2056, 4096)
+# keyed scans, name -> (h, w, (nby, nbx)); the window counts across (nx) the 8 phases px take, asserted below
+KEYED_PLACEMENT = {
+    "group-and-tail-at-px0": (24, 72, (5, 13)),      # nx 9 at px = 0, 8 elsewhere: a group and a tail of one beside the no-tail case
+    "group-and-tail": (24, 79, (5, 13)),             # nx 9 at every phase
+    "tail-of-4-and-3": (24, 96, (5, 24)),            # nx 12 and 11
+    "two-groups": (24, 128, (4, 24)),                # nx 16 (two groups, no tail) and 15
+    "two-groups-and-tail": (24, 143, (4, 36)),       # nx 17
+}
+KEYED_PLACEMENT_NX = {"group-and-tail-at-px0": {9, 8}, "group-and-tail": {9}, "tail-of-4-and-3": {12, 11}, "two-groups": {16, 15},
+                      "two-groups-and-tail": {17}}
+KEYED_WINDOWS = {
+    "one-full-trip": (24, 512, (4, 65)),             # nx 64 and 63
+    "lane-0-twice": (24, 520, (4, 67)),              # nx 65 and 64: lane 0 alone goes twice
+    "lane-0-twice-every-phase": (24, 527, (4, 67)),  # nx 65 at every phase
+    "three-trips": (16, 1039, (3, 131)),             # nx 129
+}
+KEYED_WINDOWS_NX = {"one-full-trip": {64, 63}, "lane-0-twice": {65, 64}, "lane-0-twice-every-phase": {65}, "three-trips": {129}}
+# the clip search runs the same loop bodies: one shape of each mapping, (h, w, nby, nbx)
+CLIP_TRIP_SHAPES = {"placement-tail": (24, 72, 5, 13), "windows-second-trip": (24, 520, 4, 67)}
+# the candidate chunking: (h, w, nby, nbx), tables, and the candidate counts
+CLIP_CHUNK_SHAPE = (16, 16, 3, 3)
+CLIP_CHUNK_TABLES = 5
+CLIP_CHUNK_CANDS = (1023, 1024, 1025, 2047)
+CLIP_LOCATE_CANDS = 1025
+
+
+def fb_caps(n_tiles: int, n_planes: int):
+    """(cap, cap3) of the flagged-tile lists as wm_embed_tiles_u8_dev sizes them"""
+    n_groups = (n_tiles + WAVE - 1) // WAVE
+    cap = (n_groups * n_planes + FB_SUB - 1) // FB_SUB * WAVE
+    return cap, max(FB_CAP3_MIN, cap // FB_CAP3_DIV)
+
+
+def lanes_over_windows(w: int, nbx: int) -> bool:
+    """the keyed entry points' choice of mapping (wmhip.hip: `windows`), as the GPU tests restate it"""
+    nx, n_tx = w // 8, nbx - w // 8 + 1
+    return nx * ((n_tx + 63) // 64) >= 2 * n_tx * ((nx + 63) // 64)
+
+
+def codec_items(H: int, W: int, sub, vec: bool) -> int:
+    sx, sy = sub
+    return ((H + sy - 1) // sy) * (W // 16 if vec else (W + sx - 1) // sx)
+
+
+# ---- the palettes of the flagged-tile tests (host arithmetic only) ------------------------------------------------------
+def periodic_plane(palette: np.ndarray, H: int, W: int) -> np.ndarray:
+    """[H, W] whose tile t (row-major) is palette[t % 64]; palette [64, 8, 8] (or [64, 8] rows of per-tile values -> [nby, nbx, 8])"""
+    nby, nbx = H // 8, W // 8
+    t = palette[(np.arange(nby * nbx) % 64).reshape(nby, nbx)]
+    return np.ascontiguousarray(t.transpose(0, 2, 1, 3).reshape(H, W)) if palette.ndim == 3 else np.ascontiguousarray(t)
+
+
+@functools.lru_cache(maxsize=None)
+def sigma_w_rows() -> np.ndarray:
+    """64 distinct watermark rows, sorted descending as singular values are"""
+    sw = np.sort(np.random.default_rng(64).uniform(1, 1500, (64, 8)).astype(np.float32), axis=-1)[:, ::-1].copy()
+    sw.setflags(write=False)
+    return sw
+
+
+@functools.lru_cache(maxsize=None)
+def constant_palettes():
+    """(mixed, black): 64 constant tiles, 31 of them black and 33 of distinct grey levels, shuffled so that black and grey sit
+    side by side in a wave (embed_tile_constant's general form); and 64 black ones (its <0> form)"""
+    rng = np.random.default_rng(11)
+    levels = np.concatenate([np.zeros(31, np.uint8), rng.choice(np.arange(1, 256), 33, replace=False).astype(np.uint8)])
+    rng.shuffle(levels)
+    mixed = np.broadcast_to(levels[:, None, None], (64, 8, 8)).copy()
+    return mixed, np.zeros((64, 8, 8), np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def rank1_palette() -> np.ndarray:
+    """64 rank-1 tiles that are not constant: outer products, edges of flat rectangles (both ways), equal rows, equal columns"""
+    rng = np.random.default_rng(12)
+    out = []
+    for k in range(64):
+        if k % 4 == 0:
+            t = np.outer(rng.integers(1, 16, 8), rng.integers(1, 16, 8))
+        elif k % 4 == 1:                                                  # an edge of a flat rectangle: a level above k rows / left of k columns
+            e = (np.arange(8) < 1 + k // 4 % 7).astype(int) * int(rng.integers(1, 256))
+            t = np.broadcast_to(e[:, None] if k % 8 == 1 else e[None, :], (8, 8))
+        elif k % 4 == 2:
+            t = np.broadcast_to(rng.integers(0, 256, (1, 8)), (8, 8))      # equal rows
+        else:
+            t = np.broadcast_to(rng.integers(0, 256, (8, 1)), (8, 8))      # equal columns
+        out.append(np.array(t, np.uint8))
+    return np.stack(out)
+
+
+@functools.lru_cache(maxsize=None)
+def rank7_palette() -> np.ndarray:
+    """64 exactly-rank-7 tiles: the eight of test_host_harness._one_small_tiles (as test_one_small_singular_value_tiles_on_gpu
+    takes them) and 56 more by its three recipes - two equal rows, a zero column, a column that is the mean of two others"""
+    from test_host_harness import _one_small_tiles
+    out = list(_one_small_tiles(n_want=1, seed=9)[1])
+    rng = np.random.default_rng(13)
+    for k in range(64 - len(out)):
+        a = rng.integers(0, 256, (8, 8)).astype(np.uint8)
+        if k % 3 == 0:
+            a[(k // 3 + 5) % 8] = a[(k // 3 + 2) % 8]
+        elif k % 3 == 1:
+            a[:, k // 3 % 8] = 0
+        else:
+            a[:, 0] = (a[:, 0] // 2) * 2; a[:, 1] = (a[:, 1] // 2) * 2; a[:, 6] = a[:, 0] // 2 + a[:, 1] // 2
+        out.append(a)
+    return np.stack(out)
+
+
+# ---- the tests ----------------------------------------------------------------------------------------------------------
+def test_the_caps_are_where_the_source_sets_them():
+    squeeze = lambda s: re.sub(r"\s+", " ", s)
+    text = {}
+    for what, name, statement, shapes in SOURCE:
+        path = HOSTAPI if name.endswith(".py") else os.path.join(CSRC, name)
+        if path not in text:
+            with open(path, encoding="utf-8") as f:
+                text[path] = squeeze(f.read())
+        assert squeeze(statement) in text[path], \
+            f"{what}: `{statement}` is no longer in {name} - restate the cap in tests/test_loop_trips.py and move {shapes} with it"
+    assert FLAGGED_TRIP == 131072 and SUM_TRIP == 1048576 and CODEC_ITEM_TRIP == COLOR_GROUP_TRIP == 524288
+
+
+def test_flagged_tile_shapes_cross_the_walk():
+    H, W = FLAGGED_PLANE
+    n_tiles = (H // 8) * (W // 8)
+    assert H % 8 == 0 and W % 8 == 0 and n_tiles == 132096 and n_tiles % WAVE == 0 and n_tiles // WAVE == 2064
+    assert (W // 8) % 64 == 0                                              # the periodic layout: every wave holds the palette, lane for lane
+    print(f"kinds 1 and 2: {n_tiles} flagged tiles of one kind on {FLAGGED_TRIP} a trip: {n_tiles - FLAGGED_TRIP} in the second trip")
+    assert FLAGGED_TRIP < n_tiles <= 2 * FLAGGED_TRIP
+    # the small and the medium plane keep the same waves, stay within one trip, and only the medium one overflows kind 3
+    for (h, w), n in ((FLAGGED_SMALL, 1), (RANK7_MEDIUM, 1)):
+        nt = (h // 8) * (w // 8)
+        assert nt % WAVE == 0 and ((w // 8) % 64 == 0 or nt == 64) and nt * n <= FLAGGED_TRIP
+    assert fb_caps(64, 1) == (64, 64)                                      # the small call: 64 kind-3 entries for 64 tiles
+    cap_m, cap3_m = fb_caps(128 * 128, 1)
+    assert (cap_m, cap3_m) == (256, 64) and 64 * cap3_m < 128 * 128
+    # the rank-7 case: every tile asks for kind 3; a sub-list takes the tiles of the waves w with w % 64 == s, keeps cap3, and
+    # sends the rest to kind 0
+    cap, cap3 = fb_caps(n_tiles, RANK7_PLANES)
+    assert (cap, cap3) == (4160, 260)
+    waves = n_tiles // WAVE * RANK7_PLANES
+    per_sub = [len(range(s, waves, FB_SUB)) * WAVE for s in range(FB_SUB)]
+    assert min(per_sub) >= cap3 and max(per_sub) <= cap                    # every kind-3 sub-list fills; no kind-0 sub-list can overflow
+    kind3 = FB_SUB * cap3
+    kind0 = n_tiles * RANK7_PLANES - kind3
+    print(f"rank-7 case: {kind3} tiles stay in kind 3, {kind0} go to kind 0 on {FLAGGED_TRIP} a trip: {kind0 - FLAGGED_TRIP} in the second trip")
+    assert kind3 == 16640 and kind0 == RANK7_KIND0 and FLAGGED_TRIP < kind0 <= 2 * FLAGGED_TRIP
+    assert kind3 <= FLAGGED_TRIP                                           # (kind 3 itself stays in one trip: see the docstring)
+
+
+def test_the_palettes_are_what_their_kinds_need():
+    mixed, black = constant_palettes()
+    flat = mixed.reshape(64, 64)
+    assert (flat == flat[:, :1]).all() and (flat[:, 0] == 0).sum() == 31 and len(set(flat[:, 0])) == 34 and not black.any()
+    assert 0 < (flat[:8, 0] == 0).sum() < 8                                # black and grey side by side
+    r1 = rank1_palette().astype(np.float64)
+    assert (np.linalg.matrix_rank(r1) == 1).all() and (r1.reshape(64, 64).min(axis=1) != r1.reshape(64, 64).max(axis=1)).all()
+    r7 = rank7_palette().astype(np.float64)
+    s = np.linalg.svd(r7, compute_uv=False)
+    assert (np.linalg.matrix_rank(r7) == 7).all() and (s[:, 6] > 1e-3 * s[:, 0]).all()
+    assert len({t.tobytes() for t in rank7_palette()}) == 64
+    sw = sigma_w_rows()
+    assert (np.diff(sw, axis=1) <= 0).all() and len({r.tobytes() for r in sw}) == 64
+    p = periodic_plane(rank1_palette(), *FLAGGED_SMALL)
+    assert np.array_equal(p[:, 8 * 5:8 * 6], rank1_palette()[5])
+    big = periodic_plane(rank1_palette(), 16, 1024)                         # tile (1, 3) is t = 131 -> entry 3
+    assert np.array_equal(big[8:, 24:32], rank1_palette()[3])
+
+
+def test_pixel_side_shapes_cross_their_grids():
+    for H, W in SUM_SHAPES:
+        print(f"k_sum_planes {H}x{W}: {H * W} px on {SUM_TRIP} a trip: {H * W - SUM_TRIP} in the second trip")
+        assert SUM_TRIP < H * W <= 2 * SUM_TRIP
+    assert SUM_SHAPES[0][0] % 8 == 0 and SUM_SHAPES[0][1] % 8 == 0 and SUM_SHAPES[1][0] % 8 and SUM_SHAPES[1][1] % 8
+    for H, W, sub, vec in CODEC_ITEM_CASES:
+        assert vec == (W % 16 == 0)
+        items = codec_items(H, W, sub, vec)
+        print(f"k_frame_codec {H}x{W} {sub} vec={vec}: {items} items on {CODEC_ITEM_TRIP} a trip: {items - CODEC_ITEM_TRIP} in the second trip")
+        assert CODEC_ITEM_TRIP < items <= 2 * CODEC_ITEM_TRIP
+    for n, H, W, sub in CODEC_FRAME_CASES:
+        print(f"k_frame_codec {n} frames of {H}x{W} {sub} on {CODEC_FRAME_CAP} a trip: {n - CODEC_FRAME_CAP} in the second trip")
+        assert CODEC_FRAME_CAP < n <= 2 * CODEC_FRAME_CAP and n - CODEC_FRAME_CAP >= 2
+        assert codec_items(H, W, sub, False) == 1
+    H, W = COLOUR_SHAPE
+    groups = H * W // COLOR_PX_PER_GROUP
+    blocks = groups // COLOR_GROUPS_PER_BLOCK
+    grid = min(GRID_FOR_CAP, (H * W // 16 + 1 + GRID_FOR_BLOCK - 1) // GRID_FOR_BLOCK)
+    print(f"k_color {H}x{W}: {blocks} staged blocks on {grid} workgroups: {blocks - grid} in the second trip; "
+          f"{groups} direct groups on {COLOR_GROUP_TRIP} a trip: {groups - COLOR_GROUP_TRIP} in the second trip")
+    assert grid == COLOR_BLOCK_TRIP and COLOR_BLOCK_TRIP < blocks <= 2 * COLOR_BLOCK_TRIP
+    assert COLOR_GROUP_TRIP < groups <= 2 * COLOR_GROUP_TRIP
+    assert (2160 * 3840 // 16) // 256 <= (2160 * 3840 // 16 + 1 + 255) // 256 <= GRID_FOR_CAP      # (a 4K frame stays in one trip)
+    # test_gpu_enhance_edges.py::test_colour_conversions_exhaustive (all 2^24 colours, 4096 x 4096) takes every workgroup and
+    # every thread round exactly twice; COLOUR_SHAPE adds the second trip that only some of them make
+    assert (4096 * 4096 // 16) // 256 == 2 * COLOR_BLOCK_TRIP and 4096 * 4096 // 16 == 2 * COLOR_GROUP_TRIP
+    assert blocks % COLOR_BLOCK_TRIP and groups % COLOR_GROUP_TRIP
+
+
+def test_keyed_shapes_take_their_mapping_and_their_trips():
+    for name, (h, w, (nby, nbx)) in KEYED_PLACEMENT.items():
+        nxs = {(w - px) // 8 for px in range(8)}
+        assert not lanes_over_windows(w, nbx), name
+        assert nxs == KEYED_PLACEMENT_NX[name], (name, nxs)
+        assert h == 24 and h // 8 <= nby and w // 8 <= nbx                     # three window rows: sp += nx, up += nbx count
+        print(f"keyed placement {name}: nx {sorted(nxs)}: groups of {KEYED_STEP} {[n // KEYED_STEP for n in sorted(nxs)]}, "
+              f"tails {[n % KEYED_STEP for n in sorted(nxs)]}")
+        assert max(nxs) > KEYED_STEP                                           # a group and something behind it
+    tails = {n % KEYED_STEP for nxs in KEYED_PLACEMENT_NX.values() for n in nxs}
+    groups = {n // KEYED_STEP for nxs in KEYED_PLACEMENT_NX.values() for n in nxs}
+    assert {0, 1, 3, 4, 7} <= tails and {1, 2} <= groups
+    for name, (h, w, (nby, nbx)) in KEYED_WINDOWS.items():
+        nxs = {(w - px) // 8 for px in range(8)}
+        assert lanes_over_windows(w, nbx), name
+        assert nxs == KEYED_WINDOWS_NX[name], (name, nxs)
+        assert h // 8 <= nby and w // 8 <= nbx
+        print(f"keyed windows {name}: nx {sorted(nxs)}: trips of lane 0 {[(n + WAVE - 1) // WAVE for n in sorted(nxs)]}")
+    assert max(KEYED_WINDOWS_NX["one-full-trip"]) == WAVE and min(KEYED_WINDOWS_NX["lane-0-twice"] | KEYED_WINDOWS_NX["three-trips"]) >= WAVE
+    assert max(KEYED_WINDOWS_NX["lane-0-twice"]) == WAVE + 1 and max(KEYED_WINDOWS_NX["three-trips"]) == 2 * WAVE + 1
+    assert [h for h, _, _ in KEYED_WINDOWS.values()][:3] == [24, 24, 24]
+    (hp, wp, byp, bxp), (hw, ww, byw, bxw) = CLIP_TRIP_SHAPES["placement-tail"], CLIP_TRIP_SHAPES["windows-second-trip"]
+    assert (hp, wp, (byp, bxp)) in KEYED_PLACEMENT.values() and wp // 8 > KEYED_STEP and (wp // 8) % KEYED_STEP
+    assert (hw, ww, (byw, bxw)) in KEYED_WINDOWS.values() and ww // 8 > WAVE
+
+
+def test_clip_candidate_counts_cross_one_launch():
+    for n in CLIP_CHUNK_CANDS:
+        launches = (n + CLIP_CHUNK - 1) // CLIP_CHUNK
+        print(f"clip search, {n} candidates on {CLIP_CHUNK} a launch: {launches} launches, the last of {n - (launches - 1) * CLIP_CHUNK}")
+    assert [(n + CLIP_CHUNK - 1) // CLIP_CHUNK for n in CLIP_CHUNK_CANDS] == [1, 2, 2, 3]
+    assert CLIP_CHUNK_CANDS[1] - CLIP_CHUNK == 1 and CLIP_CHUNK_CANDS[3] - 2 * CLIP_CHUNK == 1      # chunks of one candidate
+    assert 64 * CLIP_CHUNK <= 65535 < 64 * (CLIP_CHUNK + 1)                    # why 1023: grid z = 64 candidates + phase
+    # payload_locate_clip with its default split hands all 1025 candidates to one C call
+    h, w, nby, nbx = CLIP_CHUNK_SHAPE
+    per_call = CLIP_TABLE_BYTES // (nby * nbx * 2) - 1
+    print(f"payload_locate_clip: {per_call} candidates a call by default, {CLIP_LOCATE_CANDS} asked")
+    assert per_call >= CLIP_LOCATE_CANDS > CLIP_CHUNK
+    assert h // 8 <= nby and w // 8 <= nbx and not lanes_over_windows(w, nbx)
