@@ -1209,7 +1209,7 @@ __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan(const float* __rest
 // The same scores with the lanes over the windows, for a crop with few placements across (only rows cut away, say), where the
 // mapping above leaves most of a wave without a placement: a wave owns ONE placement (phase, ty, tx) = blockIdx (z, y, x), lane
 // l adds the windows c = l, l + 64, .. of every row, and the 64 shares are added by wave_sum.  Integer sums: the two mappings
-// give the same bits, whichever the entry point picks.
+// give the same bits, whichever keyed_launch picks.
 // lane l's share of one placement's windows: c = l, l + 64, .. of every row
 __device__ __forceinline__ long long keyed_windows_share(const float* __restrict__ sp, const uint16_t* __restrict__ up, const int ny,
                                                          const int nx, const int nbx, const float delta, const float inv_2delta) {
@@ -1235,7 +1235,7 @@ __global__ __launch_bounds__(WAVE) void k_payload_keyed_scan_windows(const float
 
 // Clip search (include/wmhip.h, "clip resynchronisation"): the keyed scan over several anchors' scans and many candidates, with
 // only (the largest score, its first place) per (candidate, phase) leaving the device.  Grid z = 64 candidate + phase; lanes
-// and waves own placements as in the two kernels above (the same selection rule in the entry point).  Candidate g reads anchor
+// and waves own placements as in the two kernels above (one selection rule for both forms: keyed_launch).  Candidate g reads anchor
 // a under table table_of[g][a]; an entry outside 0 .. n_tables - 1 skips the anchor (the load and the test are the wave's, not
 // the lane's).  A placement's sum stays in registers across the anchors - int32 per window row, int64 across rows and anchors -
 // and nothing is written per anchor.  Reduction: key = score * 2^24 + (2^24 - 1 - index), index = ty n_tx + tx; the index is
@@ -1428,6 +1428,37 @@ int sigma_pass(wm_ctx* ctx, const uint8_t* planes, int n_planes, int H, int W, i
   with_bools([&](auto A) {
     hipLaunchKernelGGL((k_sigma_pass<A.value, Epi>), grid, block, 0, ctx->stream, planes, g, ctx->d_status, epi);
   }, u8_aligned(planes, planes, row_stride, plane_stride));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// The launch of both phase scans, behind the caller's check_plane_args and rule check: nothing to do without a plane or a
+// whole tile; `bad` as in sigma_pass; `sums`: the scan's [plane][phase] sums to clear first, or nullptr where it has none.
+template <typename Epi>
+int phase_scan(wm_ctx* ctx, const uint8_t* stego, int n_planes, int h, int w, int row_stride, size_t plane_stride, const char* bad,
+               int64_t* sums, const Epi& epi) {
+  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
+  if (n_planes == 0 || pitch == 0) return WM_OK;
+  if (pitch > (size_t)INT32_MAX) return set_err(WM_ERR_BADARG, "more than 2^31 - 1 tiles a plane");
+  if (bad) return set_err(WM_ERR_BADARG, "%s", bad);
+  if (sums) WM_HIP(hipMemsetAsync(sums, 0, (size_t)n_planes * 64 * sizeof(int64_t), ctx->stream));
+  const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
+  const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
+  hipLaunchKernelGGL(k_payload_phase_scan<Epi>, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status, epi);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+// The lane mapping and the grid (sized for phase (7, 7); z = 64 candidates + phase) of a keyed launch, for both forms: `head`
+// is what the form's two kernels take in front of (g, delta, 1 / (2 delta)).  A lane per placement fills n_tx of every 64
+// lanes, a lane per window of a row nx of every 64: the second mapping where it fills at least twice as many (the first
+// reads s1 once a wave and the table in 16-byte pieces, so it is the cheaper one per window).
+template <typename Kernel, typename... Head>
+int keyed_launch(wm_ctx* ctx, Kernel per_placement, Kernel per_window, const KeyedGeom& g, int n_cand, float delta, Head... head) {
+  const long long n_tx = g.nbx - g.w / 8 + 1, nx = g.w / 8, n_tx_max = g.nbx - (g.w - 7) / 8 + 1;
+  const bool windows = nx * ((n_tx + WAVE - 1) / WAVE) >= 2 * n_tx * ((nx + WAVE - 1) / WAVE);
+  const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(g.nby - (g.h - 7) / 8 + 1), (unsigned)(64 * n_cand));
+  hipLaunchKernelGGL(windows ? per_window : per_placement, grid, dim3(WAVE), 0, ctx->stream, head..., g, delta, 1.0f / (2.0f * delta));
   WM_HIP(hipGetLastError());
   return WM_OK;
 }
@@ -1889,17 +1920,9 @@ int wm_payload_phase_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, int32_t* vot
                                  int row_stride, size_t plane_stride, float delta) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
   WM_TRY(check_delta(delta));
-  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
-  if (n_planes == 0 || pitch == 0) return WM_OK;
-  if (pitch > (size_t)INT32_MAX) return set_err(WM_ERR_BADARG, "more than 2^31 - 1 tiles a plane");
-  if (!sums || ((uintptr_t)sums & 7u) || ((uintptr_t)votes & 3u)) return set_err(WM_ERR_BADARG, "sums is NULL, or sums / votes is misaligned");
-  WM_HIP(hipMemsetAsync(sums, 0, (size_t)n_planes * 64 * sizeof(int64_t), ctx->stream));
-  const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
-  const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
-  const EpiPhaseVotes epi{votes, reinterpret_cast<unsigned long long*>(sums), 1.0f / (2.0f * delta)};
-  hipLaunchKernelGGL(k_payload_phase_scan<EpiPhaseVotes>, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status, epi);
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  const bool bad = !sums || ((uintptr_t)sums & 7u) || ((uintptr_t)votes & 3u);
+  return phase_scan(ctx, stego, n_planes, h, w, row_stride, plane_stride, bad ? "sums is NULL, or sums / votes is misaligned" : nullptr, sums,
+                    EpiPhaseVotes{votes, reinterpret_cast<unsigned long long*>(sums), 1.0f / (2.0f * delta)});
 }
 
 int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_t* tile_bit_index, int64_t* scores, int ny, int nx,
@@ -1930,16 +1953,8 @@ int wm_payload_offset_scores_dev(wm_ctx* ctx, const int32_t* votes, const int32_
 int wm_payload_sigma1_scan_u8_dev(wm_ctx* ctx, const uint8_t* stego, float* s1, int n_planes, int h, int w, int row_stride,
                                   size_t plane_stride) {
   WM_TRY(check_plane_args(ctx, stego, n_planes, h, w, row_stride, plane_stride));
-  const size_t pitch = (size_t)(h / 8) * (size_t)(w / 8);
-  if (n_planes == 0 || pitch == 0) return WM_OK;
-  if (pitch > (size_t)INT32_MAX) return set_err(WM_ERR_BADARG, "more than 2^31 - 1 tiles a plane");
-  if (!s1 || ((uintptr_t)s1 & 3u)) return set_err(WM_ERR_BADARG, "s1 is NULL or misaligned");
-  const PhaseGeom g{h, w, (int)pitch, (size_t)row_stride, plane_stride};
-  const dim3 grid((unsigned)((pitch + WAVE - 1) / WAVE), 64, (unsigned)n_planes);
-  hipLaunchKernelGGL(k_payload_phase_scan<EpiPhaseSigma1>, grid, dim3(WAVE), 0, ctx->stream, stego, g, ctx->d_status,
-                     EpiPhaseSigma1{s1});
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  return phase_scan(ctx, stego, n_planes, h, w, row_stride, plane_stride, !s1 || ((uintptr_t)s1 & 3u) ? "s1 is NULL or misaligned" : nullptr,
+                    nullptr, EpiPhaseSigma1{s1});
 }
 
 // the sizes of a keyed search, checked; spitch: the scores per phase (wmhip.h)
@@ -1962,17 +1977,8 @@ int wm_payload_keyed_scores_dev(wm_ctx* ctx, const float* s1, const uint16_t* ti
   if (!tile_dither || ((uintptr_t)tile_dither & 1u)) return set_err(WM_ERR_BADARG, "tile_dither is NULL or at an odd address");
   if (!s1 || !scores || ((uintptr_t)s1 & 3u) || ((uintptr_t)scores & 7u)) return set_err(WM_ERR_BADARG, "s1 / scores is NULL or misaligned");
   WM_HIP(hipMemsetAsync(scores, 0, 64 * spitch * sizeof(int64_t), ctx->stream));
-  const KeyedGeom g{h, w, nby, nbx, (h / 8) * (w / 8), spitch};
-  // The grid is sized for phase (7, 7), which has the most placements.  A lane per placement fills n_tx of every 64 lanes, a lane
-  // per window of a row nx of every 64: the second mapping where it fills at least twice as many (the first reads s1 once a
-  // wave and the table in 16-byte pieces, so it is the cheaper one per window).
-  const long long n_tx = nbx - w / 8 + 1, nx = w / 8, n_tx_max = nbx - (w - 7) / 8 + 1;
-  const bool windows = nx * ((n_tx + WAVE - 1) / WAVE) >= 2 * n_tx * ((nx + WAVE - 1) / WAVE);
-  const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(nby - (h - 7) / 8 + 1), 64);
-  hipLaunchKernelGGL(windows ? k_payload_keyed_scan_windows : k_payload_keyed_scan, grid, dim3(WAVE), 0, ctx->stream, s1, tile_dither,
-                     reinterpret_cast<long long*>(scores), g, delta, 1.0f / (2.0f * delta));
-  WM_HIP(hipGetLastError());
-  return WM_OK;
+  return keyed_launch(ctx, k_payload_keyed_scan, k_payload_keyed_scan_windows, KeyedGeom{h, w, nby, nbx, (h / 8) * (w / 8), spitch}, 1, delta,
+                      s1, tile_dither, reinterpret_cast<long long*>(scores));
 }
 
 // the sizes of a clip search, checked (both forms, before any launch or copy)
@@ -1995,17 +2001,10 @@ int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const 
   long long* const b = reinterpret_cast<long long*>(best);
   WM_HIP(hipMemsetAsync(best, 0xFF, (size_t)n_cand * 64 * 2 * sizeof(int64_t), ctx->stream));      // every entry (-1, -1)
   const KeyedGeom g{h, w, nby, nbx, (h / 8) * (w / 8), 0};
-  // the lane mapping by the rule of wm_payload_keyed_scores_dev; grid z = 64 candidates + phase, at most 1023 candidates a launch
-  const long long n_tx = nbx - w / 8 + 1, nx = w / 8, n_tx_max = nbx - (w - 7) / 8 + 1;
-  const bool windows = nx * ((n_tx + WAVE - 1) / WAVE) >= 2 * n_tx * ((nx + WAVE - 1) / WAVE);
-  constexpr int CHUNK = 1023;
+  constexpr int CHUNK = 1023;                                              // grid z = 64 candidates + phase stays within 65535
   for (int c0 = 0; c0 < n_cand; c0 += CHUNK) {
-    const int nc = std::min(CHUNK, n_cand - c0);
-    const KeyedBestArgs a{s1, tables, table_of + (size_t)c0 * n_anchor, b + (size_t)c0 * 128, n_anchor, n_tables};
-    const dim3 grid((unsigned)(windows ? n_tx_max : (n_tx_max + WAVE - 1) / WAVE), (unsigned)(nby - (h - 7) / 8 + 1), (unsigned)(64 * nc));
-    hipLaunchKernelGGL(windows ? k_payload_keyed_best_windows : k_payload_keyed_best, grid, dim3(WAVE), 0, ctx->stream, a, g, delta,
-                       1.0f / (2.0f * delta));
-    WM_HIP(hipGetLastError());
+    WM_TRY(keyed_launch(ctx, k_payload_keyed_best, k_payload_keyed_best_windows, g, std::min(CHUNK, n_cand - c0), delta,
+                        KeyedBestArgs{s1, tables, table_of + (size_t)c0 * n_anchor, b + (size_t)c0 * 128, n_anchor, n_tables}));
   }
   const size_t n = (size_t)n_cand * 64;
   hipLaunchKernelGGL(k_payload_keyed_best_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, b, n);

@@ -45,6 +45,7 @@ from . import hostapi
 from . import hostglue as hg
 from . import meta as M
 from . import payload as P
+from . import payload_flow as F
 
 K_FRAC_DEFAULT = hg.K_FRAC_DEFAULT
 TILE = 8
@@ -370,21 +371,6 @@ def detect(stego_path: str, meta_path: str, thresh: float = 0.6, *, device: int 
 # pipeline the reference's text branch uses (core:116-123) - and is read back with the password and a meta of a few
 # hundred bytes: nothing of the cover.
 # ---------------------------------------------------------------------------
-def _payload_map_of(H: int, W: int, key: bytes, n_bits: int):
-    return P.payload_map(H // TILE, W // TILE, key, n_bits)
-
-
-def _payload_dither_of(H: int, W: int, key: bytes, on) -> Optional[np.ndarray]:
-    """the image's keyed dither words (frame index 0), or None for the dither-free rule"""
-    return P.dither_table(H // TILE, W // TILE, key) if on else None
-
-
-def _payload_read(ctx, soft: np.ndarray, code: int) -> np.ndarray:
-    """The frame's bits out of the soft values of the bits the tiles carry: their signs, or with the channel code the
-    Viterbi decode of their quantised values on the device (include/wmhip.h, "channel code")"""
-    return ctx.payload_decode(P.quantise_soft(soft))[0] if code else np.asarray(soft) < 0
-
-
 def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: bytes, *, payload_type: str = "text",
                          delta: float = P.DELTA_DEFAULT, device: int = 0, verify: bool = True, dither: bool = False,
                          code=None) -> dict:
@@ -404,44 +390,21 @@ def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: byte
     if cover_bgr.dtype != np.uint8 or cover_bgr.ndim != 3 or cover_bgr.shape[2] != 3:
         raise ValueError("cover must be uint8 [H, W, 3]")
     H, W = cover_bgr.shape[:2]
-    bits = P.payload_frame(data)
-    carried = P.encode_k7(bits) if code else bits                          # what the tiles carry
-    P.check_capacity(carried.size, P.capacity_bits(H, W))                  # before any device call
     key = hg.derive_key(password, nonce)
-    tbi, order, offs = _payload_map_of(H, W, key, carried.size)
+    bits, carried, _, order, offs, tile_bit = F.embed_plan(data, code, H, W, key)
     ctx = _ctx(device)
     Y = _Gray.planes_in(ctx, cover_bgr)                                    # core:117 (_to_Y)
-    dz = _payload_dither_of(H, W, key, dither)
-    stego_y, _, Yw = ctx.embed_tiles_payload(Y, P.tile_bits(carried, tbi), delta, want_yw=True, dither=dz)
+    dz = P.dither_table(H // TILE, W // TILE, key) if dither else None     # the image's keyed dither words (frame index 0)
+    stego_y, _, Yw = ctx.embed_tiles_payload(Y, tile_bit, delta, want_yw=True, dither=dz)
     members = M.payload_members(payload_type, H, W, delta, bits.size, nonce, dither=P.DITHER_TABLE if dither else 0, code=code)
     digest = hg.hmac_digest(key, M.hmac_parts(members))
     stego = _Gray.planes_out(ctx, cover_bgr, stego_y)                      # core:123 (_from_Y)
     if verify:                                                             # one metric and reduce pass on the final BGR stego
         soft = ctx.payload_soft(_Gray.planes_in(ctx, stego), order, offs, carried.size, delta, dither=dz)
-        P.check_decodes(soft, bits, data, _payload_read(ctx, soft, code) if code else None)
+        P.check_decodes(soft, bits, data, F.read(ctx, soft, code) if code else None)
     ps = ctx.psnr(cover_bgr, stego)
     ss = ctx.ssim(ctx.color("bgr2gray", cover_bgr), Yw)
     return dict(stego=stego, meta=M.sealed(members, TILE, digest), psnr=ps, ssim=ss)
-
-
-def _payload_meta_checked(meta, password: str):
-    """(meta, H, W, delta, n_bits, payload_type, key) of an authentic payload meta; n_bits counts the frame's bits, with a
-    channel code or without"""
-    M.check_password_type(password, "extract")
-    M.require_password(password, "extract")
-    meta = M.unpack_payload(meta)
-    M.require_payload(meta)
-    key = hg.derive_key(password, M.nonce_of(meta))
-    if not M.authentic(meta, key):
-        raise ValueError(M.WRONG_PASSWORD)
-    H, W = map(int, meta["shape"])
-    n_bits = int(meta["payload_bits"])
-    carried = P.coded_bits(n_bits) if M.payload_code_of(meta) else n_bits
-    if n_bits < 8 * P.OVERHEAD_BYTES or n_bits % 8 or carried > P.capacity_bits(H, W) or M.tile_of(meta) != TILE:
-        raise ValueError("payload meta does not describe a frame of this image size")
-    ptype = str(meta["payload_type"])
-    P.check_type(ptype)
-    return meta, H, W, hostapi.check_delta(float(meta["delta"])), n_bits, ptype, key
 
 
 SEARCHES = (None, "crop", "crop-keyed")
@@ -452,55 +415,33 @@ def _check_search(search):
         raise ValueError(f"search must be None, 'crop' or 'crop-keyed', got {search!r}")
 
 
-def _check_crop_shape(stego_bgr: np.ndarray, H: int, W: int) -> tuple:
-    """(h, w) of a stego that can be a crop of the H x W marked image"""
-    if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
-        raise ValueError("stego must be uint8 [h, w, 3]")
-    h, w = stego_bgr.shape[:2]
-    if h > H or w > W:
-        raise ValueError(f"stego is {w}x{h}, larger than the {W}x{H} the meta was written for: not a crop of it")
-    if h < TILE or w < TILE:
-        raise ValueError(f"stego is {w}x{h}: a crop without a whole 8x8 tile carries nothing")
-    return h, w
-
-
-def _extract_payload_cropped(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, code, key, device):
-    """search="crop" (include/wmhip.h, "crop resynchronisation"): the stego is any axis-aligned crop of the marked image.
-    n_bits: the bits the tiles carry (the coded bits under a channel code).  Every refusal comes before the first device call."""
-    if M.payload_dither_of(meta):
+def _extract_payload_cropped(stego_bgr: np.ndarray, rule: F.Rule, keyed: bool, device: int):
+    """search="crop" and, ``keyed``, search="crop-keyed" (include/wmhip.h, "crop resynchronisation" and "keyed crop
+    resynchronisation"): the stego is any axis-aligned crop of the marked image - one marked with dither=True for the keyed
+    search, with dither=False for the other.  Every refusal comes before the first device call."""
+    if keyed and not rule.dither:
+        raise ValueError("search='crop-keyed' reads a payload embedded with dither=True; this one has none: use search='crop'")
+    if not keyed and rule.dither:
         raise ValueError("resynchronising a dithered payload is not supported: keyed dither removes the grid's keyless "
                          "signal (search='crop' needs a payload embedded with dither=False); use search='crop-keyed'")
-    if n_bits > P.SYNC_MAX_BITS:
-        raise ValueError(f"search='crop' takes payloads of at most {P.SYNC_MAX_BITS} bits, this one has {n_bits}")
-    _check_crop_shape(stego_bgr, H, W)
-    nby, nbx = H // TILE, W // TILE
-    tbi = _payload_map_of(H, W, key, n_bits)[0].reshape(nby, nbx)
+    if not keyed and rule.carried > P.SYNC_MAX_BITS:
+        raise ValueError(f"search='crop' takes payloads of at most {P.SYNC_MAX_BITS} bits, this one has {rule.carried}")
+    if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
+        raise ValueError("stego must be uint8 [h, w, 3]")
+    F.check_crop_shape(*stego_bgr.shape[:2], rule.H, rule.W, "stego")
+    tbi = rule.map()[0].reshape(rule.grid)
+    table = P.dither_table(*rule.grid, rule.key).reshape(rule.grid) if keyed else None
     ctx = _ctx(device)
-    (py, px), place, votes = ctx.payload_locate(_Gray.planes_in(ctx, stego_bgr), tbi, n_bits, delta)
-    if place is None:                                                      # (cannot happen for h <= H, w <= W; the rule names it)
-        return b"", False, 0.0, None
-    ty, tx = place
-    soft, count = P.soft_of_votes(votes, tbi[ty:ty + votes.shape[0], tx:tx + votes.shape[1]], n_bits)
-    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
-    return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
-
-
-def _extract_payload_cropped_keyed(stego_bgr: np.ndarray, meta, H, W, delta, n_bits, code, key, device):
-    """search="crop-keyed" (include/wmhip.h, "keyed crop resynchronisation"): the stego is any axis-aligned crop of an image
-    marked with dither=True.  n_bits as above.  Every refusal comes before the first device call."""
-    if not M.payload_dither_of(meta):
-        raise ValueError("search='crop-keyed' reads a payload embedded with dither=True; this one has none: use search='crop'")
-    _check_crop_shape(stego_bgr, H, W)
-    nby, nbx = H // TILE, W // TILE
-    tbi = _payload_map_of(H, W, key, n_bits)[0].reshape(nby, nbx)
-    table = _payload_dither_of(H, W, key, True).reshape(nby, nbx)
-    ctx = _ctx(device)
-    (py, px), (ty, tx), s1 = ctx.payload_locate_keyed(_Gray.planes_in(ctx, stego_bgr), table, delta)
-    ny, nx = s1.shape
-    votes = P.keyed_votes(s1, table[ty:ty + ny, tx:tx + nx], delta)
-    soft, count = P.soft_of_votes(votes, tbi[ty:ty + ny, tx:tx + nx], n_bits)
-    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
-    return data, bool(valid), P.sync_confidence(soft, count), (TILE * ty - py, TILE * tx - px)
+    Y = _Gray.planes_in(ctx, stego_bgr)
+    if keyed:
+        (py, px), (ty, tx), s1 = ctx.payload_locate_keyed(Y, table, rule.delta)
+        votes = P.keyed_votes(s1, table[ty:ty + s1.shape[0], tx:tx + s1.shape[1]], rule.delta)
+    else:
+        (py, px), place, votes = ctx.payload_locate(Y, tbi, rule.carried, rule.delta)
+        if place is None:                                                  # (cannot happen for h <= H, w <= W; the rule names it)
+            return b"", False, 0.0, None
+        ty, tx = place
+    return F.search_tail(ctx, votes, py, px, ty, tx, tbi, rule.carried, rule.code)
 
 
 def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0, *, search=None):
@@ -513,19 +454,17 @@ def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: i
     (one keyed search over grid phase and place); each refuses the other's meta ("Crop
     resynchronisation" and "Keyed crop resynchronisation")."""
     _check_search(search)
-    meta, H, W, delta, n_bits, _, key = _payload_meta_checked(meta, password)
-    code = M.payload_code_of(meta)
-    n_bits = P.coded_bits(n_bits) if code else n_bits                      # from here on: the bits the tiles carry
-    if search == "crop":
-        return _extract_payload_cropped(stego_bgr, meta, H, W, delta, n_bits, code, key, device)
-    if search == "crop-keyed":
-        return _extract_payload_cropped_keyed(stego_bgr, meta, H, W, delta, n_bits, code, key, device)
-    _check_stego_shape(stego_bgr, meta)
-    _, order, offs = _payload_map_of(H, W, key, n_bits)
+    M.check_password_type(password, "extract")
+    M.require_password(password, "extract")
+    rule = F.checked_rule(meta, password)
+    if search is not None:
+        return _extract_payload_cropped(stego_bgr, rule, search == "crop-keyed", device)
+    _check_stego_shape(stego_bgr, dict(shape=(rule.H, rule.W)))
+    _, order, offs = rule.map()
     ctx = _ctx(device)
-    dz = _payload_dither_of(H, W, key, M.payload_dither_of(meta))
-    soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, n_bits, delta, dither=dz)
-    data, valid = P.payload_unframe(_payload_read(ctx, soft, code))
+    dz = P.dither_table(*rule.grid, rule.key) if rule.dither else None
+    soft = ctx.payload_soft(_Gray.planes_in(ctx, stego_bgr), order, offs, rule.carried, rule.delta, dither=dz)
+    data, valid = P.payload_unframe(F.read(ctx, soft, rule.code))
     return data, bool(valid), P.confidence(soft, offs, 1)
 
 

@@ -607,14 +607,15 @@ class Context:
         ent = self._cached("payload", (order.size, offs.size, _digest(order), _digest(offs)), upload)
         return ent["d"], ent["d_offs"]
 
-    def _payload_dither_dev(self, words: np.ndarray) -> int:
-        """Device copy of a dither table shared by the planes, cached by content: a video decodes batch after batch of
-        one frame size under few tables."""
+    def _cached_array(self, kind: str, arr: np.ndarray) -> int:
+        """Device copy of one array, cached by shape and content under ``kind``: "dither", a dither table shared by the
+        planes, always passed flat ([n_tiles]: a video decodes batch after batch of one frame size under few tables);
+        "payload_tbi", a tile-to-bit map [nby, nbx] (one image size under one key decodes crop after crop)."""
         def upload():
-            d = self.malloc(max(words.nbytes, 2))
-            self.h2d(d, words)
+            d = self.malloc(max(arr.nbytes, arr.itemsize))
+            self.h2d(d, arr)
             return {"d": d}
-        return self._cached("dither", (words.size, _digest(words)), upload)["d"]
+        return self._cached(kind, (arr.shape, _digest(arr)), upload)["d"]
 
     def payload_soft(self, planes: np.ndarray, order: np.ndarray, offs: np.ndarray, n_bits: int, delta: float,
                      dither=None) -> np.ndarray:
@@ -632,7 +633,7 @@ class Context:
             d_soft = dev.alloc(soft.nbytes)
             d_p, = dev.up(np.ascontiguousarray(planes.reshape(n, H, W)))
             if dz is not None:             # a shared table is cached; a per-plane one lives for this call only
-                dz = (self._payload_dither_dev(dz[0]) if dz[1] == 0 else dev.up(dz[0])[0], dz[1])
+                dz = (self._cached_array("dither", dz[0]) if dz[1] == 0 else dev.up(dz[0])[0], dz[1])
             self._payload_call("wm_payload_soft_tiles_u8_dev", (d_p,),
                                (_vp(d_order), _vp(d_offs), int(n_bits), _vp(d_soft), n, H, W, W, H * W), dz, delta)
             self.d2h(soft, d_soft)
@@ -698,14 +699,6 @@ class Context:
             self._call("wm_payload_offset_scores", _p(v), _p(t), _p(scores), ny, nx, nby, nbx, n_bits)
         return scores
 
-    def _payload_tbi_dev(self, t: np.ndarray) -> int:
-        """Device copy of a tile-to-bit map, cached by content (one image size under one key decodes crop after crop)."""
-        def upload():
-            d = self.malloc(max(t.nbytes, 4))
-            self.h2d(d, t)
-            return {"d": d}
-        return self._cached("payload_tbi", (t.shape, _digest(t)), upload)["d"]
-
     def payload_locate(self, plane: np.ndarray, tile_bit_index: np.ndarray, n_bits: int, delta: float):
         """The chain of the rule's steps 1-3 on one uint8 plane [h, w]: phase scan, pick_phase, offset scan on the winner's
         votes, pick_offset.  The votes stay on the device; the 64 sums, the scores and the winner's votes come back.
@@ -721,7 +714,7 @@ class Context:
         if pitch == 0:
             return None
         sums = np.zeros((8, 8), np.int64)
-        d_t = self._payload_tbi_dev(t) if t.size else 0
+        d_t = self._cached_array("payload_tbi", t) if t.size else 0
         with self._staging() as dev:
             d_votes, d_sums = dev.alloc(64 * pitch * 4), dev.alloc(sums.nbytes)
             d_p, = dev.up(np.ascontiguousarray(plane))
@@ -780,6 +773,21 @@ class Context:
         return u, h, w, nby, nbx, check_delta(delta)
 
     @staticmethod
+    def _packed_scans(scans, h: int, w: int, name: str) -> np.ndarray:
+        """float32 [len(scans), 64, pitch] as the keyed entry points read sigma_1 scans: scans[a][py][px] is the [ny_p, nx_p]
+        grid of phase (py, px) of an [h, w] plane (payload_sigma1_scan), checked against that shape; ``name`` is what a
+        refusal calls scan a ("{}" stands for a)."""
+        raw = np.zeros((len(scans), 64, (h // TILE) * (w // TILE)), np.float32)
+        for a, scan in enumerate(scans):
+            for p in range(64):
+                g = np.asarray(scan[p // 8][p % 8], np.float32)
+                want = (max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE)
+                if g.shape != want:
+                    raise ValueError(f"phase {divmod(p, 8)} of {name.format(a)} is {g.shape}, an {h} x {w} plane has {want}")
+                raw[a, p, :g.size] = g.reshape(-1)
+        return raw
+
+    @staticmethod
     def _keyed_grids(raw: np.ndarray, h: int, w: int, nby: int, nbx: int) -> list:
         """the 64 phases' own [nby - ny_p + 1, nbx - nx_p + 1] score grids out of [64, spitch]; [0, 0] without a window"""
         out = []
@@ -795,14 +803,7 @@ class Context:
         [nby - ny_p + 1, nbx - nx_p + 1] grids: score[ty, tx] = sum of |vote| of the phase's windows read on the lattices
         of the tiles (ty + r, tx + c).  A phase without a window has an empty grid."""
         u, h, w, nby, nbx, delta = self._keyed_args(table, h, w, delta)
-        pitch = (h // TILE) * (w // TILE)
-        raw = np.zeros((64, pitch), np.float32)
-        for p in range(64):
-            g = np.asarray(s1_scan[p // 8][p % 8], np.float32)
-            want = (max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE)
-            if g.shape != want:
-                raise ValueError(f"phase {divmod(p, 8)} of the scan is {g.shape}, an {h} x {w} plane has {want}")
-            raw[p, :g.size] = g.reshape(-1)
+        raw = self._packed_scans([s1_scan], h, w, "the scan")[0]
         scores = np.zeros((64, P.keyed_score_pitch(h, w, nby, nbx)), np.int64)
         self._call("wm_payload_keyed_scores", _p(raw), _p(u), _p(scores), h, w, nby, nbx, delta)
         return self._keyed_grids(scores, h, w, nby, nbx)
@@ -817,7 +818,7 @@ class Context:
         u, h, w, nby, nbx, delta = self._keyed_args(table, plane.shape[0], plane.shape[1], delta)
         pitch = (h // TILE) * (w // TILE)
         scores = np.zeros((64, P.keyed_score_pitch(h, w, nby, nbx)), np.int64)
-        d_u = self._payload_dither_dev(u.reshape(-1))
+        d_u = self._cached_array("dither", u.reshape(-1))
         with self._staging() as dev:
             d_s1, d_scores = dev.alloc(64 * pitch * 4), dev.alloc(scores.nbytes)
             d_p, = dev.up(np.ascontiguousarray(plane))
@@ -854,15 +855,7 @@ class Context:
         (the largest summed score, the row-major index of its first maximum), (-1, -1) where there is none."""
         n_anchor = len(s1_scans)
         u, tof, h, w, nby, nbx, delta = self._clip_args(tables, table_of, n_anchor, h, w, delta)
-        pitch = (h // TILE) * (w // TILE)
-        raw = np.zeros((n_anchor, 64, pitch), np.float32)
-        for a, scan in enumerate(s1_scans):
-            for p in range(64):
-                g = np.asarray(scan[p // 8][p % 8], np.float32)
-                want = (max(h - p // 8, 0) // TILE, max(w - p % 8, 0) // TILE)
-                if g.shape != want:
-                    raise ValueError(f"phase {divmod(p, 8)} of scan {a} is {g.shape}, an {h} x {w} plane has {want}")
-                raw[a, p, :g.size] = g.reshape(-1)
+        raw = self._packed_scans(s1_scans, h, w, "scan {}")
         best = np.zeros((tof.shape[0], 64, 2), np.int64)
         self._call("wm_payload_keyed_best", _p(raw), n_anchor, _p(u), u.shape[0], _p(tof), tof.shape[0], _p(best), h, w, nby, nbx, delta)
         return best

@@ -30,6 +30,7 @@ from . import hostapi
 from . import hostglue as hg
 from . import meta as M
 from . import payload as P
+from . import payload_flow as F
 from . import sharding
 
 TILE = M.TILE
@@ -544,19 +545,15 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
     delta = hostapi.check_delta(delta)
     code = P.check_code(code)
     data = P.payload_bytes(payload, payload_type)
-    bits = P.payload_frame(data)
-    carried = P.encode_k7(bits) if code else bits                          # what the tiles carry
     batch = max(1, int(batch))
     vid = Y4M(host_video_path)
     ctx = None
     try:
         H, W = vid.H, vid.W
-        P.check_capacity(carried.size, P.capacity_bits(H, W))              # before any device call
         if nonce is None:
             nonce = os.urandom(8)
         key = hg.derive_key(password, nonce)
-        tbi, order, offs = P.payload_map(H // TILE, W // TILE, key, carried.size)
-        tile_bit = P.tile_bits(carried, tbi)
+        bits, carried, _, order, offs, tile_bit = F.embed_plan(data, code, H, W, key)
         ctx = hostapi.Context(device)
         psnrs = []
         soft = np.zeros(carried.size, np.float64)
@@ -576,7 +573,7 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             n_frames = _embed_frame_loop(vid, out, frame_interval, batch, embed_marked)
         if verify and psnrs:
             try:
-                P.check_decodes(soft, bits, data, ctx.payload_decode(P.quantise_soft(soft))[0] if code else None)
+                P.check_decodes(soft, bits, data, F.read(ctx, soft, code) if code else None)
             except ValueError:
                 os.remove(output_video_path)
                 raise
@@ -606,41 +603,37 @@ def _count_frames(vid: Y4M) -> int:
     return n
 
 
-def _extract_payload_clip(vid: Y4M, data, key: bytes, H: int, W: int, n_bits: int, delta: float, code: int, fi: int, batch: int,
-                          device: int, anchors: int, return_soft: bool):
+def _extract_payload_clip(vid: Y4M, rule: F.Rule, batch: int, device: int, anchors: int, return_soft: bool):
     """search="clip" (include/wmhip.h, "clip resynchronisation"): the file is a run of consecutive frames of a video marked
-    with dither=True, every frame cropped to the same rectangle.  n_bits: the bits the tiles carry.  Every refusal comes
-    before the first device call; the frames are read once."""
-    if not M.payload_dither_of(data):
+    with dither=True, every frame cropped to the same rectangle.  Every refusal comes before the first device call; the
+    frames are read once."""
+    if not rule.dither:
         raise ValueError("search='clip' reads a payload embedded with dither=True; this one has none")
     anchors = int(anchors)
     if anchors < 1:
         raise ValueError(f"anchors must be at least 1, got {anchors}")
-    h, w, F = vid.H, vid.W, int(data["n_frames"])
-    if h > H or w > W:
-        raise ValueError(f"clip is {w}x{h}, larger than the {W}x{H} the meta was written for: not a crop of it")
-    if h < TILE or w < TILE:
-        raise ValueError(f"clip is {w}x{h}: a crop without a whole 8x8 tile carries nothing")
+    h, w, n_f = vid.H, vid.W, rule.n_frames
+    F.check_crop_shape(h, w, rule.H, rule.W, "clip")
     n_c = _count_frames(vid)
-    if n_c > F:
-        raise ValueError(f"clip has {n_c} frames, the marked video had {F}: not a cut of it")
+    if n_c > n_f:
+        raise ValueError(f"clip has {n_c} frames, the marked video had {n_f}: not a cut of it")
     if n_c < 1:
         raise ValueError("clip has no frame")
-    fi = max(1, fi)
-    nby, nbx = H // TILE, W // TILE
+    fi = max(1, rule.frame_interval)
+    nby, nbx = rule.grid
     A = min(n_c, anchors * fi)
-    table_of = P.clip_table_of(F, fi, n_c, A)
-    n_tables = (F + fi - 1) // fi
-    tables = P.dither_tables(nby, nbx, key, [k * fi for k in range(n_tables)]).reshape(n_tables, nby, nbx)
-    tbi = P.payload_map(nby, nbx, key, n_bits)[0].reshape(nby, nbx)
+    table_of = P.clip_table_of(n_f, fi, n_c, A)
+    n_tables = (n_f + fi - 1) // fi
+    tables = P.dither_tables(nby, nbx, rule.key, [k * fi for k in range(n_tables)]).reshape(n_tables, nby, nbx)
+    tbi = rule.map()[0].reshape(nby, nbx)
     frames = iter(vid)
     held = [y for _, (_, y, _) in zip(range(A), frames)]                   # the anchors, kept for the decode
     ctx = hostapi.Context(device)
     try:
-        _, win = ctx.payload_locate_clip(np.stack(held), tables, table_of, delta, pick=True)
+        _, win = ctx.payload_locate_clip(np.stack(held), tables, table_of, rule.delta, pick=True)
         if win is None:                                                    # (n_c < fi and no candidate with a marked frame among the anchors)
             out = (b"", False, 0.0, None, None)
-            return out + (np.zeros(n_bits, np.float64),) if return_soft else out
+            return out + (np.zeros(rule.carried, np.float64),) if return_soft else out
         t0, (py, px), (ty, tx) = win
         ny, nx = (h - py) // TILE, (w - px) // TILE
         votes = np.zeros((ny, nx), np.int64)
@@ -649,7 +642,7 @@ def _extract_payload_clip(vid: Y4M, data, key: bytes, H: int, W: int, n_bits: in
         def decode(pend):
             ys = np.stack([y[py:py + TILE * ny, px:px + TILE * nx] for _, y in pend])
             dz = np.stack([tables[(t0 + i) // fi, ty:ty + ny, tx:tx + nx].reshape(-1) for i, _ in pend])
-            m = ctx.payload_metric(ys, delta, dither=dz)
+            m = ctx.payload_metric(ys, rule.delta, dither=dz)
             np.add(votes, np.rint(m * np.float32(P.VOTE_ONE)).astype(np.int64).sum(axis=0), out=votes)
 
         pend = []
@@ -660,13 +653,10 @@ def _extract_payload_clip(vid: Y4M, data, key: bytes, H: int, W: int, n_bits: in
                     decode(pend); pend = []
         if pend:
             decode(pend)
-        soft, count = P.soft_of_votes(votes, tbi[ty:ty + ny, tx:tx + nx], n_bits)
-        read = ctx.payload_decode(P.quantise_soft(soft))[0] if code else soft < 0
+        out = F.search_tail(ctx, votes, py, px, ty, tx, tbi, rule.carried, rule.code, n_marked, return_soft)
     finally:
         ctx.close()
-    payload, valid = P.payload_unframe(read)
-    out = (payload, bool(valid), P.sync_confidence(soft, count * max(n_marked, 1)), (TILE * ty - py, TILE * tx - px), int(t0))
-    return out + (soft,) if return_soft else out
+    return out[:4] + (int(t0),) + out[4:]
 
 
 def _chain_frames(held, frames):
@@ -687,40 +677,25 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     if search not in VIDEO_SEARCHES:
         raise ValueError(f"search must be None or 'clip', got {search!r}")
     M.require_password(password, "extract")
-    data = M.load_payload_meta(metadata_path)
-    M.require_payload(data)
-    if "n_frames" not in data:
-        raise ValueError("metadata was not written by embed_payload_video")
-    key = hg.derive_key(password, M.nonce_of(data))
-    if not M.authentic(data, key):
-        raise ValueError(M.WRONG_PASSWORD)
-    H, W = map(int, data["shape"])
-    n_bits, delta = int(data["payload_bits"]), hostapi.check_delta(float(data["delta"]))
-    code = M.payload_code_of(data)
-    n_bits = P.coded_bits(n_bits) if code else n_bits                      # from here on: the bits the tiles carry
-    fi = int(data["frame_interval"])
+    rule = F.checked_rule(M.load_payload_meta(metadata_path), password, video=True)
+    H, W, fi = rule.H, rule.W, rule.frame_interval
     batch = max(1, int(batch))
-    if search == P.SEARCH_CLIP:
-        vid = Y4M(stego_video_path)
-        try:
-            return _extract_payload_clip(vid, data, key, H, W, n_bits, delta, code, fi, batch, device, anchors, return_soft)
-        finally:
-            vid.close()
-    _, order, offs = P.payload_map(H // TILE, W // TILE, key, n_bits)
-    dither = M.payload_dither_of(data)
     vid = Y4M(stego_video_path)
     ctx = None
     try:
+        if search == P.SEARCH_CLIP:
+            return _extract_payload_clip(vid, rule, batch, device, anchors, return_soft)
+        _, order, offs = rule.map()
         if (vid.H, vid.W) != (H, W):
             raise ValueError(f"video is {vid.W}x{vid.H} but the meta was written for {W}x{H}")
         ctx = hostapi.Context(device)
-        soft = np.zeros(n_bits, np.float64)
+        soft = np.zeros(rule.carried, np.float64)
         n_marked = 0
         for frames in _marked_batches(vid, fi, batch):
-            dz = _payload_frame_dithers(H, W, key, n_marked, len(frames), fi) if dither else None
-            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, n_bits, delta, dither=dz)
+            dz = _payload_frame_dithers(H, W, rule.key, n_marked, len(frames), fi) if rule.dither else None
+            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, rule.carried, rule.delta, dither=dz)
             n_marked += len(frames)
-        read = ctx.payload_decode(P.quantise_soft(soft))[0] if code else soft < 0   # (one decode of the summed values)
+        read = F.read(ctx, soft, rule.code)                                # (one decode of the summed values)
     finally:
         vid.close()
         if ctx is not None:
