@@ -52,6 +52,8 @@ struct wm_ctx {
   size_t extract_f32_bytes = 0;
   void* sigma_ws = nullptr;       // grow-only output of a sigma pass inside one call: the masked / payload embed's sigma_w
   size_t sigma_ws_bytes = 0;      // rows (k_sigma_pass -> the embed launches), or the payload decode's per-tile metric
+  void* resample_ws = nullptr;    // grow-only intermediate of the resampler (wm_resample.hip): the planes after the horizontal pass
+  size_t resample_ws_bytes = 0;
   static constexpr int MAX_PAIR_TABS = 6;   // round-robin tournaments of the block Jacobi, by block count
   void* pair_tab[MAX_PAIR_TABS] = {};
   int pair_tab_nbk[MAX_PAIR_TABS] = {};

@@ -1599,6 +1599,7 @@ int wm_destroy(wm_ctx* ctx) {
   if (ctx->route_tmp) (void)hipFree(ctx->route_tmp);
   if (ctx->extract_f32) (void)hipFree(ctx->extract_f32);
   if (ctx->sigma_ws) (void)hipFree(ctx->sigma_ws);
+  if (ctx->resample_ws) (void)hipFree(ctx->resample_ws);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) if (ctx->pair_tab[i]) (void)hipFree(ctx->pair_tab[i]);
   for (int i = 0; i < wm_ctx::MAX_PAIR_TABS; ++i) {
     if (ctx->hier_dev[i]) (void)hipFree(ctx->hier_dev[i]);

@@ -46,6 +46,7 @@ from . import hostglue as hg
 from . import meta as M
 from . import payload as P
 from . import payload_flow as F
+from . import resample as R
 
 K_FRAC_DEFAULT = hg.K_FRAC_DEFAULT
 TILE = 8
@@ -407,12 +408,34 @@ def embed_payload_arrays(cover_bgr: np.ndarray, data, password: str, nonce: byte
     return dict(stego=stego, meta=M.sealed(members, TILE, digest), psnr=ps, ssim=ss)
 
 
-SEARCHES = (None, "crop", "crop-keyed")
+SEARCHES = (None, "crop", "crop-keyed")                                   # the searches for a crop
+SEARCH_RESIZE = "resize"                                                   # no search: the meta's shape says what to restore
 
 
 def _check_search(search):
-    if search not in SEARCHES:
-        raise ValueError(f"search must be None, 'crop' or 'crop-keyed', got {search!r}")
+    if search not in SEARCHES + (SEARCH_RESIZE,):
+        raise ValueError(f"search must be None, 'crop', 'crop-keyed' or 'resize', got {search!r}")
+
+
+def _extract_payload_resized(stego_bgr: np.ndarray, rule: F.Rule, device: int):
+    """search="resize" (include/wmhip.h, "resize resynchronisation"): the stego is the whole marked image, resized to any
+    shape within resample.MAX_SCALE of the meta's on either axis.  Its luma - one plane, taken at the stego's own size - is
+    resampled back to the marked shape on the device and decoded as the meta says.  Every refusal comes before the first
+    device call."""
+    if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
+        raise ValueError("stego must be uint8 [h, w, 3]")
+    h, w = stego_bgr.shape[:2]
+    R.check_resize(h, w, rule.H, rule.W, "stego")
+    _, order, offs = rule.map()
+    ctx = _ctx(device)
+    dz = P.dither_table(*rule.grid, rule.key) if rule.dither else None
+    Y = _Gray.planes_in(ctx, stego_bgr)
+    if (h, w) == (rule.H, rule.W):                                         # nothing to restore: the plain extract
+        soft = ctx.payload_soft(Y, order, offs, rule.carried, rule.delta, dither=dz)
+    else:
+        soft = ctx.payload_soft_resized(Y, rule.H, rule.W, order, offs, rule.carried, rule.delta, dither=dz)
+    data, valid = P.payload_unframe(F.read(ctx, soft, rule.code))
+    return data, bool(valid), P.confidence(soft, offs, 1), (h / rule.H, w / rule.W)
 
 
 def _extract_payload_cropped(stego_bgr: np.ndarray, rule: F.Rule, keyed: bool, device: int):
@@ -452,11 +475,17 @@ def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: i
     confidence, origin) with origin = (y0, x0) of the crop in the marked image - meaningful where valid is True.
     ``search="crop"`` takes payloads embedded with dither=False, ``search="crop-keyed"`` those embedded with dither=True
     (one keyed search over grid phase and place); each refuses the other's meta ("Crop
-    resynchronisation" and "Keyed crop resynchronisation")."""
+    resynchronisation" and "Keyed crop resynchronisation").
+    ``search="resize"``: the stego may be the whole marked image resized to another shape, the aspect included, up to
+    resample.MAX_SCALE either way on either axis; it is resampled back to the meta's shape on the device and decoded as an
+    unresized one, dither and channel code as the meta says.  The result is (data, valid, confidence, scale) with scale =
+    (h / H, w / W); a stego of the meta's own shape gives the plain extract's values ("Resize resynchronisation")."""
     _check_search(search)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")
     rule = F.checked_rule(meta, password)
+    if search == SEARCH_RESIZE:
+        return _extract_payload_resized(stego_bgr, rule, device)
     if search is not None:
         return _extract_payload_cropped(stego_bgr, rule, search == "crop-keyed", device)
     _check_stego_shape(stego_bgr, dict(shape=(rule.H, rule.W)))
@@ -497,7 +526,8 @@ def extract_payload(stego_path: str, meta_path: str, out_path: Optional[str] = N
                     device: int = 0, search=None):
     """-> (data, valid, confidence, path written or None).  With ``out_path`` the payload is written as ``_text.txt`` /
     ``_data.json`` by the reference's renaming (core:229-242).  ``search="crop"`` / ``"crop-keyed"`` as in extract_payload_arrays: the stego
-    file may be a crop of the marked image, and the result is (data, valid, confidence, path, origin)."""
+    file may be a crop of the marked image, and the result is (data, valid, confidence, path, origin).  ``search="resize"``:
+    the file may be the marked image resized as a whole, and the result is (data, valid, confidence, path, scale)."""
     _check_search(search)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")

@@ -18,6 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import payload as P
+from . import resample as R
 
 WM_OK, WM_ERR_BADARG, WM_ERR_HIP, WM_ERR_NOCONV, WM_ERR_NOMEM = 0, 1, 2, 3, 4
 TILE = 8
@@ -97,6 +98,8 @@ _DECLARED = {
     "wm_payload_keyed_best*": [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f],
     # channel code: (llr, n_info, n_codewords, llr_stride, info_bits, final_metric, decisions)
     "wm_payload_decode_k7*": [_vp, _vp, _i, _i, _sz, _vp, _vp, _vp],
+    # resize resynchronisation: (src, dst, n_planes, h_in, w_in, src strides, h_out, w_out, dst strides, first_x, w_x, T_x, first_y, w_y, T_y)
+    "wm_resample_planes_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp, _i],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -907,6 +910,75 @@ class Context:
         g, p, i = win
         n_tx = nbx - (w - p % 8) // TILE + 1
         return best, (g, (p // 8, p % 8), (i // n_tx, i % n_tx))
+
+    # ---- resize resynchronisation of the blind payload (include/wmhip.h; the tap tables are resample.py's) ----------------
+    def resample_planes(self, planes: np.ndarray, H: int, W: int) -> np.ndarray:
+        """uint8 planes [h, w] / [N, h, w] (strided views are read in place) through the rule's integer filter -> uint8
+        [N?, H, W].  Host arrays in and out: for tests and tools; the extract keeps its planes on the device
+        (payload_soft_resized)."""
+        if planes.ndim == 3 and planes.shape[0] == 0 and planes.dtype == np.uint8:
+            n, (h, w) = 0, planes.shape[1:]                                 # (an empty batch has no strides to speak of)
+            rs, ps = w, h * w
+        else:
+            n, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        H, W = int(H), int(W)
+        R.check_resize(h, w, H, W, "planes")
+        (fx, wx), (fy, wy) = R.resample_taps(w, W), R.resample_taps(h, H)
+        out = np.zeros((n, H, W), np.uint8)
+        self._call("wm_resample_planes_u8", _p(planes), _p(out), n, h, w, rs, ps, H, W, W, H * W,
+                   _p(fx), _p(wx), wx.shape[1], _p(fy), _p(wy), wy.shape[1])
+        return out[0] if planes.ndim == 2 else out
+
+    def _resample_taps_dev(self, h: int, w: int, H: int, W: int) -> tuple:
+        """The device copies of the tap tables of an [h, w] -> [H, W] resize, as wm_resample_planes_u8_dev takes them behind
+        its plane arguments: (first_x, w_x, T_x, first_y, w_y, T_y).  One buffer, cached by content: a video decodes batch
+        after batch under one pair of tables."""
+        tabs = (*R.resample_taps(w, W), *R.resample_taps(h, H))
+
+        def upload():
+            offs = np.cumsum([0] + [(t.nbytes + 255) // 256 * 256 for t in tabs])
+            d = self.malloc(int(offs[-1]))
+            for o, t in zip(offs, tabs):
+                self.h2d(d + int(o), t)
+            return {"d": d, "at": [d + int(o) for o in offs[:4]]}
+        at = self._cached("resample", tuple((t.shape, _digest(t)) for t in tabs), upload)["at"]
+        return _vp(at[0]), _vp(at[1]), tabs[1].shape[1], _vp(at[2]), _vp(at[3]), tabs[3].shape[1]
+
+    def resample_planes_dev(self, src: int, dst: int, n_planes: int, h: int, w: int, src_row_stride: int, src_plane_stride: int,
+                            H: int, W: int, dst_row_stride: int, dst_plane_stride: int):
+        """wm_resample_planes_u8_dev on device addresses under the cached tables of the sizes; enqueued, not synchronised"""
+        R.check_resize(h, w, H, W, "planes")
+        self._call("wm_resample_planes_u8_dev", _vp(src), _vp(dst), n_planes, h, w, src_row_stride, src_plane_stride, H, W,
+                   dst_row_stride, dst_plane_stride, *self._resample_taps_dev(h, w, H, W))
+
+    def payload_soft_resized(self, planes: np.ndarray, H: int, W: int, order: np.ndarray, offs: np.ndarray, n_bits: int,
+                             delta: float, dither=None) -> np.ndarray:
+        """payload_soft of uint8 planes [h, w] / [N, h, w] that are a marked [H, W] frame resized as a whole: upload,
+        the rule's resample back to [H, W] and the soft decode in one staging scope.  The restored planes never leave the
+        device (rows 16-byte multiples apart, so the resampler stores whole lines); only n_bits doubles come back."""
+        delta = check_delta(delta)
+        n, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        H, W = int(H), int(W)
+        R.check_resize(h, w, H, W, "planes")
+        n_tiles = (H // TILE) * (W // TILE)
+        order, offs = check_payload_csr(order, offs, n_bits, n_tiles)
+        dz = _dither_words(dither, n, n_tiles)
+        soft = np.zeros(int(n_bits), np.float64)
+        if n == 0:
+            return soft
+        d_order, d_offs = self._payload_csr_dev(order, offs)
+        pitch = (W + 15) // 16 * 16
+        with self._staging() as dev:
+            d_soft, d_out = dev.alloc(soft.nbytes), dev.alloc(n * H * pitch)
+            d_p, = dev.up(np.ascontiguousarray(planes.reshape(n, h, w)))
+            if dz is not None:
+                dz = (self._cached_array("dither", dz[0]) if dz[1] == 0 else dev.up(dz[0])[0], dz[1])
+            self.resample_planes_dev(d_p, d_out, n, h, w, w, h * w, H, W, pitch, H * pitch)
+            self._payload_call("wm_payload_soft_tiles_u8_dev", (d_out,),
+                               (_vp(d_order), _vp(d_offs), int(n_bits), _vp(d_soft), n, H, W, pitch, H * pitch), dz, delta)
+            self.d2h(soft, d_soft)
+            self.check_status()
+        return soft
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

@@ -31,6 +31,7 @@ from . import hostglue as hg
 from . import meta as M
 from . import payload as P
 from . import payload_flow as F
+from . import resample as R
 from . import sharding
 
 TILE = M.TILE
@@ -587,7 +588,8 @@ def embed_payload_video(host_video_path: str, payload, output_video_path: str, m
             ctx.close()
 
 
-VIDEO_SEARCHES = (None, P.SEARCH_CLIP)
+VIDEO_SEARCHES = (None, P.SEARCH_CLIP)                                     # the search for a cut, cropped clip
+SEARCH_RESIZE = "resize"                                                   # no search: the meta's shape says what to restore
 
 
 def _count_frames(vid: Y4M) -> int:
@@ -673,9 +675,13 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     axis-aligned rectangle (a payload embedded with dither=True).  The first frame, the tile grid and the crop's place are
     searched for on the device over the first ``anchors`` marked frames' worth of the clip, and the result is (data, valid,
     confidence, origin, first_frame): origin = (y0, x0) of the crop in the marked frames, first_frame the clip's first frame
-    in the marked file - meaningful where valid is True ("Clip resynchronisation")."""
-    if search not in VIDEO_SEARCHES:
-        raise ValueError(f"search must be None or 'clip', got {search!r}")
+    in the marked file - meaningful where valid is True ("Clip resynchronisation").
+    ``search="resize"``: the file may be the marked video with every frame resized to another size, the frames' number and
+    order unchanged.  Each batch of marked luma frames is resampled back to the meta's size on the device in one call and
+    decoded as unresized frames; the result is the plain one followed by scale = (h / H, w / W), ahead of the soft vector
+    where that is asked for ("Resize resynchronisation")."""
+    if search not in VIDEO_SEARCHES + (SEARCH_RESIZE,):
+        raise ValueError(f"search must be None, 'clip' or 'resize', got {search!r}")
     M.require_password(password, "extract")
     rule = F.checked_rule(M.load_payload_meta(metadata_path), password, video=True)
     H, W, fi = rule.H, rule.W, rule.frame_interval
@@ -686,14 +692,21 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
         if search == P.SEARCH_CLIP:
             return _extract_payload_clip(vid, rule, batch, device, anchors, return_soft)
         _, order, offs = rule.map()
-        if (vid.H, vid.W) != (H, W):
+        resized = search == SEARCH_RESIZE and (vid.H, vid.W) != (H, W)
+        if search == SEARCH_RESIZE:
+            R.check_resize(vid.H, vid.W, H, W, "video")
+        elif (vid.H, vid.W) != (H, W):
             raise ValueError(f"video is {vid.W}x{vid.H} but the meta was written for {W}x{H}")
         ctx = hostapi.Context(device)
         soft = np.zeros(rule.carried, np.float64)
         n_marked = 0
         for frames in _marked_batches(vid, fi, batch):
             dz = _payload_frame_dithers(H, W, rule.key, n_marked, len(frames), fi) if rule.dither else None
-            soft += ctx.payload_soft(np.stack([y for y, _ in frames]), order, offs, rule.carried, rule.delta, dither=dz)
+            ys = np.stack([y for y, _ in frames])
+            if resized:
+                soft += ctx.payload_soft_resized(ys, H, W, order, offs, rule.carried, rule.delta, dither=dz)
+            else:
+                soft += ctx.payload_soft(ys, order, offs, rule.carried, rule.delta, dither=dz)
             n_marked += len(frames)
         read = F.read(ctx, soft, rule.code)                                # (one decode of the summed values)
     finally:
@@ -702,4 +715,6 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
             ctx.close()
     payload, valid = P.payload_unframe(read)
     out = (payload, bool(valid), P.confidence(soft, offs, n_marked))
+    if search == SEARCH_RESIZE:
+        out += ((vid.H / H, vid.W / W),)
     return out + (soft,) if return_soft else out

@@ -496,6 +496,42 @@ int wm_payload_decode_k7_dev(wm_ctx* ctx, const int32_t* llr, int n_info, int n_
 int wm_payload_decode_k7(wm_ctx* ctx, const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, uint8_t* info_bits,
                          int32_t* final_metric, uint64_t* decisions);
 
+/* ---- Blind payload, resize resynchronisation: a stego that was resized as a whole --
+ * sigma_1 of an 8x8 tile is dominated by 8 x the tile's mean, and a smooth resize followed by a smooth resize back to the
+ * marked size moves that mean very little.  The meta holds the marked shape (H, W), so a whole-frame resize needs no
+ * search: the stego's luma is resampled back to H x W by the filter below and decoded as an unresized one (DESIGN.md,
+ * "Resize resynchronisation").  The filter is separable and integer, so the device and a NumPy restatement agree to the bit.
+ * The horizontal pass runs first, into a uint8 intermediate [h_in][w_out]; then the vertical pass.  Each pass rounds to uint8.
+ *
+ * Taps of one axis, n_in -> n_out samples, float64 on the host (resample.py: resample_taps):
+ *   scale = n_in / n_out;  fs = max(scale, 1);  sup = 2 fs;  T = 2 ceil(sup) + 1        (5 when enlarging, at most 33)
+ *   output i:  c = (i + 0.5) scale;  lo = max(0, int(c - sup + 0.5));  hi = min(n_in, int(c + sup + 0.5))
+ *              f_k = cubic((k + 0.5 - c) / fs) for k in [lo, hi), cubic the Catmull-Rom kernel with a = -0.5:
+ *                ((a + 2) |x| - (a + 3)) x^2 + 1 for |x| < 1,  a (((|x| - 5) |x| + 8) |x| - 4) for 1 <= |x| < 2,  0 otherwise
+ *              the f_k normalised to sum 1;  iw_k = rint(f_k 2^14);  the residue 2^14 - sum iw is added to the largest tap,
+ *              the first of equals: a constant row stays constant to the byte
+ *   first[i] = lo;  w[i][0 .. hi - lo) = iw, the rest of the row of T is 0
+ * A pixel:  acc = sum over t < T of w[i][t] * px[min(first[i] + t, n_in - 1)]  in int32 (|acc| < 2^23)
+ *           out = clip((acc + 2^13) >> 14, 0, 255)  with an arithmetic (floor) shift
+ * n_in == n_out gives w = 2^14 at the centre: the pass is the identity.  Neither axis may change by more than 8x.
+ *
+ *   src      [n_planes] uint8 planes [h_in][w_in], src_row_stride / src_plane_stride in elements
+ *   dst      [n_planes] uint8 planes [h_out][w_out] (out), dst_row_stride / dst_plane_stride in elements; never in place
+ *   first_x  [w_out] int32, w_x [w_out][T_x] int16: the horizontal taps (w_in -> w_out)
+ *   first_y  [h_out] int32, w_y [h_out][T_y] int16: the vertical taps (h_in -> h_out)
+ * The intermediate lives in a buffer the context owns.  An index first[i] + t outside the source reads its last sample: the
+ * device does not trust the tables.  n_planes == 0 returns WM_OK without a launch.  WM_ERR_BADARG, before any launch: NULL
+ * pointers, non-positive sizes, more than 65535 rows or planes, a ratio beyond 8 on either axis, strides smaller than a row
+ * or a plane, T outside 1..33, an odd-addressed w or a first off a 4-byte boundary.  A destination whose base or strides are
+ * not multiples of 16 is written byte by byte. */
+int wm_resample_planes_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h_in, int w_in, int src_row_stride,
+                              size_t src_plane_stride, int h_out, int w_out, int dst_row_stride, size_t dst_plane_stride,
+                              const int32_t* first_x, const int16_t* w_x, int T_x, const int32_t* first_y, const int16_t* w_y,
+                              int T_y);
+int wm_resample_planes_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h_in, int w_in, int src_row_stride,
+                          size_t src_plane_stride, int h_out, int w_out, int dst_row_stride, size_t dst_plane_stride,
+                          const int32_t* first_x, const int16_t* w_x, int T_x, const int32_t* first_y, const int16_t* w_y, int T_y);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
