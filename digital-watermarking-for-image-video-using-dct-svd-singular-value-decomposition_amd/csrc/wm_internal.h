@@ -1,10 +1,11 @@
 // Internal declarations shared by the translation units of libwmhip.so
-// (wmhip.hip: tile-mode kernels + context; wm_ref.hip: full-frame mode).
+// (wmhip.hip: tile-mode kernels + context; wm_payload.hip: blind payload; wm_ref.hip: full-frame mode).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 
+#include <functional>
 #include <type_traits>
 
 #include "../../include/wmhip.h"
@@ -101,6 +102,13 @@ inline int use_ctx(const wm_ctx* ctx) {
 }
 // grow-only device buffer (synchronises the stream before freeing the old one)
 int grow(wm_ctx* ctx, void** buf, size_t* have, size_t bytes, const char* what);
+// wmhip.hip: the checks every entry point over a batch of strided planes starts with (makes the context's device current)
+int check_plane_args(const wm_ctx* ctx, const void* p, int n_planes, int H, int W, int row_stride, size_t plane_stride);
+// wmhip.hip: the embed fed with a sigma_w derived from the cover - the masked embed, and the payload embed of wm_payload.hip.
+// `pass(eff, black)` enqueues the caller's sigma pass (described at the definition)
+int embed_derived_dev(wm_ctx* ctx, const uint8_t* host, uint8_t* stego, float* sigma_c, float* yw, int n_planes, int H, int W,
+                      int row_stride, size_t plane_stride, float alpha, int K, const char* missing,
+                      const std::function<int(float*, uint8_t*)>& pass);
 // arrays carved out of such a buffer, each on a 256-byte line.  base == nullptr is the sizing pass: the same takes return
 // nullptr and pad256(off) is what the buffer must hold
 struct Carve {
@@ -158,16 +166,44 @@ int staged_call(wm_ctx* ctx, Lay&& lay, Dev&& dev, bool sync_only = false) {
   WM_HIP(hipStreamSynchronize(ctx->stream));
   return WM_OK;
 }
+// elements from the first sample of the first plane to the last sample of the last one
+inline size_t plane_span(int n_planes, int H, int row_stride, size_t plane_stride, int W) {
+  if (n_planes == 0 || H == 0) return 0;
+  return (size_t)(n_planes - 1) * plane_stride + (size_t)(H - 1) * row_stride + (size_t)W;
+}
+// The round trip of the plain, the masked and the payload embed.  `rule` is the per-tile input of the form (sigma_w, or
+// the payload's tile bits: n_rule elements), dev(d_host, d_rule, d_stego, d_sc, d_yw) its _dev call.  `more(cv)` stages
+// what a form takes beside them (the payload's dither table) behind the shared arrays.
+template <typename T, typename Dev, typename More>
+int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_rule, uint8_t* stego, float* sigma_c, float* yw,
+                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev, const More& more) {
+  const size_t nt = (size_t)(H / 8) * (W / 8);
+  const size_t span = plane_span(n_planes, H, row_stride, plane_stride, W);
+  uint8_t *d_host, *d_stego; T* d_rule; float *d_sc, *d_yw;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_host = cv.in(span, host);
+    // bytes between rows / planes that belong to the caller must survive the round trip, so stego goes up first; in place,
+    // host and stego are ONE device array (k_copy_border and in-place embedding rely on the equal pointers)
+    d_stego = cv.take<uint8_t>(span);
+    if (stego != host) cv.up(d_stego, stego, span);
+    else d_stego = d_host;
+    cv.down(stego, d_stego, span);
+    d_rule = cv.in(n_rule, rule);
+    d_sc = cv.out((size_t)n_planes * nt * 8, sigma_c);
+    d_yw = yw ? cv.out((size_t)n_planes * H * W, yw) : nullptr;
+    more(cv);
+  }, [&] { return dev(d_host, d_rule, d_stego, d_sc, d_yw); });
+}
+template <typename T, typename Dev>
+int embed_round_trip(wm_ctx* ctx, const uint8_t* host, const T* rule, size_t n_rule, uint8_t* stego, float* sigma_c, float* yw,
+                     int n_planes, int H, int W, int row_stride, size_t plane_stride, const Dev& dev) {
+  return embed_round_trip(ctx, host, rule, n_rule, stego, sigma_c, yw, n_planes, H, W, row_stride, plane_stride, dev, [](Carve&) {});
+}
 // runtime bools as template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})
 template <typename F> void with_bools(F&& f) { f(); }
 template <typename F, typename... Bs> void with_bools(F&& f, bool b, Bs... rest) {
   if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
   else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
-// elements from the first sample of the first plane to the last sample of the last one
-inline size_t plane_span(int n_planes, int H, int row_stride, size_t plane_stride, int W) {
-  if (n_planes == 0 || H == 0) return 0;
-  return (size_t)(n_planes - 1) * plane_stride + (size_t)(H - 1) * row_stride + (size_t)W;
 }
 // wm_ref.hip: releases the host part of a two-level tournament table (wm_ctx::hier_host)
 void hier_host_free(void* tab);

@@ -32,7 +32,7 @@ TIES += TRIPS
 
 
 def _lanes_over_windows(w, nbx):
-    """the entry point's choice (csrc/wmhip.hip), restated only to see that the shapes below take both kernels"""
+    """the entry point's choice (csrc/wm_payload.hip), restated only to see that the shapes below take both kernels"""
     nx, n_tx = w // 8, nbx - w // 8 + 1
     return nx * ((n_tx + 63) // 64) >= 2 * n_tx * ((nx + 63) // 64)
 

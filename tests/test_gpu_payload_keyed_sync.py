@@ -107,7 +107,7 @@ def _scores_against_restatement(gpu_ctx, scan, U, h, w, delta, exact=True):
 
 
 def _lanes_over_windows(w, nbx):
-    """the entry point's choice (csrc/wmhip.hip): a lane per window of a row where that fills at least twice as many of a
+    """the entry point's choice (csrc/wm_payload.hip): a lane per window of a row where that fills at least twice as many of a
     wave's 64 lanes as a lane per placement - restated here only to see that the shapes below take both kernels"""
     nx, n_tx = w // 8, nbx - w // 8 + 1
     return nx * ((n_tx + 63) // 64) >= 2 * n_tx * ((nx + 63) // 64)

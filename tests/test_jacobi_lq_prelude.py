@@ -18,7 +18,7 @@ import emu_jacobi_asm as emu          # noqa: E402
 
 CSRC = os.path.join(ROOT, "digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd", "csrc")
 
-# (conv2, skip2, min_sweeps, skip_from): what embed_group / sigma_tile_dev of csrc/wmhip.hip pass to the stream; the
+# (conv2, skip2, min_sweeps, skip_from): what embed_group (csrc/wmhip.hip) / sigma_tile_dev (csrc/wm_tile_pass.h) pass to the stream; the
 # fifth entry chooses the generated stream (1) or the baseline the test generates for itself (0)
 EMBED = (1e-7, 1e-12, 4, 3, 1)
 SIGMA = (1e-2, 1e-8, 3, 2, 1)

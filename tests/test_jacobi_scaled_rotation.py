@@ -18,7 +18,7 @@ import jacobi_stream_cost as cost     # noqa: E402
 import scaled_rotation_inputs as inp  # noqa: E402
 
 CSRC = os.path.join(ROOT, "digital-watermarking-for-image-video-using-dct-svd-singular-value-decomposition_amd", "csrc")
-EMBED = (1e-7, 1e-12, 4, 3)           # (conv2, skip2, min_sweeps, skip_from) of embed_group / sigma_tile_dev (csrc/wmhip.hip)
+EMBED = (1e-7, 1e-12, 4, 3)           # (conv2, skip2, min_sweeps, skip_from) of embed_group (csrc/wmhip.hip) / sigma_tile_dev (csrc/wm_tile_pass.h)
 SIGMA = (1e-2, 1e-8, 3, 2)
 CFG = {"embed": EMBED, "sigma": SIGMA}
 

@@ -45,8 +45,8 @@ CODEC_FRAME_CAP = 65535             # launch_frame_codec: (unsigned)min(n_frames
 COLOR_PX_PER_GROUP, COLOR_GROUPS_PER_BLOCK = 16, 256     # k_color: n_groups = n_px / 16, n_full = n_groups / 256
 COLOR_BLOCK_TRIP = GRID_FOR_CAP                 # color_dispatch: grid_for(n_px / 16 + 1); staged loop: blk += gridDim.x
 COLOR_GROUP_TRIP = GRID_FOR_CAP * GRID_FOR_BLOCK  # direct loop: gidx += gridDim.x * blockDim.x -> 524 288 groups = 8 388 608 px
-KEYED_STEP = 8                      # wmhip.hip, keyed_placement_sum: constexpr int STEP = 8;
-CLIP_CHUNK = 1023                   # wmhip.hip, wm_payload_keyed_best_dev: constexpr int CHUNK = 1023;
+KEYED_STEP = 8                      # wm_payload.hip, keyed_placement_sum: constexpr int STEP = 8;
+CLIP_CHUNK = 1023                   # wm_payload.hip, wm_payload_keyed_best_dev: constexpr int CHUNK = 1023;
 CLIP_TABLE_BYTES = 64 << 20         # hostapi.py, Context: CLIP_TABLE_BYTES = 64 << 20
 
 SOURCE = [      # (what, file, the statement, the shapes that move with it)
@@ -65,9 +65,9 @@ SOURCE = [      # (what, file, the statement, the shapes that move with it)
     ("frame codec frame stride", "wm_pixel.hip", "for (int fr = blockIdx.y; fr < n_frames; fr += gridDim.y)", "CODEC_FRAME_CASES"),
     ("colour grid", "wm_pixel.hip", "const dim3 grid(grid_for(n_px / 16 + 1)), block(256);", "COLOUR_SHAPE"),
     ("colour staged blocks", "wm_pixel.hip", "const size_t n_full = OUT3 ? n_groups / 256 : 0;", "COLOUR_SHAPE"),
-    ("keyed placement step", "wmhip.hip", "constexpr int STEP = 8;", "KEYED_PLACEMENT"),
-    ("keyed window stride", "wmhip.hip", "for (int c = threadIdx.x; c < nx; c += WAVE)", "KEYED_WINDOWS"),
-    ("clip candidates per launch", "wmhip.hip", "constexpr int CHUNK = 1023;", "CLIP_CHUNK_CANDS"),
+    ("keyed placement step", "wm_payload.hip", "constexpr int STEP = 8;", "KEYED_PLACEMENT"),
+    ("keyed window stride", "wm_payload.hip", "for (int c = threadIdx.x; c < nx; c += WAVE)", "KEYED_WINDOWS"),
+    ("clip candidates per launch", "wm_payload.hip", "constexpr int CHUNK = 1023;", "CLIP_CHUNK_CANDS"),
     ("clip tables per call", "hostapi.py", "CLIP_TABLE_BYTES = 64 << 20", "CLIP_CHUNK_CANDS (payload_locate_clip)"),
 ]
 
@@ -120,7 +120,7 @@ def fb_caps(n_tiles: int, n_planes: int):
 
 
 def lanes_over_windows(w: int, nbx: int) -> bool:
-    """the keyed entry points' choice of mapping (wmhip.hip: `windows`), as the GPU tests restate it"""
+    """the keyed entry points' choice of mapping (wm_payload.hip: `windows`), as the GPU tests restate it"""
     nx, n_tx = w // 8, nbx - w // 8 + 1
     return nx * ((n_tx + 63) // 64) >= 2 * n_tx * ((nx + 63) // 64)
 

@@ -339,7 +339,7 @@ if __name__ == "__main__":
     tiles[0] = (yy + xx) % 2 * 255
     tiles[1] = 9
     tiles[2] = 0
-    for conv, skip, mn, sf in ((1e-7, 1e-12, 4, 3), (1e-2, 1e-8, 3, 2)):      # embed, sigma-only (csrc/wmhip.hip)
+    for conv, skip, mn, sf in ((1e-7, 1e-12, 4, 3), (1e-2, 1e-8, 3, 2)):      # embed (csrc/wmhip.hip), sigma-only (csrc/wm_tile_pass.h)
         a, n2, more, sw = run(tiles, conv, skip, mn, sf)
         ref = np.linalg.svd(tiles.astype(np.float64), compute_uv=False)
         err = np.abs(np.sqrt(np.maximum(n2, 0)) - ref) / ref[:, :1].clip(1)

@@ -23,7 +23,7 @@ import emu_jacobi_asm as emu
 # v_dot4_u32_u8 and v_cvt_f32_u32 (one class, "dot4"): 1.77 / 1.73 ns per wave-instruction at three waves per SIMD
 # against 1.19 for v_mul_f32 and 1.9-2.4 for the packed classes in the same run (profiles/r08_ubench_dot4.log) - 1.5 v_mul
 PRICE = {"valu": 2.35, "v_pk_mul_f32": 4.3, "v_pk_fma_f32": 5.3, "trans": 8.0, "dot4": 3.5}
-CONFIGS = {"embed": (1e-7, 1e-12, 4, 3), "sigma": (1e-2, 1e-8, 3, 2)}       # what csrc/wmhip.hip passes to the stream
+CONFIGS = {"embed": (1e-7, 1e-12, 4, 3), "sigma": (1e-2, 1e-8, 3, 2)}       # what csrc/wmhip.hip / wm_tile_pass.h pass to the stream
 
 
 def noise_waves():

@@ -117,7 +117,7 @@ LANE_MAPPINGS = {False: "k_payload_keyed_scan: a wave owns 64 consecutive tx of 
 
 
 def lanes_over_windows(w, nbx):
-    """the entry points' choice between their two kernels (csrc/wmhip.hip, keyed_launch), restated for the record"""
+    """the entry points' choice between their two kernels (csrc/wm_payload.hip, keyed_launch), restated for the record"""
     nx, n_tx = w // 8, nbx - w // 8 + 1
     return nx * ((n_tx + 63) // 64) >= 2 * n_tx * ((nx + 63) // 64)
 
