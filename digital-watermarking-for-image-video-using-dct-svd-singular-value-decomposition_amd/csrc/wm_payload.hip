@@ -424,6 +424,52 @@ __global__ __launch_bounds__(WAVE) void k_payload_viterbi(const int32_t* __restr
   }
 }
 
+// Angle scores (include/wmhip.h, "rotation resynchronisation"): per candidate rotation the sum of payload_vote(|m|) over the
+// tiles of the restored H x W plane whose whole footprint lies inside the h x w source, and their number.  Grid (2048-tile
+// strips, candidates); a lane owns 8 tiles, 256 apart, and for each: the rule's validity test at the tile's four corner pixels (the map is affine, so
+// the interior follows), its vote, then wave_sum and one integer atomic per wave into scores[a] / counts[a], which the entry
+// point zeroed.  Integer sums: the same inputs give the same bits in any order.  valid (may be NULL): the test's outcome,
+// one byte a tile.
+struct AngleGeom {
+  int h, w, H, W, nbx, n_tiles;
+};
+
+__device__ __forceinline__ bool angle_corner_ok(const AngleGeom& g, const int C, const int S, const int y, const int x) {
+  const unsigned X2 = (unsigned)(2 * x + 1 - g.W), Y2 = (unsigned)(2 * y + 1 - g.H);
+  const int U = (int)((unsigned)C * X2 - (unsigned)S * Y2 + ((unsigned)(g.w - 1) << 16));
+  const int V = (int)((unsigned)S * X2 + (unsigned)C * Y2 + ((unsigned)(g.h - 1) << 16));
+  const int x0 = U >> 17, y0 = V >> 17;
+  return x0 >= 1 && x0 + 2 <= g.w - 1 && y0 >= 1 && y0 + 2 <= g.h - 1;
+}
+
+constexpr int ANGLE_THREADS = 256;
+constexpr int ANGLE_TRIPS = 8;       // tiles a lane takes, 256 apart: 2048 tiles a workgroup, so few waves meet at a candidate's sums
+
+__global__ __launch_bounds__(ANGLE_THREADS) void k_payload_angle_scores(const float* __restrict__ metric, const int32_t* __restrict__ cand,
+                                                                    unsigned long long* __restrict__ scores, int* __restrict__ counts,
+                                                                    uint8_t* __restrict__ valid, const AngleGeom g) {
+  const int a = blockIdx.y;
+  const int C = cand[2 * a], S = cand[2 * a + 1];
+  int v = 0, n = 0;                  // (8 votes of at most 2^15 stay far below 2^31)
+#pragma unroll 2
+  for (int k = 0; k < ANGLE_TRIPS; ++k) {
+    const int t = (blockIdx.x * ANGLE_TRIPS + k) * ANGLE_THREADS + threadIdx.x;
+    if (t >= g.n_tiles) break;
+    const int r = t / g.nbx, c = t - r * g.nbx;
+    const bool ok = angle_corner_ok(g, C, S, 8 * r, 8 * c) && angle_corner_ok(g, C, S, 8 * r, 8 * c + 7) &&
+                    angle_corner_ok(g, C, S, 8 * r + 7, 8 * c) && angle_corner_ok(g, C, S, 8 * r + 7, 8 * c + 7);
+    const size_t i = (size_t)a * g.n_tiles + t;
+    if (ok) v += wm::payload_vote(fabsf(metric[i])), n += 1;
+    if (valid) valid[i] = ok ? 1 : 0;
+  }
+  const long long vs = wave_sum((long long)v);
+  n = wave_sum(n);
+  if ((threadIdx.x & (WAVE - 1)) == 0 && n) {
+    atomicAdd(scores + a, (unsigned long long)vs);
+    atomicAdd(counts + a, n);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host-side argument checking / launch helpers
 // ---------------------------------------------------------------------------
@@ -695,6 +741,33 @@ int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const 
   return WM_OK;
 }
 
+// ---- rotation resynchronisation: the angle scores ---------------------------------
+// the sizes and pointers of a score call, checked (both forms, before any launch or copy)
+static int check_angle_scores(const float* metric, const int32_t* cand, int n_angles, const int64_t* scores, const int32_t* counts,
+                              int h, int w, int H, int W) {
+  if (h < 1 || w < 1 || H < 1 || W < 1 || h > 8192 || w > 8192 || H > 8192 || W > 8192)
+    return set_err(WM_ERR_BADARG, "a rotation takes sides in 1..8192");
+  if (H % 8 || W % 8) return set_err(WM_ERR_BADARG, "the restored plane's H and W must be multiples of 8");
+  if (n_angles < 1 || n_angles > 65535) return set_err(WM_ERR_BADARG, "n_angles must be in 1..65535");
+  if (!metric || !cand || !scores || !counts) return set_err(WM_ERR_BADARG, "metric / candidates / scores / counts is NULL");
+  return WM_OK;
+}
+
+int wm_payload_angle_scores_dev(wm_ctx* ctx, const float* metric, const int32_t* cand, int n_angles, int64_t* scores, int32_t* counts,
+                                uint8_t* valid, int h, int w, int H, int W) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_angle_scores(metric, cand, n_angles, scores, counts, h, w, H, W));
+  if ((((uintptr_t)metric | (uintptr_t)cand | (uintptr_t)counts) & 3u) || ((uintptr_t)scores & 7u))
+    return set_err(WM_ERR_BADARG, "metric / candidates / scores / counts is misaligned");
+  WM_HIP(hipMemsetAsync(scores, 0, (size_t)n_angles * sizeof(int64_t), ctx->stream));
+  WM_HIP(hipMemsetAsync(counts, 0, (size_t)n_angles * sizeof(int32_t), ctx->stream));
+  const AngleGeom g{h, w, H, W, W / 8, (H / 8) * (W / 8)};
+  hipLaunchKernelGGL(k_payload_angle_scores, dim3((unsigned)((g.n_tiles + ANGLE_THREADS * ANGLE_TRIPS - 1) / (ANGLE_THREADS * ANGLE_TRIPS)), (unsigned)n_angles),
+                     dim3(ANGLE_THREADS), 0, ctx->stream, metric, cand, reinterpret_cast<unsigned long long*>(scores), counts, valid, g);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
 // ---- channel code: the Viterbi decode -----------------------------------------
 // the sizes of a decode, checked (both forms, before any launch or copy)
 static int check_k7_sizes(const int32_t* llr, int n_info, int n_codewords, size_t llr_stride, const uint8_t* info_bits) {
@@ -945,6 +1018,22 @@ int wm_payload_keyed_best(wm_ctx* ctx, const float* s1, int n_anchor, const uint
     d_of = cv.in(n_of, table_of);
     d_best = cv.out((size_t)n_cand * 128, best);
   }, [&] { return wm_payload_keyed_best_dev(ctx, d_s1, n_anchor, d_u, n_tables, d_of, n_cand, d_best, h, w, nby, nbx, delta); }, true);
+}
+
+// ---- rotation resynchronisation, host pointers -----------------------------------
+int wm_payload_angle_scores(wm_ctx* ctx, const float* metric, const int32_t* cand, int n_angles, int64_t* scores, int32_t* counts,
+                            uint8_t* valid, int h, int w, int H, int W) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_angle_scores(metric, cand, n_angles, scores, counts, h, w, H, W));
+  const size_t n = (size_t)n_angles * (size_t)(H / 8) * (size_t)(W / 8);
+  float* d_m; int32_t *d_c, *d_n; int64_t* d_s; uint8_t* d_v;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_m = cv.in(n, metric);
+    d_c = cv.in((size_t)2 * n_angles, cand);
+    d_s = cv.out((size_t)n_angles, scores);
+    d_n = cv.out((size_t)n_angles, counts);
+    d_v = valid ? cv.out(n, valid) : nullptr;
+  }, [&] { return wm_payload_angle_scores_dev(ctx, d_m, d_c, n_angles, d_s, d_n, d_v, h, w, H, W); }, true);
 }
 
 // ---- channel code, host pointers ------------------------------------------------

@@ -22,6 +22,8 @@
 // No grid is capped: (column blocks, rows, planes), rows and planes at most 65535.  The only strided loops are the LDS
 // form's staging loops, 256 elements a trip, which take several trips at any width above 256.
 // The device does not trust `first`: an index outside the source clamps to its last sample, as the rule's min() does.
+//
+// Below them, k_rotate_planes: the integer rotation of the rotation resynchronisation, one pass, described where it stands.
 #include "wm_internal.h"
 
 using namespace wmi;
@@ -183,9 +185,161 @@ int check_resample(const wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_pl
   return check_taps(first_y, w_y, T_y, "vertical");
 }
 
+// ---------------------------------------------------------------------------
+// Rotation resynchronisation (include/wmhip.h, "rotation resynchronisation"): n_angles candidate rotations of n_planes planes
+// ---------------------------------------------------------------------------
+// A workgroup makes one 32 x 32 block of one destination plane dst[a][p]; a lane makes 4 adjacent pixels of one row of it.  The
+// map is affine, so the block's source footprint is the bounding box of its four corners' 4 x 4 windows: the corners differ
+// by 31 (|C| + |S|) 2^-16 < 43.85 pixels on either axis, so x0 takes at most 45 values and the box is at most 48 x 48
+// (RT_SEG).  The box comes into LDS by byte loads, a row of it per 64 lanes, its indices clamped to the source there - once,
+// so a pixel's 16 taps need no clamp of their own beyond the one that keeps an untrusted candidate inside the segment - and K
+// by one 8-byte load a lane.  A tap is an LDS byte and a 24-bit multiply-add; the 4 pixels leave as one dword where the
+// destination's base and strides are multiples of 4 and the lane's pixels are all inside the plane, byte by byte otherwise.
+// Integers only, no atomics, no scratch.  Grid (column blocks, row blocks, n_angles * n_planes): nothing capped, no strided
+// loop but the staging one, which takes 12 trips at any angle.
+constexpr int RT_BLOCK = 32;
+constexpr int RT_PX = 4;
+constexpr int RT_SEG = 48;
+constexpr int RT_PHASES = 256;
+
+struct RotGeom {
+  int h, w, H, W, n_planes;
+  int src_row_stride, dst_row_stride;
+  size_t src_plane_stride, dst_plane_stride;
+};
+
+// (U, V) of destination pixel (y, x) under candidate (C, S), in 2^-17 source pixels.  Unsigned products: an untrusted
+// candidate wraps, it does not overflow.
+__device__ __forceinline__ void rot_uv(const RotGeom& g, const int C, const int S, const int y, const int x, int& U, int& V) {
+  const unsigned X2 = (unsigned)(2 * x + 1 - g.W), Y2 = (unsigned)(2 * y + 1 - g.H);
+  U = (int)((unsigned)C * X2 - (unsigned)S * Y2 + ((unsigned)(g.w - 1) << 16));
+  V = (int)((unsigned)S * X2 + (unsigned)C * Y2 + ((unsigned)(g.h - 1) << 16));
+}
+
+__global__ __launch_bounds__(RS_NT) void k_rotate_planes(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const RotGeom g,
+                                                         const int32_t* __restrict__ cand, const int16_t* __restrict__ K,
+                                                         const int dst4) {
+  __shared__ __attribute__((aligned(16))) uint8_t seg[RT_SEG * RT_SEG];
+  __shared__ __attribute__((aligned(16))) int16_t kl[RT_PHASES * 4];
+  const int a = blockIdx.z / g.n_planes, p = blockIdx.z - a * g.n_planes;
+  const int C = cand[2 * a], S = cand[2 * a + 1];
+  const int bx = blockIdx.x * RT_BLOCK, by = blockIdx.y * RT_BLOCK;
+  // the footprint: the least and the largest x0 - 1 / y0 - 1 of the block's corners (the same in every lane)
+  int x_lo = INT32_MAX, y_lo = INT32_MAX, x_hi = INT32_MIN, y_hi = INT32_MIN;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int U, V;
+    rot_uv(g, C, S, by + (c >> 1) * (RT_BLOCK - 1), bx + (c & 1) * (RT_BLOCK - 1), U, V);
+    x_lo = min(x_lo, (U >> 17) - 1); x_hi = max(x_hi, (U >> 17) - 1);
+    y_lo = min(y_lo, (V >> 17) - 1); y_hi = max(y_hi, (V >> 17) - 1);
+  }
+  const int nc = min(x_hi - x_lo + 4, RT_SEG), nr = min(y_hi - y_lo + 4, RT_SEG);
+  const uint8_t* s = src + (size_t)p * g.src_plane_stride;
+  {
+    const int c = threadIdx.x & 63;
+    if (c < nc) {
+      const int sx = min(max(x_lo + c, 0), g.w - 1);
+      for (int r = threadIdx.x >> 6; r < nr; r += RS_NT / 64)
+        seg[r * RT_SEG + c] = s[(size_t)min(max(y_lo + r, 0), g.h - 1) * g.src_row_stride + sx];
+    }
+  }
+  reinterpret_cast<uint2*>(kl)[threadIdx.x] = reinterpret_cast<const uint2*>(K)[threadIdx.x];
+  __syncthreads();
+  const int y = by + (int)(threadIdx.x >> 3), x4 = bx + (int)(threadIdx.x & 7) * RT_PX;
+  if (y >= g.H || x4 >= g.W) return;
+  int U, V;
+  rot_uv(g, C, S, y, x4, U, V);
+  unsigned packed = 0;
+#pragma unroll
+  for (int k = 0; k < RT_PX; ++k, U = (int)((unsigned)U + 2u * (unsigned)C), V = (int)((unsigned)V + 2u * (unsigned)S)) {
+    const int cx = (U >> 17) - 1 - x_lo, cy = (V >> 17) - 1 - y_lo;
+    const int16_t* kx = kl + ((U >> 9) & 255) * 4;
+    const int16_t* ky = kl + ((V >> 9) & 255) * 4;
+    int col[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) col[i] = min(max(cx + i, 0), RT_SEG - 1);
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint8_t* row = seg + min(max(cy + j, 0), RT_SEG - 1) * RT_SEG;
+      int r = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r = __mul24((int)row[col[i]], (int)kx[i]) + r;
+      acc = __mul24((r + (1 << 7)) >> 8, (int)ky[j]) + acc;
+    }
+    packed |= (unsigned)min(max((acc + (1 << 19)) >> 20, 0), 255) << (8 * k);
+  }
+  uint8_t* d = dst + ((size_t)a * g.n_planes + p) * g.dst_plane_stride + (size_t)y * g.dst_row_stride + x4;
+  if (dst4 && x4 + RT_PX <= g.W) {
+    *reinterpret_cast<unsigned*>(d) = packed;
+  } else {
+    const int n = min(RT_PX, g.W - x4);
+#pragma unroll
+    for (int k = 0; k < RT_PX; ++k)
+      if (k < n) d[k] = (uint8_t)(packed >> (8 * k));
+  }
+}
+
+constexpr int ROT_MAX_SIDE = 8192;
+
+// what both forms refuse, in one place
+int check_rotate(const wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h, int w, int src_row_stride,
+                 size_t src_plane_stride, int H, int W, int dst_row_stride, size_t dst_plane_stride, const int32_t* cand, int n_angles,
+                 const int16_t* K) {
+  WM_TRY(use_ctx(ctx));
+  if (h < 1 || w < 1 || H < 1 || W < 1 || h > ROT_MAX_SIDE || w > ROT_MAX_SIDE || H > ROT_MAX_SIDE || W > ROT_MAX_SIDE)
+    return set_err(WM_ERR_BADARG, "a rotation takes sides in 1..8192");
+  if (n_angles < 1) return set_err(WM_ERR_BADARG, "n_angles must be at least 1");
+  if (n_planes < 1 || (long long)n_planes * n_angles > 65535) return set_err(WM_ERR_BADARG, "n_planes must be at least 1 and n_angles * n_planes at most 65535");
+  if (!src || !dst || !cand || !K) return set_err(WM_ERR_BADARG, "src / dst / candidates / K is NULL");
+  if (src_row_stride < w || dst_row_stride < W) return set_err(WM_ERR_BADARG, "row_stride smaller than a row");
+  if ((n_planes > 1 && src_plane_stride < plane_span(1, h, src_row_stride, 0, w)) ||
+      ((long long)n_planes * n_angles > 1 && dst_plane_stride < plane_span(1, H, dst_row_stride, 0, W)))
+    return set_err(WM_ERR_BADARG, "plane_stride smaller than one plane");
+  return WM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wm_rotate_planes_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h, int w, int src_row_stride,
+                            size_t src_plane_stride, int H, int W, int dst_row_stride, size_t dst_plane_stride, const int32_t* cand,
+                            int n_angles, const int16_t* K) {
+  WM_TRY(check_rotate(ctx, src, dst, n_planes, h, w, src_row_stride, src_plane_stride, H, W, dst_row_stride, dst_plane_stride, cand,
+                      n_angles, K));
+  if (((uintptr_t)cand & 3u) || ((uintptr_t)K & 7u)) return set_err(WM_ERR_BADARG, "candidates / K is misaligned (4 / 8 bytes)");
+  const RotGeom g{h, w, H, W, n_planes, src_row_stride, dst_row_stride, src_plane_stride, dst_plane_stride};
+  const int dst4 = (((uintptr_t)dst | (uintptr_t)dst_row_stride | (n_planes * n_angles > 1 ? (uintptr_t)dst_plane_stride : 0)) & 3u) == 0;
+  const dim3 grid((unsigned)((W + RT_BLOCK - 1) / RT_BLOCK), (unsigned)((H + RT_BLOCK - 1) / RT_BLOCK), (unsigned)(n_planes * n_angles));
+  hipLaunchKernelGGL(k_rotate_planes, grid, dim3(RS_NT), 0, ctx->stream, src, dst, g, cand, K, dst4);
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
+int wm_rotate_planes_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h, int w, int src_row_stride,
+                        size_t src_plane_stride, int H, int W, int dst_row_stride, size_t dst_plane_stride, const int32_t* cand,
+                        int n_angles, const int16_t* K) {
+  WM_TRY(check_rotate(ctx, src, dst, n_planes, h, w, src_row_stride, src_plane_stride, H, W, dst_row_stride, dst_plane_stride, cand,
+                      n_angles, K));
+  // the destination is staged dense (its gaps on the host are neither read nor written) and copied back row by row
+  const size_t dense = (size_t)H * W, n_out = (size_t)n_planes * n_angles;
+  uint8_t *d_src, *d_dst; int32_t* d_cand; int16_t* d_K;
+  WM_TRY(staged_call(ctx, [&](Carve& cv) {
+    d_src = cv.in(plane_span(n_planes, h, src_row_stride, src_plane_stride, w), src);
+    d_dst = cv.take<uint8_t>(dense * n_out);
+    d_cand = cv.in((size_t)2 * n_angles, cand);
+    d_K = cv.in((size_t)RT_PHASES * 4, K);
+  }, [&] {
+    WM_TRY(wm_rotate_planes_u8_dev(ctx, d_src, d_dst, n_planes, h, w, src_row_stride, src_plane_stride, H, W, W, dense, d_cand, n_angles,
+                                   d_K));
+    for (size_t q = 0; q < n_out; ++q)
+      WM_HIP(hipMemcpy2DAsync(dst + q * dst_plane_stride, (size_t)dst_row_stride, d_dst + q * dense, (size_t)W, (size_t)W, (size_t)H,
+                              hipMemcpyDeviceToHost, ctx->stream));
+    return WM_OK;
+  }, true));
+  return WM_OK;
+}
 
 int wm_resample_planes_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h_in, int w_in, int src_row_stride,
                               size_t src_plane_stride, int h_out, int w_out, int dst_row_stride, size_t dst_plane_stride,

@@ -412,9 +412,36 @@ SEARCHES = (None, "crop", "crop-keyed")                                   # the 
 SEARCH_RESIZE = "resize"                                                   # no search: the meta's shape says what to restore
 
 
-def _check_search(search):
-    if search not in SEARCHES + (SEARCH_RESIZE,):
-        raise ValueError(f"search must be None, 'crop', 'crop-keyed' or 'resize', got {search!r}")
+SEARCH_ROTATE = "rotate"                                                   # the one number the meta does not hold: the angle
+
+
+def _check_search(search, max_angle=None):
+    if search not in SEARCHES + (SEARCH_RESIZE, SEARCH_ROTATE):
+        raise ValueError(f"search must be None, 'crop', 'crop-keyed', 'resize' or 'rotate', got {search!r}")
+    if max_angle is not None and search != SEARCH_ROTATE:
+        raise ValueError("max_angle goes with search='rotate' only")
+    if search == SEARCH_ROTATE:
+        P.check_max_angle(P.MAX_ANGLE_DEFAULT if max_angle is None else max_angle)
+
+
+def _extract_payload_rotated(stego_bgr: np.ndarray, rule: F.Rule, max_angle: float, device: int):
+    """search="rotate" (include/wmhip.h, "rotation resynchronisation"): the stego is the whole marked image rotated about its
+    centre by at most ``max_angle`` degrees, on a canvas of the marked size (corners cut) or an expanded one.  The angle is
+    searched for on the device - every candidate rotates the luma back, the plain metric reads it - and the winner is
+    decoded as the meta says, the tiles whose footprint leaves the stego not voting.  Every refusal comes before the first
+    device call."""
+    if stego_bgr.dtype != np.uint8 or stego_bgr.ndim != 3 or stego_bgr.shape[2] != 3:
+        raise ValueError("stego must be uint8 [h, w, 3]")
+    R.check_rotate(*stego_bgr.shape[:2], rule.H, rule.W, "stego")
+    tbi = rule.map()[0].reshape(rule.grid)
+    dz = P.dither_table(*rule.grid, rule.key) if rule.dither else None
+    ctx = _ctx(device)
+    found = ctx.payload_locate_angle(_Gray.planes_in(ctx, stego_bgr), rule.H, rule.W, max_angle, rule.delta, dither=dz)
+    if found is None:                                                      # no candidate has a whole tile inside the stego
+        return b"", False, 0.0, None
+    theta, m, tile_ok, _ = found
+    data, valid, conf, _ = F.search_tail(ctx, P.votes_of_metric(m, tile_ok), 0, 0, 0, 0, tbi, rule.carried, rule.code)
+    return data, valid, conf, float(np.degrees(theta))
 
 
 def _extract_payload_resized(stego_bgr: np.ndarray, rule: F.Rule, device: int):
@@ -467,7 +494,7 @@ def _extract_payload_cropped(stego_bgr: np.ndarray, rule: F.Rule, keyed: bool, d
     return F.search_tail(ctx, votes, py, px, ty, tx, tbi, rule.carried, rule.code)
 
 
-def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0, *, search=None):
+def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: int = 0, *, search=None, max_angle=None):
     """-> (data bytes, valid, confidence).  valid: the decoded frame's length header and CRC hold.  confidence: the mean
     over the bits of |soft| / (tiles voting), 1 for an untouched stego and near 0 for an image that carries nothing.
     ``search="crop"``: the stego may be any axis-aligned crop of the marked image (h <= H, w <= W, origin anywhere); the
@@ -479,13 +506,20 @@ def extract_payload_arrays(stego_bgr: np.ndarray, meta, password: str, device: i
     ``search="resize"``: the stego may be the whole marked image resized to another shape, the aspect included, up to
     resample.MAX_SCALE either way on either axis; it is resampled back to the meta's shape on the device and decoded as an
     unresized one, dither and channel code as the meta says.  The result is (data, valid, confidence, scale) with scale =
-    (h / H, w / W); a stego of the meta's own shape gives the plain extract's values ("Resize resynchronisation")."""
-    _check_search(search)
+    (h / H, w / W); a stego of the meta's own shape gives the plain extract's values ("Resize resynchronisation").
+    ``search="rotate"``: the stego may be the whole marked image rotated about its centre by up to ``max_angle`` degrees
+    (10 by default, at most 45), on a canvas of the marked size or an expanded one; the angle is searched for on the device
+    and the winner decoded, dither and channel code as the meta says.  The result is (data, valid, confidence, angle), angle
+    the winning candidate's theta in degrees in the rule's sense - the rotation that was undone ("Rotation
+    resynchronisation").  ``max_angle`` goes with this search only."""
+    _check_search(search, max_angle)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")
     rule = F.checked_rule(meta, password)
     if search == SEARCH_RESIZE:
         return _extract_payload_resized(stego_bgr, rule, device)
+    if search == SEARCH_ROTATE:
+        return _extract_payload_rotated(stego_bgr, rule, P.MAX_ANGLE_DEFAULT if max_angle is None else float(max_angle), device)
     if search is not None:
         return _extract_payload_cropped(stego_bgr, rule, search == "crop-keyed", device)
     _check_stego_shape(stego_bgr, dict(shape=(rule.H, rule.W)))
@@ -523,16 +557,19 @@ def embed_payload(cover_path: str, payload, out_path: str, meta_path: str, *, pa
 
 
 def extract_payload(stego_path: str, meta_path: str, out_path: Optional[str] = None, *, password: Optional[str] = None,
-                    device: int = 0, search=None):
+                    device: int = 0, search=None, max_angle=None):
     """-> (data, valid, confidence, path written or None).  With ``out_path`` the payload is written as ``_text.txt`` /
     ``_data.json`` by the reference's renaming (core:229-242).  ``search="crop"`` / ``"crop-keyed"`` as in extract_payload_arrays: the stego
     file may be a crop of the marked image, and the result is (data, valid, confidence, path, origin).  ``search="resize"``:
-    the file may be the marked image resized as a whole, and the result is (data, valid, confidence, path, scale)."""
-    _check_search(search)
+    the file may be the marked image resized as a whole, and the result is (data, valid, confidence, path, scale).
+    ``search="rotate"``, with ``max_angle`` degrees (10 by default): the file may be the marked image rotated about its centre,
+    and the result is (data, valid, confidence, path, angle)."""
+    _check_search(search, max_angle)
     M.check_password_type(password, "extract")
     M.require_password(password, "extract")
     meta = M.load_payload_meta(meta_path)
-    data, valid, conf, *origin = extract_payload_arrays(hg.read_image_bgr(stego_path), meta, password, device, search=search)
+    data, valid, conf, *origin = extract_payload_arrays(hg.read_image_bgr(stego_path), meta, password, device, search=search,
+                                                           max_angle=max_angle)
     written = P.write_payload(out_path, data, str(meta["payload_type"])) if out_path else None
     return (data, valid, conf, written, *origin)
 

@@ -100,6 +100,10 @@ _DECLARED = {
     "wm_payload_decode_k7*": [_vp, _vp, _i, _i, _sz, _vp, _vp, _vp],
     # resize resynchronisation: (src, dst, n_planes, h_in, w_in, src strides, h_out, w_out, dst strides, first_x, w_x, T_x, first_y, w_y, T_y)
     "wm_resample_planes_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp, _i],
+    # rotation resynchronisation: (src, dst, n_planes, h, w, src strides, H, W, dst strides, cand, n_angles, K);
+    # (metric, cand, n_angles, scores, counts, valid, h, w, H, W)
+    "wm_rotate_planes_u8*": [_vp, _vp, _vp, _i, _i, _i, _i, _sz, _i, _i, _i, _sz, _vp, _i, _vp],
+    "wm_payload_angle_scores*": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i],
     "wm_ref_embed_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i],
     "wm_ref_sigma_u8": [_vp, _vp, _vp, _i, _i, _i],
     "wm_ref_last_sweeps": [_vp, C.POINTER(_i)],
@@ -979,6 +983,116 @@ class Context:
             self.d2h(soft, d_soft)
             self.check_status()
         return soft
+
+    # ---- rotation resynchronisation of the blind payload (include/wmhip.h; weights and candidates are resample.py's, the
+    # schedule and the winner's rule payload.py's) -------------------------------------------------------------------------
+    ROTATE_PLANE_BYTES = 256 << 20                   # device memory payload_locate_angle spends on one chunk's restored planes
+
+    @staticmethod
+    def _angle_cands(cands) -> np.ndarray:
+        c = np.asarray(cands)
+        if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1 or c.dtype.kind not in "iu":
+            raise ValueError("candidates must be integers [n_angles >= 1, 2]: (C, S) of every angle")
+        return np.ascontiguousarray(c, np.int32)
+
+    @staticmethod
+    def _rotate_sizes(h: int, w: int, H, W, tiles: bool) -> tuple:
+        H, W = int(H), int(W)
+        R.check_rotate(h, w, H, W, "planes")
+        if tiles and (H % TILE or W % TILE):
+            raise ValueError(f"the restored frame is {W}x{H}: both sides must be multiples of {TILE}")
+        return H, W
+
+    def rotate_planes(self, planes: np.ndarray, H: int, W: int, cands) -> np.ndarray:
+        """uint8 planes [h, w] / [N, h, w] (strided views are read in place) rotated onto an [H, W] frame about the common
+        centre under every candidate (C, S) of ``cands`` int [n_angles, 2] -> uint8 [n_angles, N?, H, W].  Host arrays in and
+        out: for tests and tools; the search keeps its planes on the device (payload_locate_angle)."""
+        n, h, w, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")
+        H, W = self._rotate_sizes(h, w, H, W, False)
+        c = self._angle_cands(cands)
+        if n < 1:
+            raise ValueError("a rotation takes at least one plane")
+        out = np.zeros((c.shape[0], n, H, W), np.uint8)
+        self._call("wm_rotate_planes_u8", _p(planes), _p(out), n, h, w, rs, ps, H, W, W, H * W, _p(c), c.shape[0],
+                   _p(np.ascontiguousarray(R.rotate_weights())))
+        return out[:, 0] if planes.ndim == 2 else out
+
+    def payload_angle_scores(self, metric: np.ndarray, cands, h: int, w: int) -> tuple:
+        """The candidates' scores over the metrics float32 [n_angles, nby, nbx] of their restored planes, which came from an
+        [h, w] source -> (scores int64 [n_angles], counts int32 [n_angles], valid bool [n_angles, nby, nbx]): the sum of
+        rint(|m| 2^15) over a candidate's valid tiles, their number, and which they are."""
+        c = self._angle_cands(cands)
+        m = np.asarray(metric)
+        if m.dtype != np.float32 or m.ndim != 3 or m.shape[0] != c.shape[0]:
+            raise ValueError(f"metric must be float32 [n_angles = {c.shape[0]}, nby, nbx]")
+        m = np.ascontiguousarray(m)
+        _, nby, nbx = m.shape
+        self._rotate_sizes(int(h), int(w), TILE * nby, TILE * nbx, True)
+        scores, counts = np.zeros(c.shape[0], np.int64), np.zeros(c.shape[0], np.int32)
+        valid = np.zeros(m.shape, np.uint8)
+        self._call("wm_payload_angle_scores", _p(m), _p(c), c.shape[0], _p(scores), _p(counts), _p(valid), int(h), int(w),
+                   TILE * nby, TILE * nbx)
+        return scores, counts, valid.astype(bool)
+
+    def payload_locate_angle(self, plane: np.ndarray, H: int, W: int, max_angle: float, delta: float, dither=None):
+        """The rule's search on one uint8 plane [h, w], a marked [H, W] frame rotated about its centre by at most
+        ``max_angle`` degrees: the coarse and the fine stage of payload.angle_candidates, each candidate rotated back,
+        read by the plain metric (``dither``: the frame's shared table, uint16 [n_tiles], or None) and scored, all resident;
+        the candidates go in chunks whose restored planes stay within ROTATE_PLANE_BYTES, and the fine winner is run once more
+        alone for its metrics and mask.  Only the scores, the counts and those come back.  -> (theta in radians, metric float32 [nby, nbx], valid bool [nby, nbx],
+        stages), stages = [(numerators, denominator, scores, counts, winner's index)] of the two stages; None where no
+        candidate has a valid tile."""
+        delta = check_delta(delta)
+        if plane.ndim != 2:
+            raise ValueError("plane must be [h, w]")
+        _, h, w, rs, ps = _planes_of(plane, np.uint8, "plane must be uint8")
+        H, W = self._rotate_sizes(h, w, H, W, True)
+        max_angle = P.check_max_angle(max_angle)
+        nby, nbx = H // TILE, W // TILE
+        n_tiles = nby * nbx
+        dz = _dither_words(dither, 1, n_tiles)
+        if dz is not None and dz[1] != 0:
+            dz = (dz[0].reshape(-1), 0)                                    # (one plane: a [1, n_tiles] table is the shared one)
+        pitch = (W + 15) // 16 * 16
+        per = max(1, self.ROTATE_PLANE_BYTES // (H * pitch))
+        d_K = self._cached_array("rotate_k", R.rotate_weights())
+        if dz is not None:
+            dz = (self._cached_array("dither", dz[0]), 0)
+        stages, around = [], None
+        with self._staging() as dev:
+            d_p, = dev.up(np.ascontiguousarray(plane))
+            for stage in range(2):
+                nums, den = P.angle_candidates(H, W, max_angle, around)
+                cs = R.angle_candidates_cs(nums / den)
+                n = cs.shape[0]
+                scores, counts = np.zeros(n, np.int64), np.zeros(n, np.int32)
+                with self._staging() as run:
+                    d_out, d_m, d_v = run.alloc(min(per, n) * H * pitch), run.alloc(min(per, n) * n_tiles * 4), run.alloc(n_tiles)
+                    d_s, d_n = run.alloc(scores.nbytes), run.alloc(counts.nbytes)
+                    d_c, = run.up(cs)
+
+                    def chunk(a0, k, d_valid):                             # candidates a0 .. a0 + k - 1: restored, read, scored
+                        self._call("wm_rotate_planes_u8_dev", _vp(d_p), _vp(d_out), 1, h, w, w, h * w, H, W, pitch, H * pitch,
+                                   _vp(d_c + 8 * a0), k, _vp(d_K))
+                        self._payload_call("wm_payload_metric_tiles_u8_dev", (d_out,), (_vp(d_m), k, H, W, pitch, H * pitch), dz, delta)
+                        self._call("wm_payload_angle_scores_dev", _vp(d_m), _vp(d_c + 8 * a0), k, _vp(d_s + 8 * a0), _vp(d_n + 4 * a0),
+                                   _vp(d_valid) if d_valid else None, h, w, H, W)
+                    for a0 in range(0, n, per):
+                        chunk(a0, min(per, n - a0), 0)
+                    self.d2h(scores, d_s); self.d2h(counts, d_n)
+                    self.check_status()
+                    win = P.pick_angle(scores, counts)
+                    stages.append((nums, den, scores, counts, win))
+                    if win is None:
+                        return None
+                    if stage == 0:
+                        around = int(nums[win])
+                        continue
+                    chunk(win, 1, d_v)                                     # the winner once more, alone: its metrics and mask
+                    m, valid = np.empty((nby, nbx), np.float32), np.empty((nby, nbx), np.uint8)
+                    self.d2h(m, d_m); self.d2h(valid, d_v)
+                    self.sync()
+        return float(nums[win] / den), m, valid.astype(bool), stages
 
     def sigma_tiles(self, planes: np.ndarray) -> np.ndarray:
         n, H, W, rs, ps = _planes_of(planes, np.uint8, "planes must be uint8")

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import hashlib
 import json
+import math
 import os
 import zlib
 
@@ -211,8 +212,56 @@ def keyed_votes(s1, u, delta: float) -> np.ndarray:
     return np.rint(m * F(VOTE_ONE)).astype(np.int32)
 
 
+# ---- rotation resynchronisation (include/wmhip.h): a stego rotated about its centre ----------------
+ANGLE_FINE = 8                                      # fine steps in a coarse one
+MAX_ANGLE_DEFAULT, MAX_ANGLE_LIMIT = 10.0, 45.0     # degrees
+
+
+def check_max_angle(max_angle) -> float:
+    """the search's reach in degrees, in (0, 45], or a ValueError"""
+    try:
+        a = float(max_angle)
+    except (TypeError, ValueError):
+        raise ValueError("max_angle must be a number of degrees") from None
+    if not (0.0 < a <= MAX_ANGLE_LIMIT):                                   # (NaN fails both comparisons)
+        raise ValueError(f"max_angle must lie in (0, {MAX_ANGLE_LIMIT:g}] degrees, got {max_angle}")
+    return a
+
+
+def angle_candidates(H: int, W: int, max_angle: float, around=None) -> tuple:
+    """The search's schedule on an H x W frame, R = hypot(H, W) / 2: an angle error of 1 / R rad moves a corner tile by a pixel.
+    -> (numerators int64 [n], denominator): theta = numerator / denominator rad.  Coarse (``around`` None): k / R for
+    |k| <= floor(radians(max_angle) R).  Fine: (8 k* + j) / (8 R) for |j| <= 8 around the coarse winner's k* = ``around``."""
+    Rr = math.hypot(int(H), int(W)) / 2.0
+    if around is None:
+        n = int(math.floor(math.radians(check_max_angle(max_angle)) * Rr))
+        return np.arange(-n, n + 1, dtype=np.int64), Rr
+    return ANGLE_FINE * int(around) + np.arange(-ANGLE_FINE, ANGLE_FINE + 1, dtype=np.int64), ANGLE_FINE * Rr
+
+
+def pick_angle(scores, counts):
+    """The candidate with the largest scores / counts, compared exactly (cross-multiplied Python integers); ties go to the
+    smallest index; a candidate with count 0 takes no part.  None when every count is 0."""
+    s = np.asarray(scores).reshape(-1)
+    n = np.asarray(counts).reshape(-1)
+    if s.size != n.size:
+        raise ValueError(f"{s.size} scores for {n.size} counts")
+    best = None
+    for a in range(s.size):
+        sa, ca = int(s[a]), int(n[a])
+        if ca > 0 and (best is None or sa * best[2] > best[1] * ca):
+            best = (a, sa, ca)
+    return None if best is None else best[0]
+
+
+def votes_of_metric(m, valid=None) -> np.ndarray:
+    """int32 votes rint(m 2^15) of float32 metrics, 0 where ``valid`` (same shape) is false: a tile that does not vote"""
+    v = np.rint(np.asarray(m, np.float32) * np.float32(VOTE_ONE)).astype(np.int32)
+    return v if valid is None else np.where(np.asarray(valid) != 0, v, 0).astype(np.int32)
+
+
 # ---- clip resynchronisation (include/wmhip.h, DESIGN.md section 14): a dithered video's clip, cut in time and cropped ------
-SEARCH_CLIP = "clip"                                # extract_payload_video's ``search`` value
+SEARCH_CLIP = "clip"                               # extract_payload_video's ``search`` value
 CLIP_ANCHORS = 4                                    # marked anchor frames a candidate's score adds up, by default
 
 

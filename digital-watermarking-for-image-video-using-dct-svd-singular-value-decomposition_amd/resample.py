@@ -10,6 +10,9 @@ One axis, n_in -> n_out samples:
     first[i] = lo;  w[i] = the iw_k, then zeros
     out[i] = clip((sum_t w[i][t] px[min(first[i] + t, n_in - 1)] + 2^13) >> 14, 0, 255)      (int32, a floor shift)
 A plane goes through the horizontal pass into a uint8 intermediate, then through the vertical one.
+
+Below, for the rotation resynchronisation ("rotation resynchronisation" there): the 256-phase weight table K of the integer
+rotation and the (C, S) = rint((cos, sin) 2^16) of a candidate angle.
 """
 from __future__ import annotations
 
@@ -68,6 +71,41 @@ def resample_taps(n_in: int, n_out: int) -> tuple:
     """(first int32 [n_out], w int16 [n_out, T]) of one axis, by the rule above; read-only, memoised"""
     check_scale(n_in, n_out)
     return _taps(int(n_in), int(n_out))
+
+
+# ---- rotation resynchronisation (include/wmhip.h, "rotation resynchronisation"): the weights and the candidates ---------------
+ROTATE_PHASES = 256
+ROTATE_MAX_SIDE = 8192
+ANGLE_ONE = 1 << 16
+
+
+@functools.lru_cache(maxsize=1)
+def rotate_weights() -> np.ndarray:
+    """K int16 [256, 4]: row f is Catmull-Rom at offsets -1, 0, 1, 2 for phase f / 256, rint(. 2^14), the residue to 2^14 added
+    to the largest tap, the first of equals; K[0] = (0, 2^14, 0, 0).  Read-only, memoised."""
+    t = np.arange(ROTATE_PHASES, dtype=np.float64)[:, None] / ROTATE_PHASES
+    iw = np.rint(cubic(t + 1.0 - np.arange(4)) * WEIGHT_ONE).astype(np.int64)
+    big = np.argmax(iw, axis=1)                                            # (argmax: the first of equals)
+    iw[np.arange(ROTATE_PHASES), big] += WEIGHT_ONE - iw.sum(axis=1)
+    K = iw.astype(np.int16)
+    K.setflags(write=False)
+    return K
+
+
+def angle_candidate(theta: float) -> tuple:
+    """(C, S) of an angle in radians: rint(cos 2^16), rint(sin 2^16), float64 on the host"""
+    return int(np.rint(math.cos(float(theta)) * ANGLE_ONE)), int(np.rint(math.sin(float(theta)) * ANGLE_ONE))
+
+
+def angle_candidates_cs(thetas) -> np.ndarray:
+    """int32 [n, 2]: angle_candidate of every theta"""
+    return np.array([angle_candidate(t) for t in np.asarray(thetas, np.float64).reshape(-1)], np.int32).reshape(-1, 2)
+
+
+def check_rotate(h: int, w: int, H: int, W: int, noun: str = "stego") -> None:
+    """an h x w ``noun`` and an H x W frame whose every side the rotation's 32-bit coordinates hold, or a ValueError"""
+    if min(int(h), int(w), int(H), int(W)) < 1 or max(int(h), int(w), int(H), int(W)) > ROTATE_MAX_SIDE:
+        raise ValueError(f"{noun} is {w}x{h} for a {W}x{H} frame: a rotation takes sides in 1..{ROTATE_MAX_SIDE}")
 
 
 def check_resize(h: int, w: int, H: int, W: int, noun: str = "stego") -> None:

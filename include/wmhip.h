@@ -532,6 +532,63 @@ int wm_resample_planes_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_p
                           size_t src_plane_stride, int h_out, int w_out, int dst_row_stride, size_t dst_plane_stride,
                           const int32_t* first_x, const int16_t* w_x, int T_x, const int32_t* first_y, const int16_t* w_y, int T_y);
 
+/* ---- Blind payload, rotation resynchronisation: a stego that was rotated about its centre --
+ * A rotation resamples every tile, so no window has its sigma_1 on the lattice - until the rotation is undone.  The meta
+ * holds everything but the angle; the angle is searched for: every candidate rotates the stego's luma back onto the marked
+ * H x W frame by the filter below, the plain metric reads the restored plane, and the candidate whose valid tiles sit
+ * closest to their lattice points (the largest mean |m|) wins and is decoded ("Rotation resynchronisation").
+ * Integers throughout, so the device and a NumPy restatement (tests/rotate_refs.py) agree to the bit.
+ *
+ * Candidate: an angle theta, on the host in float64:  C = rint(cos theta 2^16),  S = rint(sin theta 2^16),  both int32.
+ * Coordinates: the source is h x w, the destination the marked H x W, their centres coincide (a same-size canvas with cut
+ *   corners and an expanded canvas are one case).  Destination pixel (y, x):
+ *     X2 = 2 x + 1 - W;   Y2 = 2 y + 1 - H
+ *     U = C X2 - S Y2 + (w - 1) 2^16;   V = S X2 + C Y2 + (h - 1) 2^16        int32, in units of 2^-17 source pixels
+ *     x0 = U >> 17,  fx = (U >> 9) & 255;   y0 = V >> 17,  fy = (V >> 9) & 255  (floor shifts)
+ *   Every side is at most 8192, so U and V fit 32 bits.
+ * Weights: K[256][4] int16 (resample.py: rotate_weights), row f the Catmull-Rom kernel (a = -0.5, as above) at offsets
+ *   -1, 0, 1, 2 for phase f / 256:  rint(cubic(f / 256 + 1 - i) 2^14), i = 0..3, the residue to 2^14 added to the largest
+ *   tap, the first of equals.  K[0] = (0, 2^14, 0, 0): theta = 0 onto the same size is the identity to the byte.
+ * A pixel, all int32:
+ *     row_j = (sum_i K[fx][i] px[clamp(y0 - 1 + j)][clamp(x0 - 1 + i)] + 2^7) >> 8                       j = 0..3
+ *     out   = clip((sum_j K[fy][j] row_j + 2^19) >> 20, 0, 255)
+ *   clamp: the index brought into the source (the device does not trust the candidates).
+ * A destination TILE is valid iff at each of its four corner pixels x0 - 1 >= 0, x0 + 2 <= w - 1, y0 - 1 >= 0 and
+ *   y0 + 2 <= h - 1; the map is affine, so the interior follows.  Invalid tiles neither score nor vote.
+ * Score of a candidate: sum of payload_vote(|m|) over its valid tiles (int64), m the metric of the restored plane read with
+ *   the meta's dither table or without one; count: the number of valid tiles.  The largest score / count wins, compared
+ *   exactly (cross-multiplied integers, payload.py: pick_angle), ties to the smallest candidate index; count 0 takes no part.
+ * Schedule (payload.py: angle_candidates): R = hypot(H, W) / 2; coarse theta_k = k / R, |k| <= floor(radians(max_angle) R);
+ *   fine theta = (8 k* + j) / (8 R), |j| <= 8, around the coarse winner k*.  Only the fine winner is decoded.
+ *
+ *   src    [n_planes] uint8 planes [h][w], src_row_stride / src_plane_stride in elements
+ *   dst    [n_angles][n_planes] uint8 planes [H][W] (out): plane (a, p) at dst + (a n_planes + p) dst_plane_stride,
+ *          dst_row_stride in elements; never in place
+ *   cand   [n_angles][2] int32: (C, S)
+ *   K      [256][4] int16, on an 8-byte boundary in the device form
+ * WM_ERR_BADARG, before any launch: NULL pointers, a side outside 1..8192, n_angles < 1, n_planes < 1, n_angles * n_planes
+ * above 65535, strides smaller than a row or a plane, (device form) misaligned cand or K.  A destination whose base or
+ * strides are not multiples of 4 is written byte by byte. */
+int wm_rotate_planes_u8_dev(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h, int w, int src_row_stride,
+                            size_t src_plane_stride, int H, int W, int dst_row_stride, size_t dst_plane_stride, const int32_t* cand,
+                            int n_angles, const int16_t* K);
+int wm_rotate_planes_u8(wm_ctx* ctx, const uint8_t* src, uint8_t* dst, int n_planes, int h, int w, int src_row_stride,
+                        size_t src_plane_stride, int H, int W, int dst_row_stride, size_t dst_plane_stride, const int32_t* cand,
+                        int n_angles, const int16_t* K);
+
+/* The scores of the candidates:
+ *   metric  [n_angles][n_tiles] float32, n_tiles = (H / 8) (W / 8): wm_payload_metric_tiles[_dither]_u8_dev of the n_angles
+ *           restored planes (a shared dither table: dither_plane_stride 0)
+ *   cand    [n_angles][2] int32, as above;  h, w: the source the planes were restored from
+ *   scores  [n_angles] int64 (out), counts [n_angles] int32 (out): zeroed by the call
+ *   valid   [n_angles][n_tiles] uint8 (out), may be NULL: 1 for a valid tile
+ * WM_ERR_BADARG, before any launch: NULL pointers (valid excepted), a side outside 1..8192, H or W not a multiple of 8,
+ * n_angles outside 1..65535, (device form) a misaligned pointer. */
+int wm_payload_angle_scores_dev(wm_ctx* ctx, const float* metric, const int32_t* cand, int n_angles, int64_t* scores, int32_t* counts,
+                                uint8_t* valid, int h, int w, int H, int W);
+int wm_payload_angle_scores(wm_ctx* ctx, const float* metric, const int32_t* cand, int n_angles, int64_t* scores, int32_t* counts,
+                            uint8_t* valid, int h, int w, int H, int W);
+
 
 /* ==========================================================================
  * Full-frame mode ("tile=None", the reference's own semantics): ONE dense
