@@ -1,5 +1,5 @@
 // libwmhip.so - the blind payload (include/wmhip.h): sigma_1 quantisation and its keyed dither, the phase, offset and keyed
-// searches, the clip search and the channel code's Viterbi decoder - kernels and C ABI.  A translation unit of its own over
+// searches, the clip search, the frame scores and the channel code's Viterbi decoder - kernels and C ABI.  A translation unit of its own over
 // wm_tile_pass.h (the sigma pass it shares with the tile-mode watermark of wmhip.hip) and wm_internal.h: every kernel here
 // is compiled in this unit only, and none of wmhip.hip's is compiled here.
 //
@@ -369,6 +369,72 @@ __global__ __launch_bounds__(256) void k_payload_keyed_best_unpack(long long* __
   if (key < 0) return;
   best[2 * i] = key >> 24;
   best[2 * i + 1] = KEYED_INDEX_MASK - (key & KEYED_INDEX_MASK);
+}
+
+// Frame scores (include/wmhip.h, "frame resynchronisation"): every clip frame against every table at ONE grid phase and ONE
+// placement - scores[f][k] = sum over the ny x nx windows of keyed_abs_vote(s1[f][r][c], tables[k][ty + r][tx + c]).  A product
+// over a (vote, +) semiring, blocked like one: grid (window chunks, table blocks, frame blocks); a wave owns FRAME_CHUNK
+// consecutive windows of the row-major window list, a block of FRAME_FB frames and a block of FRAME_TB tables.  Lane l takes
+// the windows i = chunk + l, l + 64, ..: it loads its window's sigma_1 of the 8 frames (registers) and the window's word of
+// the 8 tables - consecutive lanes read consecutive words of a table row, 128 bytes a wave - forms each word's dither once
+// (the 8 calls of keyed_abs_vote share it after inlining) and adds the 64 votes to 64 int32 accumulators: 48 bytes loaded
+// per 64 evaluations.  A lane sees FRAME_CHUNK / 64 = 8 windows of at most 2^15 a chunk, so an accumulator stays below 2^18
+// and the wave's sum below 2^24.  At the end of the chunk every accumulator is added over the wave and leaves by one 64-bit
+// integer atomic add into scores, which the entry point zeroed: integer addition is associative, so the same inputs give
+// the same bits whatever order the waves arrive in.  Grid y and z are capped at FRAME_GRID_CAP blocks; the kernel strides
+// over the rest.  A frame behind n_frames or a table behind n_tables is read as the last one (no divergence) and stores
+// nothing; a lane behind the last window adds nothing.  The compiler keeps the 16 frame and table bases and the epilogue's
+// 64 store masks in scalar registers and parks 26 of them in the lanes of one vector register (v_writelane / v_readlane, outside
+// the window loop; nothing goes to memory).  The epilogue holds a score row's address in vector registers for that: with all 64
+// addresses scalar it parked 42.  Tried and not taken: the 64 sums gathered into the lanes and stored by one vector atomic
+// (through readfirstlane 150 parked, through a butterfly sum 122 and 165 VGPRs), the atomics under one lane-0 branch (167 VGPRs).
+constexpr int FRAME_FB = 8;              // frames a lane holds in registers
+constexpr int FRAME_TB = 8;              // tables it walks against them
+#ifndef WM_FRAME_CHUNK
+#define WM_FRAME_CHUNK 512
+#endif
+constexpr int FRAME_CHUNK = WM_FRAME_CHUNK;   // windows of a wave's chunk (512): 64 frames x 64 tables are 4 096 waves at 1080p and 1 024,
+                                            // one a SIMD, at a half-size crop of it (-DWM_FRAME_CHUNK=..: a build to measure another against)
+constexpr int FRAME_GRID_CAP = 1024;     // table blocks (grid y) and frame blocks (grid z) of a launch
+
+struct FrameScoreGeom {
+  int n_frames, n_tables, n_win, nx, nbx;
+  size_t wstride, fstride;               // floats between the windows of a frame and between frames
+  size_t tsize, at;                      // words of a table; the placement's first word, ty nbx + tx
+};
+
+__global__ __launch_bounds__(WAVE) void k_payload_frame_scores(const float* __restrict__ s1, const uint16_t* __restrict__ tables,
+                                                           unsigned long long* __restrict__ scores, const FrameScoreGeom g,
+                                                           const float delta, const float inv_2delta) {
+  const int i0 = blockIdx.x * FRAME_CHUNK, i1 = min(i0 + FRAME_CHUNK, g.n_win);
+  for (int f0 = blockIdx.z * FRAME_FB; f0 < g.n_frames; f0 += gridDim.z * FRAME_FB)
+    for (int t0 = blockIdx.y * FRAME_TB; t0 < g.n_tables; t0 += gridDim.y * FRAME_TB) {
+      int acc[FRAME_FB][FRAME_TB] = {};
+      for (int i = i0 + (int)threadIdx.x; i < i1; i += WAVE) {
+        const int r = i / g.nx, c = i - r * g.nx;
+        const size_t si = (size_t)i * g.wstride, ui = g.at + (size_t)r * g.nbx + c;
+        float s[FRAME_FB];
+        uint16_t u[FRAME_TB];
+#pragma unroll
+        for (int k = 0; k < FRAME_FB; ++k) s[k] = s1[(size_t)min(f0 + k, g.n_frames - 1) * g.fstride + si];
+#pragma unroll
+        for (int t = 0; t < FRAME_TB; ++t) u[t] = tables[(size_t)min(t0 + t, g.n_tables - 1) * g.tsize + ui];
+#pragma unroll
+        for (int t = 0; t < FRAME_TB; ++t)
+#pragma unroll
+          for (int k = 0; k < FRAME_FB; ++k) acc[k][t] += keyed_abs_vote(s[k], u[t], delta, inv_2delta);
+      }
+#pragma unroll
+      for (int k = 0; k < FRAME_FB; ++k) {
+        unsigned long long* row = scores + (size_t)(f0 + k) * g.n_tables + t0;
+        asm volatile("" : "+v"(row));                                      // the row's address in vector registers: table t is an immediate offset
+#pragma unroll
+        for (int t = 0; t < FRAME_TB; ++t) {
+          const int sum = wave_sum(acc[k][t]);
+          if (threadIdx.x == 0 && f0 + k < g.n_frames && t0 + t < g.n_tables) atomicAdd(row + t, (unsigned long long)sum);
+        }
+      }
+    }
 }
 
 // The channel code's decoder (wmhip.h, "channel code"; the per-state arithmetic is wm_tile_math.h's): one wave per codeword,
@@ -741,6 +807,39 @@ int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const 
   return WM_OK;
 }
 
+// ---- frame resynchronisation: every clip frame against every table at one phase and place --------
+// the sizes and pointers of a frame-score call, checked (both forms, before any launch or copy)
+static int check_frame_scores(const float* s1, size_t s1_window_stride, int n_frames, const uint16_t* tables, int n_tables,
+                              const int64_t* scores, int ny, int nx, int nby, int nbx, int ty, int tx, float delta) {
+  if (n_frames < 1 || n_tables < 1 || ny < 1 || nx < 1) return set_err(WM_ERR_BADARG, "n_frames, n_tables, ny and nx must be at least 1");
+  if (n_frames > (1 << 24) || n_tables > (1 << 24)) return set_err(WM_ERR_BADARG, "more than 2^24 frames or tables");
+  if (ty < 0 || tx < 0 || nby < 0 || nbx < 0 || (long long)ty + ny > nby || (long long)tx + nx > nbx)
+    return set_err(WM_ERR_BADARG, "the window grid at (ty, tx) does not lie inside the table");
+  if ((size_t)nby * (size_t)nbx > ((size_t)1 << 30)) return set_err(WM_ERR_BADARG, "tile grid too large");
+  if (s1_window_stride == 0) return set_err(WM_ERR_BADARG, "s1_window_stride must be at least 1");
+  WM_TRY(check_delta(delta));
+  if (!tables || ((uintptr_t)tables & 1u)) return set_err(WM_ERR_BADARG, "tables is NULL or at an odd address");
+  if (!s1 || !scores || ((uintptr_t)s1 & 3u) || ((uintptr_t)scores & 7u)) return set_err(WM_ERR_BADARG, "s1 / scores is NULL or misaligned");
+  return WM_OK;
+}
+
+int wm_payload_frame_scores_dev(wm_ctx* ctx, const float* s1, size_t s1_window_stride, size_t s1_frame_stride, int n_frames,
+                                const uint16_t* tables, int n_tables, int64_t* scores, int ny, int nx, int nby, int nbx, int ty, int tx,
+                                float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_frame_scores(s1, s1_window_stride, n_frames, tables, n_tables, scores, ny, nx, nby, nbx, ty, tx, delta));
+  WM_HIP(hipMemsetAsync(scores, 0, (size_t)n_frames * (size_t)n_tables * sizeof(int64_t), ctx->stream));
+  const int n_win = ny * nx;
+  const FrameScoreGeom g{n_frames, n_tables, n_win, nx, nbx, s1_window_stride, s1_frame_stride, (size_t)nby * (size_t)nbx,
+                         (size_t)ty * (size_t)nbx + (size_t)tx};
+  const dim3 grid((unsigned)((n_win - 1) / FRAME_CHUNK + 1), (unsigned)std::min((n_tables - 1) / FRAME_TB + 1, FRAME_GRID_CAP),
+                  (unsigned)std::min((n_frames - 1) / FRAME_FB + 1, FRAME_GRID_CAP));
+  hipLaunchKernelGGL(k_payload_frame_scores, grid, dim3(WAVE), 0, ctx->stream, s1, tables, reinterpret_cast<unsigned long long*>(scores), g,
+                     delta, 1.0f / (2.0f * delta));
+  WM_HIP(hipGetLastError());
+  return WM_OK;
+}
+
 // ---- rotation resynchronisation: the angle scores ---------------------------------
 // the sizes and pointers of a score call, checked (both forms, before any launch or copy)
 static int check_angle_scores(const float* metric, const int32_t* cand, int n_angles, const int64_t* scores, const int32_t* counts,
@@ -1018,6 +1117,24 @@ int wm_payload_keyed_best(wm_ctx* ctx, const float* s1, int n_anchor, const uint
     d_of = cv.in(n_of, table_of);
     d_best = cv.out((size_t)n_cand * 128, best);
   }, [&] { return wm_payload_keyed_best_dev(ctx, d_s1, n_anchor, d_u, n_tables, d_of, n_cand, d_best, h, w, nby, nbx, delta); }, true);
+}
+
+// ---- frame resynchronisation, host pointers --------------------------------------
+int wm_payload_frame_scores(wm_ctx* ctx, const float* s1, size_t s1_window_stride, size_t s1_frame_stride, int n_frames,
+                            const uint16_t* tables, int n_tables, int64_t* scores, int ny, int nx, int nby, int nbx, int ty, int tx,
+                            float delta) {
+  WM_TRY(wmi::use_ctx(ctx));
+  WM_TRY(check_frame_scores(s1, s1_window_stride, n_frames, tables, n_tables, scores, ny, nx, nby, nbx, ty, tx, delta));
+  const size_t n_s1 = (size_t)(n_frames - 1) * s1_frame_stride + ((size_t)ny * (size_t)nx - 1) * s1_window_stride + 1;
+  float* d_s1; uint16_t* d_u; int64_t* d_sc;
+  return staged_call(ctx, [&](Carve& cv) {
+    d_s1 = cv.in(n_s1, s1);
+    d_u = cv.in((size_t)n_tables * (size_t)nby * (size_t)nbx, tables);
+    d_sc = cv.out((size_t)n_frames * (size_t)n_tables, scores);
+  }, [&] {
+    return wm_payload_frame_scores_dev(ctx, d_s1, s1_window_stride, s1_frame_stride, n_frames, d_u, n_tables, d_sc, ny, nx, nby, nbx, ty,
+                                       tx, delta);
+  }, true);
 }
 
 // ---- rotation resynchronisation, host pointers -----------------------------------

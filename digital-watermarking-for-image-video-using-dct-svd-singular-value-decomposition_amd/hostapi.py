@@ -96,6 +96,8 @@ _DECLARED = {
     "wm_payload_keyed_scores*": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f],
     # clip resynchronisation: (s1, n_anchor, tables, n_tables, table_of, n_cand, best, h, w, nby, nbx, delta)
     "wm_payload_keyed_best*": [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f],
+    # frame resynchronisation: (s1, s1_window_stride, s1_frame_stride, n_frames, tables, n_tables, scores, ny, nx, nby, nbx, ty, tx, delta)
+    "wm_payload_frame_scores*": [_vp, _vp, _sz, _sz, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f],
     # channel code: (llr, n_info, n_codewords, llr_stride, info_bits, final_metric, decisions)
     "wm_payload_decode_k7*": [_vp, _vp, _i, _i, _sz, _vp, _vp, _vp],
     # resize resynchronisation: (src, dst, n_planes, h_in, w_in, src strides, h_out, w_out, dst strides, first_x, w_x, T_x, first_y, w_y, T_y)
@@ -617,7 +619,8 @@ class Context:
     def _cached_array(self, kind: str, arr: np.ndarray) -> int:
         """Device copy of one array, cached by shape and content under ``kind``: "dither", a dither table shared by the
         planes, always passed flat ([n_tiles]: a video decodes batch after batch of one frame size under few tables);
-        "payload_tbi", a tile-to-bit map [nby, nbx] (one image size under one key decodes crop after crop)."""
+        "payload_tbi", a tile-to-bit map [nby, nbx] (one image size under one key decodes crop after crop); "frame_tables", the
+        tables of a frame search, flat (payload_match_frames: batch after batch of one file under the same tables)."""
         def upload():
             d = self.malloc(max(arr.nbytes, arr.itemsize))
             self.h2d(d, arr)
@@ -914,6 +917,69 @@ class Context:
         g, p, i = win
         n_tx = nbx - (w - p % 8) // TILE + 1
         return best, (g, (p // 8, p % 8), (i // n_tx, i % n_tx))
+
+    # ---- frame resynchronisation: a dithered video's frames in any order (include/wmhip.h; the assignment is payload.pick_frames) ----
+    @staticmethod
+    def _frame_args(tables, ny, nx, ty, tx, delta):
+        u = np.ascontiguousarray(tables, np.uint16)
+        if u.ndim != 3 or u.shape[0] < 1:
+            raise ValueError("the dither tables must be [n_tables, nby, nbx] with at least one table")
+        ny, nx, ty, tx = int(ny), int(nx), int(ty), int(tx)
+        nby, nbx = u.shape[1:]
+        if ny < 1 or nx < 1 or ty < 0 or tx < 0 or ty + ny > nby or tx + nx > nbx:
+            raise ValueError(f"a {ny} x {nx} window grid at ({ty}, {tx}) does not lie inside the {nby} x {nbx} table")
+        return u, ny, nx, ty, tx, nby, nbx, check_delta(delta)
+
+    def payload_frame_scores(self, s1: np.ndarray, tables: np.ndarray, ny: int, nx: int, ty: int, tx: int, delta: float) -> np.ndarray:
+        """wm_payload_frame_scores on host arrays: ``s1`` float32 [n_frames, ny, nx] (the frames' sigma_1 at one grid phase),
+        ``tables`` uint16 [n_tables, nby, nbx] -> scores int64 [n_frames, n_tables]: frame f's windows read on the lattices
+        of table k's tiles (ty + r, tx + c), |vote| added."""
+        u, ny, nx, ty, tx, nby, nbx, delta = self._frame_args(tables, ny, nx, ty, tx, delta)
+        s = _f32(s1)
+        if s.ndim != 3 or s.shape[0] < 1 or s.shape[1:] != (ny, nx):
+            raise ValueError(f"s1 must be [n_frames >= 1, {ny}, {nx}], got {s.shape}")
+        scores = np.zeros((s.shape[0], u.shape[0]), np.int64)
+        self._call("wm_payload_frame_scores", _p(s), 1, ny * nx, s.shape[0], _p(u), u.shape[0], _p(scores), ny, nx, nby, nbx, ty, tx, delta)
+        return scores
+
+    def payload_match_frames(self, planes_view: np.ndarray, tables: np.ndarray, ty: int, tx: int, delta: float,
+                             tables_per_call: Optional[int] = None):
+        """Step 2 of the frame search on uint8 views [n, 8 ny, 8 nx] of the frames at the found grid phase: the sigma pass,
+        then the scores against all tables with sigma_1 resident (the sigma pass's [n][ny nx][8] output is read in place,
+        window stride 8).  Tables go to the device in runs of ``tables_per_call`` (by default as many as stay within
+        CLIP_TABLE_BYTES); tables that fit one run are uploaded once and stay resident from call to call (the device cache),
+        longer lists go up run by run on every call; the result does not depend on the split.  -> (scores int64 [n, K], s1 float32 [n, ny, nx])."""
+        if planes_view.ndim != 3 or planes_view.shape[0] < 1:
+            raise ValueError("planes_view must be [n >= 1, h, w]")
+        n, h, w = _planes_of(planes_view, np.uint8, "planes must be uint8")[:3]         # (the view is uploaded dense)
+        if h < TILE or w < TILE or h % TILE or w % TILE:
+            raise ValueError(f"the view must be whole tiles, got {h} x {w}")
+        u, ny, nx, ty, tx, nby, nbx, delta = self._frame_args(tables, h // TILE, w // TILE, ty, tx, delta)
+        K = u.shape[0]
+        if tables_per_call is None:
+            tables_per_call = max(1, self.CLIP_TABLE_BYTES // max(u[0].nbytes, 1))
+        step = max(1, int(tables_per_call))
+        scores = np.zeros((n, K), np.int64)
+        sig = np.empty((n, ny, nx, 8), np.float32)
+        # tables that fit one run stay on the device from batch to batch (a file is matched batch after batch under the same ones)
+        d_all = self._cached_array("frame_tables", u.reshape(-1)) if step >= K else 0
+        with self._staging() as dev:
+            d_sig = dev.alloc(sig.nbytes)
+            d_p, = dev.up(np.ascontiguousarray(planes_view))
+            self._call("wm_sigma_tiles_u8_dev", _vp(d_p), _vp(d_sig), n, h, w, w, h * w)
+            for k0 in range(0, K, step):
+                part = np.zeros((n, min(step, K - k0)), np.int64)
+                with self._staging() as run:
+                    d_sc = run.alloc(part.nbytes)
+                    d_u = d_all or run.up(np.ascontiguousarray(u[k0:k0 + step]))[0]
+                    self._call("wm_payload_frame_scores_dev", _vp(d_sig), 8, ny * nx * 8, n, _vp(d_u), part.shape[1], _vp(d_sc),
+                               ny, nx, nby, nbx, ty, tx, delta)
+                    self.d2h(part, d_sc)
+                    self.sync()
+                scores[:, k0:k0 + step] = part
+            self.d2h(sig, d_sig)
+            self.check_status()
+        return scores, np.ascontiguousarray(sig[..., 0])
 
     # ---- resize resynchronisation of the blind payload (include/wmhip.h; the tap tables are resample.py's) ----------------
     def resample_planes(self, planes: np.ndarray, H: int, W: int) -> np.ndarray:

@@ -297,6 +297,54 @@ def pick_clip(best, counts, marked):
     return None if win is None else win[2:]
 
 
+# ---- frame resynchronisation (include/wmhip.h): a dithered video's frames dropped, repeated, reordered ---
+SEARCH_FRAMES = "frames"                           # extract_payload_video's ``search`` value
+FRAME_GAP_DEN = 10                                  # a frame names its table when it leads the runner-up by 1 / 10 of full scale
+
+
+def leads_by_the_bar(s_w: int, n_w: int, s_e: int, n_e: int) -> bool:
+    """s_w / n_w - s_e / n_e >= 32768 / FRAME_GAP_DEN, in exact integers: the bar of the frame search between two scores
+    over n_w and n_e windows"""
+    s_w, n_w, s_e, n_e = int(s_w), int(n_w), int(s_e), int(n_e)
+    return FRAME_GAP_DEN * (s_w * n_e - s_e * n_w) >= VOTE_ONE * n_w * n_e
+
+
+def anchor_accepted(best, counts, win) -> bool:
+    """Step 1 of the frame search: does the winner ``win`` = (g, p, index) of one anchor's ``best`` int64 [K, 64, 2]
+    (pick_clip with marked = 1) lead every other (candidate, phase) entry by the bar?  Entries of -1 and phases without a
+    window do not take part."""
+    b = np.asarray(best)
+    n = np.asarray(counts).reshape(-1)
+    g, p = int(win[0]), int(win[1])
+    s_w, n_w = int(b[g, p, 0]), int(n[p])
+    for e in range(b.shape[0]):
+        for q in range(64):
+            if (e, q) == (g, p) or int(b[e, q, 0]) < 0 or int(n[q]) <= 0:
+                continue
+            if not leads_by_the_bar(s_w, n_w, int(b[e, q, 0]), int(n[q])):
+                return False
+    return True
+
+
+def pick_frames(scores, n_win: int) -> np.ndarray:
+    """Step 3 of the frame search: int32 [n_frames], for every row of ``scores`` int64 [n_frames, K] the index k* of its
+    FIRST maximum where the row names a table, else -1.  second = max(the largest score among the other tables, 16384 n_win)
+    - the floor is the score of a uniform phase, so one table follows the same rule - and the row names k* when
+    FRAME_GAP_DEN * (score[k*] - second) >= 32768 * n_win, in Python integers."""
+    s = np.asarray(scores)
+    n_win = int(n_win)
+    if s.ndim != 2 or s.shape[1] < 1 or n_win < 1:
+        raise ValueError("scores must be [n_frames, n_tables >= 1] and n_win at least 1")
+    out = np.full(s.shape[0], -1, np.int32)
+    for f in range(s.shape[0]):
+        row = [int(x) for x in s[f]]
+        k = row.index(max(row))                                            # (the first of equals)
+        second = max(row[:k] + row[k + 1:] + [(VOTE_ONE // 2) * n_win])
+        if FRAME_GAP_DEN * (row[k] - second) >= VOTE_ONE * n_win:
+            out[f] = k
+    return out
+
+
 # ---- channel code (include/wmhip.h, "channel code"; DESIGN.md section 14): rate 1/2, K = 7, generators 171 / 133 octal --------
 CODES = (None, "k7")                                # what a caller's ``code`` argument may be
 CODE_K7 = 1                                         # the meta's ``code`` member: this code

@@ -668,6 +668,79 @@ def _chain_frames(held, frames):
         yield y
 
 
+def _extract_payload_frames(vid: Y4M, rule: F.Rule, batch: int, device: int, anchors: int, return_soft: bool):
+    """search="frames" (include/wmhip.h, "frame resynchronisation"): the file holds frames of a video marked with dither=True
+    in any order - dropped, repeated, reordered, unmarked or foreign ones among them - every frame cropped to the same
+    rectangle.  Every refusal comes before the first device call; the frames are read once, and beside the anchors only one
+    batch of them, its sigma_1, the int64 vote grid and frame_map live on the host."""
+    if not rule.dither:
+        raise ValueError("search='frames' reads a payload embedded with dither=True; this one has none")
+    anchors = int(anchors)
+    if anchors < 1:
+        raise ValueError(f"anchors must be at least 1, got {anchors}")
+    h, w = vid.H, vid.W
+    F.check_crop_shape(h, w, rule.H, rule.W, "clip")
+    n_c = _count_frames(vid)
+    if n_c < 1:
+        raise ValueError("clip has no frame")
+    fi = max(1, rule.frame_interval)
+    nby, nbx = rule.grid
+    K = (rule.n_frames + fi - 1) // fi
+    tables = P.dither_tables(nby, nbx, rule.key, [k * fi for k in range(K)]).reshape(K, nby, nbx)
+    tbi = rule.map()[0].reshape(nby, nbx)
+    frame_map = np.full(n_c, -1, np.int32)
+    empty = (b"", False, 0.0, None, frame_map)
+    if return_soft:
+        empty += (np.zeros(rule.carried, np.float64),)
+    if K < 1:
+        return empty
+    frames = iter(vid)
+    held = [y for _, (_, y, _) in zip(range(min(n_c, anchors * fi)), frames)]
+    ctx = hostapi.Context(device)
+    try:
+        # step 1: the first anchor whose own table, phase and place stand out fixes the geometry of every frame
+        geometry = None
+        counts = P.phase_counts(h, w)
+        every_table = np.arange(K, dtype=np.int32)[:, None]
+        for y in held:
+            best, win = ctx.payload_locate_clip(y[None], tables, every_table, rule.delta, pick=True)
+            if win is not None and P.anchor_accepted(best, counts, (win[0], 8 * win[1][0] + win[1][1])):
+                geometry = win[1:]
+                break
+        if geometry is None:
+            return empty
+        (py, px), (ty, tx) = geometry
+        ny, nx = (h - py) // TILE, (w - px) // TILE
+        votes = np.zeros((ny, nx), np.int64)
+        n_accepted = 0
+
+        def match(f0, pend):
+            # steps 2 - 4 on one batch: sigma pass and scores on the device, assignment and votes on the host
+            ys = np.stack([y[py:py + TILE * ny, px:px + TILE * nx] for y in pend])
+            scores, s1 = ctx.payload_match_frames(ys, tables, ty, tx, rule.delta)
+            named = P.pick_frames(scores, ny * nx)
+            for j, k in enumerate(named):
+                if k >= 0:
+                    frame_map[f0 + j] = k * fi
+                    np.add(votes, P.keyed_votes(s1[j], tables[k, ty:ty + ny, tx:tx + nx], rule.delta), out=votes)
+            return int(np.count_nonzero(named >= 0))
+
+        pend, f0 = [], 0
+        for y in _chain_frames(held, frames):
+            pend.append(y)
+            if len(pend) >= batch:
+                n_accepted += match(f0, pend)
+                f0 += len(pend); pend = []
+        if pend:
+            n_accepted += match(f0, pend)
+        if n_accepted == 0:
+            return empty
+        out = F.search_tail(ctx, votes, py, px, ty, tx, tbi, rule.carried, rule.code, n_accepted, return_soft)
+    finally:
+        ctx.close()
+    return out[:4] + (frame_map,) + out[4:]
+
+
 def extract_payload_video(stego_video_path: str, metadata_path: str, *, password: str = "", batch: int = 32,
                           device: int = 0, return_soft: bool = False, search=None, anchors: int = P.CLIP_ANCHORS):
     """-> (data, valid, confidence) from the marked frames' luma; with ``return_soft`` the summed soft vector follows.
@@ -679,9 +752,18 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     ``search="resize"``: the file may be the marked video with every frame resized to another size, the frames' number and
     order unchanged.  Each batch of marked luma frames is resampled back to the meta's size on the device in one call and
     decoded as unresized frames; the result is the plain one followed by scale = (h / H, w / W), ahead of the soft vector
-    where that is asked for ("Resize resynchronisation")."""
-    if search not in VIDEO_SEARCHES + (SEARCH_RESIZE,):
-        raise ValueError(f"search must be None, 'clip' or 'resize', got {search!r}")
+    where that is asked for ("Resize resynchronisation").
+    ``search="frames"``: the file may hold frames of the marked video in any order - frames dropped or repeated (a frame-rate
+    conversion), scenes spliced, a reversed or reordered reel - with frames that were never marked mixed in (the unmarked
+    ones of ``frame_interval`` > 1, a title card), every frame cropped to the same axis-aligned rectangle; it may have more
+    frames than the marked video had (a payload embedded with dither=True).  The tile grid and the crop's place come from
+    the first of the first ``anchors`` marked frames' worth of the file that names a table of its own; then every frame is
+    scored against every marked frame's table on the device and votes under the one it names.  The result is (data, valid,
+    confidence, origin, frame_map): frame_map int32 [frames of the file], the marked file's frame index every frame was
+    matched to, -1 for a frame that took no part.  Where no anchor or no frame names a table the result is (b"", False, 0.0,
+    None, frame_map of -1), not an exception ("Frame resynchronisation")."""
+    if search not in VIDEO_SEARCHES + (SEARCH_RESIZE, P.SEARCH_FRAMES):
+        raise ValueError(f"search must be None, 'clip', 'resize' or 'frames', got {search!r}")
     M.require_password(password, "extract")
     rule = F.checked_rule(M.load_payload_meta(metadata_path), password, video=True)
     H, W, fi = rule.H, rule.W, rule.frame_interval
@@ -691,6 +773,8 @@ def extract_payload_video(stego_video_path: str, metadata_path: str, *, password
     try:
         if search == P.SEARCH_CLIP:
             return _extract_payload_clip(vid, rule, batch, device, anchors, return_soft)
+        if search == P.SEARCH_FRAMES:
+            return _extract_payload_frames(vid, rule, batch, device, anchors, return_soft)
         _, order, offs = rule.map()
         resized = search == SEARCH_RESIZE and (vid.H, vid.W) != (H, W)
         if search == SEARCH_RESIZE:

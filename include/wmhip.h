@@ -460,6 +460,49 @@ int wm_payload_keyed_best_dev(wm_ctx* ctx, const float* s1, int n_anchor, const 
 int wm_payload_keyed_best(wm_ctx* ctx, const float* s1, int n_anchor, const uint16_t* tables, int n_tables, const int32_t* table_of,
                           int n_cand, int64_t* best, int h, int w, int nby, int nbx, float delta);
 
+/* ---- Blind payload, frame resynchronisation: a dithered video with frames dropped, repeated, reordered or mixed in --
+ * The clip search pairs clip frame i with file frame t0 + i, so a frame-rate conversion, a splice, a reversed reel or a title
+ * card in the middle loses the payload although every surviving pixel still sits on its lattice point.  At a known grid
+ * phase and place a marked frame only has to be told apart from the other TABLES, and it names its own by a wide gap; a
+ * frame that carries nothing has no table that stands out.  The rule ("Frame resynchronisation"); all arithmetic
+ * past the metric is integer.
+ *   inputs    the file is n_c luma frames of h x w, every one cropped to the same rectangle, in any order; the meta holds
+ *             (H, W), F = n_frames, fi = frame_interval, delta and dither = 1.  K = ceil(F / fi) and tables[k] = the dither
+ *             table of file frame k fi.
+ *   1 geometry  the first A = min(n_c, anchors fi) frames are tried in file order, each ALONE through the clip search above:
+ *             one anchor, candidate g = table g (table_of = arange(K)[:, None]).  The winner of its `best` is step 4 above
+ *             with m_g = 1.  The anchor is accepted when its winner leads every other (candidate, phase) entry of `best` by
+ *             the bar of step 3: 10 (s_w n_e - s_e n_w) >= 32768 n_w n_e for the winner's (score, windows) = (s_w, n_w) and
+ *             every other entry's (s_e, n_e), in exact integers.  The first accepted anchor fixes (py, px), (ty, tx),
+ *             ny = (h - py) / 8 and nx = (w - px) / 8 for every frame.  No accepted anchor: the empty result.
+ *   2 scores  s1[f][r][c] = sigma_1 of the window at (py + 8 r, px + 8 c) of frame f (wm_sigma_tiles_u8 of the view
+ *             [py : py + 8 ny, px : px + 8 nx], element 0 of a tile's 8), and for every table k
+ *             score[f][k] = sum over r < ny, c < nx of |vote| of s1[f][r][c] on the lattice of tables[k][ty + r][tx + c]
+ *             (step 2 of the keyed search), int64: wm_payload_frame_scores below.
+ *   3 assign  n_win = ny nx.  For frame f: k* the FIRST maximum of its row; second = max(the largest score among the other
+ *             tables, 16384 n_win) - the floor is the score of a uniform phase, so K = 1 follows the same rule.  The frame is
+ *             accepted when 10 (score[f][k*] - second) >= 32768 n_win (a tenth of full scale); frame_map[f] = k* fi if
+ *             accepted, else -1.  Several frames may name one table; all of them vote.  Host work.
+ *   4 decode  every accepted frame's votes of its s1 under tables[k*][ty : ty + ny, tx : tx + nx], added (int64), then as
+ *             step 5 above with the accepted frames as the multiplicity; origin = (8 ty - py, 8 tx - px).  No accepted
+ *             frame: the empty result.
+ *
+ * Step 2 in one call:
+ *   s1      frame f's window i = r nx + c at s1[f * s1_frame_stride + i * s1_window_stride] (strides in floats): window
+ *           stride 8 reads the output of wm_sigma_tiles_u8_dev in place, 1 a dense grid
+ *   tables  [n_tables][nby nbx] uint16
+ *   scores  [n_frames][n_tables] int64 (out), zeroed first
+ * WM_ERR_BADARG, before anything is written: a NULL pointer; tables at an odd address; s1 or scores not aligned to its
+ * element; n_frames, n_tables, ny or nx < 1 (or n_frames, n_tables above 2^24); ty < 0, tx < 0, ty + ny > nby or
+ * tx + nx > nbx; nby nbx above 2^30; s1_window_stride 0; delta outside 8..512.  The sums are integers and leave by 64-bit
+ * integer atomic adds: the same inputs give the same bits. */
+int wm_payload_frame_scores_dev(wm_ctx* ctx, const float* s1, size_t s1_window_stride, size_t s1_frame_stride, int n_frames,
+                                const uint16_t* tables, int n_tables, int64_t* scores, int ny, int nx, int nby, int nbx, int ty, int tx,
+                                float delta);
+int wm_payload_frame_scores(wm_ctx* ctx, const float* s1, size_t s1_window_stride, size_t s1_frame_stride, int n_frames,
+                            const uint16_t* tables, int n_tables, int64_t* scores, int ny, int nx, int nby, int nbx, int ty, int tx,
+                            float delta);
+
 /* --------------------------------------------------------------------------
  * Channel code of the blind payload (optional; the meta's ``code`` member = 1): the industry-standard rate-1/2 convolutional
  * code of constraint length 7, generators 171 and 133 octal, with a zero tail, decoded by a soft-decision Viterbi decoder on
